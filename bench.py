@@ -8,9 +8,14 @@ constraints. One process per GPU (torch.distributed, RCCL backend); each rank so
 batch (weak scaling, no data-path collective: the QPs are independent); the timed region is
 bracketed by barrier + synchronize and the max over ranks is reported.
 
-Extra JSON fields: "roofline" (dominant kernel = the solve kernel: algorithmic bytes and
-flops per launch / its average duration from HIP events on the launch stream) and
-"cpu_baseline" (the CPU oracle timed on a bounded sample on the host cores; rank 0, N=1).
+A plain run sets up, warms up, times the steps and prints the result line (value, ms_per_step
+and the solver statistics of the timed steps); --dump-outputs DIR also writes what the last timed
+step returned as DIR/<name>.npy.
+
+Extra JSON fields with --full: "roofline" (dominant kernel = the solve kernel: algorithmic bytes
+and flops per launch / its average duration from HIP events on the launch stream), "latency"
+(single-QP and per-launch wall latency) and "cpu_baseline" (the CPU oracle timed on a bounded
+sample on the host cores; rank 0, N=1).
 """
 from __future__ import annotations
 
@@ -338,6 +343,28 @@ def _halfspaces_host(w, B):
     return hs
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path: str, arrays: dict, suffix: str = "", max_bytes: int = DUMP_MAX_BYTES) -> dict:
+    """Write the per-QP output arrays (first axis = the QP) as path/<name><suffix>.npy in float32.
+    When they would exceed max_bytes in all, the same fixed, seeded sample of QPs is written from
+    every array, and its indices as path/sample_rows<suffix>.npy (float64). Returns {file name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    B = next(iter(arrays.values())).shape[0]
+    per_qp = sum(a.nbytes // max(1, B) for a in arrays.values()) + 8
+    if per_qp * B > max_bytes:
+        rows = np.sort(np.random.default_rng(20240531).choice(B, size=max(1, max_bytes // per_qp), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    written = {}
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), a)
+        written[f"{k}{suffix}.npy"] = list(a.shape)
+    return written
+
+
 def _free_port() -> int:
     import socket
 
@@ -401,8 +428,18 @@ def main():
     ap.add_argument("--backend", default="auto", choices=["auto", "wave", "lane"],
                     help="solver back end (auto: lane-per-QP for box-only batches >= capi.LANE_MIN_BATCH = 1024 "
                          "at N <= 32, >= capi.LANE_MIN_BATCH_WIDE = 1 at N > 32; f110qp_backend_info)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the dominant kernel's "
+                         "duration and the roofline, the latency probes and the CPU baseline (--no-latency and "
+                         "--no-cpu drop single legs); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (u, x, status, iters; the planning outputs of "
+                         "the tick config) to DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--print-launch", action="store_true", help=argparse.SUPPRESS)  # test hook: the rank plan
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        sys.exit(2)
 
     # one process per GPU: under torch.distributed.run (WORLD_SIZE set) it must agree with --gpus;
     # without a launcher, --gpus N > 1 starts the N ranks itself (before any GPU call here)
@@ -600,43 +637,54 @@ def main():
     itn = IT[args.warmup:args.warmup + args.steps].cpu().numpy() if stream_cfg else it.cpu().numpy()
     solved = float((stn == capi.SOLVED).mean())
 
-    # dominant kernel duration: HIP events on the launch stream around back-to-back launches
-    # (the queue stays full, so host launch overhead is not counted; rocprofv3 --stats agrees)
-    KEV = 20 if not stream_cfg else 18
-    a = torch.cuda.Event(enable_timing=True)
-    b = torch.cuda.Event(enable_timing=True)
-    step()
-    a.record(stream)
-    for _ in range(KEV):
-        step()
-    b.record(stream)
-    torch.cuda.synchronize(dev)
-    kms = a.elapsed_time(b) / KEV  # ms per launch
-    plan_ms = None
-    hs_ms = None
-    if gap:  # the FindHalfSpaces kernel alone, same stream
-        a.record(stream)
-        for _ in range(20):
-            hs_step()
-        b.record(stream)
-        torch.cuda.synchronize(dev)
-        hs_ms = a.elapsed_time(b) / 20
-        kms = kms - hs_ms  # the QP kernel of the step
-    if tick_cfg:  # the planning kernel alone, same stream
-        a.record(stream)
-        for _ in range(20):
-            plan_step()
-        b.record(stream)
-        torch.cuda.synchronize(dev)
-        plan_ms = a.elapsed_time(b) / 20
-        kms = kms - plan_ms  # the QP kernel(s) of the step
+    # what the last timed step returned to its caller, before anything else runs on these buffers
+    dumped = None
+    if args.dump_outputs:
+        arrays = {"u": uo.cpu().numpy(), "x": xo.cpu().numpy(), "status": stn,
+                  "iters": itn[-1] if stream_cfg else itn}
+        if tick_cfg:
+            arrays.update(plan_x_ref=pxr.cpu().numpy(), plan_x0=px0.cpu().numpy(), plan_best_traj=pbt.cpu().numpy(),
+                          plan_best_global=pbg.cpu().numpy(), plan_status=pst.cpu().numpy())
+        dumped = dump_outputs(args.dump_outputs, arrays, suffix=f"_rank{rank}" if world > 1 else "",
+                              max_bytes=DUMP_MAX_BYTES // world)
 
-    # per-QP latency: single-QP solves (B = 1) through the device entry point (launch + sync)
-    # and through the host-pointer entry point (H2D + launch + D2H), plus the per-launch
-    # distribution of the configured batch; rank 0 only, outside the timed region
+    kms = plan_ms = hs_ms = None
     latency = None
-    if rank == 0 and not args.no_latency:
-        latency = measure_latency(capi, solver, cfg, w, hs, N, dev, stream, step)
+    if args.full:
+        # dominant kernel duration: HIP events on the launch stream around back-to-back launches
+        # (the queue stays full, so host launch overhead is not counted; rocprofv3 --stats agrees)
+        KEV = 20 if not stream_cfg else 18
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        step()
+        a.record(stream)
+        for _ in range(KEV):
+            step()
+        b.record(stream)
+        torch.cuda.synchronize(dev)
+        kms = a.elapsed_time(b) / KEV  # ms per launch
+        if gap:  # the FindHalfSpaces kernel alone, same stream
+            a.record(stream)
+            for _ in range(20):
+                hs_step()
+            b.record(stream)
+            torch.cuda.synchronize(dev)
+            hs_ms = a.elapsed_time(b) / 20
+            kms = kms - hs_ms  # the QP kernel of the step
+        if tick_cfg:  # the planning kernel alone, same stream
+            a.record(stream)
+            for _ in range(20):
+                plan_step()
+            b.record(stream)
+            torch.cuda.synchronize(dev)
+            plan_ms = a.elapsed_time(b) / 20
+            kms = kms - plan_ms  # the QP kernel(s) of the step
+
+        # per-QP latency: single-QP solves (B = 1) through the device entry point (launch + sync)
+        # and through the host-pointer entry point (H2D + launch + D2H), plus the per-launch
+        # distribution of the configured batch; rank 0 only, outside the timed region
+        if rank == 0 and not args.no_latency:
+            latency = measure_latency(capi, solver, cfg, w, hs, N, dev, stream, step)
 
     if strong:
         total_qps = int(round(allreduce(float(Bper), dist.ReduceOp.SUM) if world > 1 else Bper)) * args.steps
@@ -644,34 +692,65 @@ def main():
         total_qps = Bper * world * args.steps
     value = total_qps / el
     ms_per_step = el / args.steps * 1e3
-    bpq = bytes_per_qp(N, gap, warm, be_name)
-    # active-set size ~ iterations for an add-only run; use iterations as the upper bound
-    seg_overhead = None
-    if be_name == "lane":
-        # Riccati + forward + adjoint sweeps: (active-set changes + 1) passes over N stages, priced at
-        # the sequential algorithm's flops (the segmented kernel's redundancy is reported apart)
-        fpq = LANE_FLOPS_PER_STAGE * N * (float(itn.mean()) + 1.0)
-        if lane_seg > 1 and not gap:
-            seg_overhead = {"executed_flops_per_stage_pass": seg_flops_per_stage(lane_seg, N),
-                            "algorithmic_flops_per_stage_pass": LANE_FLOPS_PER_STAGE,
-                            "ratio": seg_flops_per_stage(lane_seg, N) / LANE_FLOPS_PER_STAGE,
-                            "note": "parallel-in-time redundancy of the partitioned horizon (closed-loop map "
-                                    "per stage, S - 1 segment steps); not counted in fp64_compute"}
-        cpeak, cname = FP64_PEAK_TFLOPS, "fp64_compute"
-    else:
-        # pivots >= bounds active at the solution (each entered the active set once)
-        un = uo.cpu().numpy()
-        lo = np.float32([cfg.u_min[0], cfg.u_min[1]])
-        hi = np.float32([cfg.u_max[0], cfg.u_max[1]])
-        n_act = float(((np.abs(un - lo) < 1e-6) | (np.abs(un - hi) < 1e-6)).sum(axis=(1, 2)).mean())
-        fpq = flops_per_qp(N, float(itn.mean()), n_act, gap)
-        cpeak, cname = FP32_PEAK_TFLOPS, "fp32_compute"
-    achieved_gbs = bpq * Bper / (kms * 1e-3) / 1e9
-    achieved_tf = fpq * Bper / (kms * 1e-3) / 1e12
-    # the PMC summary's back-end key (tools/summarize_profiles.py KERNELS): the partitioned-horizon
-    # kernel is "lane_seg"
-    prof_be = be_name if be_name == "wave" else ("lane_seg" if lane_seg > 1 else "lane")
-    traffic = load_traffic(args.config, Bper, N, prof_be)
+
+    def roofline():
+        """The "roofline" field (--full): the dominant kernel's measured duration against its
+        algorithmic bytes and flops."""
+        bpq = bytes_per_qp(N, gap, warm, be_name)
+        # active-set size ~ iterations for an add-only run; use iterations as the upper bound
+        seg_overhead = None
+        if be_name == "lane":
+            # Riccati + forward + adjoint sweeps: (active-set changes + 1) passes over N stages, priced at
+            # the sequential algorithm's flops (the segmented kernel's redundancy is reported apart)
+            fpq = LANE_FLOPS_PER_STAGE * N * (float(itn.mean()) + 1.0)
+            if lane_seg > 1 and not gap:
+                seg_overhead = {"executed_flops_per_stage_pass": seg_flops_per_stage(lane_seg, N),
+                                "algorithmic_flops_per_stage_pass": LANE_FLOPS_PER_STAGE,
+                                "ratio": seg_flops_per_stage(lane_seg, N) / LANE_FLOPS_PER_STAGE,
+                                "note": "parallel-in-time redundancy of the partitioned horizon (closed-loop map "
+                                        "per stage, S - 1 segment steps); not counted in fp64_compute"}
+            cpeak, cname = FP64_PEAK_TFLOPS, "fp64_compute"
+        else:
+            # pivots >= bounds active at the solution (each entered the active set once)
+            un = uo.cpu().numpy()
+            lo = np.float32([cfg.u_min[0], cfg.u_min[1]])
+            hi = np.float32([cfg.u_max[0], cfg.u_max[1]])
+            n_act = float(((np.abs(un - lo) < 1e-6) | (np.abs(un - hi) < 1e-6)).sum(axis=(1, 2)).mean())
+            fpq = flops_per_qp(N, float(itn.mean()), n_act, gap)
+            cpeak, cname = FP32_PEAK_TFLOPS, "fp32_compute"
+        achieved_gbs = bpq * Bper / (kms * 1e-3) / 1e9
+        achieved_tf = fpq * Bper / (kms * 1e-3) / 1e12
+        # the PMC summary's back-end key (tools/summarize_profiles.py KERNELS): the partitioned-horizon
+        # kernel is "lane_seg"
+        prof_be = be_name if be_name == "wave" else ("lane_seg" if lane_seg > 1 else "lane")
+        traffic = load_traffic(args.config, Bper, N, prof_be)
+        return {
+            "bound": "hbm",
+            "achieved": achieved_gbs,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved_gbs / HBM_PEAK_GBS,
+            "traffic": traffic,
+            "kernel": {"wave": "f110qp::solve_kernel",
+                       "lane": ("f110qp::lane_kernel" if lane_seg == 1 else
+                                f"f110qp::lane_seg_kernel<{lane_seg}> (partitioned horizon)")
+                               + (" box screen + the wave kernel's GI over its list" if gap else
+                                  " (the only launch of the step)")}[be_name],
+            "kernel_ms_per_launch": kms,
+            "algorithmic_bytes_per_qp": bpq,
+            cname: {"achieved": achieved_tf, "peak": cpeak, "unit": "TFLOP/s",
+                    "frac": achieved_tf / cpeak, "flops_per_qp": fpq},
+            **({"segmentation_overhead": seg_overhead} if seg_overhead else {}),
+            "note": ("lane kernel: fp64 VALU-issue and scratch-latency bound (Riccati sweeps, 64 QPs per "
+                     "wave); traffic = PMC HBM bytes incl. the Riccati scratch" if be_name == "lane" and lane_seg == 1 else
+                     f"partitioned-horizon lane kernel: one QP per {lane_seg} lanes"
+                     + (" x 2 PDAS starts (twin: the first to converge answers)" if lane_starts == 2 else "")
+                     + ", latency-bound by the slowest QP's PDAS passes x (N/S stages + S-1 segment steps); "
+                     "scratch in LDS, HBM = inputs/outputs"
+                     if be_name == "lane" else
+                     "wave kernel: latency-bound (serial active-set chain per wave); neither HBM nor FP32 "
+                     "peak binds"),
+        }
 
     out = {
         "metric": f"QP solves/s (horizon={N}, nx=3 reference model, nu=2)",
@@ -703,14 +782,16 @@ def main():
             "parallelism": f"independent QP shards x{world} (no collective)"
                            + (f", scenario-aligned ({GROUP}) split of one global batch" if strong else ""),
             "solved_fraction": solved,
-            **({"step": "f110qp_find_half_spaces_dev (one 1,080-beam scan per QP) + f110qp_solve_batch_dev",
-                "halfspace_kernel_ms": hs_ms,
+            **({"step": "f110qp_find_half_spaces_dev (one 1,080-beam scan per QP) + f110qp_solve_batch_dev"}
+               if gap else {}),
+            **({"halfspace_kernel_ms": hs_ms,
                 "halfspace_roofline": {"bound": "hbm", "bytes_per_scan": 4 * (ranges.shape[1] + 3 + 6 + 2),
                                        "achieved_gbs": 4 * (ranges.shape[1] + 11) * Bper / (hs_ms * 1e-3) / 1e9,
                                        "peak_gbs": HBM_PEAK_GBS,
                                        "frac": 4 * (ranges.shape[1] + 11) * Bper / (hs_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}}
-               if gap else {}),
-            **({"plan_kernel_ms": plan_ms, "planned_fraction": float((pst.cpu().numpy() == 0).mean()),
+               if gap and args.full else {}),
+            **({"plan_kernel_ms": plan_ms} if tick_cfg and args.full else {}),
+            **({"planned_fraction": float((pst.cpu().numpy() == 0).mean()),
                 "step": "f110qp_plan_batch_dev + f110qp_solve_batch_dev (x_ref_points = 50)"} if tick_cfg else {}),
             "mean_active_set_iters": float(itn.mean()),
             "max_active_set_iters": int(itn.max()),
@@ -719,37 +800,14 @@ def main():
                if stream_cfg else {}),
             **({"warm_effective": warm_eff} if warm_eff is not None else {}),
         },
-        "roofline": {
-            "bound": "hbm",
-            "achieved": achieved_gbs,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": achieved_gbs / HBM_PEAK_GBS,
-            "traffic": traffic,
-            "kernel": {"wave": "f110qp::solve_kernel",
-                       "lane": ("f110qp::lane_kernel" if lane_seg == 1 else
-                                f"f110qp::lane_seg_kernel<{lane_seg}> (partitioned horizon)")
-                               + (" box screen + the wave kernel's GI over its list" if gap else
-                                  " (the only launch of the step)")}[be_name],
-            "kernel_ms_per_launch": kms,
-            "algorithmic_bytes_per_qp": bpq,
-            cname: {"achieved": achieved_tf, "peak": cpeak, "unit": "TFLOP/s",
-                    "frac": achieved_tf / cpeak, "flops_per_qp": fpq},
-            **({"segmentation_overhead": seg_overhead} if seg_overhead else {}),
-            "note": ("lane kernel: fp64 VALU-issue and scratch-latency bound (Riccati sweeps, 64 QPs per "
-                     "wave); traffic = PMC HBM bytes incl. the Riccati scratch" if be_name == "lane" and lane_seg == 1 else
-                     f"partitioned-horizon lane kernel: one QP per {lane_seg} lanes"
-                     + (" x 2 PDAS starts (twin: the first to converge answers)" if lane_starts == 2 else "")
-                     + ", latency-bound by the slowest QP's PDAS passes x (N/S stages + S-1 segment steps); "
-                     "scratch in LDS, HBM = inputs/outputs"
-                     if be_name == "lane" else
-                     "wave kernel: latency-bound (serial active-set chain per wave); neither HBM nor FP32 "
-                     "peak binds"),
-        },
     }
+    if args.full:
+        out["roofline"] = roofline()
     if latency is not None:
         out["latency"] = latency
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if dumped is not None:
+        out["outputs"] = {"dir": args.dump_outputs, "files": dumped}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         try:
             out["cpu_baseline"] = cpu_baseline(args.config, N, gap, args.cpu_seconds,
                                                args.cpu_threads or cpu_threads_default(), args.c1_ticks,

@@ -1,6 +1,6 @@
 """Sensitivity of the C3 gap rows to one unverifiable detail of the reference: the unqualified
 cos(angle1) / sin(angle1) on a float angle in Constraints::FindHalfSpaces
-(/root/reference/src/constraints.cpp:182-186). It resolves to ::cos(double) unless some header of
+(src/constraints.cpp:182-186 of the reference). It resolves to ::cos(double) unless some header of
 the ROS / Eigen include chain brings the libstdc++ <math.h> wrapper's float overload into the global
 namespace; neither can be built here. The oracle and the device kernel assume the double overload
 (oracle/f110_oracle.c, csrc/halfspace_kernels.hip); this test measures what the float overload

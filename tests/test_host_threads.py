@@ -2,6 +2,7 @@
 under ThreadSanitizer, CPU only. The reference's DriveLoop thread races OdomCallback on
 current_inputs_ / inputs_idx_ (src/project.cpp:190-191 vs :210-234, no lock although
 project.h:13 includes <mutex>); the mirror hands the solution over behind one mutex."""
+import ctypes
 import json
 import os
 import shutil
@@ -23,11 +24,27 @@ def _build(tmp_path, *defines):
 
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 
+_LIBC = ctypes.CDLL(None, use_errno=True)
+ADDR_NO_RANDOMIZE = 0x0040000  # <sys/personality.h>
+
+
+def _no_aslr():
+    """Runs in the child before exec, as `setarch -R` would: ThreadSanitizer's fixed shadow layout
+    refuses the mappings of a kernel with high-entropy address randomisation ("FATAL:
+    ThreadSanitizer: unexpected memory mapping", vm.mmap_rnd_bits = 32), so the instrumented
+    program starts with randomisation off. A per-process flag; nothing of the host changes."""
+    persona = _LIBC.personality(0xFFFFFFFF)
+    if persona != -1:
+        _LIBC.personality(persona | ADDR_NO_RANDOMIZE)
+
+
+def _run(exe, **kw):
+    return subprocess.run([exe], capture_output=True, text=True, timeout=120, preexec_fn=_no_aslr, **kw)
+
 
 def test_handoff_is_race_free_under_tsan(tmp_path):
     exe = _build(tmp_path)
-    p = subprocess.run([exe], capture_output=True, text=True, timeout=120,
-                       env={**os.environ, "TSAN_OPTIONS": "halt_on_error=1"})
+    p = _run(exe, env={**os.environ, "TSAN_OPTIONS": "halt_on_error=1"})
     assert "ThreadSanitizer" not in p.stderr, p.stderr[:2000]
     assert p.returncode == 0, (p.returncode, p.stdout, p.stderr[:500])
     out = json.loads(p.stdout)
@@ -38,5 +55,5 @@ def test_reference_handoff_races_under_tsan(tmp_path):
     """The same threads on the reference's unsynchronised members: ThreadSanitizer reports the race
     (so the clean run above is evidence, not a blind spot)."""
     exe = _build(tmp_path, "-DHANDOFF_REFERENCE")
-    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    p = _run(exe)
     assert "WARNING: ThreadSanitizer: data race" in p.stderr

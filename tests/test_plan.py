@@ -9,11 +9,11 @@ float running minimum is checked against the sequential loop itself.
 import os
 
 import numpy as np
-import pytest
+from conftest import GOLDEN
 
 from f110qp import capi, workload
 
-REF_CSV = "/root/reference/csv/skirk.csv"
+REF_CSV = os.path.join(GOLDEN, "skirk.csv")  # the reference's csv/skirk.csv, stored as a fixture
 
 
 def test_traj_table_host_oracle_numpy(oracle):
@@ -57,7 +57,6 @@ def test_parse_waypoints_quirks(oracle):
     assert a[5, 2] == np.float32(np.arctan2(np.float64(y[5] - y[4]), np.float64(x[5] - x[4])))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CSV), reason="reference checkout not present")
 def test_parse_reference_csv(oracle):
     """The reference's own global path (csv/skirk.csv, 500 rows of 6 columns)."""
     text = open(REF_CSV).read()

@@ -18,7 +18,7 @@ tail -1 $out/gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { cat $out/smoke.log; exit 4; }
 tail -1 $out/smoke.log
 fi
-b() { n=$1; shift; timeout -k 10 300 python bench.py "$@" > $out/bench_$n.json 2> $out/bench_$n.err || { tail -5 $out/bench_$n.err; exit 5; }
+b() { n=$1; shift; timeout -k 10 300 python bench.py --full "$@" > $out/bench_$n.json 2> $out/bench_$n.err || { tail -5 $out/bench_$n.err; exit 5; }
   python -c "import json;d=json.load(open('$out/bench_$n.json'));c=d['config'];r=d['roofline'];print('$n', '%.3e'%d['value'], '%.1f us'%(d['ms_per_step']*1e3), 'k %.1f us'%(r['kernel_ms_per_launch']*1e3), c['backend'][:12], c.get('lane_segments'), d['dtype'], c['mean_active_set_iters'], c['max_active_set_iters'], 'traffic', r.get('traffic'))"; }
 if [ $part = bench ] || [ $part = all ]; then
 b default
@@ -45,7 +45,7 @@ bash tools/sq_pass.sh c3 --config c3 || exit 9
 timeout -k 10 300 python tools/c2_growth_probe.py > $out/c2_growth_probe.txt 2>&1 || exit 10
 timeout -k 10 300 python tools/recheck_counts.py > $out/recheck_counts.json 2> $out/recheck_counts.err || exit 11
 for c in c2 c4; do  # bench.py starts its two ranks itself (gloo: both on GPU 0)
-  timeout -k 10 300 python bench.py --gpus 2 --config $c --dist-backend gloo --no-cpu --no-latency --steps 20 \
+  timeout -k 10 300 python bench.py --full --gpus 2 --config $c --dist-backend gloo --no-cpu --no-latency --steps 20 \
     2> $out/bench_2rank_$c.err | grep "^{\"metric\"" > $out/bench_2rank_gloo_$c.json || exit 8
 done
 fi

@@ -9,5 +9,5 @@ mkdir -p $out
 export TMPDIR=/tmp
 timeout -s KILL 90 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU \
   SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS --output-format csv -d $out/pmc -o run -- \
-  python3 bench.py --no-cpu --no-latency --steps 10 --warmup 2 "$@" > $out/bench.json 2> $out/err.log || exit 3
+  python3 bench.py --full --no-cpu --no-latency --steps 10 --warmup 2 "$@" > $out/bench.json 2> $out/err.log || exit 3
 echo "sq pass $name done"

@@ -69,7 +69,7 @@ def main():
             "horizon": bench["config"]["horizon"],
             "backend": be,
             "kernel": f"f110qp::{kname} (config {c}: {B} QPs, N={bench['config']['horizon']}, {bench['config']['backend']})",
-            "passes": f"rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate runs of bench.py --no-cpu --config {c} --steps 20",
+            "passes": f"rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate runs of bench.py --full --no-cpu --no-latency --config {c} --steps 20",
             "rocprof_avg_kernel_us": avg_us,
             "bench_hip_event_kernel_us": bench["roofline"]["kernel_ms_per_launch"] * 1e3,
             "fetch_size_kb_per_launch": fetch,
