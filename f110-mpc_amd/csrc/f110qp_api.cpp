@@ -382,18 +382,25 @@ static bool gap_screen(const f110qp_ctx* c, int batch, bool grouped) {
   return c->gap_screen == 1 || batch >= F110QP_GAP_SCREEN_MIN_BATCH;
 }
 
+// The lane back end's variant knobs of a context (the defaults, or the test build's F110QP_LANE_*):
+// one copy for the launch and for the introspection calls, so that both resolve the same kernel.
+static f110qp::LaneWork lane_knobs(const f110qp_ctx* c) {
+  f110qp::LaneWork lw;
+  lw.kmax = c->lane_kmax;
+  lw.mode = c->lane_mode;
+  lw.qpw = c->lane_qpw;
+  lw.rot = c->lane_rot;
+  lw.dref = c->lane_dref;
+  lw.seg = c->lane_seg;
+  lw.seg32 = c->lane_seg32;
+  lw.twin = c->lane_twin;
+  return lw;
+}
+
 // Back end of a call and, for the lane back end (or the gap screen), its workspace.
 static int lane_work(f110qp_ctx* c, int batch, hipStream_t s, int* backend, f110qp::LaneWork* lw,
                      bool grouped = false) {
-  *lw = f110qp::LaneWork();
-  lw->kmax = c->lane_kmax;
-  lw->mode = c->lane_mode;
-  lw->qpw = c->lane_qpw;
-  lw->rot = c->lane_rot;
-  lw->dref = c->lane_dref;
-  lw->seg = c->lane_seg;
-  lw->seg32 = c->lane_seg32;
-  lw->twin = c->lane_twin;
+  *lw = lane_knobs(c);
   *backend = resolve_backend(c, batch, grouped) == F110QP_BACKEND_LANE ? f110qp::BACKEND_LANE
                                                                       : f110qp::BACKEND_WAVE;
   hipError_t e;
@@ -606,17 +613,12 @@ int f110qp_backend_info(f110qp_ctx* c, int batch, int grouped, int* backend, int
                         int* scratch) {
   if (!c) return fail(F110QP_ERR_INVALID, "ctx is NULL");
   if (batch < 1) return fail(F110QP_ERR_INVALID, "batch must be >= 1");
-  f110qp::LaneWork lw;
-  lw.mode = c->lane_mode;
-  lw.qpw = c->lane_qpw;
-  lw.seg = c->lane_seg;
+  const f110qp::LaneWork lw = lane_knobs(c);
   const int be = resolve_backend(c, batch, grouped != 0);
   const bool lane = be == F110QP_BACKEND_LANE;  // gap rows: the box screen's lane solve
   const int segs = lane ? f110qp::lane_segments(c->kp, batch, lw) : 1;
   if (backend) *backend = be;
   if (qps_per_wave) *qps_per_wave = lane ? (segs > 1 ? 64 / segs : f110qp::lane_qps_per_wave(batch, lw.qpw)) : 1;
-  lw.seg32 = c->lane_seg32;
-  lw.twin = c->lane_twin;
   if (scratch)
     *scratch = !lane ? 0 : segs > 1 ? f110qp::lane_seg_scratch(c->kp, batch, segs, lw)
                                     : f110qp::lane_scratch_mode(c->kp, batch, lw);
@@ -629,10 +631,7 @@ int f110qp_lane_segments(f110qp_ctx* c, int batch, int* segments) {
   int be = 0;
   const int rc = f110qp_backend_info(c, batch, 0, &be, nullptr, nullptr);
   if (rc) return rc;
-  f110qp::LaneWork lw;
-  lw.mode = c->lane_mode;
-  lw.qpw = c->lane_qpw;
-  lw.seg = c->lane_seg;
+  const f110qp::LaneWork lw = lane_knobs(c);
   if (be != F110QP_BACKEND_LANE) *segments = 1;
   else *segments = f110qp::lane_segments(c->kp, batch, lw);
   return F110QP_OK;
@@ -644,12 +643,7 @@ int f110qp_lane_starts(f110qp_ctx* c, int batch, int* starts) {
   int segs = 1;
   const int rc = f110qp_lane_segments(c, batch, &segs);
   if (rc) return rc;
-  f110qp::LaneWork lw;
-  lw.mode = c->lane_mode;
-  lw.qpw = c->lane_qpw;
-  lw.seg = c->lane_seg;
-  lw.seg32 = c->lane_seg32;
-  lw.twin = c->lane_twin;
+  const f110qp::LaneWork lw = lane_knobs(c);
   *starts = segs > 1 ? f110qp::lane_seg_starts(c->kp, batch, segs, lw) : 1;
   return F110QP_OK;
 }

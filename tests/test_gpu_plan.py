@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from f110qp import capi, workload
+from test_gpu_xref_stride import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -116,6 +117,7 @@ def test_tick_plan_then_qp_on_device(oracle, cuda):
     ok = dev["status"] == 0
     x0 = torch.from_numpy(dev["x0"][ok]).to(cuda)
     xr = torch.from_numpy(np.ascontiguousarray(dev["x_ref"][ok])).to(cuda)  # whole miniPath (P = 50)
+    xr_n = torch.from_numpy(np.ascontiguousarray(dev["x_ref"][ok][:, :N])).to(cuda)  # its first N points alone
     Bk = int(ok.sum())
     ul = torch.from_numpy(np.tile(np.float32([4.5, 0.0]), (Bk, 1))).to(cuda)  # set_v(4.5) (project.cpp:170)
     uo = torch.empty((Bk, N, 2), device=cuda)
@@ -123,11 +125,15 @@ def test_tick_plan_then_qp_on_device(oracle, cuda):
     st = torch.empty(Bk, dtype=torch.int32, device=cuda)
     outs = []
     for be in (capi.BACKEND_WAVE, capi.BACKEND_LANE):  # x_ref_points = 50 on both back ends
-        s = capi.Solver(capi.default_config(N, x_ref_points=50, backend=be))
-        s.solve_dev(x0, ul, xr, None, uo, xo, st)
-        torch.cuda.synchronize()
-        s.close()
-        outs.append((uo.cpu().numpy().astype(np.float64), st.cpu().numpy()))
+        raw = []
+        for pts, ref in ((50, xr), (0, xr_n)):
+            s = capi.Solver(capi.default_config(N, x_ref_points=pts, backend=be))
+            s.solve_dev(x0, ul, ref, None, uo, xo, st)
+            torch.cuda.synchronize()
+            s.close()
+            raw.append((uo.cpu().numpy(), xo.cpu().numpy(), st.cpu().numpy()))
+        same_bits(raw[0], raw[1], f"back end {be}: miniPath rows against compact rows")
+        outs.append((raw[0][0].astype(np.float64), raw[0][2], raw[0][1].astype(np.float64)))
     x0r, xrr = [], []
     for b in np.nonzero(ok)[0]:
         g, off = oracle.fill_occ_grid(pp, sc["pose"][b], sc["ranges"][b], sc["angle_min"], sc["angle_inc"],
@@ -137,7 +143,9 @@ def test_tick_plan_then_qp_on_device(oracle, cuda):
         xrr.append(r["x_ref"][:N])
     ur, xref_r, sr = oracle.solve_batch(oracle.params(N), np.array(x0r), np.tile(np.float32([4.5, 0.0]), (Bk, 1)),
                                         np.array(xrr))
-    for u, stn in outs:
+    for u, stn, x in outs:
         assert (stn == sr).all()
         err = np.abs(u - ur).max(axis=(1, 2)) / np.maximum(1.0, np.abs(ur).max(axis=(1, 2)))
         assert err.max() <= 1e-4
+        errx = np.abs(x - xref_r).max(axis=(1, 2)) / np.maximum(1.0, np.abs(xref_r).max(axis=(1, 2)))
+        assert errx.max() <= 1e-4
