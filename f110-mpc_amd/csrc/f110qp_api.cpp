@@ -486,16 +486,21 @@ int f110qp_solve_batch_dev(f110qp_ctx* c, int batch, const float* x0, const floa
   return f110qp_solve_batch_ex_dev(c, batch, x0, ul, xr, hs, uo, xo, st, it, nullptr, nullptr, stream);
 }
 
+}  // extern "C"
+
 // device-pointer solve; sync: wait for it before returning (the completion word where the call's
-// kernel raises it, else the stream)
-static int solve_dev(f110qp_ctx* c, int batch, const float* x0, const float* ul, const float* xr,
+// kernel raises it, else the stream). IN = float, or double for the *_dbl entry points: the kernels
+// read the doubles themselves, and such a call neither reads nor updates the warm-start state (its
+// 16-byte slot key holds float bits).
+template <typename IN>
+static int solve_dev(f110qp_ctx* c, int batch, const IN* x0, const IN* ul, const IN* xr,
                      const float* hs, float* uo, float* xo, int* st, int* it, double* obj,
                      double* cost, hipStream_t s, bool sync) {
   int rc = check_batch_args(c, batch, x0, ul, xr, hs, uo, xo, st);
   if (rc || batch == 0) return rc;
   const float* h = (c->cfg.gap_mode == F110QP_GAP_ACTIVE) ? hs : nullptr;
   f110qp::WarmState ws;
-  rc = warm_state(c, batch, s, &ws);
+  if (sizeof(IN) == 4) rc = warm_state(c, batch, s, &ws);
   if (rc) return rc;
   int backend;
   f110qp::LaneWork lw;
@@ -511,6 +516,20 @@ static int solve_dev(f110qp_ctx* c, int batch, const float* x0, const float* ul,
   return sync ? wait_done(c, s, armed) : F110QP_OK;
 }
 
+extern "C" {
+
+int f110qp_solve_batch_dev_dbl(f110qp_ctx* c, int batch, const double* x0, const double* ul,
+                               const double* xr, const float* hs, float* uo, float* xo, int* st,
+                               int* it, double* obj, double* cost, void* stream) {
+  return solve_dev(c, batch, x0, ul, xr, hs, uo, xo, st, it, obj, cost, (hipStream_t)stream, false);
+}
+
+int f110qp_solve_batch_dev_sync_dbl(f110qp_ctx* c, int batch, const double* x0, const double* ul,
+                                    const double* xr, const float* hs, float* uo, float* xo,
+                                    int* st, int* it, void* stream) {
+  return solve_dev(c, batch, x0, ul, xr, hs, uo, xo, st, it, nullptr, nullptr, (hipStream_t)stream, true);
+}
+
 int f110qp_solve_batch_dev_sync(f110qp_ctx* c, int batch, const float* x0, const float* ul,
                                 const float* xr, const float* hs, float* uo, float* xo, int* st,
                                 int* it, void* stream) {
@@ -524,11 +543,14 @@ int f110qp_solve_batch_ex_dev(f110qp_ctx* c, int batch, const float* x0, const f
 }
 
 // Per-group W cache of a grouped call (grows only; every call re-fills the slots it uses).
+// key_words: unsigned words per group key (f110qp::kGroupKeyWords: 4 for float inputs, 8 for double
+// ones, whose key holds all 64 bits of theta0, v and delta).
 static int group_state(f110qp_ctx* c, const int* group, int num_groups, f110qp::WarmState* gws,
-                       int** leader) {
+                       int** leader, int key_words) {
   const size_t G = (size_t)num_groups, nu = 2 * (size_t)c->cfg.horizon;
   hipError_t e;
-  if ((e = c->gW.ensure(G * nu * nu * 4)) || (e = c->gkey.ensure(G * 16)) || (e = c->glead.ensure(G * 4)))
+  if ((e = c->gW.ensure(G * nu * nu * 4)) || (e = c->gkey.ensure(G * 4 * (size_t)key_words)) ||
+      (e = c->glead.ensure(G * 4)))
     return hip_fail(e, "hipMalloc group state");
   *gws = f110qp::WarmState();
   gws->W = (float*)c->gW.p;
@@ -553,17 +575,19 @@ int f110qp_solve_grouped_dev(f110qp_ctx* c, int batch, const float* x0, const fl
                                      nullptr, nullptr, stream);
 }
 
-int f110qp_solve_grouped_ex_dev(f110qp_ctx* c, int batch, const float* x0, const float* ul,
-                                const float* xr, const float* hs, const int* group, int num_groups,
-                                float* uo, float* xo, int* st, int* it, double* obj, double* cost,
-                                void* stream) {
+}  // extern "C"
+
+template <typename IN>
+static int solve_grouped_dev(f110qp_ctx* c, int batch, const IN* x0, const IN* ul, const IN* xr,
+                             const float* hs, const int* group, int num_groups, float* uo, float* xo,
+                             int* st, int* it, double* obj, double* cost, void* stream) {
   int rc = check_batch_args(c, batch, x0, ul, xr, hs, uo, xo, st);
   if (rc || batch == 0) return rc;
   if ((rc = check_groups(group, num_groups, batch))) return rc;
   const float* h = (c->cfg.gap_mode == F110QP_GAP_ACTIVE) ? hs : nullptr;
   f110qp::WarmState gws;
   int* leader;
-  if ((rc = group_state(c, group, num_groups, &gws, &leader))) return rc;
+  if ((rc = group_state(c, group, num_groups, &gws, &leader, f110qp::kGroupKeyWords<IN>))) return rc;
   int backend;
   f110qp::LaneWork lw;
   if ((rc = lane_work(c, batch, (hipStream_t)stream, &backend, &lw, true))) return rc;
@@ -576,9 +600,42 @@ int f110qp_solve_grouped_ex_dev(f110qp_ctx* c, int batch, const float* x0, const
   return F110QP_OK;
 }
 
-static int solve_host(f110qp_ctx* c, int batch, const float* x0, const float* ul, const float* xr,
+template <typename IN>
+static int solve_host(f110qp_ctx* c, int batch, const IN* x0, const IN* ul, const IN* xr,
                       const float* hs, const int* group, int num_groups, float* uo, float* xo,
                       int* st, int* it, double* obj, double* cost);
+
+extern "C" {
+
+int f110qp_solve_grouped_ex_dev(f110qp_ctx* c, int batch, const float* x0, const float* ul,
+                                const float* xr, const float* hs, const int* group, int num_groups,
+                                float* uo, float* xo, int* st, int* it, double* obj, double* cost,
+                                void* stream) {
+  return solve_grouped_dev(c, batch, x0, ul, xr, hs, group, num_groups, uo, xo, st, it, obj, cost, stream);
+}
+
+int f110qp_solve_grouped_dev_dbl(f110qp_ctx* c, int batch, const double* x0, const double* ul,
+                                 const double* xr, const float* hs, const int* group,
+                                 int num_groups, float* uo, float* xo, int* st, int* it,
+                                 double* obj, double* cost, void* stream) {
+  return solve_grouped_dev(c, batch, x0, ul, xr, hs, group, num_groups, uo, xo, st, it, obj, cost, stream);
+}
+
+int f110qp_solve_batch_dbl(f110qp_ctx* c, int batch, const double* x0, const double* ul,
+                           const double* xr, const float* hs, float* uo, float* xo, int* st,
+                           int* it, double* obj, double* cost) {
+  return solve_host(c, batch, x0, ul, xr, hs, nullptr, 0, uo, xo, st, it, obj, cost);
+}
+
+int f110qp_solve_grouped_dbl(f110qp_ctx* c, int batch, const double* x0, const double* ul,
+                             const double* xr, const float* hs, const int* group, int num_groups,
+                             float* uo, float* xo, int* st, int* it, double* obj, double* cost) {
+  if (batch > 0) {
+    const int rc = check_groups(group, num_groups, batch);
+    if (rc) return rc;
+  }
+  return solve_host(c, batch, x0, ul, xr, hs, group, num_groups, uo, xo, st, it, obj, cost);
+}
 
 int f110qp_solve_batch(f110qp_ctx* c, int batch, const float* x0, const float* ul,
                        const float* xr, const float* hs, float* uo, float* xo, int* st,
@@ -669,7 +726,8 @@ int f110qp_select_dev(int batch, const int* group, int num_groups, const double*
 
 }  // extern "C"
 
-static int solve_host(f110qp_ctx* c, int batch, const float* x0, const float* ul, const float* xr,
+template <typename IN>
+static int solve_host(f110qp_ctx* c, int batch, const IN* x0, const IN* ul, const IN* xr,
                       const float* hs, const int* group, int num_groups, float* uo, float* xo,
                       int* st, int* it, double* obj, double* cost) {
   int rc = check_batch_args(c, batch, x0, ul, xr, hs, uo, xo, st);
@@ -684,9 +742,11 @@ static int solve_host(f110qp_ctx* c, int batch, const float* x0, const float* ul
   const bool gap = c->cfg.gap_mode == F110QP_GAP_ACTIVE;
   const size_t B = (size_t)batch;
   const size_t S = (size_t)c->kp.xr_stride;
-  const size_t s_x0 = B * 3 * 4, s_ul = B * 2 * 4, s_xr = B * S * 3 * 4, s_hs = B * 6 * 4;
+  const size_t s_x0 = B * 3 * sizeof(IN), s_ul = B * 2 * sizeof(IN), s_xr = B * S * 3 * sizeof(IN), s_hs = B * 6 * 4;
   const size_t s_uo = B * N * 2 * 4, s_xo = B * (N + 1) * 3 * 4, s_st = B * 4;
-  // packed layouts (every size a multiple of 4 bytes): in = x0 | u_lin | x_ref | halfspace,
+  // packed layouts (every size a multiple of 4 bytes; with double inputs the three input fields are
+  // multiples of 8 bytes from an aligned base, so the doubles stay 8-byte aligned and the float
+  // half-spaces follow them): in = x0 | u_lin | x_ref | halfspace,
   // out = u | x | status | iters | obj | cost (the doubles 8-byte aligned)
   const size_t o_ul = s_x0, o_xr = o_ul + s_ul, o_hs = o_xr + s_xr, in_bytes = o_hs + (gap ? s_hs : 0);
   const size_t o_xo = s_uo, o_st = o_xo + s_xo, o_it = o_st + s_st;
@@ -723,22 +783,22 @@ static int solve_host(f110qp_ctx* c, int batch, const float* x0, const float* ul
       return hip_fail(e, "group ids H2D");
     f110qp::WarmState gws;
     int* leader;
-    if ((rc = group_state(c, (const int*)c->dgrp.p, num_groups, &gws, &leader))) return rc;
+    if ((rc = group_state(c, (const int*)c->dgrp.p, num_groups, &gws, &leader, f110qp::kGroupKeyWords<IN>))) return rc;
     if ((rc = lane_work(c, batch, s, &backend, &lw, true))) return rc;
-    e = f110qp::launch_solve_grouped(c->kp, batch, (const float*)di, (const float*)(di + o_ul),
-                                     (const float*)(di + o_xr), gap ? (const float*)(di + o_hs) : nullptr,
+    e = f110qp::launch_solve_grouped(c->kp, batch, (const IN*)di, (const IN*)(di + o_ul),
+                                     (const IN*)(di + o_xr), gap ? (const float*)(di + o_hs) : nullptr,
                                      (float*)dq, (float*)(dq + o_xo), (int*)(dq + o_st),
                                      (int*)(dq + o_it), gws, leader, backend, lw, oo, s);
   } else {
     f110qp::WarmState ws;
-    if ((rc = warm_state(c, batch, s, &ws))) return rc;
+    if (sizeof(IN) == 4 && (rc = warm_state(c, batch, s, &ws))) return rc;  // (double inputs: cold)
     if ((rc = lane_work(c, batch, s, &backend, &lw))) return rc;
     // zero-copy: the kernel's stores are the outputs the host reads, so its completion word ends
     // the wait (staged batches wait for the D2H copy on the stream)
     if (zc && (rc = arm_signal(c, batch, backend, gap ? (const float*)(di + o_hs) : nullptr, lw, s, &oo, &armed)))
       return rc;
-    e = f110qp::launch_solve(c->kp, batch, (const float*)di, (const float*)(di + o_ul),
-                             (const float*)(di + o_xr), gap ? (const float*)(di + o_hs) : nullptr,
+    e = f110qp::launch_solve(c->kp, batch, (const IN*)di, (const IN*)(di + o_ul),
+                             (const IN*)(di + o_xr), gap ? (const float*)(di + o_hs) : nullptr,
                              (float*)dq, (float*)(dq + o_xo), (int*)(dq + o_st), (int*)(dq + o_it),
                              ws, backend, lw, oo, s);
   }

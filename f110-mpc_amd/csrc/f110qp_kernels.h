@@ -172,33 +172,43 @@ int lane_seg_starts(const KParams& P, int B, int S, const LaneWork& lw);
 // fp64 re-check of the gap-row QPs the wave kernel did not report SOLVED (its certificate
 // failed, or GI ended infeasible / at its cap): the fp64 Goldfarb-Idnani of gi64_kernel.h over
 // the device-side list (count, list: HandLayout c_rc / rc), every listed QP, its outputs rewritten.
-hipError_t launch_gap_recheck(const KParams& P, int B, const float* x0, const float* u_lin,
-                              const float* x_ref, const float* hs, float* u_out, float* x_out,
+template <typename IN>
+hipError_t launch_gap_recheck(const KParams& P, int B, const IN* x0, const IN* u_lin,
+                              const IN* x_ref, const float* hs, float* u_out, float* x_out,
                               int* status, int* iters, const int* list, const int* count,
                               const ObjOut& oo, hipStream_t stream);
 
 enum Backend { BACKEND_WAVE = 0, BACKEND_LANE = 1 };
 
+// IN in the launch functions below: the input scalar of x0, u_lin and x_ref, float or double (the
+// *_dbl entry points of include/f110qp.h); both are instantiated in the kernels' objects. The
+// per-group key of a grouped call (gws.key) holds kGroupKeyWords<IN> unsigned words per group.
+template <typename IN>
+constexpr int kGroupKeyWords = sizeof(IN) == 8 ? 8 : 4;
+
 // Solve B QPs. hs == nullptr -> box-only kernels (gap rows inactive). backend LANE: box rows, the
 // lane-per-QP Riccati/PDAS kernel alone (one launch, no hand-over). Gap rows: lw.screen, the box
 // solve on the lane kernel, GI for the QPs whose box optimum violates a gap row; else GI for every
 // QP; then the fp64 re-check of what GI did not certify.
-hipError_t launch_solve(const KParams& P, int B, const float* x0, const float* u_lin,
-                        const float* x_ref, const float* hs, float* u_out, float* x_out,
+template <typename IN>
+hipError_t launch_solve(const KParams& P, int B, const IN* x0, const IN* u_lin,
+                        const IN* x_ref, const float* hs, float* u_out, float* x_out,
                         int* status, int* iters, const WarmState& warm, int backend,
                         const LaneWork& lw, const ObjOut& oo, hipStream_t stream);
 
 // The lane-per-QP kernel alone (box rows).
-hipError_t launch_lane(const KParams& P, int B, const float* x0, const float* u_lin,
-                       const float* x_ref, float* u_out, float* x_out, int* status, int* iters,
+template <typename IN>
+hipError_t launch_lane(const KParams& P, int B, const IN* x0, const IN* u_lin,
+                       const IN* x_ref, float* u_out, float* x_out, int* status, int* iters,
                        const WarmState& warm, const LaneWork& lw, const ObjOut& oo,
                        hipStream_t stream);
 
 // Grouped solve: leader (smallest member) of every group, W = H^-1 per group from its leader,
 // then the solve (wave back end; the lane back end has no factor to share and ignores groups).
 // ws.W/ws.key hold ngroups slots, leader ngroups ints.
-hipError_t launch_solve_grouped(const KParams& P, int B, const float* x0, const float* u_lin,
-                                const float* x_ref, const float* hs, float* u_out, float* x_out,
+template <typename IN>
+hipError_t launch_solve_grouped(const KParams& P, int B, const IN* x0, const IN* u_lin,
+                                const IN* x_ref, const float* hs, float* u_out, float* x_out,
                                 int* status, int* iters, const WarmState& gws, int* leader,
                                 int backend, const LaneWork& lw, const ObjOut& oo,
                                 hipStream_t stream);

@@ -9,25 +9,28 @@
 
 namespace f110qp {
 
-template <int NUM, bool GAP>
-hipError_t launch_t(const KParams& P, int B, const float* x0, const float* ul, const float* xr,
+// IN below: the input scalar of x0 / u_lin / x_ref, float or double (the *_dbl entry points of
+// include/f110qp.h). The host dispatch is one template over it; the kernels' IN instantiations are
+// objects of their own (Makefile).
+template <int NUM, bool GAP, typename IN>
+hipError_t launch_t(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
                     const float* hs, float* uo, float* xo, int* st, int* its, double* Hd,
                     double* gd, const WarmState& ws, const int* list, const int* count, int grid,
                     const ObjOut& oo, hipStream_t s);  // solve_inst.hip
-template <int NUM, bool GAP>
-hipError_t launch_prep_t(const KParams& P, int B, const float* x0, const float* ul,
-                         const float* xr, const float* hs, const WarmState& ws, const int* leader,
+template <int NUM, bool GAP, typename IN>
+hipError_t launch_prep_t(const KParams& P, int B, const IN* x0, const IN* ul,
+                         const IN* xr, const float* hs, const WarmState& ws, const int* leader,
                          hipStream_t s);  // solve_inst.hip
 
-template <bool GAP>
-static hipError_t launch_g(const KParams& P, int B, const float* x0, const float* ul,
-                           const float* xr, const float* hs, float* uo, float* xo, int* st,
+template <bool GAP, typename IN>
+static hipError_t launch_g(const KParams& P, int B, const IN* x0, const IN* ul,
+                           const IN* xr, const float* hs, float* uo, float* xo, int* st,
                            int* its, double* Hd, double* gd, const WarmState& ws, const int* list,
                            const int* count, int grid, const ObjOut& oo, hipStream_t s) {
   const int NU = 2 * P.N;
 #define F110QP_CASE(NUM)                                                                    \
   if (NU <= NUM)                                                                            \
-    return launch_t<NUM, GAP>(P, B, x0, ul, xr, hs, uo, xo, st, its, Hd, gd, ws, list, count, \
+    return launch_t<NUM, GAP, IN>(P, B, x0, ul, xr, hs, uo, xo, st, its, Hd, gd, ws, list, count, \
                               grid, oo, s);
   F110QP_CASE(8) F110QP_CASE(16) F110QP_CASE(24) F110QP_CASE(32) F110QP_CASE(40)
   F110QP_CASE(48) F110QP_CASE(56) F110QP_CASE(64) F110QP_CASE(80) F110QP_CASE(96)
@@ -45,8 +48,9 @@ static hipError_t launch_g(const KParams& P, int B, const float* x0, const float
 // kernel serves the sequential lane kernel's batches (from stored float x); the segmented kernel
 // evaluates the same test in its output sweep, in fp64. Output: the GI priority of each QP (0: the
 // box optimum stands, else 1 + the violated rows; 1 for the stage-0 / status cases).
+template <typename IN>
 __global__ __launch_bounds__(256) void gap_screen_kernel(const int B, const int N,
-                                                         const float* __restrict__ x0g,
+                                                         const IN* __restrict__ x0g,
                                                          const float* __restrict__ hsg,
                                                          const float* __restrict__ xo,
                                                          const int* __restrict__ status,
@@ -171,8 +175,9 @@ bool launch_signals(const KParams& P, int B, int backend, const float* hs, const
   return grid <= kSignalMaxGrid;
 }
 
-hipError_t launch_solve(const KParams& P, int B, const float* x0, const float* ul,
-                        const float* xr, const float* hs, float* uo, float* xo, int* st,
+template <typename IN>
+hipError_t launch_solve(const KParams& P, int B, const IN* x0, const IN* ul,
+                        const IN* xr, const float* hs, float* uo, float* xo, int* st,
                         int* its, const WarmState& ws, int backend, const LaneWork& lw,
                         const ObjOut& oo_in, hipStream_t s) {
   if (B <= 0) return hipSuccess;
@@ -206,7 +211,7 @@ hipError_t launch_solve(const KParams& P, int B, const float* x0, const float* u
       }
       if ((e = launch_lane(P, B, x0, ul, xr, uo, xo, st, its, WarmState(), lw, so, s)) != hipSuccess) return e;
       if (!fused) {
-        hipLaunchKernelGGL(gap_screen_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, P.N, x0, hs, xo, st, H.prio);
+        hipLaunchKernelGGL(gap_screen_kernel<IN>, dim3((B + 255) / 256), dim3(256), 0, s, B, P.N, x0, hs, xo, st, H.prio);
         if ((e = hipGetLastError()) != hipSuccess) return e;
       }
       hipLaunchKernelGGL(gap_order_kernel, dim3(1), dim3(1024), 0, s, B, H.prio, H.c_list, H.list, H.c_rc);
@@ -225,13 +230,13 @@ hipError_t launch_solve(const KParams& P, int B, const float* x0, const float* u
                          nullptr, B, oo, s);
 }
 
-template <bool GAP>
-static hipError_t launch_prep_g(const KParams& P, int B, const float* x0, const float* ul,
-                                const float* xr, const float* hs, const WarmState& ws,
+template <bool GAP, typename IN>
+static hipError_t launch_prep_g(const KParams& P, int B, const IN* x0, const IN* ul,
+                                const IN* xr, const float* hs, const WarmState& ws,
                                 const int* leader, hipStream_t s) {
   const int NU = 2 * P.N;
 #define F110QP_CASE(NUM) \
-  if (NU <= NUM) return launch_prep_t<NUM, GAP>(P, B, x0, ul, xr, hs, ws, leader, s);
+  if (NU <= NUM) return launch_prep_t<NUM, GAP, IN>(P, B, x0, ul, xr, hs, ws, leader, s);
   F110QP_CASE(8) F110QP_CASE(16) F110QP_CASE(24) F110QP_CASE(32) F110QP_CASE(40)
   F110QP_CASE(48) F110QP_CASE(56) F110QP_CASE(64) F110QP_CASE(80) F110QP_CASE(96)
 #undef F110QP_CASE
@@ -248,8 +253,9 @@ __global__ __launch_bounds__(256) void group_mark_kernel(const int B, const int*
   }
 }
 
-hipError_t launch_solve_grouped(const KParams& P, int B, const float* x0, const float* ul,
-                                const float* xr, const float* hs, float* uo, float* xo, int* st,
+template <typename IN>
+hipError_t launch_solve_grouped(const KParams& P, int B, const IN* x0, const IN* ul,
+                                const IN* xr, const float* hs, float* uo, float* xo, int* st,
                                 int* its, const WarmState& gws, int* leader, int backend,
                                 const LaneWork& lw, const ObjOut& oo, hipStream_t s) {
   if (B <= 0) return hipSuccess;
@@ -276,6 +282,18 @@ hipError_t launch_solve_grouped(const KParams& P, int B, const float* x0, const 
   }
   return launch_g<false>(P, B, x0, ul, xr, hs, uo, xo, st, its, nullptr, nullptr, gws, nullptr, nullptr, B, oo, s);
 }
+
+#define F110QP_SOLVE_LAUNCH_INST(IN)                                                               \
+  template hipError_t launch_solve<IN>(const KParams&, int, const IN*, const IN*, const IN*,       \
+                                       const float*, float*, float*, int*, int*, const WarmState&, \
+                                       int, const LaneWork&, const ObjOut&, hipStream_t);          \
+  template hipError_t launch_solve_grouped<IN>(const KParams&, int, const IN*, const IN*,          \
+                                               const IN*, const float*, float*, float*, int*,      \
+                                               int*, const WarmState&, int*, int, const LaneWork&, \
+                                               const ObjOut&, hipStream_t);
+F110QP_SOLVE_LAUNCH_INST(float)
+F110QP_SOLVE_LAUNCH_INST(double)
+#undef F110QP_SOLVE_LAUNCH_INST
 
 hipError_t launch_condense_debug(const KParams& P, int B, const float* x0, const float* ul,
                                  const float* xr, double* Hd, double* gd, hipStream_t s) {

@@ -10,10 +10,19 @@
 namespace f110qp {
 
 #if defined(F110QP_GI64_NUM) || defined(F110QP_GI64_ALL)
-#define F110QP_GI64_INSTANTIATE(NUM)                                                                   \
-  template hipError_t launch_gi64_t<NUM>(const KParams&, int, const float*, const float*, const float*, \
-                                         const float*, float*, float*, int*, int*, const int*,          \
-                                         const int*, const ObjOut&, hipStream_t);
+// F110QP_IN: the input scalar of x0 / u_lin / x_ref (float; double in the *_dbl objects)
+#ifndef F110QP_IN
+#define F110QP_IN float
+#endif
+#define F110QP_GI64_INSTANTIATE_IN(NUM, IN)                                                          \
+  template hipError_t launch_gi64_t<NUM, IN>(const KParams&, int, const IN*, const IN*, const IN*,   \
+                                             const float*, float*, float*, int*, int*, const int*,   \
+                                             const int*, const ObjOut&, hipStream_t);
+#ifdef F110QP_GI64_ALL
+#define F110QP_GI64_INSTANTIATE(NUM) F110QP_GI64_INSTANTIATE_IN(NUM, float) F110QP_GI64_INSTANTIATE_IN(NUM, double)
+#else
+#define F110QP_GI64_INSTANTIATE(NUM) F110QP_GI64_INSTANTIATE_IN(NUM, F110QP_IN)
+#endif
 #ifdef F110QP_GI64_ALL
 F110QP_GI64_INSTANTIATE(8) F110QP_GI64_INSTANTIATE(16) F110QP_GI64_INSTANTIATE(24) F110QP_GI64_INSTANTIATE(32)
 F110QP_GI64_INSTANTIATE(40) F110QP_GI64_INSTANTIATE(48) F110QP_GI64_INSTANTIATE(56) F110QP_GI64_INSTANTIATE(64)
@@ -35,12 +44,13 @@ F110QP_GI64_INSTANTIATE(F110QP_GI64_NUM)
 #endif
 constexpr int kRecheckGrid = F110QP_RECHECK_GRID;
 
-template <int NUM>
-hipError_t launch_gi64_t(const KParams& P, int grid, const float* x0, const float* ul, const float* xr,
+template <int NUM, typename IN>
+hipError_t launch_gi64_t(const KParams& P, int grid, const IN* x0, const IN* ul, const IN* xr,
                          const float* hs, float* uo, float* xo, int* st, int* its, const int* list,
-                         const int* count, const ObjOut& oo, hipStream_t s);  // one object per NUM
+                         const int* count, const ObjOut& oo, hipStream_t s);  // one object per NUM and IN
 
-hipError_t launch_gap_recheck(const KParams& P, int B, const float* x0, const float* ul, const float* xr,
+template <typename IN>
+hipError_t launch_gap_recheck(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
                               const float* hs, float* uo, float* xo, int* st, int* its, const int* list,
                               const int* count, const ObjOut& oo, hipStream_t s) {
   if (B <= 0) return hipSuccess;
@@ -50,12 +60,19 @@ hipError_t launch_gap_recheck(const KParams& P, int B, const float* x0, const fl
   o.rc_list = nullptr;
   const int NU = 2 * P.N;
 #define F110QP_CASE(NUM) \
-  if (NU <= NUM) return launch_gi64_t<NUM>(P, grid, x0, ul, xr, hs, uo, xo, st, its, list, count, o, s);
+  if (NU <= NUM) return launch_gi64_t<NUM, IN>(P, grid, x0, ul, xr, hs, uo, xo, st, its, list, count, o, s);
   F110QP_CASE(8) F110QP_CASE(16) F110QP_CASE(24) F110QP_CASE(32) F110QP_CASE(40)
   F110QP_CASE(48) F110QP_CASE(56) F110QP_CASE(64) F110QP_CASE(80) F110QP_CASE(96)
 #undef F110QP_CASE
   return hipErrorInvalidValue;
 }
+#define F110QP_RECHECK_INST(IN)                                                                        \
+  template hipError_t launch_gap_recheck<IN>(const KParams&, int, const IN*, const IN*, const IN*,     \
+                                             const float*, float*, float*, int*, int*, const int*,     \
+                                             const int*, const ObjOut&, hipStream_t);
+F110QP_RECHECK_INST(float)
+F110QP_RECHECK_INST(double)
+#undef F110QP_RECHECK_INST
 #endif
 
 }  // namespace f110qp

@@ -104,23 +104,25 @@ __device__ __forceinline__ void adjoint_xy(const Lin& M, int lane, double (&ex)[
   }
 }
 
-template <int NUM>
-__device__ void gi64_qp(G64Smem<NUM>& sm, const int b, const KParams& P, const float* __restrict__ x0g,
-                        const float* __restrict__ ulg, const float* __restrict__ xrg,
+// IN = float or double: the scalar of x0, u_lin and x_ref in global memory (the *_dbl entry points of
+// include/f110qp.h); each is widened to fp64 at its load, the code past the loads is the same.
+template <int NUM, typename IN = float>
+__device__ void gi64_qp(G64Smem<NUM>& sm, const int b, const KParams& P, const IN* __restrict__ x0g,
+                        const IN* __restrict__ ulg, const IN* __restrict__ xrg,
                         const float* __restrict__ hsg, float* __restrict__ uout, float* __restrict__ xout,
                         int* __restrict__ status_out, int* __restrict__ iters_out, const ObjOut& oo) {
   constexpr int R = (NUM + 63) / 64;
   const int t = threadIdx.x;
   const int N = P.N;
   const int NU = 2 * N;
-  const float fX0 = x0g[3 * b + 0], fY0 = x0g[3 * b + 1], fTH0 = x0g[3 * b + 2];
-  const float ul0 = ulg[2 * b + 0], ul1 = ulg[2 * b + 1];
+  const IN fX0 = x0g[3 * b + 0], fY0 = x0g[3 * b + 1], fTH0 = x0g[3 * b + 2];
+  const IN ul0 = ulg[2 * b + 0], ul1 = ulg[2 * b + 1];
   const Lin M0 = linearize((double)fTH0, (double)ul0, (double)ul1, P.dt);
   // the exact verdicts (non-finite data, a violated stage-0 row) need no solve: uniform per QP,
   // so the whole workgroup skips the inverse
   bool early;
   {
-    const float* xq = xrg + (size_t)b * P.xr_stride * 3;
+    const IN* xq = xrg + (size_t)b * P.xr_stride * 3;
     bool nf = !(isfinite(fX0) && isfinite(fY0) && isfinite(fTH0) && isfinite(ul0) && isfinite(ul1));
     for (int i = 0; i < 3 * N; i++) nf = nf || !isfinite(xq[i]);
     const float* h6e = hsg + 6 * b;
@@ -228,9 +230,9 @@ __device__ void gi64_qp(G64Smem<NUM>& sm, const int b, const KParams& P, const f
   }
   const double X0 = (double)fX0, Y0 = (double)fY0;
   bool bad = !(isfinite(fX0) && isfinite(fY0) && isfinite(fTH0) && isfinite(ul0) && isfinite(ul1));
-  float x00[3] = {0.f, 0.f, 0.f};
+  IN x00[3] = {0, 0, 0};
   if (lane == 0) {
-    const float* xq = xrg + (size_t)b * P.xr_stride * 3;
+    const IN* xq = xrg + (size_t)b * P.xr_stride * 3;
     x00[0] = xq[0]; x00[1] = xq[1]; x00[2] = xq[2];
     bad = bad || !(isfinite(x00[0]) && isfinite(x00[1]) && isfinite(x00[2]));
   }
@@ -240,8 +242,8 @@ __device__ void gi64_qp(G64Smem<NUM>& sm, const int b, const KParams& P, const f
     rxd[r] = 0.0; ryd[r] = 0.0; rthd[r] = 0.0;
     if (valid[r]) {
       const int ri = (kk[r] + 1 < N) ? kk[r] + 1 : N - 1;  // terminal stage reuses x_ref[N-1] (mpc.cpp:228)
-      const float* xr = xrg + ((size_t)b * P.xr_stride + ri) * 3;
-      const float f0 = xr[0], f1 = xr[1], f2 = xr[2];
+      const IN* xr = xrg + ((size_t)b * P.xr_stride + ri) * 3;
+      const IN f0 = xr[0], f1 = xr[1], f2 = xr[2];
       bad = bad || !(isfinite(f0) && isfinite(f1) && isfinite(f2));
       rxd[r] = (double)f0 - X0;
       ryd[r] = (double)f1 - Y0;
@@ -679,9 +681,9 @@ __device__ void gi64_qp(G64Smem<NUM>& sm, const int b, const KParams& P, const f
     const float nanv = __int_as_float(0x7fc00000);
     float* xo = xout + (size_t)b * 3 * (N + 1);
     if (lane == 0) {
-      xo[0] = ok ? fX0 : nanv;
-      xo[1] = ok ? fY0 : nanv;
-      xo[2] = ok ? fTH0 : nanv;
+      xo[0] = ok ? (float)fX0 : nanv;
+      xo[1] = ok ? (float)fY0 : nanv;
+      xo[2] = ok ? (float)fTH0 : nanv;
     }
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -733,10 +735,10 @@ __device__ void gi64_qp(G64Smem<NUM>& sm, const int b, const KParams& P, const f
 // One workgroup per list item, a grid-stride loop over the device-side count: every listed QP is
 // re-checked whatever the grid. Each item ends at a workgroup barrier that the waves other than
 // wave 0 wait at while wave 0 runs GI.
-template <int NUM>
-__global__ __launch_bounds__(64 * ((2 * NUM + 63) / 64)) void gi64_kernel(const KParams P, const float* __restrict__ x0g,
-                                                                   const float* __restrict__ ulg,
-                                                                   const float* __restrict__ xrg,
+template <int NUM, typename IN = float>
+__global__ __launch_bounds__(64 * ((2 * NUM + 63) / 64)) void gi64_kernel(const KParams P, const IN* __restrict__ x0g,
+                                                                   const IN* __restrict__ ulg,
+                                                                   const IN* __restrict__ xrg,
                                                                    const float* __restrict__ hsg,
                                                                    float* __restrict__ uout,
                                                                    float* __restrict__ xout,
@@ -749,17 +751,17 @@ __global__ __launch_bounds__(64 * ((2 * NUM + 63) / 64)) void gi64_kernel(const 
   const int n = __builtin_amdgcn_readfirstlane(*count);
   for (int item = blockIdx.x; item < n; item += gridDim.x) {
     const int b = __builtin_amdgcn_readfirstlane(list[item]);
-    gi64_qp<NUM>(sm, b, P, x0g, ulg, xrg, hsg, uout, xout, status_out, iters_out, oo);
+    gi64_qp<NUM, IN>(sm, b, P, x0g, ulg, xrg, hsg, uout, xout, status_out, iters_out, oo);
     __syncthreads();
   }
   signal_call_done(oo, (int)blockIdx.x < n);  // the completion word of a synchronous gap-row call
 }
 
-template <int NUM>
-hipError_t launch_gi64_t(const KParams& P, int grid, const float* x0, const float* ul, const float* xr,
+template <int NUM, typename IN>
+hipError_t launch_gi64_t(const KParams& P, int grid, const IN* x0, const IN* ul, const IN* xr,
                          const float* hs, float* uo, float* xo, int* st, int* its, const int* list,
                          const int* count, const ObjOut& oo, hipStream_t s) {
-  hipLaunchKernelGGL((gi64_kernel<NUM>), dim3(grid), dim3(64 * ((2 * NUM + 63) / 64)), 0, s, P, x0, ul, xr, hs, uo,
+  hipLaunchKernelGGL((gi64_kernel<NUM, IN>), dim3(grid), dim3(64 * ((2 * NUM + 63) / 64)), 0, s, P, x0, ul, xr, hs, uo,
                      xo, st, its, list, count, oo);
   return hipGetLastError();
 }

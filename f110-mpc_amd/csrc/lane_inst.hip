@@ -4,6 +4,11 @@
 // and in the general one, with fp64 or float references in LDS (DREF).
 #include "lane_kernel.h"
 
+// F110QP_IN: the input scalar of x0 / u_lin / x_ref (float; double in the *_dbl objects)
+#ifndef F110QP_IN
+#define F110QP_IN float
+#endif
+
 #ifndef F110QP_LQ
 #error "F110QP_LQ (QPs per wave) must be defined"
 #endif
@@ -15,8 +20,8 @@ namespace f110qp {
   F110QP_INST_R(ST, SLDS, true, false)                                                         \
   F110QP_INST_R(ST, SLDS, false, false)
 #define F110QP_INST_R(ST, SLDS, ROT, DREF)                                                     \
-  template hipError_t launch_lane_t<ST, SLDS, F110QP_LQ, ROT, DREF>(                           \
-      const KParams&, int, const float*, const float*, const float*, float*, float*, int*, int*, \
+  template hipError_t launch_lane_t<ST, SLDS, F110QP_LQ, ROT, DREF, F110QP_IN>(                \
+      const KParams&, int, const F110QP_IN*, const F110QP_IN*, const F110QP_IN*, float*, float*, int*, int*, \
       const WarmState&, const LaneWork&, const ObjOut&, size_t, hipStream_t);
 F110QP_INST(double, true)
 F110QP_INST(float, true)

@@ -56,6 +56,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "f110qp_kernels.h"
 
 namespace f110qp {
@@ -102,11 +104,17 @@ struct ModeTag {
 #else
 #define F110QP_LANE_ATTR __attribute__((amdgpu_waves_per_eu(SLDS ? 2 : 1, SLDS ? 2 : 1)))
 #endif
-template <typename ST, bool SLDS, int L, bool ROT, bool DREF>
+// IN = float or double: the scalar of x0, u_lin and x_ref in global memory (the *_dbl entry points
+// of include/f110qp.h). Every input is widened to fp64 at its load, so past the loads the two
+// instantiations run the same code, with one exception: without DREF the references wait in LDS as
+// floats, absolute for IN = float (recentred at each use), already recentred on x0 in fp64 and then
+// rounded to float for IN = double (absolute doubles do not fit the 12 N L bytes, and an absolute
+// float would lose what the double input carries).
+template <typename ST, bool SLDS, int L, bool ROT, bool DREF, typename IN = float>
 __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams P, const int B,
-                                                  const float* __restrict__ x0g,
-                                                  const float* __restrict__ ulg,
-                                                  const float* __restrict__ xrg,
+                                                  const IN* __restrict__ x0g,
+                                                  const IN* __restrict__ ulg,
+                                                  const IN* __restrict__ xrg,
                                                   float* __restrict__ uout,
                                                   float* __restrict__ xout,
                                                   int* __restrict__ status_out,
@@ -121,7 +129,12 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
   // at 12 N L + 12 (i + 1) L, so the in-order conversion never overwrites an unread float).
   // Layout: DREF [3N][L] fp64 refs | (SLDS) scratch | [N][L] state; else [3N][L] float refs |
   // [N][L] state | (SLDS) scratch.
-  float* const stg = DREF ? xr_s + 3 * P.N * L : xr_s;
+  // IN = double with DREF stages the raw doubles in the fp64 region itself (24 N L bytes, exactly
+  // what they need) and recentres them in place: each lane reads and writes its own QP's elements.
+  constexpr bool DIN = sizeof(IN) == 8;
+  float* const stg = (DREF && !DIN) ? xr_s + 3 * P.N * L : xr_s;
+  using StgT = std::conditional_t<DIN && DREF, double, float>;
+  StgT* const stgt = reinterpret_cast<StgT*>(stg);
   LSTAMP(t_start);
 #ifdef F110QP_STAMPS
   unsigned long long acc_bw = 0, acc_fw = 0, acc_out = 0, t_setup = 0, npass = 0;
@@ -148,19 +161,25 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
   {
     const int S3 = 3 * P.xr_stride;  // floats per QP in x_ref (>= 3N)
     const int tot = nq * n3;
-    const float* src = xrg + (size_t)b0 * S3;
+    const IN* src = xrg + (size_t)b0 * S3;
+    const IN* x0w = x0g + (size_t)b0 * 3;  // IN = double without DREF: recentred before rounding
     const int dq = 64 / n3, dc = 64 - dq * n3;
     int q = lane / n3, c = lane - (lane / n3) * n3;
     const int last_off = (nq - 1) * S3 + (n3 - 1);
     constexpr int kChunk = 8;
     for (int e0 = 0; e0 < tot; e0 += kChunk * 64) {
-      float vbuf[kChunk];
+      StgT vbuf[kChunk];
       int dst[kChunk];
 #pragma unroll
       for (int j = 0; j < kChunk; j++) {
         const bool in = e0 + j * 64 + lane < tot;
         dst[j] = in ? c * L + q : -1;
-        vbuf[j] = src[in ? q * S3 + c : last_off];
+        if constexpr (DIN && !DREF) {
+          const int qq = in ? q : nq - 1, cc = in ? c : n3 - 1;
+          vbuf[j] = (float)(src[qq * S3 + cc] - x0w[3 * qq + cc % 3]);
+        } else {
+          vbuf[j] = src[in ? q * S3 + c : last_off];
+        }
         q += dq;
         c += dc;
         const bool wrap = c >= n3;
@@ -169,11 +188,11 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
       }
       if (e0 + kChunk * 64 <= tot) {  // wave-uniform
 #pragma unroll
-        for (int j = 0; j < kChunk; j++) stg[dst[j]] = vbuf[j];
+        for (int j = 0; j < kChunk; j++) stgt[dst[j]] = vbuf[j];
       } else {
 #pragma unroll
         for (int j = 0; j < kChunk; j++)
-          if (dst[j] >= 0) stg[dst[j]] = vbuf[j];
+          if (dst[j] >= 0) stgt[dst[j]] = vbuf[j];
       }
     }
     __syncthreads();
@@ -198,11 +217,11 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
   // a non-finite reference entry flags the QP: each lane scans its QP's staged row (~10
   // instructions per entry; a ballot per staged element measured more at C4 and c2_big sizes)
   bool nonfin = false;
-  for (int e = 0; e < n3; e++) nonfin |= !isfinite(stg[e * L + slot]);
+  for (int e = 0; e < n3; e++) nonfin |= !isfinite(stgt[e * L + slot]);
 
   // ---- per-lane QP data (Model::Linearize, model.cpp:30-59; fp64 of the float inputs) ----
   const double X0 = (double)x0g[3 * b + 0], Y0 = (double)x0g[3 * b + 1];
-  const float fTH0 = x0g[3 * b + 2];
+  const IN fTH0 = x0g[3 * b + 2];
   const double th0 = (double)fTH0;
   const double v = (double)ulg[2 * b + 0], d = (double)ulg[2 * b + 1];
   const double dt = (double)P.dt;
@@ -268,15 +287,20 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
         reinterpret_cast<ST*>(scr) + (size_t)blockIdx.x * N * 8 * L + (size_t)slot * 8, 32));
     ap = reinterpret_cast<int*>(xr_s + (DREF ? 6 : 3) * N * L) + slot;
   }
-  const unsigned kth = __float_as_uint(fTH0), kv = __float_as_uint(ulg[2 * b + 0]);
-  const unsigned kd = __float_as_uint(ulg[2 * b + 1]);
+  // (IN = double: the *_dbl calls pass no warm state, the 16-byte slot key holds float bits only)
+  unsigned kth = 0u, kv = 0u, kd = 0u;
+  if constexpr (!DIN) {
+    kth = __float_as_uint(fTH0);
+    kv = __float_as_uint(ulg[2 * b + 0]);
+    kd = __float_as_uint(ulg[2 * b + 1]);
+  }
   {
     // previous tick's active bounds seed the first pass (C5) when the slot's linearisation point
     // (theta0, v, steer bits) repeats: on the closed-loop stream, where it changes every tick, a
     // stale seed measured 1.61 vs 1.49 passes per QP cold. Key valid flag: 1 = written by the
     // wave kernel with its W = H^-1, 2 = by this kernel (act masks only, never a W for the wave
     // kernel to reuse).
-    const bool hit = wkey.w != 0u && wkey.x == kth && wkey.y == kv && wkey.z == kd;
+    const bool hit = !DIN && wkey.w != 0u && wkey.x == kth && wkey.y == kv && wkey.z == kd;
     if (ws.hit_call && __ballot(hit) != 0ull && lane == 0) *ws.hit_call = ws.call;
     wst.x += (unsigned)__popcll(__ballot(hit && owner));  // hits (owner lanes), stored at the end
     const unsigned long long lo0 = hit ? wact[0] : 0ull, hi0 = hit ? wact[1] : 0ull;
@@ -299,8 +323,13 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
   }
   // recentred (ROT: rotated) reference of stage i from the float staging
   auto ref_f = [&](int i, double& rx, double& ry, double& rt) {
-    const double dx = (double)stg[(3 * i + 0) * L + slot] - X0;
-    const double dy = (double)stg[(3 * i + 1) * L + slot] - Y0;
+    double dx = (double)stgt[(3 * i + 0) * L + slot], dy = (double)stgt[(3 * i + 1) * L + slot];
+    double dth = (double)stgt[(3 * i + 2) * L + slot];
+    if constexpr (!(DIN && !DREF)) {  // (else staged recentred)
+      dx -= X0;
+      dy -= Y0;
+      dth -= th0;
+    }
     if constexpr (ROT) {
       rx = cs * dx + sn * dy;
       ry = cs * dy - sn * dx;
@@ -308,7 +337,7 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
       rx = dx;
       ry = dy;
     }
-    rt = (double)stg[(3 * i + 2) * L + slot] - th0;
+    rt = dth;
   };
   if constexpr (DREF) {  // once per kernel instead of once per stage and sweep
     for (int i = 0; i < N; i++) {
@@ -618,9 +647,9 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
     float* uo = uout + (size_t)b * 2 * N;
     float* xo = xout + (size_t)b * 3 * (N + 1);
     if (owner) {
-      xo[0] = solved ? x0g[3 * b + 0] : nanv;  // x*_0 = x0 exactly, as the dynamics rows fix it
-      xo[1] = solved ? x0g[3 * b + 1] : nanv;
-      xo[2] = solved ? fTH0 : nanv;
+      xo[0] = solved ? (float)x0g[3 * b + 0] : nanv;  // x*_0 = x0 exactly, as the dynamics rows fix it
+      xo[1] = solved ? (float)x0g[3 * b + 1] : nanv;
+      xo[2] = solved ? (float)fTH0 : nanv;
     }
     // u* = K_i x_i + k_i from the gains of the last backward sweep (the set of the converged
     // pass: a converged lane's later sweeps rewrote the same gains), the same expression the
@@ -749,17 +778,17 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
   signal_call_done(oo);  // a synchronous call's completion word (f110qp_kernels.h)
 }
 
-template <typename ST, bool SLDS, int L, bool ROT, bool DREF>
-hipError_t launch_lane_t(const KParams& P, int B, const float* x0, const float* ul, const float* xr,
+template <typename ST, bool SLDS, int L, bool ROT, bool DREF, typename IN>
+hipError_t launch_lane_t(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
                          float* uo, float* xo, int* st, int* its, const WarmState& ws,
                          const LaneWork& lw, const ObjOut& oo, size_t lds, hipStream_t s) {
   const int waves = (B + L - 1) / L;
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lane_kernel<ST, SLDS, L, ROT, DREF>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lane_kernel<ST, SLDS, L, ROT, DREF, IN>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((lane_kernel<ST, SLDS, L, ROT, DREF>), dim3(waves), dim3(64), lds, s, P, B, x0, ul, xr,
+  hipLaunchKernelGGL((lane_kernel<ST, SLDS, L, ROT, DREF, IN>), dim3(waves), dim3(64), lds, s, P, B, x0, ul, xr,
                      uo, xo, st, its, lw.scratch, ws, lw.kmax, oo);
   return hipGetLastError();
 }

@@ -11,8 +11,10 @@
 
 namespace f110qp {
 
-template <int S, bool ROT, bool SCR>
-hipError_t launch_lane_seg_t(const KParams& P, int B, const float* x0, const float* ul, const float* xr,
+// IN below: the input scalar of x0 / u_lin / x_ref, float or double (the *_dbl entry points). The
+// policy (QPs per wave, scratch placement, segments, twin starts) does not depend on it.
+template <int S, bool ROT, bool SCR, typename IN>
+hipError_t launch_lane_seg_t(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
                              float* uo, float* xo, int* st, int* its, const WarmState& ws,
                              const LaneWork& lw, const ObjOut& oo, hipStream_t s);  // lane_seg_inst.hip
 // LDS per wave of the segmented kernel with fp64 / fp32 references and scratch (lane_seg_kernel.h
@@ -70,8 +72,8 @@ int lane_segments(const KParams& P, int B, const LaneWork& lw) {
 }
 
 #ifndef F110QP_LANE_ALL
-template <typename ST, bool SLDS, int L, bool ROT, bool DREF>
-hipError_t launch_lane_t(const KParams& P, int B, const float* x0, const float* ul, const float* xr,
+template <typename ST, bool SLDS, int L, bool ROT, bool DREF, typename IN>
+hipError_t launch_lane_t(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
                          float* uo, float* xo, int* st, int* its, const WarmState& ws,
                          const LaneWork& lw, const ObjOut& oo, size_t lds, hipStream_t s);  // lane_inst.hip
 #endif
@@ -89,18 +91,18 @@ int lane_qps_per_wave(int B, int qpw) {
 // references converted once to fp64 in LDS (DREF: 12 N L more bytes per wave than the float
 // references) when the grid runs one wave per CU. Measured: C4 shard 8,192 x N=40 195.8 ->
 // 184.6 us, C5 66.9 -> 65.3; at four waves per CU (65,536 x N=20) 107.0 -> 109.1, so not there.
-template <typename ST, bool SLDS, int L, bool DREF>
-static hipError_t launch_rot_d(const KParams& P, int B, const float* x0, const float* ul,
-                               const float* xr, float* uo, float* xo, int* st, int* its,
+template <typename ST, bool SLDS, int L, bool DREF, typename IN>
+static hipError_t launch_rot_d(const KParams& P, int B, const IN* x0, const IN* ul,
+                               const IN* xr, float* uo, float* xo, int* st, int* its,
                                const WarmState& ws, const LaneWork& lw, const ObjOut& oo, size_t lds,
                                hipStream_t s) {
   if (lw.rot && P.q[0] == P.q[1])
-    return launch_lane_t<ST, SLDS, L, true, DREF>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, lds, s);
-  return launch_lane_t<ST, SLDS, L, false, DREF>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, lds, s);
+    return launch_lane_t<ST, SLDS, L, true, DREF, IN>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, lds, s);
+  return launch_lane_t<ST, SLDS, L, false, DREF, IN>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, lds, s);
 }
-template <typename ST, bool SLDS, int L>
-static hipError_t launch_rot(const KParams& P, int B, const float* x0, const float* ul,
-                             const float* xr, float* uo, float* xo, int* st, int* its,
+template <typename ST, bool SLDS, int L, typename IN>
+static hipError_t launch_rot(const KParams& P, int B, const IN* x0, const IN* ul,
+                             const IN* xr, float* uo, float* xo, int* st, int* its,
                              const WarmState& ws, const LaneWork& lw, const ObjOut& oo, size_t lds,
                              hipStream_t s) {
   const size_t ldsd = lds + (size_t)P.N * L * 12;
@@ -135,8 +137,8 @@ int lane_scratch_mode(const KParams& P, int B, const LaneWork& lw) {
   return scratch_mode(P, B, lane_qps_per_wave(B, lw.qpw), lw.mode);
 }
 
-template <int L>
-static hipError_t launch_lq(const KParams& P, int B, const float* x0, const float* ul, const float* xr,
+template <int L, typename IN>
+static hipError_t launch_lq(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
                             float* uo, float* xo, int* st, int* its, const WarmState& ws,
                             const LaneWork& lw, const ObjOut& oo, hipStream_t s) {
   const size_t N = (size_t)P.N;
@@ -153,18 +155,19 @@ static hipError_t launch_lq(const KParams& P, int B, const float* x0, const floa
 // LDS per wave: the staged references (12 N L B) + PDAS state (4 N L B) + Riccati scratch
 // (8 N L sizeof(ST)) (lane_mode 0 = auto; 1/2/3/4 force LDS fp64 / LDS fp32 / HBM fp64 / HBM
 // fp32).
-hipError_t launch_lane(const KParams& P, int B, const float* x0, const float* ul,
-                       const float* xr, float* uo, float* xo, int* st, int* its,
+template <typename IN>
+hipError_t launch_lane(const KParams& P, int B, const IN* x0, const IN* ul,
+                       const IN* xr, float* uo, float* xo, int* st, int* its,
                        const WarmState& ws, const LaneWork& lw, const ObjOut& oo, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   const bool rot = lw.rot && P.q[0] == P.q[1];
   const bool scr = oo.scr_hs != nullptr;  // the gap-row screen variant (f110qp_kernels.hip)
 #define F110QP_SEG_CASE(S)                                                                        \
   case S:                                                                                         \
-    return scr ? (rot ? launch_lane_seg_t<S, true, true>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, s)  \
-                      : launch_lane_seg_t<S, false, true>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, s)) \
-               : (rot ? launch_lane_seg_t<S, true, false>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, s) \
-                      : launch_lane_seg_t<S, false, false>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, s));
+    return scr ? (rot ? launch_lane_seg_t<S, true, true, IN>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, s)  \
+                      : launch_lane_seg_t<S, false, true, IN>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, s)) \
+               : (rot ? launch_lane_seg_t<S, true, false, IN>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, s) \
+                      : launch_lane_seg_t<S, false, false, IN>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, s));
   switch (lane_segments(P, B, lw)) {
     F110QP_SEG_CASE(2)
     F110QP_SEG_CASE(4)
@@ -182,5 +185,12 @@ hipError_t launch_lane(const KParams& P, int B, const float* x0, const float* ul
     default: return launch_lq<64>(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, s);
   }
 }
+#define F110QP_LANE_LAUNCH_INST(IN)                                                                  \
+  template hipError_t launch_lane<IN>(const KParams&, int, const IN*, const IN*, const IN*, float*, \
+                                      float*, int*, int*, const WarmState&, const LaneWork&,         \
+                                      const ObjOut&, hipStream_t);
+F110QP_LANE_LAUNCH_INST(float)
+F110QP_LANE_LAUNCH_INST(double)
+#undef F110QP_LANE_LAUNCH_INST
 
 }  // namespace f110qp

@@ -10,11 +10,21 @@
 #endif
 
 namespace f110qp {
-#define F110QP_SEG_INST(S, ROT, SCR)                                                                \
-  template hipError_t launch_lane_seg_t<S, ROT, SCR>(const KParams&, int, const float*, const float*, \
-                                                     const float*, float*, float*, int*, int*,       \
-                                                     const WarmState&, const LaneWork&, const ObjOut&, \
-                                                     hipStream_t);
+// F110QP_IN: the input scalar of x0 / u_lin / x_ref (float; double in the *_dbl objects, which
+// define F110QP_SEG_DBL and leave the policy functions below to the float objects)
+#ifndef F110QP_IN
+#define F110QP_IN float
+#endif
+#define F110QP_SEG_INST_IN(S, ROT, SCR, IN)                                                          \
+  template hipError_t launch_lane_seg_t<S, ROT, SCR, IN>(const KParams&, int, const IN*, const IN*,  \
+                                                         const IN*, float*, float*, int*, int*,      \
+                                                         const WarmState&, const LaneWork&, const ObjOut&, \
+                                                         hipStream_t);
+#ifdef F110QP_SEG_ALL
+#define F110QP_SEG_INST(S, ROT, SCR) F110QP_SEG_INST_IN(S, ROT, SCR, float) F110QP_SEG_INST_IN(S, ROT, SCR, double)
+#else
+#define F110QP_SEG_INST(S, ROT, SCR) F110QP_SEG_INST_IN(S, ROT, SCR, F110QP_IN)
+#endif
 #define F110QP_SEG_INST_ALL(SCR) \
   F110QP_SEG_INST(2, true, SCR)  \
   F110QP_SEG_INST(2, false, SCR) \
@@ -31,7 +41,7 @@ F110QP_SEG_INST_ALL(true)
 #undef F110QP_SEG_INST_ALL
 #undef F110QP_SEG_INST
 
-#if defined(F110QP_SEG_ALL) || F110QP_SEG_SCR == 0
+#if defined(F110QP_SEG_ALL) || (F110QP_SEG_SCR == 0 && !defined(F110QP_SEG_DBL))
 int lane_seg_scratch(const KParams& P, int B, int S, const LaneWork& lw) {
   return seg_scratch_mode(P, seg_twin(P, B, S, lw) ? 2 * B : B, S, lw);
 }

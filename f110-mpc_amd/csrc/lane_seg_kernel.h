@@ -133,10 +133,14 @@ __device__ __forceinline__ double seg_dn(double v, int lane) {
 // neutral (tools/ab_seg_variant.sh)
 #define F110QP_SEG_WPE 2
 #endif
-template <int S, bool ROT, bool FST, typename ST = double, bool SCR = false, bool TWIN = false, bool EVEN = false>
+// IN = float or double: the scalar of x0, u_lin and x_ref in global memory (the *_dbl entry points of
+// include/f110qp.h). The raw references are staged as IN and every input is widened to fp64 at its
+// first use, so past the conversion to recentred references the two instantiations run the same code.
+template <int S, bool ROT, bool FST, typename ST = double, bool SCR = false, bool TWIN = false, bool EVEN = false,
+          typename IN = float>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(F110QP_SEG_WPE, F110QP_SEG_WPE))) void lane_seg_kernel(
-    const KParams P, const int B, const float* __restrict__ x0g, const float* __restrict__ ulg,
-    const float* __restrict__ xrg, float* __restrict__ uout, float* __restrict__ xout,
+    const KParams P, const int B, const IN* __restrict__ x0g, const IN* __restrict__ ulg,
+    const IN* __restrict__ xrg, float* __restrict__ uout, float* __restrict__ xout,
     int* __restrict__ status_out, int* __restrict__ iters_out, const WarmState ws, const int kmax,
     const ObjOut oo) {
   constexpr int twin = TWIN ? 1 : 0;
@@ -190,10 +194,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(F110QP_SEG_W
   double* const ftab = btab + 16 * 8;  // (ST = double only)
 
   // per-QP inputs and the warm-start traffic switch (warm_traffic), issued before the staging loads
-  const float fX0 = x0g[3 * b + 0], fY0 = x0g[3 * b + 1], fTH0 = x0g[3 * b + 2];
-  const float fv = ulg[2 * b + 0], fd = ulg[2 * b + 1];
+  const IN fX0 = x0g[3 * b + 0], fY0 = x0g[3 * b + 1], fTH0 = x0g[3 * b + 2];
+  const IN fv = ulg[2 * b + 0], fd = ulg[2 * b + 1];
   const unsigned wlast = warm_last_hit(ws);
-  // ---- stage the wave's reference paths (float, [3N][L]) into the scratch region ----
+  // ---- stage the wave's reference paths (IN, [3N][L]) into the scratch region ----
+  // (room: (3 N LR + 64) sizeof(IN) bytes, junk row included, at most 24 N 64 / S + 512 for doubles,
+  // in a region of mM NV 64 sizeof(ST) >= 44 (N / S) 64 bytes: fits whenever N / S >= 2, which
+  // lane_segments requires of every S it returns)
   // Element e = q 3N + c of the wave's nq rows (row stride 3 xr_stride in HBM) goes to
   // stg[c L + q]. (q, c) advance by 64 elements per step without a division, every load reads a
   // valid address (clamped) and every store lands (past the staged rows for e >= tot), so the
@@ -203,19 +210,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(F110QP_SEG_W
   // Twin starts: the two starts of a QP share its row, staged once ([3N][L / 2] QP rows)
   constexpr int LR = L >> twin;
   {
-    float* stg = reinterpret_cast<float*>(lbase + o_sc);
+    IN* stg = reinterpret_cast<IN*>(lbase + o_sc);
     const int nqr = (nq + twin) >> twin;  // QP rows of the wave (b0 is even with twin starts)
     const int n3 = 3 * N, S3 = 3 * P.xr_stride, tot = nqr * n3;
     const int rb0 = b0 >> twin;
-    const float* src = xrg + (size_t)rb0 * S3;
+    const IN* src = xrg + (size_t)rb0 * S3;
     const int dq = 64 / n3, dc = 64 - dq * n3;
     int q = lane / n3, c = lane - (lane / n3) * n3;
     const int junk = n3 * LR + lane;                 // inside the scratch rows, never read
     const int last_off = (nqr - 1) * S3 + (n3 - 1);  // a valid element
     // C5 and the C4 shard stage 960 floats per wave, the twin kernels 480: one round trip
-    constexpr int kChunk = TWIN ? 8 : 16;
+    // (doubles: half the elements per chunk, the same bytes in flight and registers held)
+    constexpr int kChunk = (TWIN ? 8 : 16) / (int)(sizeof(IN) / 4);
     for (int e0 = 0; e0 < tot; e0 += kChunk * 64) {
-      float vbuf[kChunk];
+      IN vbuf[kChunk];
       int dst[kChunk];
 #pragma unroll
       for (int j = 0; j < kChunk; j++) {
@@ -287,12 +295,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(F110QP_SEG_W
   // the loop has no EXEC-masked exits; its flag only counts stages < m)
   bool nonfin = false;
   {
-    const float* stg = reinterpret_cast<const float*>(lbase + o_sc);
+    const IN* stg = reinterpret_cast<const IN*>(lbase + o_sc);
     const int row = slot >> twin;
     for (int t = 0; t < mM; t++) {
       const int i = s0 + t;
-      const float fx = stg[(3 * i + 0) * LR + row], fy = stg[(3 * i + 1) * LR + row];
-      const float ft = stg[(3 * i + 2) * LR + row];
+      const IN fx = stg[(3 * i + 0) * LR + row], fy = stg[(3 * i + 1) * LR + row];
+      const IN ft = stg[(3 * i + 2) * LR + row];
       nonfin |= (t < m) & !(isfinite(fx) && isfinite(fy) && isfinite(ft));
       const double dx = (double)fx - X0, dy = (double)fy - Y0;
       r64[(3 * t + 0) * 64] = ROT ? cs * dx + sn * dy : dx;
@@ -335,13 +343,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(F110QP_SEG_W
 
   // warm start: previous tick's active bounds when the slot's (theta0, v, steer) bits repeat
   const int R = (2 * N + 63) / 64;
-  const unsigned kth = __float_as_uint(fTH0), kv = __float_as_uint(fv), kd = __float_as_uint(fd);
+  // (IN = double: the *_dbl calls pass no warm state, wt is false; the slot key holds float bits)
+  const unsigned kth = __float_as_uint((float)fTH0), kv = __float_as_uint((float)fv), kd = __float_as_uint((float)fd);
   {
 #ifdef F110QP_SEG_SEED_ANY  // measurement knob: seed from the slot's previous set on any key
                             // (measured C5 31.2 -> 34.9 us: the stale set costs passes)
     const bool hit = wt && key3 != 0u;
 #else
-    const bool hit = wt && key3 != 0u && key0 == kth && key1 == kv && key2 == kd;
+    const bool hit = sizeof(IN) == 4 && wt && key3 != 0u && key0 == kth && key1 == kv && key2 == kd;
 #endif
     unsigned long long lw = 0, hw = 0;
     if (wt) {  // (wave-uniform: a call that moves no warm state skips the mask window)
@@ -785,9 +794,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(F110QP_SEG_W
   float* uo = uout + (size_t)b * 2 * N;
   float* xo = xout + (size_t)b * 3 * (N + 1);
   if (qowner) {
-    xo[0] = solved ? fX0 : nanv;
-    xo[1] = solved ? fY0 : nanv;
-    xo[2] = solved ? fTH0 : nanv;
+    xo[0] = solved ? (float)fX0 : nanv;
+    xo[1] = solved ? (float)fY0 : nanv;
+    xo[2] = solved ? (float)fTH0 : nanv;
   }
   const bool want_obj = oo.obj || oo.cost;
   double J = 0.0, Cr = 0.0;
@@ -955,8 +964,8 @@ inline bool seg_twin(const KParams& P, int B, int S, const LaneWork& lw) {
          per_cu * seg_lds_bytes(P.N, S, true) <= 160 * 1024;  // the FST kernel, all waves resident
 }
 
-template <int S, bool ROT, bool SCR>
-hipError_t launch_lane_seg_t(const KParams& P, int B, const float* x0, const float* ul, const float* xr,
+template <int S, bool ROT, bool SCR, typename IN>
+hipError_t launch_lane_seg_t(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
                              float* uo, float* xo, int* st, int* its, const WarmState& ws,
                              const LaneWork& lw, const ObjOut& oo, hipStream_t s) {
   constexpr int L = 64 / S;
@@ -980,8 +989,8 @@ hipError_t launch_lane_seg_t(const KParams& P, int B, const float* x0, const flo
   };
   const bool even = P.N % S == 0;  // equal segments: the EVEN instantiation
 #define F110QP_SEG_GO(FST_, ST_, TWIN_, LDS_)                                              \
-  (even ? go1(&lane_seg_kernel<S, ROT, FST_, ST_, SCR, TWIN_, true>, LDS_)                 \
-        : go1(&lane_seg_kernel<S, ROT, FST_, ST_, SCR, TWIN_, false>, LDS_))
+  (even ? go1(&lane_seg_kernel<S, ROT, FST_, ST_, SCR, TWIN_, true, IN>, LDS_)                 \
+        : go1(&lane_seg_kernel<S, ROT, FST_, ST_, SCR, TWIN_, false, IN>, LDS_))
   if (twin) return F110QP_SEG_GO(true, double, true, seg_lds_bytes(P.N, S, true));
   if (mode == 2) return F110QP_SEG_GO(false, float, false, seg_lds_bytes(P.N, S, false, true));
   return fst ? F110QP_SEG_GO(true, double, false, seg_lds_bytes(P.N, S, true))

@@ -1,18 +1,28 @@
 // solve_inst.hip — explicit instantiations of the solve kernel (solve_kernel.h).
 //
 // The Makefile compiles this file once per (NUM, GAP) pair (-DF110QP_NUM=.. -DF110QP_GAP=..)
-// so the 20 instantiations build in parallel; the diagnostic stamps build compiles it once with
+// and once more per pair for the double-input kernels, so the instantiations build in parallel; the diagnostic stamps build compiles it once with
 // -DF110QP_ALL_INST (the per-wave stamp buffer must live in a single translation unit).
 #include "solve_kernel.h"
 
-#define F110QP_INSTANTIATE(NUM, GAP)                                                           \
-  template hipError_t f110qp::launch_t<NUM, GAP>(                                              \
-      const KParams&, int, const float*, const float*, const float*, const float*, float*,      \
+// F110QP_IN: the input scalar of x0 / u_lin / x_ref (float; double in the *_dbl objects, which the
+// Makefile builds from this file with -DF110QP_IN=double). F110QP_ALL_INST instantiates both.
+#ifndef F110QP_IN
+#define F110QP_IN float
+#endif
+#define F110QP_INSTANTIATE_IN(NUM, GAP, IN)                                                    \
+  template hipError_t f110qp::launch_t<NUM, GAP, IN>(                                          \
+      const KParams&, int, const IN*, const IN*, const IN*, const float*, float*,              \
       float*, int*, int*, double*, double*, const WarmState&, const int*, const int*, int,       \
       const ObjOut&, hipStream_t);                                                             \
-  template hipError_t f110qp::launch_prep_t<NUM, GAP>(const KParams&, int, const float*,       \
-                                                      const float*, const float*, const float*,  \
-                                                      const WarmState&, const int*, hipStream_t);
+  template hipError_t f110qp::launch_prep_t<NUM, GAP, IN>(const KParams&, int, const IN*,      \
+                                                          const IN*, const IN*, const float*,  \
+                                                          const WarmState&, const int*, hipStream_t);
+#ifdef F110QP_ALL_INST
+#define F110QP_INSTANTIATE(NUM, GAP) F110QP_INSTANTIATE_IN(NUM, GAP, float) F110QP_INSTANTIATE_IN(NUM, GAP, double)
+#else
+#define F110QP_INSTANTIATE(NUM, GAP) F110QP_INSTANTIATE_IN(NUM, GAP, F110QP_IN)
+#endif
 
 #ifdef F110QP_ALL_INST
 #define F110QP_BOTH(NUM) F110QP_INSTANTIATE(NUM, false) F110QP_INSTANTIATE(NUM, true)

@@ -365,7 +365,9 @@ __device__ __forceinline__ void hv_f64(const Lin& M, const KParams& P, int lane,
 // ------------------------------------------------------------------------------------------
 // shared memory of one wave / one QP
 // ------------------------------------------------------------------------------------------
-template <int NUM, bool GAP>
+// RT: the scalar the reference heading waits in (float as the float inputs deliver it; double for
+// the double-input instantiations, whose x_ref carries more than a float holds)
+template <int NUM, bool GAP, typename RT = float>
 struct Smem {
   static constexpr int R = (NUM + 63) / 64;
   static constexpr int VN = 64 * R;      // per-variable vectors (one entry per lane and row)
@@ -382,7 +384,7 @@ struct Smem {
   float stX[NST], stY[NST];        // per-stage linear rollout (stage 1..N)
   double rx[VN], ry[VN];           // recentred reference of the variable's stage (fp64: x_ref - x0
                                    // of two floats is not always a float)
-  float rth[VN];
+  RT rth[VN];
   double cmult[3 * VN];            // multiplier per constraint id (fp64: the refinement's)
   alignas(16) float prow[NUM];     // box PDAS: pivot row of T broadcast (pivot_T)
   alignas(16) float yb[NUM];       // box PDAS: right-hand side broadcast (matvec_T)
@@ -399,8 +401,8 @@ constexpr int kTriBlock = 8;  // steps per block of the triangular solves (loads
 
 // l = L^-1 v, one lane per active slot (slot j: lane j mod 64, row j / 64); L read from LDS.
 // A plain q-step loop: the slot count is uniform, each step is mul -> readlane -> fma.
-template <int NUM, bool GAP, int R>
-__device__ __forceinline__ void tri_forward(Smem<NUM, GAP>& sm, int lane, int q,
+template <int NUM, bool GAP, int R, typename RT>
+__device__ __forceinline__ void tri_forward(Smem<NUM, GAP, RT>& sm, int lane, int q,
                                             const float (&rdiag)[R], const float (&v)[R],
                                             float (&lv)[R]) {
   float acc[R];
@@ -451,8 +453,8 @@ __device__ __forceinline__ void tri_forward(Smem<NUM, GAP>& sm, int lane, int q,
 }
 
 // r = L^-T l (backward substitution, column-oriented)
-template <int NUM, bool GAP, int R>
-__device__ __forceinline__ void tri_backward(Smem<NUM, GAP>& sm, int lane, int q,
+template <int NUM, bool GAP, int R, typename RT>
+__device__ __forceinline__ void tri_backward(Smem<NUM, GAP, RT>& sm, int lane, int q,
                                              const float (&rdiag)[R], const float (&l)[R],
                                              float (&out)[R]) {
   float acc[R];
@@ -501,8 +503,8 @@ __device__ __forceinline__ void tri_backward(Smem<NUM, GAP>& sm, int lane, int q
 // O(q^2) work and q - 1 - kd short dependent steps (hypot -> readlane -> 4 FMAs), instead of the
 // O(q^3) refactorisation of S_A with its q dependent column steps. After the shift every lane
 // touches only its own row, so the rotation loop needs no barrier.
-template <int NUM, bool GAP, int R>
-__device__ __forceinline__ void chol_delete(Smem<NUM, GAP>& sm, int lane, int q, int kd,
+template <int NUM, bool GAP, int R, typename RT>
+__device__ __forceinline__ void chol_delete(Smem<NUM, GAP, RT>& sm, int lane, int q, int kd,
                                             float (&rd)[R]) {
   constexpr int kChunk = 8;
   for (int c0 = 0; c0 < q; c0 += kChunk) {  // row s <- row s + 1 (columns 0..s + 1)
@@ -567,8 +569,8 @@ __device__ __forceinline__ void chol_delete(Smem<NUM, GAP>& sm, int lane, int q,
 #ifndef F110QP_MATVEC_SPLIT
 #define F110QP_MATVEC_SPLIT 1
 #endif
-template <int NUM, bool GAP, int R>
-__device__ __forceinline__ void matvec_W(Smem<NUM, GAP>& sm, int lane, float (&y)[R]) {
+template <int NUM, bool GAP, int R, typename RT>
+__device__ __forceinline__ void matvec_W(Smem<NUM, GAP, RT>& sm, int lane, float (&y)[R]) {
   int c[R];
 #pragma unroll
   for (int r = 0; r < R; r++) {
@@ -617,8 +619,8 @@ __device__ __forceinline__ void matvec_W(Smem<NUM, GAP>& sm, int lane, float (&y
 
 // n_j' w for the active slot with id slot_id (w in sm.vec2 by variable, gap rows from the
 // per-stage linear rollout in sm.stX/stY).
-template <int NUM, bool GAP>
-__device__ __forceinline__ float slot_dot(Smem<NUM, GAP>& sm, int slot_id, float ga0, float ga1,
+template <int NUM, bool GAP, typename RT>
+__device__ __forceinline__ float slot_dot(Smem<NUM, GAP, RT>& sm, int slot_id, float ga0, float ga1,
                                           float gb0, float gb1) {
   const int owner = slot_id / 3, t = slot_id - 3 * owner;
   if (t == 0) return sm.vec2[owner];
@@ -628,8 +630,8 @@ __device__ __forceinline__ float slot_dot(Smem<NUM, GAP>& sm, int slot_id, float
 }
 
 // column c of V[j] = W n_j for uniform slot j with id sid_j
-template <int NUM, bool GAP>
-__device__ __forceinline__ float vcol(Smem<NUM, GAP>& sm, int j, int sid_j, int c) {
+template <int NUM, bool GAP, typename RT>
+__device__ __forceinline__ float vcol(Smem<NUM, GAP, RT>& sm, int j, int sid_j, int c) {
   if constexpr (GAP) return sm.V[j][c];
   else return box_sign(sid_j) * sm.W[sid_j / 3][c];
 }
@@ -692,8 +694,8 @@ struct Sweep<NUM, R, NUM> {
 // T_kj - (1 - sg / T_kk) T_kj cancels when |T_kk| >> 1: 5e-4 relative on stiff QPs); its
 // diagonal entry then ends sg away from -1/T_kk: the exact diagonal is carried in dg, and ed
 // (+-1 or 0, exact in fp32) records the offset of the register copy, which matvec_T removes.
-template <int NUM, bool GAP, int R>
-__device__ __forceinline__ void pivot_T(Smem<NUM, GAP>& sm, float (&h)[R][NUM], float (&dg)[R],
+template <int NUM, bool GAP, int R, typename RT>
+__device__ __forceinline__ void pivot_T(Smem<NUM, GAP, RT>& sm, float (&h)[R][NUM], float (&dg)[R],
                                         float (&ed)[R], int lane, const int (&vv)[R], int k,
                                         float sg) {
   const int kl = k & 63, kr = k >> 6;
@@ -740,8 +742,8 @@ __device__ __forceinline__ void pivot_T(Smem<NUM, GAP>& sm, float (&h)[R][NUM], 
 }
 
 // x = T y (y one entry per variable, zero outside the valid rows)
-template <int NUM, bool GAP, int R>
-__device__ __forceinline__ void matvec_T(Smem<NUM, GAP>& sm, const float (&h)[R][NUM],
+template <int NUM, bool GAP, int R, typename RT>
+__device__ __forceinline__ void matvec_T(Smem<NUM, GAP, RT>& sm, const float (&h)[R][NUM],
                                          const float (&ed)[R], const int (&vv)[R],
                                          const float (&y)[R], float (&x)[R]) {
 #pragma unroll
@@ -799,11 +801,41 @@ constexpr float kRobTight = 1e-14f;  // keep going to fp64 level: the multiplier
 template <int NUM>
 constexpr int kRobPasses = kHikPasses + NUM;
 
-template <int NUM, bool GAP>
-__device__ __forceinline__ void solve_qp(Smem<NUM, GAP>& sm, const int b, const KParams& P,
-                                         const float* __restrict__ x0g,
-                                         const float* __restrict__ ulg,
-                                         const float* __restrict__ xrg,
+// IN = float or double: the scalar of x0, u_lin and x_ref in global memory (the *_dbl entry points
+// of include/f110qp.h). Each input is widened to fp64 where the float path widens it, so past the
+// loads both instantiations run the same code. The W-cache key compares the inputs' own bits: three
+// words for float, six for double (kKeyWords; only the per-group cache of the grouped calls ever
+// sees a double key, the per-slot warm state is float-only).
+template <typename IN>
+constexpr int kKeyWords = sizeof(IN) == 8 ? 8 : 4;  // unsigned words per key slot, the last = valid flag
+__device__ __forceinline__ bool key_equal(const unsigned* key, float th, float v, float d) {
+  return key[0] == __float_as_uint(th) && key[1] == __float_as_uint(v) && key[2] == __float_as_uint(d);
+}
+__device__ __forceinline__ bool key_equal(const unsigned* key, double th, double v, double d) {
+  const unsigned long long* k = reinterpret_cast<const unsigned long long*>(key);
+  return k[0] == (unsigned long long)__double_as_longlong(th) && k[1] == (unsigned long long)__double_as_longlong(v) &&
+         k[2] == (unsigned long long)__double_as_longlong(d);
+}
+__device__ __forceinline__ void key_store(unsigned* key, float th, float v, float d) {
+  key[0] = __float_as_uint(th);
+  key[1] = __float_as_uint(v);
+  key[2] = __float_as_uint(d);
+  key[3] = 1u;
+}
+__device__ __forceinline__ void key_store(unsigned* key, double th, double v, double d) {
+  unsigned long long* k = reinterpret_cast<unsigned long long*>(key);
+  k[0] = (unsigned long long)__double_as_longlong(th);
+  k[1] = (unsigned long long)__double_as_longlong(v);
+  k[2] = (unsigned long long)__double_as_longlong(d);
+  key[6] = 0u;
+  key[7] = 1u;
+}
+
+template <int NUM, bool GAP, typename IN = float>
+__device__ __forceinline__ void solve_qp(Smem<NUM, GAP, IN>& sm, const int b, const KParams& P,
+                                         const IN* __restrict__ x0g,
+                                         const IN* __restrict__ ulg,
+                                         const IN* __restrict__ xrg,
                                          const float* __restrict__ hsg,
                                          float* __restrict__ uout,
                                          float* __restrict__ xout,
@@ -834,24 +866,24 @@ __device__ __forceinline__ void solve_qp(Smem<NUM, GAP>& sm, const int b, const 
                      acc_step = 0, acc_upd = 0, acc_pdas = 0;
 #endif
   // ---- 1. inputs + Model::Linearize ----------------------------------------------------
-  const float fX0 = x0g[3 * b + 0], fY0 = x0g[3 * b + 1], fTH0 = x0g[3 * b + 2];
-  const float ul0 = ulg[2 * b + 0], ul1 = ulg[2 * b + 1];
+  const IN fX0 = x0g[3 * b + 0], fY0 = x0g[3 * b + 1], fTH0 = x0g[3 * b + 2];
+  const IN ul0 = ulg[2 * b + 0], ul1 = ulg[2 * b + 1];
   const double X0 = (double)fX0, Y0 = (double)fY0;
   // The reference point of each variable's state stage (i = k+1; the terminal stage reuses
   // x_ref[N-1], mpc.cpp:228) is loaded here and consumed after the inverse: H depends only on
   // the linearisation point, so the load latency hides behind the Hessian and the sweep.
-  float xrv[R][3], x00[3] = {0.f, 0.f, 0.f};
+  IN xrv[R][3], x00[3] = {0, 0, 0};
 #pragma unroll
   for (int r = 0; r < R; r++) {
-    xrv[r][0] = 0.f; xrv[r][1] = 0.f; xrv[r][2] = 0.f;
+    xrv[r][0] = 0; xrv[r][1] = 0; xrv[r][2] = 0;
     if (valid[r]) {
       const int ri = (kk[r] + 1 < N) ? kk[r] + 1 : N - 1;
-      const float* xr = xrg + ((size_t)b * P.xr_stride + ri) * 3;
+      const IN* xr = xrg + ((size_t)b * P.xr_stride + ri) * 3;
       xrv[r][0] = xr[0]; xrv[r][1] = xr[1]; xrv[r][2] = xr[2];
     }
   }
   if (lane == 0) {
-    const float* xq = xrg + (size_t)b * P.xr_stride * 3;
+    const IN* xq = xrg + (size_t)b * P.xr_stride * 3;
     x00[0] = xq[0]; x00[1] = xq[1]; x00[2] = xq[2];
   }
   {
@@ -897,10 +929,9 @@ __device__ __forceinline__ void solve_qp(Smem<NUM, GAP>& sm, const int b, const 
   if (prep) wslot = prep_slot;
   bool whit = false, wvalid = false;
   if (warm && !prep && wslot >= 0) {
-    const unsigned* key = ws.key + 4 * wslot;
-    wvalid = key[3] == 1u;
-    whit = wvalid && key[0] == __float_as_uint(fTH0) && key[1] == __float_as_uint(ul0) &&
-           key[2] == __float_as_uint(ul1);
+    const unsigned* key = ws.key + kKeyWords<IN> * wslot;
+    wvalid = key[kKeyWords<IN> - 1] == 1u;
+    whit = wvalid && key_equal(key, fTH0, ul0, ul1);
   }
   // previous tick's active set seeds the PDAS guess only when the linearisation point repeats:
   // on the closed-loop C5 stream (theta0 changes every tick) a stale seed measured 1.62 vs 1.49
@@ -1137,11 +1168,7 @@ __device__ __forceinline__ void solve_qp(Smem<NUM, GAP>& sm, const int b, const 
         if (valid[r]) Wc[(size_t)j * NU + vv[r]] = sm.W[j][cl[r]];
     }
     if (lane == 0) {
-      unsigned* key = ws.key + 4 * wslot;
-      key[0] = __float_as_uint(fTH0);
-      key[1] = __float_as_uint(ulg[2 * b + 0]);
-      key[2] = __float_as_uint(ulg[2 * b + 1]);
-      key[3] = 1u;
+      key_store(ws.key + kKeyWords<IN> * wslot, fTH0, ulg[2 * b + 0], ulg[2 * b + 1]);
     }
   }
   wsync();
@@ -2256,9 +2283,9 @@ __device__ __forceinline__ void solve_qp(Smem<NUM, GAP>& sm, const int b, const 
     const float nanv = __int_as_float(0x7fc00000);
     float* xo = xout + (size_t)b * 3 * (N + 1);
     if (lane == 0) {
-      xo[0] = ok ? fX0 : nanv;
-      xo[1] = ok ? fY0 : nanv;
-      xo[2] = ok ? fTH0 : nanv;
+      xo[0] = ok ? (float)fX0 : nanv;
+      xo[1] = ok ? (float)fY0 : nanv;
+      xo[2] = ok ? (float)fTH0 : nanv;
     }
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -2338,16 +2365,16 @@ __device__ __forceinline__ void solve_qp(Smem<NUM, GAP>& sm, const int b, const 
 
 // One QP per workgroup (= one wave). With `list` the grid walks the index list instead
 // (count read on the device): the lane-per-QP kernel hands its non-converged QPs over this way.
-template <int NUM, bool GAP>
+template <int NUM, bool GAP, typename IN = float>
 #ifdef F110QP_SOLVE_WPE  // measurement knob: occupancy hint for the register allocator
 #define F110QP_SOLVE_ATTR __attribute__((amdgpu_waves_per_eu(F110QP_SOLVE_WPE, F110QP_SOLVE_WPE)))
 #else
 #define F110QP_SOLVE_ATTR
 #endif
 __global__ __launch_bounds__(64) F110QP_SOLVE_ATTR void solve_kernel(const KParams P, const int B,
-                                                   const float* __restrict__ x0g,
-                                                   const float* __restrict__ ulg,
-                                                   const float* __restrict__ xrg,
+                                                   const IN* __restrict__ x0g,
+                                                   const IN* __restrict__ ulg,
+                                                   const IN* __restrict__ xrg,
                                                    const float* __restrict__ hsg,
                                                    float* __restrict__ uout,
                                                    float* __restrict__ xout,
@@ -2359,7 +2386,7 @@ __global__ __launch_bounds__(64) F110QP_SOLVE_ATTR void solve_kernel(const KPara
                                                    const int* __restrict__ list,
                                                    const int* __restrict__ count,
                                                    const ObjOut oo) {
-  __shared__ Smem<NUM, GAP> sm;
+  __shared__ Smem<NUM, GAP, IN> sm;
   const int n = list ? __builtin_amdgcn_readfirstlane(*count) : B;
   // XCD-aware order: workgroup i runs on XCD i mod 8, so with one workgroup per QP each XCD
   // takes a contiguous range of QPs and the 128-B lines of x_ref / u / x are fetched and
@@ -2370,7 +2397,7 @@ __global__ __launch_bounds__(64) F110QP_SOLVE_ATTR void solve_kernel(const KPara
     const int xi = item & 7;
     const int b = list ? __builtin_amdgcn_readfirstlane(list[item])
                        : (xcd ? xi * per + (xi < rem ? xi : rem) + (item >> 3) : item);
-    solve_qp<NUM, GAP>(sm, b, P, x0g, ulg, xrg, hsg, uout, xout, status_out, iters_out, Hdbg,
+    solve_qp<NUM, GAP, IN>(sm, b, P, x0g, ulg, xrg, hsg, uout, xout, status_out, iters_out, Hdbg,
                        gdbg, ws, oo);
     wsync();
   }
@@ -2380,45 +2407,45 @@ __global__ __launch_bounds__(64) F110QP_SOLVE_ATTR void solve_kernel(const KPara
 // Grouped mode, prepare launch: one wave per group builds the closed-form Hessian and the swept
 // inverse of the group's leader (the smallest member index; none -> the slot is marked empty)
 // and publishes W and the key of its linearisation point (theta0, v, delta) to the group slot.
-template <int NUM, bool GAP>
+template <int NUM, bool GAP, typename IN = float>
 __global__ __launch_bounds__(64) void group_prep_kernel(const KParams P, const int G,
-                                                        const float* __restrict__ x0g,
-                                                        const float* __restrict__ ulg,
-                                                        const float* __restrict__ xrg,
+                                                        const IN* __restrict__ x0g,
+                                                        const IN* __restrict__ ulg,
+                                                        const IN* __restrict__ xrg,
                                                         const float* __restrict__ hsg,
                                                         const WarmState ws,
                                                         const int* __restrict__ leader,
                                                         const int B) {
-  __shared__ Smem<NUM, GAP> sm;
+  __shared__ Smem<NUM, GAP, IN> sm;
   const int g = blockIdx.x;
   const int b = __builtin_amdgcn_readfirstlane(leader[g]);
   if (b < 0 || b >= B) {
-    if (threadIdx.x == 0) ws.key[4 * g + 3] = 0u;
+    if (threadIdx.x == 0) ws.key[kKeyWords<IN> * g + kKeyWords<IN> - 1] = 0u;
     return;
   }
-  solve_qp<NUM, GAP>(sm, b, P, x0g, ulg, xrg, hsg, nullptr, nullptr, nullptr, nullptr, nullptr,
+  solve_qp<NUM, GAP, IN>(sm, b, P, x0g, ulg, xrg, hsg, nullptr, nullptr, nullptr, nullptr, nullptr,
                      nullptr, ws, ObjOut(), g);
 }
 
 // ------------------------------------------------------------------------------------------
 // launch of one instantiation
 // ------------------------------------------------------------------------------------------
-template <int NUM, bool GAP>
-hipError_t launch_t(const KParams& P, int B, const float* x0, const float* ul, const float* xr,
+template <int NUM, bool GAP, typename IN>
+hipError_t launch_t(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
                     const float* hs, float* uo, float* xo, int* st, int* its, double* Hd,
                     double* gd, const WarmState& ws, const int* list, const int* count, int grid,
                     const ObjOut& oo, hipStream_t s) {
-  hipLaunchKernelGGL((solve_kernel<NUM, GAP>), dim3(grid), dim3(64), 0, s, P, B, x0, ul, xr, hs,
+  hipLaunchKernelGGL((solve_kernel<NUM, GAP, IN>), dim3(grid), dim3(64), 0, s, P, B, x0, ul, xr, hs,
                      uo, xo, st, its, Hd, gd, ws, list, count, oo);
   return hipGetLastError();
 }
 
-template <int NUM, bool GAP>
-hipError_t launch_prep_t(const KParams& P, int B, const float* x0, const float* ul,
-                         const float* xr, const float* hs, const WarmState& ws, const int* leader,
+template <int NUM, bool GAP, typename IN>
+hipError_t launch_prep_t(const KParams& P, int B, const IN* x0, const IN* ul,
+                         const IN* xr, const float* hs, const WarmState& ws, const int* leader,
                          hipStream_t s) {
   if (ws.ngroups <= 0) return hipSuccess;
-  hipLaunchKernelGGL((group_prep_kernel<NUM, GAP>), dim3(ws.ngroups), dim3(64), 0, s, P,
+  hipLaunchKernelGGL((group_prep_kernel<NUM, GAP, IN>), dim3(ws.ngroups), dim3(64), 0, s, P,
                      ws.ngroups, x0, ul, xr, hs, ws, leader, B);
   return hipGetLastError();
 }

@@ -94,6 +94,11 @@ EXPORTED = (
     "f110qp_warm_hits",
     "f110qp_sync_signals",
     "f110qp_test_build",
+    "f110qp_solve_batch_dbl",
+    "f110qp_solve_batch_dev_dbl",
+    "f110qp_solve_batch_dev_sync_dbl",
+    "f110qp_solve_grouped_dbl",
+    "f110qp_solve_grouped_dev_dbl",
 )
 SCRATCH_NAMES = {0: "none (wave back end)", 1: "LDS fp64", 2: "LDS fp32", 3: "HBM fp64", 4: "HBM fp32"}
 
@@ -161,6 +166,11 @@ def load(test: bool = False):
     L.f110qp_solve_batch_ex_dev.argtypes = [C.c_void_p, C.c_int] + [fp] * 11
     L.f110qp_solve_grouped_ex.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 6
     L.f110qp_solve_grouped_ex_dev.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 7
+    L.f110qp_solve_batch_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 10
+    L.f110qp_solve_batch_dev_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 11
+    L.f110qp_solve_batch_dev_sync_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 9
+    L.f110qp_solve_grouped_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 6
+    L.f110qp_solve_grouped_dev_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 7
     L.f110qp_select_dev.argtypes = [C.c_int, fp, C.c_int, fp, fp, fp, fp, fp]
     L.f110qp_backend_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
     L.f110qp_lane_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -219,6 +229,15 @@ def qp_dims(horizon: int):
 
 def _p(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _f64(a, shape, name: str):
+    """A host input of a *_dbl call: a float64 numpy array, taken as it is (no cast: a float32 array
+    here is a caller that has already lost what these entry points exist to keep)."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.float64:
+        got = a.dtype if isinstance(a, np.ndarray) else type(a).__name__
+        raise F110QPError(f"{name} must be a float64 numpy array, got {got}")
+    return np.ascontiguousarray(a).reshape(shape)
 
 
 def _tp(t):
@@ -363,12 +382,13 @@ class Solver:
         return u, x, st, it
 
     def _check_dev(self, x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters=None, obj=None, cost=None,
-                   group=None):
-        """Shapes, element types and placement of a device call's tensors (see _dev)."""
+                   group=None, fin="f32"):
+        """Shapes, element types and placement of a device call's tensors (see _dev). fin: the
+        element type of x0 / u_lin / x_ref ("f64" for the *_dbl calls)."""
         B = int(x0.shape[0])
         N = self.horizon
         S = self.config.x_ref_points or N
-        specs = [(x0, "f32", 3 * B, "x0"), (u_lin, "f32", 2 * B, "u_lin"), (x_ref, "f32", 3 * S * B, "x_ref"),
+        specs = [(x0, fin, 3 * B, "x0"), (u_lin, fin, 2 * B, "u_lin"), (x_ref, fin, 3 * S * B, "x_ref"),
                  (halfspace, "f32", 6 * B, "halfspace", self.config.gap_mode == GAP_INACTIVE),
                  (u_out, "f32", 2 * N * B, "u_out"), (x_out, "f32", 3 * (N + 1) * B, "x_out"),
                  (status, "i32", B, "status"), (iters, "i32", B, "iters", True), (obj, "f64", B, "obj", True),
@@ -397,6 +417,84 @@ class Solver:
         self._chk(self.lib.f110qp_solve_batch_dev(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace),
                                                _tp(u_out), _tp(x_out), _tp(status), _tp(iters),
                                                C.c_void_p(stream.cuda_stream)), "f110qp_solve_batch_dev")
+
+    def solve_dbl(self, x0, u_lin, x_ref, halfspace=None, objective=False):
+        """solve() on float64 x0 / u_lin / x_ref, passed unrounded (f110qp_solve_batch_dbl); any
+        other element type is rejected. Outputs as solve()."""
+        N = self.horizon
+        x0 = _f64(x0, (-1, 3), "x0")
+        B = x0.shape[0]
+        ul = _f64(u_lin, (B, 2), "u_lin")
+        xr = _f64(x_ref, (B, self.config.x_ref_points or N, 3), "x_ref")
+        hs = None if halfspace is None else np.ascontiguousarray(halfspace, np.float32).reshape(B, 6)
+        u = np.empty((B, N, 2), np.float32)
+        x = np.empty((B, N + 1, 3), np.float32)
+        st = np.empty(B, np.int32)
+        it = np.empty(B, np.int32)
+        ob = np.empty(B, np.float64) if objective else None
+        co = np.empty(B, np.float64) if objective else None
+        self._chk(self.lib.f110qp_solve_batch_dbl(self._h, B, _p(x0), _p(ul), _p(xr), _p(hs), _p(u), _p(x), _p(st),
+                                                  _p(it), _p(ob), _p(co)), "f110qp_solve_batch_dbl")
+        return (u, x, st, it, ob, co) if objective else (u, x, st, it)
+
+    def solve_dev_dbl(self, x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters=None, stream=None,
+                      obj=None, cost=None, sync=False):
+        """solve_dev() on float64 device tensors x0 / u_lin / x_ref (f110qp_solve_batch_dev_dbl);
+        sync=True: f110qp_solve_batch_dev_sync_dbl (returns with the results in device memory; no
+        obj / cost)."""
+        import torch
+
+        if sync and (obj is not None or cost is not None):
+            raise F110QPError("f110qp_solve_batch_dev_sync_dbl has no obj / cost outputs")
+        B = self._check_dev(x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, obj, cost, fin="f64")
+        if stream is None:
+            stream = torch.cuda.current_stream(x0.device)
+        if sync:
+            self._chk(self.lib.f110qp_solve_batch_dev_sync_dbl(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref),
+                                                               _tp(halfspace), _tp(u_out), _tp(x_out), _tp(status),
+                                                               _tp(iters), C.c_void_p(stream.cuda_stream)),
+                      "f110qp_solve_batch_dev_sync_dbl")
+            return
+        self._chk(self.lib.f110qp_solve_batch_dev_dbl(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace),
+                                                      _tp(u_out), _tp(x_out), _tp(status), _tp(iters), _tp(obj),
+                                                      _tp(cost), C.c_void_p(stream.cuda_stream)),
+                  "f110qp_solve_batch_dev_dbl")
+
+    def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
+        """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
+        N = self.horizon
+        x0 = _f64(x0, (-1, 3), "x0")
+        B = x0.shape[0]
+        ul = _f64(u_lin, (B, 2), "u_lin")
+        xr = _f64(x_ref, (B, self.config.x_ref_points or N, 3), "x_ref")
+        hs = None if halfspace is None else np.ascontiguousarray(halfspace, np.float32).reshape(B, 6)
+        g = np.ascontiguousarray(group, np.int32).reshape(B)
+        G = int(g.max()) + 1 if num_groups is None else int(num_groups)
+        u = np.empty((B, N, 2), np.float32)
+        x = np.empty((B, N + 1, 3), np.float32)
+        st = np.empty(B, np.int32)
+        it = np.empty(B, np.int32)
+        ob = np.empty(B, np.float64) if objective else None
+        co = np.empty(B, np.float64) if objective else None
+        self._chk(self.lib.f110qp_solve_grouped_dbl(self._h, B, _p(x0), _p(ul), _p(xr), _p(hs), _p(g), G, _p(u),
+                                                    _p(x), _p(st), _p(it), _p(ob), _p(co)), "f110qp_solve_grouped_dbl")
+        return (u, x, st, it, ob, co) if objective else (u, x, st, it)
+
+    def solve_grouped_dev_dbl(self, x0, u_lin, x_ref, halfspace, group, num_groups, u_out, x_out, status,
+                              iters=None, stream=None, obj=None, cost=None):
+        """solve_grouped_dev() on float64 device tensors x0 / u_lin / x_ref
+        (f110qp_solve_grouped_dev_dbl)."""
+        import torch
+
+        B = self._check_dev(x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, obj, cost, group=group,
+                            fin="f64")
+        if stream is None:
+            stream = torch.cuda.current_stream(x0.device)
+        self._chk(self.lib.f110qp_solve_grouped_dev_dbl(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace),
+                                                        _tp(group), int(num_groups), _tp(u_out), _tp(x_out),
+                                                        _tp(status), _tp(iters), _tp(obj), _tp(cost),
+                                                        C.c_void_p(stream.cuda_stream)),
+                  "f110qp_solve_grouped_dev_dbl")
 
     def prepare_dev(self, x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters=None, stream=None,
                     sync=False):

@@ -58,14 +58,16 @@ void MPC::Update(State current_state, Input input, std::vector<State>& desired) 
     return;
   }
   const int N = horizon_;
-  float x0[3] = {static_cast<float>(current_state.x()), static_cast<float>(current_state.y()),
-                 static_cast<float>(current_state.ori())};
-  float ul[2] = {static_cast<float>(input.v()), static_cast<float>(input.steer_ang())};
-  std::vector<float> xr(3 * N), u(2 * N), x(3 * (N + 1));
+  // State / Input hold doubles (state.h:41-43, input.h:31-32) and the reference uses them unrounded
+  // (mpc.cpp:225-228,299,305): they cross the ABI as they are (f110qp_solve_batch_dbl)
+  const double x0[3] = {current_state.x(), current_state.y(), current_state.ori()};
+  const double ul[2] = {input.v(), input.steer_ang()};
+  std::vector<double> xr(3 * N);
+  std::vector<float> u(2 * N), x(3 * (N + 1));
   for (int i = 0; i < N; i++) {
-    xr[3 * i + 0] = static_cast<float>(desired[i].x());
-    xr[3 * i + 1] = static_cast<float>(desired[i].y());
-    xr[3 * i + 2] = static_cast<float>(desired[i].ori());
+    xr[3 * i + 0] = desired[i].x();
+    xr[3 * i + 1] = desired[i].y();
+    xr[3 * i + 2] = desired[i].ori();
   }
   float hs[6];
   const float* hsp = nullptr;
@@ -82,8 +84,8 @@ void MPC::Update(State current_state, Input input, std::vector<State>& desired) 
     hsp = hs;
   }
   int status = 0;
-  if (f110qp_solve_batch(ctx_, 1, x0, ul, xr.data(), hsp, u.data(), x.data(), &status, nullptr) !=
-      F110QP_OK) {
+  if (f110qp_solve_batch_dbl(ctx_, 1, x0, ul, xr.data(), hsp, u.data(), x.data(), &status, nullptr, nullptr,
+                             nullptr) != F110QP_OK) {
     std::fprintf(stderr, "solve failed: %s\n", f110qp_last_error());
     return;
   }
@@ -104,19 +106,19 @@ std::vector<int> MPC::UpdateBatch(State current_state, Input input,
   const int N = horizon_;
   std::vector<int> status(B, 0);
   if (!ctx_ || B == 0) return status;
-  std::vector<float> x0(3 * B), ul(2 * B), xr(static_cast<size_t>(3) * N * B);
+  std::vector<double> x0(3 * B), ul(2 * B), xr(static_cast<size_t>(3) * N * B);  // unrounded, as Update
   for (int b = 0; b < B; b++) {
-    x0[3 * b + 0] = static_cast<float>(current_state.x());
-    x0[3 * b + 1] = static_cast<float>(current_state.y());
-    x0[3 * b + 2] = static_cast<float>(current_state.ori());
-    ul[2 * b + 0] = static_cast<float>(input.v());
-    ul[2 * b + 1] = static_cast<float>(input.steer_ang());
+    x0[3 * b + 0] = current_state.x();
+    x0[3 * b + 1] = current_state.y();
+    x0[3 * b + 2] = current_state.ori();
+    ul[2 * b + 0] = input.v();
+    ul[2 * b + 1] = input.steer_ang();
     const auto& c = candidates[b];
     for (int i = 0; i < N; i++) {
       const State& s = c[i < static_cast<int>(c.size()) ? i : c.size() - 1];
-      xr[(static_cast<size_t>(b) * N + i) * 3 + 0] = static_cast<float>(s.x());
-      xr[(static_cast<size_t>(b) * N + i) * 3 + 1] = static_cast<float>(s.y());
-      xr[(static_cast<size_t>(b) * N + i) * 3 + 2] = static_cast<float>(s.ori());
+      xr[(static_cast<size_t>(b) * N + i) * 3 + 0] = s.x();
+      xr[(static_cast<size_t>(b) * N + i) * 3 + 1] = s.y();
+      xr[(static_cast<size_t>(b) * N + i) * 3 + 2] = s.ori();
     }
   }
   std::vector<float> hsv;
@@ -132,8 +134,8 @@ std::vector<int> MPC::UpdateBatch(State current_state, Input input,
   }
   u_out->assign(static_cast<size_t>(2) * N * B, 0.f);
   x_out->assign(static_cast<size_t>(3) * (N + 1) * B, 0.f);
-  if (f110qp_solve_batch(ctx_, B, x0.data(), ul.data(), xr.data(), hsv.empty() ? nullptr : hsv.data(),
-                         u_out->data(), x_out->data(), status.data(), nullptr) != F110QP_OK)
+  if (f110qp_solve_batch_dbl(ctx_, B, x0.data(), ul.data(), xr.data(), hsv.empty() ? nullptr : hsv.data(),
+                             u_out->data(), x_out->data(), status.data(), nullptr, nullptr, nullptr) != F110QP_OK)
     std::fill(status.begin(), status.end(), 0);
   return status;
 }

@@ -241,6 +241,62 @@ int f110qp_solve_grouped_ex_dev(f110qp_ctx* ctx, int batch, const float* x0, con
                                 int num_groups, float* u_out, float* x_out, int* status,
                                 int* iters, double* obj, double* cost, void* stream);
 
+/* ---- double-precision inputs ------------------------------------------------------------------
+ * The reference holds State, Input and the reference path as double (include/f110-mpc/state.h:41-43,
+ * include/f110-mpc/input.h:31-32, used unrounded in src/mpc.cpp:225-228,299,305). The *_dbl entry
+ * points take x0 [B][3], u_lin [B][2] and x_ref [B][S][3] as double, same row-major shapes; every
+ * other argument keeps its type (halfspace float32, as the reference's float pairs; u_out / x_out
+ * float32; status, iters, obj, cost unchanged; obj and cost may be NULL). Additive: the float entry
+ * points above are unchanged and F110QP_API_VERSION stays 6.
+ *  - The kernels read the doubles themselves (double-input instantiations of every kernel family):
+ *    nothing is narrowed on the host, no conversion launch runs in front of the solve, and a call
+ *    makes the same launches as its float twin. Past the loads the arithmetic is the float call's:
+ *    x_ref - x0, theta0, v and delta in fp64. For doubles that are float32 values the outputs are
+ *    bit-identical to the float call's, except on the sequential lane kernel with float references
+ *    in LDS (scratch modes of large batches, more than one wave per CU): there the _dbl kernel
+ *    stages x_ref - x0, subtracted in fp64 and rounded to float32, where the float kernel stages
+ *    the absolute float32 reference.
+ *  - The launch policy is the float call's: f110qp_backend_info, f110qp_lane_segments,
+ *    f110qp_lane_starts and f110qp_gap_screen answer for both.
+ *  - The completion-word waits (f110qp_sync_signals) and the <= 64-QP zero-copy staging of the
+ *    host-pointer call work as for float; its packed pinned input layout has 8-byte fields for the
+ *    three double arrays (8-byte aligned), the float half-spaces behind them.
+ *  - Warm start: on a warm_start = 1 context a _dbl call solves cold and neither reads nor updates
+ *    the per-slot state (as the grouped calls). The slot key is three float bit patterns in 16
+ *    bytes; a key that does not compare all 64 bits of theta0, v and delta could reuse a factor
+ *    built for another linearisation point. A wider slot key is not part of this ABI version.
+ *    f110qp_warm_hits is not moved by _dbl calls; float calls on the same context hit as before.
+ *  - Grouped, wave back end: the per-group key of a _dbl call holds the full doubles of
+ *    (x0[b][2], u_lin[b]) (32 bytes per group, allocated per call), so two scenarios whose
+ *    linearisation points share their float32 rounding but differ as doubles never share a W.
+ *    Results are bit-identical to f110qp_solve_batch_dev_dbl on the wave back end. The lane back
+ *    end ignores the groups, as for float.
+ *  - x_out is the absolute state in float32: far from the origin it carries the float32 rounding of
+ *    the position, up to half an ulp of |x| (6e-5 m at 1 km), and x_out[b][0] is x0 rounded to
+ *    float32. u_out, which MPC::Update consumes (src/mpc.cpp:148-157), is not affected.
+ *  - The debug hooks f110qp_condense_debug_dev / f110qp_assemble_debug_dev stay float-only. */
+int f110qp_solve_batch_dbl(f110qp_ctx* ctx, int batch, const double* x0, const double* u_lin,
+                           const double* x_ref, const float* halfspace, float* u_out, float* x_out,
+                           int* status, int* iters, double* obj, double* cost);
+/* device pointers, asynchronous on `stream` */
+int f110qp_solve_batch_dev_dbl(f110qp_ctx* ctx, int batch, const double* x0, const double* u_lin,
+                               const double* x_ref, const float* halfspace, float* u_out,
+                               float* x_out, int* status, int* iters, double* obj, double* cost,
+                               void* stream);
+/* as f110qp_solve_batch_dev_sync */
+int f110qp_solve_batch_dev_sync_dbl(f110qp_ctx* ctx, int batch, const double* x0,
+                                    const double* u_lin, const double* x_ref,
+                                    const float* halfspace, float* u_out, float* x_out, int* status,
+                                    int* iters, void* stream);
+int f110qp_solve_grouped_dbl(f110qp_ctx* ctx, int batch, const double* x0, const double* u_lin,
+                             const double* x_ref, const float* halfspace, const int* group,
+                             int num_groups, float* u_out, float* x_out, int* status, int* iters,
+                             double* obj, double* cost);
+int f110qp_solve_grouped_dev_dbl(f110qp_ctx* ctx, int batch, const double* x0, const double* u_lin,
+                                 const double* x_ref, const float* halfspace, const int* group,
+                                 int num_groups, float* u_out, float* x_out, int* status,
+                                 int* iters, double* obj, double* cost, void* stream);
+
 /* Per-scenario selection on the device: the candidate argmin of
  * project::OdomCallback (src/project.cpp:125-136), taken over the QP costs of each scenario's
  * candidates instead of the end-point distance. winner[g] = the smallest b with group[b] == g,
