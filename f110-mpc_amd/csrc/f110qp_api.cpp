@@ -8,6 +8,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -102,6 +103,8 @@ struct f110qp_ctx {
   DevBuf dgrp;               // host-pointer grouped calls: device copy of the group ids
   DevBuf lscr;               // lane back end: HBM Riccati scratch (when not in LDS)
   DevBuf hand;               // gap rows: counts and lists (f110qp::HandLayout, kHandInts(B) ints)
+  DevBuf rplan;              // rollout: one tick's u_plan | x_plan when the caller keeps neither
+  DevBuf rdev;               // host-pointer rollout: device copies of its arrays
   int lane_kmax = 16;        // lane back end: PDAS passes before single (least-index) flips
   int lane_mode = 0;         // lane scratch placement (LaneWork::mode)
   int lane_qpw = 0;          // lane QPs per wave (LaneWork::qpw, 0 = auto)
@@ -304,6 +307,7 @@ void f110qp_destroy(f110qp_ctx* c) {
   c->wW.release(); c->wkey.release(); c->wact.release();
   c->lscr.release();
   c->hand.release();
+  c->rplan.release(); c->rdev.release();
   c->gW.release(); c->gkey.release(); c->glead.release(); c->dgrp.release();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -721,6 +725,177 @@ int f110qp_select_dev(int batch, const int* group, int num_groups, const double*
   hipError_t e = f110qp::launch_select(batch, group, num_groups, cost, status, winner, best_cost,
                                        (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "select kernel launch");
+  return F110QP_OK;
+}
+
+}  // extern "C"
+
+// ---- closed loop on the device (f110qp_advance_dev, f110qp_rollout[_dev]) ------------------------
+
+static int rollout_params(const f110qp_rollout_config* rc, bool ticks, f110qp::AdvanceParams* ap) {
+  if (!rc) return fail(F110QP_ERR_INVALID, "rollout config is NULL");
+  if (ticks && rc->ticks < 1) return fail(F110QP_ERR_INVALID, "ticks must be >= 1");
+  if (!(rc->plant_dt > 0.0) || !std::isfinite(rc->plant_dt))
+    return fail(F110QP_ERR_INVALID, "plant_dt must be positive and finite");
+  if (!(rc->car_length > 0.0) || !std::isfinite(rc->car_length))
+    return fail(F110QP_ERR_INVALID, "car_length must be positive and finite");
+  if (!std::isfinite(rc->v_lin) || !std::isfinite(rc->fail_u[0]) || !std::isfinite(rc->fail_u[1]))
+    return fail(F110QP_ERR_INVALID, "v_lin and fail_u must be finite");
+  ap->plant_dt = rc->plant_dt;
+  ap->car_length = rc->car_length;
+  ap->v_lin = rc->v_lin;
+  ap->fail_u[0] = rc->fail_u[0];
+  ap->fail_u[1] = rc->fail_u[1];
+  return F110QP_OK;
+}
+
+static bool aligned8(const void* p) { return ((uintptr_t)p & 7u) == 0; }
+
+// Argument checks of f110qp_rollout[_dev], all before any device call.
+static int check_rollout_args(f110qp_ctx* c, const f110qp_rollout_config* rc, int batch, const void* xr,
+                              const void* hs, const void* xt, const void* ult, const void* ua,
+                              const void* stt, f110qp::AdvanceParams* ap) {
+  if (!c) return fail(F110QP_ERR_INVALID, "ctx is NULL");
+  const int rv = rollout_params(rc, true, ap);
+  if (rv) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  if (batch == 0) return F110QP_OK;
+  if (!xr || !xt || !ult || !ua || !stt)
+    return fail(F110QP_ERR_INVALID, "x_ref/x_traj/u_lin_traj/u_applied/status_traj must be non-NULL");
+  if (c->cfg.gap_mode == F110QP_GAP_ACTIVE && !hs)
+    return fail(F110QP_ERR_INVALID, "gap_mode ACTIVE needs the halfspace array");
+  if (batch > (1 << 30) / 64) return fail(F110QP_ERR_INVALID, "batch too large");
+  return F110QP_OK;
+}
+
+// The T ticks of a checked rollout on device pointers: every workspace is sized in front of the
+// loop, the loop itself only launches (per tick the launches of one _dbl solve call, then the plant
+// step).
+static int rollout_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, int T, int batch, const double* xr,
+                         const float* hs, double* xt, double* ult, float* ua, int* stt, int* itt,
+                         double* cot, float* up, float* xp, hipStream_t s) {
+  const size_t B = (size_t)batch, N = (size_t)c->cfg.horizon;
+  const size_t n_up = B * N * 2, n_xp = B * (N + 1) * 3;
+  if (!aligned8(ua) || !aligned8(up)) return fail(F110QP_ERR_INVALID, "u_applied / u_plan must be 8-byte aligned");
+  float* wup = nullptr;
+  float* wxp = nullptr;
+  if (!up || !xp) {
+    const hipError_t e = c->rplan.ensure((n_up + n_xp) * sizeof(float));
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc rollout plan workspace");
+    wup = (float*)c->rplan.p;
+    wxp = wup + n_up;
+  }
+  const float* h = (c->cfg.gap_mode == F110QP_GAP_ACTIVE) ? hs : nullptr;
+  int backend;
+  f110qp::LaneWork lw;
+  const int rc = lane_work(c, batch, s, &backend, &lw);
+  if (rc) return rc;
+  for (size_t t = 0; t < (size_t)T; t++) {
+    float* u_t = up ? up + t * n_up : wup;
+    float* x_t = xp ? xp + t * n_xp : wxp;
+    int* st_t = stt + t * B;
+    f110qp::ObjOut oo;
+    oo.cost = cot ? cot + t * B : nullptr;
+    hipError_t e = f110qp::launch_solve(c->kp, batch, (const double*)(xt + t * B * 3),
+                                        (const double*)(ult + t * B * 2), xr, h, u_t, x_t, st_t,
+                                        itt ? itt + t * B : nullptr, f110qp::WarmState(), backend, lw, oo, s);
+    if (e != hipSuccess) return hip_fail(e, "rollout solve launch");
+    e = f110qp::launch_advance(ap, batch, (int)N, xt + t * B * 3, u_t, st_t, xt + (t + 1) * B * 3,
+                               ult + (t + 1) * B * 2, ua + t * B * 2, s);
+    if (e != hipSuccess) return hip_fail(e, "plant step launch");
+  }
+  return F110QP_OK;
+}
+
+extern "C" {
+
+void f110qp_default_rollout_config(f110qp_rollout_config* rc) {
+  if (!rc) return;
+  std::memset(rc, 0, sizeof(*rc));
+  rc->ticks = 1;
+  rc->plant_dt = 0.01;    // params.yaml:13
+  rc->car_length = 0.35;  // CAR_LENGTH, src/model.cpp:2
+  rc->v_lin = 4.5;        // src/project.cpp:170
+  rc->fail_u[0] = 0.5;    // Input(0.5, 0.0), src/project.cpp:215
+  rc->fail_u[1] = 0.0;
+}
+
+int f110qp_advance_dev(const f110qp_rollout_config* rc, int batch, int horizon, const double* x,
+                       const float* u_plan, const int* status, double* x_next, double* u_lin_next,
+                       float* u_applied, void* stream) {
+  f110qp::AdvanceParams ap;
+  const int rv = rollout_params(rc, false, &ap);
+  if (rv) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  if (horizon < 1 || horizon > F110QP_MAX_HORIZON) return fail(F110QP_ERR_INVALID, "horizon must be in [1, 48]");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !u_plan || !status || !x_next || !u_lin_next)
+    return fail(F110QP_ERR_INVALID, "x/u_plan/status/x_next/u_lin_next must be non-NULL");
+  if (x_next == x) return fail(F110QP_ERR_INVALID, "x_next must not alias x");
+  if (!aligned8(u_plan) || !aligned8(u_applied))
+    return fail(F110QP_ERR_INVALID, "u_plan / u_applied must be 8-byte aligned");
+  const hipError_t e = f110qp::launch_advance(ap, batch, horizon, x, u_plan, status, x_next, u_lin_next,
+                                              u_applied, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "plant step launch");
+  return F110QP_OK;
+}
+
+int f110qp_rollout_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, int batch, const double* xr,
+                       const float* hs, double* xt, double* ult, float* ua, int* stt, int* itt,
+                       double* cot, float* up, float* xp, void* stream) {
+  f110qp::AdvanceParams ap;
+  const int rv = check_rollout_args(c, rc, batch, xr, hs, xt, ult, ua, stt, &ap);
+  if (rv || batch == 0) return rv;
+  return rollout_ticks(c, ap, rc->ticks, batch, xr, hs, xt, ult, ua, stt, itt, cot, up, xp, (hipStream_t)stream);
+}
+
+int f110qp_rollout(f110qp_ctx* c, const f110qp_rollout_config* rc, int batch, const double* xr,
+                   const float* hs, double* xt, double* ult, float* ua, int* stt, int* itt,
+                   double* cot, float* up, float* xp) {
+  f110qp::AdvanceParams ap;
+  const int rv = check_rollout_args(c, rc, batch, xr, hs, xt, ult, ua, stt, &ap);
+  if (rv || batch == 0) return rv;
+  hipError_t e = hipSetDevice(c->cfg.device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  if (!c->stream) {
+    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamCreate");
+  }
+  hipStream_t s = c->stream;
+  const bool gap = c->cfg.gap_mode == F110QP_GAP_ACTIVE;
+  const size_t B = (size_t)batch, N = (size_t)c->cfg.horizon, S = (size_t)c->kp.xr_stride, T = (size_t)rc->ticks;
+  // device layout, the 8-byte fields first: x_ref | x_traj | u_lin_traj | cost | halfspace |
+  // u_applied | status | iters | u_plan | x_plan (status and iters padded to 8 bytes; every other
+  // 4-byte field in front of u_plan is a whole number of 8 bytes, so u_applied and u_plan are aligned)
+  const size_t s_xr = B * S * 3 * 8, s_xt = (T + 1) * B * 3 * 8, s_ul = (T + 1) * B * 2 * 8;
+  const size_t s_co = cot ? T * B * 8 : 0, s_hs = gap ? B * 6 * 4 : 0, s_ua = T * B * 2 * 4;
+  const size_t s_st = T * B * 4, p_st = (s_st + 7) & ~(size_t)7, s_it = itt ? s_st : 0, p_it = itt ? p_st : 0;
+  const size_t s_up = up ? T * B * N * 2 * 4 : 0, s_xp = xp ? T * B * (N + 1) * 3 * 4 : 0;
+  const size_t o_xt = s_xr, o_ul = o_xt + s_xt, o_co = o_ul + s_ul, o_hs = o_co + s_co, o_ua = o_hs + s_hs;
+  const size_t o_st = o_ua + s_ua, o_it = o_st + p_st, o_up = o_it + p_it, o_xp = o_up + s_up;
+  if ((e = c->rdev.ensure(o_xp + s_xp)) != hipSuccess) return hip_fail(e, "hipMalloc rollout staging");
+  char* d = (char*)c->rdev.p;
+  if ((e = hipMemcpyAsync(d, xr, s_xr, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(d + o_xt, xt, B * 3 * 8, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(d + o_ul, ult, B * 2 * 8, hipMemcpyHostToDevice, s)) ||
+      (gap && (e = hipMemcpyAsync(d + o_hs, hs, s_hs, hipMemcpyHostToDevice, s))))
+    return hip_fail(e, "hipMemcpyAsync H2D");
+  const int rt = rollout_ticks(c, ap, rc->ticks, batch, (const double*)d, gap ? (const float*)(d + o_hs) : nullptr,
+                               (double*)(d + o_xt), (double*)(d + o_ul), (float*)(d + o_ua), (int*)(d + o_st),
+                               itt ? (int*)(d + o_it) : nullptr, cot ? (double*)(d + o_co) : nullptr,
+                               up ? (float*)(d + o_up) : nullptr, xp ? (float*)(d + o_xp) : nullptr, s);
+  if (rt) return rt;
+  // rows 1..T of the trajectories (row 0 is the caller's), then every recorded array
+  if ((e = hipMemcpyAsync(xt + B * 3, d + o_xt + B * 3 * 8, T * B * 3 * 8, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(ult + B * 2, d + o_ul + B * 2 * 8, T * B * 2 * 8, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(ua, d + o_ua, s_ua, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(stt, d + o_st, s_st, hipMemcpyDeviceToHost, s)) ||
+      (itt && (e = hipMemcpyAsync(itt, d + o_it, s_it, hipMemcpyDeviceToHost, s))) ||
+      (cot && (e = hipMemcpyAsync(cot, d + o_co, s_co, hipMemcpyDeviceToHost, s))) ||
+      (up && (e = hipMemcpyAsync(up, d + o_up, s_up, hipMemcpyDeviceToHost, s))) ||
+      (xp && (e = hipMemcpyAsync(xp, d + o_xp, s_xp, hipMemcpyDeviceToHost, s))))
+    return hip_fail(e, "hipMemcpyAsync D2H");
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
   return F110QP_OK;
 }
 

@@ -219,6 +219,23 @@ hipError_t launch_solve_grouped(const KParams& P, int B, const IN* x0, const IN*
 hipError_t launch_select(int B, const int* group, int G, const double* cost, const int* status,
                          int* winner, double* best, hipStream_t stream);
 
+// Plant step of the closed loop (rollout_kernels.hip): kernel-side copy of f110qp_rollout_config
+// without its tick count.
+struct AdvanceParams {
+  double plant_dt;    // Euler step of Model::simulate_dynamics
+  double car_length;  // CAR_LENGTH of src/model.cpp:2
+  double v_lin;       // v of the next linearisation input (src/project.cpp:170)
+  double fail_u[2];   // Input of GetNextInput() without a solution (src/project.cpp:215)
+};
+
+// One Euler step of B cars on the first input of their plans u_plan [B][N][2] (a solve's u_out,
+// 8-byte aligned), and the next linearisation input: x [B][3] -> x_next [B][3], u_lin_next [B][2],
+// u_applied [B][2] (float32, 8-byte aligned, may be null). A car whose status is not SOLVED /
+// SOLVED_INACCURATE (its plan is NaN) takes fail_u. One thread per car, one launch.
+hipError_t launch_advance(const AdvanceParams& P, int B, int N, const double* x, const float* u_plan,
+                          const int* status, double* x_next, double* u_lin_next, float* u_applied,
+                          hipStream_t stream);
+
 // Dump the condensed H (B x 2N x 2N) and g (B x 2N) as built by the solve kernel.
 hipError_t launch_condense_debug(const KParams& P, int B, const float* x0, const float* u_lin,
                                  const float* x_ref, double* H, double* g, hipStream_t stream);

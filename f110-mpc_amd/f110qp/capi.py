@@ -99,6 +99,10 @@ EXPORTED = (
     "f110qp_solve_batch_dev_sync_dbl",
     "f110qp_solve_grouped_dbl",
     "f110qp_solve_grouped_dev_dbl",
+    "f110qp_default_rollout_config",
+    "f110qp_advance_dev",
+    "f110qp_rollout_dev",
+    "f110qp_rollout",
 )
 SCRATCH_NAMES = {0: "none (wave back end)", 1: "LDS fp64", 2: "LDS fp32", 3: "HBM fp64", 4: "HBM fp32"}
 
@@ -132,6 +136,16 @@ class PlanConfig(C.Structure):
         ("steer_discrete", C.c_int),
         ("traj_discrete", C.c_int),
         ("dt", C.c_double),
+    ]
+
+
+class RolloutConfig(C.Structure):
+    _fields_ = [
+        ("ticks", C.c_int),
+        ("plant_dt", C.c_double),
+        ("car_length", C.c_double),
+        ("v_lin", C.c_double),
+        ("fail_u", C.c_double * 2),
     ]
 
 
@@ -171,6 +185,10 @@ def load(test: bool = False):
     L.f110qp_solve_batch_dev_sync_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 9
     L.f110qp_solve_grouped_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 6
     L.f110qp_solve_grouped_dev_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 7
+    L.f110qp_default_rollout_config.argtypes = [C.POINTER(RolloutConfig)]
+    L.f110qp_advance_dev.argtypes = [C.POINTER(RolloutConfig), C.c_int, C.c_int] + [fp] * 7
+    L.f110qp_rollout_dev.argtypes = [C.c_void_p, C.POINTER(RolloutConfig), C.c_int] + [fp] * 11
+    L.f110qp_rollout.argtypes = [C.c_void_p, C.POINTER(RolloutConfig), C.c_int] + [fp] * 10
     L.f110qp_select_dev.argtypes = [C.c_int, fp, C.c_int, fp, fp, fp, fp, fp]
     L.f110qp_backend_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
     L.f110qp_lane_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -215,6 +233,19 @@ def default_config(horizon: int, **over) -> Config:
             arr = getattr(c, k)
             for i, x in enumerate(v):
                 arr[i] = x
+        else:
+            setattr(c, k, v)
+    return c
+
+
+def default_rollout_config(**over) -> RolloutConfig:
+    """f110qp_default_rollout_config: ticks 1, plant_dt 0.01, car_length 0.35, v_lin 4.5, fail_u
+    (0.5, 0.0)."""
+    c = RolloutConfig()
+    load().f110qp_default_rollout_config(C.byref(c))
+    for k, v in over.items():
+        if k == "fail_u":
+            c.fail_u[0], c.fail_u[1] = v
         else:
             setattr(c, k, v)
     return c
@@ -460,6 +491,67 @@ class Solver:
                                                       _tp(cost), C.c_void_p(stream.cuda_stream)),
                   "f110qp_solve_batch_dev_dbl")
 
+    def rollout_dev(self, rc: RolloutConfig, x_ref, halfspace, x_traj, u_lin_traj, u_applied, status_traj,
+                    iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, stream=None):
+        """rc.ticks closed-loop ticks on device (torch) tensors, enqueued on `stream`, asynchronous
+        and without a host synchronisation (f110qp_rollout_dev): x_ref [B,S,3] f64 and halfspace
+        [B,2,3] f32 held fixed; x_traj [T+1,B,3] / u_lin_traj [T+1,B,2] f64 with row 0 the start;
+        u_applied [T,B,2] f32, status_traj [T,B] i32; iters_traj [T,B] i32, cost_traj [T,B] f64,
+        u_plan [T,B,N,2] and x_plan [T,B,N+1,3] f32 optional."""
+        import torch
+
+        T, N = int(rc.ticks), self.horizon
+        if T < 1:
+            raise F110QPError("ticks must be >= 1")
+        S = self.config.x_ref_points or N
+        B = int(x_ref.shape[0])
+        if tuple(x_traj.shape) != (T + 1, B, 3):
+            raise F110QPError(f"x_traj must be [ticks + 1, B, 3] = {(T + 1, B, 3)}, got {tuple(x_traj.shape)}")
+        _devs((x_ref, "f64", 3 * S * B, "x_ref"),
+              (halfspace, "f32", 6 * B, "halfspace", self.config.gap_mode == GAP_INACTIVE),
+              (x_traj, "f64", 3 * B * (T + 1), "x_traj"), (u_lin_traj, "f64", 2 * B * (T + 1), "u_lin_traj"),
+              (u_applied, "f32", 2 * B * T, "u_applied"), (status_traj, "i32", B * T, "status_traj"),
+              (iters_traj, "i32", B * T, "iters_traj", True), (cost_traj, "f64", B * T, "cost_traj", True),
+              (u_plan, "f32", 2 * N * B * T, "u_plan", True), (x_plan, "f32", 3 * (N + 1) * B * T, "x_plan", True))
+        if stream is None:
+            stream = torch.cuda.current_stream(x_traj.device)
+        self._chk(self.lib.f110qp_rollout_dev(self._h, C.byref(rc), B, _tp(x_ref), _tp(halfspace), _tp(x_traj),
+                                              _tp(u_lin_traj), _tp(u_applied), _tp(status_traj), _tp(iters_traj),
+                                              _tp(cost_traj), _tp(u_plan), _tp(x_plan),
+                                              C.c_void_p(stream.cuda_stream)), "f110qp_rollout_dev")
+
+    def rollout(self, x0, u_lin, x_ref, ticks, halfspace=None, plans=False, objective=False, rc=None):
+        """`ticks` closed-loop ticks from float64 host arrays x0 [B,3], u_lin [B,2], x_ref [B,S,3]
+        (f110qp_rollout, synchronous). rc: a RolloutConfig whose plant parameters to use (its ticks
+        is replaced). Returns a dict of numpy arrays: x_traj [T+1,B,3], u_lin_traj [T+1,B,2],
+        u_applied [T,B,2], status [T,B], iters [T,B]; plans=True adds u_plan [T,B,N,2] and x_plan
+        [T,B,N+1,3], objective=True adds cost [T,B]."""
+        N, T = self.horizon, int(ticks)
+        if T < 1:
+            raise F110QPError("ticks must be >= 1")
+        x0 = _f64(x0, (-1, 3), "x0")
+        B = x0.shape[0]
+        ul = _f64(u_lin, (B, 2), "u_lin")
+        xr = _f64(x_ref, (B, self.config.x_ref_points or N, 3), "x_ref")
+        hs = None if halfspace is None else np.ascontiguousarray(halfspace, np.float32).reshape(B, 6)
+        cfg = RolloutConfig()
+        C.memmove(C.byref(cfg), C.byref(rc if rc is not None else default_rollout_config()), C.sizeof(cfg))
+        cfg.ticks = T
+        out = {"x_traj": np.empty((T + 1, B, 3), np.float64), "u_lin_traj": np.empty((T + 1, B, 2), np.float64),
+               "u_applied": np.empty((T, B, 2), np.float32), "status": np.empty((T, B), np.int32),
+               "iters": np.empty((T, B), np.int32)}
+        out["x_traj"][0], out["u_lin_traj"][0] = x0, ul
+        if objective:
+            out["cost"] = np.empty((T, B), np.float64)
+        if plans:
+            out["u_plan"] = np.empty((T, B, N, 2), np.float32)
+            out["x_plan"] = np.empty((T, B, N + 1, 3), np.float32)
+        self._chk(self.lib.f110qp_rollout(self._h, C.byref(cfg), B, _p(xr), _p(hs), _p(out["x_traj"]),
+                                          _p(out["u_lin_traj"]), _p(out["u_applied"]), _p(out["status"]),
+                                          _p(out["iters"]), _p(out.get("cost")), _p(out.get("u_plan")),
+                                          _p(out.get("x_plan"))), "f110qp_rollout")
+        return out
+
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
         N = self.horizon
@@ -622,6 +714,23 @@ class Solver:
         self._chk(self.lib.f110qp_condense_debug_dev(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(H_out),
                                                   _tp(g_out), C.c_void_p(stream.cuda_stream)),
                "f110qp_condense_debug_dev")
+
+
+def advance_dev(rc: RolloutConfig, horizon: int, x, u_plan, status, x_next, u_lin_next, u_applied=None, stream=None):
+    """One plant step on the device (f110qp_advance_dev): x [B,3] f64, u_plan [B,N,2] f32 and status
+    [B] i32 of a solve -> x_next [B,3] f64 (not x itself), u_lin_next [B,2] f64, u_applied [B,2] f32
+    (optional). Asynchronous on `stream`."""
+    import torch
+
+    B, N = int(x.shape[0]), int(horizon)
+    _devs((x, "f64", 3 * B, "x"), (u_plan, "f32", 2 * N * B, "u_plan"), (status, "i32", B, "status"),
+          (x_next, "f64", 3 * B, "x_next"), (u_lin_next, "f64", 2 * B, "u_lin_next"),
+          (u_applied, "f32", 2 * B, "u_applied", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_advance_dev(C.byref(rc), B, N, _tp(x), _tp(u_plan), _tp(status), _tp(x_next),
+                                     _tp(u_lin_next), _tp(u_applied), C.c_void_p(stream.cuda_stream)),
+           "f110qp_advance_dev")
 
 
 def select_dev(group, num_groups, cost, status, winner, best_cost, stream=None):

@@ -297,6 +297,73 @@ int f110qp_solve_grouped_dev_dbl(f110qp_ctx* ctx, int batch, const double* x0, c
                                  int num_groups, float* u_out, float* x_out, int* status,
                                  int* iters, double* obj, double* cost, void* stream);
 
+/* ---- closed loop on the device ------------------------------------------------------------------
+ * The MPC branch of project::OdomCallback (src/project.cpp:160-198) driven by a simulated car, for B
+ * cars and T ticks without a host round trip: per tick the solve of f110qp_solve_batch_dev_dbl on
+ * the car's fp64 pose, then one plant-step launch (Model::simulate_dynamics, src/model.cpp:61-75)
+ * that also forms the next linearisation input (GetNextInput() with v forced to 4.5,
+ * src/project.cpp:169-170,210-218). Additive: F110QP_API_VERSION stays 6. */
+typedef struct {
+  int    ticks;        /* T >= 1 (f110qp_rollout[_dev]; f110qp_advance_dev ignores it)             */
+  double plant_dt;     /* Euler step of the plant; default 0.01 (params.yaml:13 as a double)       */
+  double car_length;   /* 0.35, CAR_LENGTH of src/model.cpp:2 (not the 0.3302f of Linearize)       */
+  double v_lin;        /* 4.5: v of the next linearisation input, src/project.cpp:170               */
+  double fail_u[2];    /* (0.5, 0.0): Input of GetNextInput() without a solution, project.cpp:215  */
+} f110qp_rollout_config;
+
+/* ticks = 1 and the defaults above. */
+void f110qp_default_rollout_config(f110qp_rollout_config* rc);
+
+/* One plant step of B cars on the first input of their plans (device pointers, asynchronous on
+ * `stream`, one launch; replaces Model::simulate_dynamics + GetNextInput() per car):
+ *   x [B][3] double, u_plan [B][N][2] float32 (a solve's u_out), status [B] (that solve's)
+ *   -> x_next [B][3] double, u_lin_next [B][2] double, u_applied [B][2] float32 (may be NULL).
+ * A car is usable when its status is F110QP_SOLVED or F110QP_SOLVED_INACCURATE (the statuses for
+ * which u_out is finite). Two modelling choices:
+ *  - the applied input is u_plan[b][0], a float32 widened to double (the reference's drive message
+ *    carries float32 too), or fail_u when the car is not usable;
+ *  - u_lin_next = (v_lin, steer of u_plan[b][1]) (of u_plan[b][0] when N == 1); when not usable
+ *    (v_lin, fail_u[1]): after a failed solve solved_trajectory() is empty and GetNextInput()
+ *    returns Input(0.5, 0).
+ * x_next = x + plant_dt * (v cos(ori), v sin(ori), tan(steer) v / car_length) in fp64, in the
+ * reference's expression order, every product and sum rounded (no fused multiply-add).
+ * x_next must not alias x; u_plan and u_applied must be 8-byte aligned. rc->ticks is not read;
+ * plant_dt and car_length must be positive and finite, v_lin and fail_u finite. */
+int f110qp_advance_dev(const f110qp_rollout_config* rc, int batch, int horizon, const double* x,
+                       const float* u_plan, const int* status, double* x_next, double* u_lin_next,
+                       float* u_applied, void* stream);
+
+/* T closed-loop ticks of B cars (device pointers, asynchronous on `stream`):
+ *   x_ref      [B][S][3] double, halfspace [B][2][3] float32 or NULL: held fixed over the T ticks
+ *              (the reference passes the same miniPath_ every tick between re-plans,
+ *              src/project.cpp:188; the half-spaces are world-frame lines)
+ *   x_traj     [T+1][B][3] double, u_lin_traj [T+1][B][2] double: row 0 holds the start on entry,
+ *              row t+1 is written by tick t
+ *   u_applied  [T][B][2] float32, status_traj [T][B]
+ *   iters_traj [T][B], cost_traj [T][B] double, u_plan [T][B][N][2], x_plan [T][B][N+1][3] float32:
+ *              each may be NULL.
+ * Tick t is f110qp_solve_batch_dev_dbl on (x_traj[t], u_lin_traj[t], x_ref, halfspace), writing
+ * straight into row t of status_traj / iters_traj / cost_traj / u_plan / x_plan (a NULL u_plan or
+ * x_plan: into a workspace of the context, sized once), then f110qp_advance_dev into row t+1 of
+ * x_traj / u_lin_traj and row t of u_applied. A call makes exactly the launches of T such solve
+ * calls plus T plant-step launches, with the solve call's launch policy (f110qp_backend_info,
+ * f110qp_lane_segments, ... answer for it) and, as every _dbl call, without reading or updating the
+ * warm-start state. It performs no host synchronisation, reads back no device value and allocates
+ * nothing inside the tick loop; every argument is checked before the first launch (ticks >= 1,
+ * required pointers, the plant parameters as for f110qp_advance_dev). */
+int f110qp_rollout_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc, int batch,
+                       const double* x_ref, const float* halfspace, double* x_traj,
+                       double* u_lin_traj, float* u_applied, int* status_traj, int* iters_traj,
+                       double* cost_traj, float* u_plan, float* x_plan, void* stream);
+
+/* Same on host pointers (synchronous): staged through device buffers of the context, one stream
+ * synchronisation at the end. It does not wait on a completion word: f110qp_sync_signals does not
+ * move. */
+int f110qp_rollout(f110qp_ctx* ctx, const f110qp_rollout_config* rc, int batch, const double* x_ref,
+                   const float* halfspace, double* x_traj, double* u_lin_traj, float* u_applied,
+                   int* status_traj, int* iters_traj, double* cost_traj, float* u_plan,
+                   float* x_plan);
+
 /* Per-scenario selection on the device: the candidate argmin of
  * project::OdomCallback (src/project.cpp:125-136), taken over the QP costs of each scenario's
  * candidates instead of the end-point distance. winner[g] = the smallest b with group[b] == g,
