@@ -212,6 +212,8 @@ def load(test: bool = False):
     L.f110qp_parse_waypoints.argtypes = [C.c_char_p, fp, C.c_int, C.POINTER(C.c_int)]
     L.f110qp_plan_batch_dev.argtypes = [C.POINTER(PlanConfig), C.c_int, fp, fp, C.c_int, C.c_float, C.c_float,
                                         C.c_float, fp, fp, C.c_int, fp, fp, fp, fp, fp, fp, fp, fp]
+    L.f110qp_plan_batch.argtypes = [C.POINTER(PlanConfig), C.c_int, fp, fp, C.c_int, C.c_float, C.c_float,
+                                    C.c_float, fp, fp, C.c_int, fp, fp, fp, fp, fp, fp, fp]
     _libs[path] = L
     return L
 
@@ -828,3 +830,49 @@ def plan_batch_dev(cfg: PlanConfig, pose, ranges, angle_min, angle_inc, angle_ma
                                         waypoints.shape[0], _tp(grid), _tp(valid), _tp(best_global), _tp(best_traj),
                                         _tp(x_ref), _tp(x0), _tp(status), C.c_void_p(stream.cuda_stream)),
            "f110qp_plan_batch_dev")
+
+
+def _host(a, dtype, n: int, name: str, optional: bool = False):
+    """Check a host output array before its raw pointer crosses the C ABI: a C-contiguous numpy
+    array of the ABI's element type with at least n elements (the call writes exactly n)."""
+    if a is None:
+        if optional:
+            return
+        raise F110QPError(f"{name} is required")
+    if not isinstance(a, np.ndarray) or a.dtype != dtype:
+        got = a.dtype if isinstance(a, np.ndarray) else type(a).__name__
+        raise F110QPError(f"{name} must be a {np.dtype(dtype).name} numpy array, got {got}")
+    if not a.flags.c_contiguous or not a.flags.writeable:
+        raise F110QPError(f"{name} must be C-contiguous and writeable")
+    if a.size < n:
+        raise F110QPError(f"{name} holds {a.size} elements, the call needs {n}")
+
+
+def plan_batch(cfg: PlanConfig, pose, ranges, angle_min, angle_inc, angle_max, table, waypoints, x_ref, x0,
+               best_traj, best_global, status, valid=None, grid=None):
+    """Batched planning stage on host memory (f110qp_plan_batch, synchronous; the library stages
+    through grow-only device buffers of the calling thread). Inputs as plan_batch_dev, as numpy
+    arrays: pose [B,4], ranges [B,R], table [T,P,3], waypoints [W,2]. The outputs are the caller's
+    arrays, of which the first B rows are written: x_ref [>=B,P,3] f32, x0 [>=B,3] f32, best_traj /
+    best_global / status [>=B] i32 (valid [>=B,T] u8 and grid [>=B,G,G] u8 optional)."""
+    pose = np.ascontiguousarray(pose, np.float64)
+    ranges = np.ascontiguousarray(ranges, np.float32)
+    table = np.ascontiguousarray(table, np.float64)
+    wp = np.ascontiguousarray(np.asarray(waypoints, np.float64)[:, :2])
+    B, T, P, G = pose.shape[0], cfg.steer_discrete + 1, cfg.traj_discrete, grid_blocks(cfg)
+    if pose.shape != (B, 4) or ranges.ndim != 2 or ranges.shape[0] != B:
+        raise F110QPError(f"pose must be [B,4] and ranges [B,R], got {pose.shape} and {ranges.shape}")
+    if table.shape != (T, P, 3):
+        raise F110QPError(f"table must be [{T},{P},3] for this config, got {table.shape}")
+    _host(x_ref, np.float32, B * P * 3, "x_ref")
+    _host(x0, np.float32, B * 3, "x0")
+    _host(best_traj, np.int32, B, "best_traj")
+    _host(best_global, np.int32, B, "best_global")
+    _host(status, np.int32, B, "status")
+    _host(valid, np.uint8, B * T, "valid", True)
+    _host(grid, np.uint8, B * G * G, "grid", True)
+    _check(load().f110qp_plan_batch(C.byref(cfg), B, _p(pose), _p(ranges), ranges.shape[1], float(angle_min),
+                                    float(angle_inc), float(angle_max), _p(table), _p(wp) if wp.shape[0] else None,
+                                    wp.shape[0], _p(grid), _p(valid), _p(best_global), _p(best_traj), _p(x_ref),
+                                    _p(x0), _p(status)),
+           "f110qp_plan_batch")

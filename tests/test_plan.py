@@ -6,9 +6,11 @@ here against an independent numpy restatement of the same reference lines, again
 simulate_dynamics rollout, and the device kernel's parallel form of the reference's sequential
 float running minimum is checked against the sequential loop itself.
 """
+import ctypes as C
 import os
 
 import numpy as np
+import pytest
 from conftest import GOLDEN
 
 from f110qp import capi, workload
@@ -81,6 +83,7 @@ def np_fill_grid(pose, ranges, amin, ainc, amax, size=10, disc=np.float32(0.1), 
     o0 = f(px + 0.275 * np.cos(np.float64(cur)))
     o1 = f(py + 0.275 * np.sin(np.float64(cur)))
     ns = int((f(amax) - f(amin)) / f(ainc) + f(1))
+    ns = max(0, min(ns, len(ranges)))  # the project's clamp: the reference reads past a shorter scan
     ii = np.arange(ns)
     ang = (f(amin) + (ii.astype(np.float32) * f(ainc))).astype(np.float32) + cur
     ang = ang.astype(np.float32)
@@ -174,6 +177,94 @@ def test_oracle_planner_against_numpy_restatement(oracle):
             assert r["x_ref"].shape == (50, 3) and np.all(r["x_ref"][:, 2] == 0)
             assert np.allclose(r["x_ref"][0, :2], sc["pose"][b, :2], atol=1e-5)
     assert statuses.count(0) >= 12 and g.sum() > 100
+
+
+def _edge_cases():
+    """(name, scene builder, config overrides) of the plan_cases corners the GPU parity tests
+    (test_gpu_plan_edges.py) lean on the oracle for."""
+    import plan_cases as pc
+
+    cases = [(f"offsets{n}", lambda: pc.base(3), pc.dilation_over(dil, disc))
+             for dil, disc, n in pc.DILATION_CASES if n != 9 or disc == 0.1]
+    cases += [(f"G{G}", lambda: pc.base(3), pc.grid_over(size, disc)) for size, disc, G in pc.GRID_SHAPES[::2]]
+    cases += [("far", lambda: pc.far_origin(3), {}), ("doubled", lambda: pc.doubled_lap(3), {}),
+              ("truncated", lambda: pc.scan_truncated(2), {}), ("half_angle", lambda: pc.scan_half_angle(2), {}),
+              ("reversed", lambda: pc.scan_reversed(2), {}), ("yaws", lambda: pc.axis_yaws(8), {})]
+    cases += [(f"quat{s}", lambda s=s: pc.scaled_quaternions(3, s), {}) for s in pc.QUAT_SCALES]
+    return cases
+
+
+@pytest.mark.parametrize("name,build,over", _edge_cases(), ids=[c[0] for c in _edge_cases()])
+def test_oracle_planner_against_numpy_restatement_at_the_edges(oracle, name, build, over):
+    """The same two-sided check at the corners: 1, 8, 9 and 24 dilation offsets, G = 35 and G = 1,
+    scans longer and shorter than their computed beam count (the clamp to num_ranges is the
+    project's: the reference reads past a shorter scan) and with reversed angles, a pose a
+    kilometre out, yaw +-pi and +-pi/2, non-unit quaternions, and a doubled lap (exact ties)."""
+    sc = build()
+    pp = oracle.plan_params(**over)
+    table = oracle.traj_table(pp)
+    if name.startswith("offsets"):
+        assert len(oracle.dilation_offsets(pp)) == int(name[7:])
+    if name.startswith("G"):
+        assert capi.grid_blocks(capi.default_plan_config(**over)) == int(name[1:])
+    for b in range(sc["pose"].shape[0]):
+        geom = (sc["angle_min"], sc["angle_inc"], sc["angle_max"])
+        g, off = oracle.fill_occ_grid(pp, sc["pose"][b], sc["ranges"][b], *geom)
+        gn, offn = np_fill_grid(sc["pose"][b], sc["ranges"][b], *geom, size=pp.size, disc=np.float32(pp.discrete),
+                                dil=np.float32(pp.dilation))
+        np.testing.assert_array_equal(off, offn)
+        np.testing.assert_array_equal(g, gn)
+        r = oracle.plan(pp, sc["pose"][b], g, off, table, sc["waypoints"])
+        v, bg, bt, st = np_plan(sc["pose"][b], g, off, table, sc["waypoints"], disc=np.float32(pp.discrete))
+        np.testing.assert_array_equal(r["valid"], v)
+        assert (r["status"], r["best_global"], r["best_traj"]) == (st, bg, bt)
+    if name == "reversed":
+        assert g.sum() == 0
+    elif name != "G1":
+        assert g.sum() > 0
+
+
+def test_candidate_of_point_index_is_exact():
+    """plan_kernels.hip finds the candidate of table point k as (int)(((float)k + 0.5f) * (1.0f / P)):
+    equal to k / P for every P the ABI admits (2..1024) and every k < 256 P, in float32 arithmetic."""
+    f = np.float32
+    for P in range(2, 1025):
+        k = np.arange(256 * P, dtype=np.int32)
+        got = ((k.astype(np.float32) + f(0.5)) * (f(1.0) / f(P))).astype(np.int32)
+        assert got.dtype == np.int32 and np.array_equal(got, k // P), P
+
+
+def test_plan_batch_argument_checks():
+    """f110qp_plan_batch's return codes, all decided before any device call: an empty batch is a
+    no-op, a scan without beams, a negative waypoint count and a table of 257 candidates are
+    invalid. None of the caller's arrays is touched."""
+    L = capi.load()
+    cfg = capi.default_plan_config()
+    P = cfg.traj_discrete
+    pose, ranges = np.zeros((2, 4)), np.ones((2, 8), np.float32)
+    pose[:, 3] = 1.0
+    table, wp = capi.traj_table(cfg), np.zeros((4, 2))
+    out = dict(bg=np.full(2, -77, np.int32), bt=np.full(2, -77, np.int32), xr=np.full((2, P, 3), -7.0, np.float32),
+               x0=np.full((2, 3), -7.0, np.float32), st=np.full(2, -77, np.int32))
+    p = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+
+    def call(c, batch, nr, W):
+        return L.f110qp_plan_batch(C.byref(c), batch, p(pose), p(ranges), nr, -1.0, 0.1, 1.0, p(table), p(wp), W, None,
+                                   None, p(out["bg"]), p(out["bt"]), p(out["xr"]), p(out["x0"]), p(out["st"]))
+
+    assert call(cfg, 0, 8, 4) == capi.OK
+    assert call(cfg, 2, 0, 4) == capi.ERR_INVALID
+    assert call(cfg, 2, 8, -1) == capi.ERR_INVALID
+    assert call(cfg, -1, 8, 4) == capi.ERR_INVALID
+    assert call(capi.default_plan_config(steer_discrete=256), 2, 8, 4) == capi.ERR_INVALID
+    assert "steer_discrete" in capi.last_error()
+    assert all((v == (-7.0 if v.dtype == np.float32 else -77)).all() for v in out.values())
+    with pytest.raises(capi.F110QPError, match="status must be a int32"):
+        capi.plan_batch(cfg, pose, ranges, -1.0, 0.1, 1.0, table, wp, out["xr"], out["x0"], out["bt"], out["bg"],
+                        np.zeros(2, np.int64))
+    with pytest.raises(capi.F110QPError, match="x_ref holds"):
+        capi.plan_batch(cfg, pose, ranges, -1.0, 0.1, 1.0, table, wp, out["xr"][:1], out["x0"], out["bt"], out["bg"],
+                        out["st"])
 
 
 def _sequential_float_min(d):
