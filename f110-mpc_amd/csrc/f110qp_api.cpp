@@ -113,6 +113,7 @@ struct f110qp_ctx {
   int lane_seg = 0;          // lane horizon segments per QP (LaneWork::seg: 0 auto, 1 off, 2/4/8)
   int lane_seg32 = 0;        // segmented kernel: force fp32 references + scratch (LaneWork::seg32)
   int lane_twin = 1;         // segmented kernel: twin PDAS starts where they fit (LaneWork::twin)
+  int seg_fixedq = 1;        // segmented kernel: the fixed-length kernels where they apply (LaneWork::fixedq)
   int gap_screen = -1;      // gap rows, AUTO: box screen on the lane kernel (-1 by batch, 0 off, 1 on)
   int recheck_all = 0;      // gap rows: every QP of a call through the fp64 re-check alone (test build)
   HostBuf hsig;              // synchronous calls: the completion word they poll (wait_done)
@@ -157,6 +158,8 @@ static void test_hooks(f110qp_ctx* c) {
   if (env_int("F110QP_LANE_SEG_F32", 0, 1, &v)) c->lane_seg32 = v;
   // 0: one PDAS start per QP in the segmented kernel (the twin start off)
   if (env_int("F110QP_LANE_TWIN", 0, 1, &v)) c->lane_twin = v;
+  // 0: the run-time-length segmented kernel where the fixed-length one would run
+  if (env_int("F110QP_SEG_FIXEDQ", 0, 1, &v)) c->seg_fixedq = v;
   // gap rows: the box screen on (1) / off (0) at every batch size
   if (env_int("F110QP_GAP_SCREEN", 0, 1, &v)) c->gap_screen = v;
   // wave GI: 0 picks gap and box candidates by one ranking
@@ -398,6 +401,7 @@ static f110qp::LaneWork lane_knobs(const f110qp_ctx* c) {
   lw.seg = c->lane_seg;
   lw.seg32 = c->lane_seg32;
   lw.twin = c->lane_twin;
+  lw.fixedq = c->seg_fixedq;
   return lw;
 }
 
@@ -706,6 +710,18 @@ int f110qp_lane_starts(f110qp_ctx* c, int batch, int* starts) {
   if (rc) return rc;
   const f110qp::LaneWork lw = lane_knobs(c);
   *starts = segs > 1 ? f110qp::lane_seg_starts(c->kp, batch, segs, lw) : 1;
+  return F110QP_OK;
+}
+
+int f110qp_lane_fixed_q(f110qp_ctx* c, int batch, int* stages) {
+  if (!c || !stages) return fail(F110QP_ERR_INVALID, "ctx / stages is NULL");
+  if (batch < 1) return fail(F110QP_ERR_INVALID, "batch must be >= 1");
+  int segs = 1;
+  const int rc = f110qp_lane_segments(c, batch, &segs);
+  if (rc) return rc;
+  const f110qp::LaneWork lw = lane_knobs(c);
+  const bool box = c->cfg.gap_mode != F110QP_GAP_ACTIVE;  // (the gap-row screen's kernels have no fixed-length variant)
+  *stages = (box && segs > 1) ? f110qp::lane_seg_fixedq(c->kp, batch, segs, lw) : 0;
   return F110QP_OK;
 }
 

@@ -46,5 +46,8 @@ int lane_seg_scratch(const KParams& P, int B, int S, const LaneWork& lw) {
   return seg_scratch_mode(P, seg_twin(P, B, S, lw) ? 2 * B : B, S, lw);
 }
 int lane_seg_starts(const KParams& P, int B, int S, const LaneWork& lw) { return seg_twin(P, B, S, lw) ? 2 : 1; }
+int lane_seg_fixedq(const KParams& P, int B, int S, const LaneWork& lw) {
+  return seg_fixedq(P, B, S, lw.rot && P.q[0] == P.q[1], false, lw);
+}
 #endif
 }  // namespace f110qp

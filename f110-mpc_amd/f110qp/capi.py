@@ -91,6 +91,7 @@ EXPORTED = (
     "f110qp_gap_screen",
     "f110qp_last_recheck_count",
     "f110qp_lane_starts",
+    "f110qp_lane_fixed_q",
     "f110qp_warm_hits",
     "f110qp_sync_signals",
     "f110qp_test_build",
@@ -195,6 +196,7 @@ def load(test: bool = False):
     L.f110qp_gap_screen.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.f110qp_last_recheck_count.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.f110qp_lane_starts.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.f110qp_lane_fixed_q.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.f110qp_warm_hits.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.f110qp_sync_signals.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
     L.f110qp_test_build.restype = C.c_int
@@ -356,6 +358,13 @@ class Solver:
         partitioned-horizon kernel's twin start, else 1."""
         v = C.c_int()
         self._chk(self.lib.f110qp_lane_starts(self._h, int(batch), C.byref(v)), "f110qp_lane_starts")
+        return v.value
+
+    def lane_fixed_q(self, batch: int) -> int:
+        """Stages per segment when a solve call of `batch` QPs runs a partitioned-horizon kernel
+        compiled for a fixed segment length (f110qp_lane_fixed_q): 5, else 0."""
+        v = C.c_int()
+        self._chk(self.lib.f110qp_lane_fixed_q(self._h, int(batch), C.byref(v)), "f110qp_lane_fixed_q")
         return v.value
 
     def last_recheck_count(self) -> int:

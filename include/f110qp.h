@@ -396,6 +396,11 @@ int f110qp_lane_segments(f110qp_ctx* ctx, int batch, int* segments);
  * smaller of the two pass counts (DESIGN.md 2b'). */
 int f110qp_lane_starts(f110qp_ctx* ctx, int batch, int* starts);
 
+/* Stages per segment of that launch when it runs a partitioned-horizon kernel compiled for a fixed
+ * segment length (5: box rows, 4 segments of a 20-stage horizon in the heading frame; DESIGN.md
+ * 2b'), else 0: the kernels that take the segment length at run time. Same results either way. */
+int f110qp_lane_fixed_q(f110qp_ctx* ctx, int batch, int* stages);
+
 /* on = 1 when a gap-row call of `batch` QPs takes the box screen (F110QP_GAP_SCREEN_MIN_BATCH):
  * the lane back end solves the box-only problem, the wave kernel's GI only the QPs whose box
  * optimum does not keep every gap row (an ungrouped solve call; replaces nothing in the reference:
