@@ -18,6 +18,7 @@
 
 #include "f110qp.h"
 #include "f110qp_kernels.h"
+#include "halfspace_geom.h"
 
 namespace {
 
@@ -105,6 +106,8 @@ struct f110qp_ctx {
   DevBuf hand;               // gap rows: counts and lists (f110qp::HandLayout, kHandInts(B) ints)
   DevBuf rplan;              // rollout: one tick's u_plan | x_plan when the caller keeps neither
   DevBuf rdev;               // host-pointer rollout: device copies of its arrays
+  DevBuf rgap;               // scan rollout: one GapRecord per scan (scan_rows x B)
+  DevBuf rhs;                // scan rollout without hs_traj: the current tick's rows (B x 6 floats)
   int lane_kmax = 16;        // lane back end: PDAS passes before single (least-index) flips
   int lane_mode = 0;         // lane scratch placement (LaneWork::mode)
   int lane_qpw = 0;          // lane QPs per wave (LaneWork::qpw, 0 = auto)
@@ -787,9 +790,20 @@ static int check_rollout_args(f110qp_ctx* c, const f110qp_rollout_config* rc, in
 // The T ticks of a checked rollout on device pointers: every workspace is sized in front of the
 // loop, the loop itself only launches (per tick the launches of one _dbl solve call, then the plant
 // step).
+// sl (f110qp_rollout_scan[_dev]): the half-spaces follow the car. One gap search and the rows of tick
+// 0 in front of the loop; tick t's plant step is the fused one, which writes the rows of tick t + 1
+// (the last tick's is the plain one: there is no row T).
+static_assert(sizeof(f110qp_gap_record) == sizeof(f110qp::GapRecord) && sizeof(f110qp_gap_record) == 16,
+              "the ABI's gap record is the kernels' GapRecord");
+struct ScanLoop {
+  const f110qp_scan_config* sc;
+  const float* ranges;  // [scan_rows][B][num_ranges]
+  float* hs_traj;       // [T][B][6] or null: one row set in the context
+};
+
 static int rollout_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, int T, int batch, const double* xr,
                          const float* hs, double* xt, double* ult, float* ua, int* stt, int* itt,
-                         double* cot, float* up, float* xp, hipStream_t s) {
+                         double* cot, float* up, float* xp, hipStream_t s, const ScanLoop* sl = nullptr) {
   const size_t B = (size_t)batch, N = (size_t)c->cfg.horizon;
   const size_t n_up = B * N * 2, n_xp = B * (N + 1) * 3;
   if (!aligned8(ua) || !aligned8(up)) return fail(F110QP_ERR_INVALID, "u_applied / u_plan must be 8-byte aligned");
@@ -801,27 +815,99 @@ static int rollout_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, int T, 
     wup = (float*)c->rplan.p;
     wxp = wup + n_up;
   }
-  const float* h = (c->cfg.gap_mode == F110QP_GAP_ACTIVE) ? hs : nullptr;
+  const bool gap = c->cfg.gap_mode == F110QP_GAP_ACTIVE;
+  const float* h = gap ? hs : nullptr;
+  f110qp::GapRecord* rec = nullptr;
+  float* rows = nullptr;  // tick t's rows: hs_traj + t * rstep
+  size_t rstep = 0;
+  if (sl) {
+    const size_t nrec = (size_t)sl->sc->scan_rows * B;
+    hipError_t e = c->rgap.ensure(nrec * sizeof(f110qp::GapRecord));
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc gap records");
+    rec = (f110qp::GapRecord*)c->rgap.p;
+    rows = sl->hs_traj;
+    rstep = B * 6;
+    if (!rows) {
+      if ((e = c->rhs.ensure(B * 6 * sizeof(float))) != hipSuccess) return hip_fail(e, "hipMalloc half-space rows");
+      rows = (float*)c->rhs.p;
+      rstep = 0;
+    }
+  }
   int backend;
   f110qp::LaneWork lw;
   const int rc = lane_work(c, batch, s, &backend, &lw);
   if (rc) return rc;
+  if (sl) {
+    const f110qp_scan_config& k = *sl->sc;
+    hipError_t e = f110qp::launch_gap_search(k.scan_rows * batch, sl->ranges, k.num_ranges, k.angle_min,
+                                             k.angle_increment, k.angle_max, k.ftg_thresh, k.divider, k.buffer,
+                                             rec, s);
+    if (e != hipSuccess) return hip_fail(e, "gap search launch");
+    e = f110qp::launch_half_space_rows(batch, k.num_ranges, k.angle_min, k.angle_increment, rec, xt, rows, s);
+    if (e != hipSuccess) return hip_fail(e, "half-space rows launch");
+  }
+  // the scan rollout's NaN rows mean a scan without a gap: non-finite data, F110QP_NUMERICAL
+  f110qp::KParams kp = c->kp;
+  if (sl) kp.hs_nan_numerical = 1;
   for (size_t t = 0; t < (size_t)T; t++) {
+    if (sl && gap) h = rows + t * rstep;
     float* u_t = up ? up + t * n_up : wup;
     float* x_t = xp ? xp + t * n_xp : wxp;
     int* st_t = stt + t * B;
     f110qp::ObjOut oo;
     oo.cost = cot ? cot + t * B : nullptr;
-    hipError_t e = f110qp::launch_solve(c->kp, batch, (const double*)(xt + t * B * 3),
+    hipError_t e = f110qp::launch_solve(kp, batch, (const double*)(xt + t * B * 3),
                                         (const double*)(ult + t * B * 2), xr, h, u_t, x_t, st_t,
                                         itt ? itt + t * B : nullptr, f110qp::WarmState(), backend, lw, oo, s);
     if (e != hipSuccess) return hip_fail(e, "rollout solve launch");
-    e = f110qp::launch_advance(ap, batch, (int)N, xt + t * B * 3, u_t, st_t, xt + (t + 1) * B * 3,
-                               ult + (t + 1) * B * 2, ua + t * B * 2, s);
+    if (sl && t + 1 < (size_t)T)
+      e = f110qp::launch_advance_scan(ap, batch, (int)N, xt + t * B * 3, u_t, st_t, sl->sc->num_ranges,
+                                      sl->sc->angle_min, sl->sc->angle_increment,
+                                      rec + (sl->sc->scan_rows == 1 ? 0 : (t + 1) * B), xt + (t + 1) * B * 3,
+                                      ult + (t + 1) * B * 2, ua + t * B * 2, rows + (t + 1) * rstep, s);
+    else
+      e = f110qp::launch_advance(ap, batch, (int)N, xt + t * B * 3, u_t, st_t, xt + (t + 1) * B * 3,
+                                 ult + (t + 1) * B * 2, ua + t * B * 2, s);
     if (e != hipSuccess) return hip_fail(e, "plant step launch");
   }
   return F110QP_OK;
 }
+
+// The limits of f110qp_find_half_spaces_dev on a scan config; rows: scan_rows must be 1 or `ticks`.
+static int check_scan_config(const f110qp_scan_config* sc, bool rows, int ticks) {
+  if (!sc) return fail(F110QP_ERR_INVALID, "scan config is NULL");
+  if (sc->num_ranges < 1 || sc->num_ranges > 65535)
+    return fail(F110QP_ERR_INVALID, "num_ranges must be in 1..65535");
+  if (!(sc->angle_increment > 0.f)) return fail(F110QP_ERR_INVALID, "angle_increment must be > 0");
+  if (rows && sc->scan_rows != 1 && sc->scan_rows != ticks)
+    return fail(F110QP_ERR_INVALID, "scan_rows must be 1 or ticks");
+  return F110QP_OK;
+}
+
+// Argument checks of f110qp_rollout_scan[_dev], all before any device call.
+static int check_rollout_scan_args(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                                   int batch, const void* xr, const void* ranges, const void* xt,
+                                   const void* ult, const void* ua, const void* stt, f110qp::AdvanceParams* ap) {
+  if (!c) return fail(F110QP_ERR_INVALID, "ctx is NULL");
+  int rv = rollout_params(rc, true, ap);
+  if (rv) return rv;
+  if ((rv = check_scan_config(sc, true, rc->ticks))) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  if (batch == 0) return F110QP_OK;
+  if (!xr || !xt || !ult || !ua || !stt)
+    return fail(F110QP_ERR_INVALID, "x_ref/x_traj/u_lin_traj/u_applied/status_traj must be non-NULL");
+  if (!ranges) return fail(F110QP_ERR_INVALID, "ranges must be non-NULL");
+  if (batch > (1 << 30) / 64 || (long long)sc->scan_rows * batch > (1ll << 30))
+    return fail(F110QP_ERR_INVALID, "batch too large");
+  return F110QP_OK;
+}
+
+// The host-pointer rollouts: f110qp_rollout (sc null: hs [B][6] held) and f110qp_rollout_scan (sc,
+// ranges [scan_rows][B][num_ranges], hst [T][B][6] or null), staged through c->rdev.
+static int rollout_host(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp::AdvanceParams& ap,
+                        int batch, const double* xr, const float* hs, double* xt, double* ult, float* ua,
+                        int* stt, int* itt, double* cot, float* up, float* xp,
+                        const f110qp_scan_config* sc, const float* ranges, float* hst);
 
 extern "C" {
 
@@ -871,6 +957,100 @@ int f110qp_rollout(f110qp_ctx* c, const f110qp_rollout_config* rc, int batch, co
   f110qp::AdvanceParams ap;
   const int rv = check_rollout_args(c, rc, batch, xr, hs, xt, ult, ua, stt, &ap);
   if (rv || batch == 0) return rv;
+  return rollout_host(c, rc, ap, batch, xr, hs, xt, ult, ua, stt, itt, cot, up, xp, nullptr, nullptr, nullptr);
+}
+
+void f110qp_default_scan_config(f110qp_scan_config* sc) {
+  if (!sc) return;
+  std::memset(sc, 0, sizeof(*sc));
+  sc->ftg_thresh = 3.0f;  // the defaults of the half-space calls' bindings (params.yaml)
+  sc->divider = 1.5f;
+  sc->buffer = 3.0f;
+  sc->scan_rows = 1;
+}
+
+int f110qp_gap_search_dev(const f110qp_scan_config* sc, int count, const float* ranges,
+                          f110qp_gap_record* gap, void* stream) {
+  const int rv = check_scan_config(sc, false, 0);
+  if (rv) return rv;
+  if (count < 0) return fail(F110QP_ERR_INVALID, "count < 0");
+  if (count == 0) return F110QP_OK;
+  if (!ranges || !gap) return fail(F110QP_ERR_INVALID, "ranges/gap_out must be non-NULL");
+  const hipError_t e = f110qp::launch_gap_search(count, ranges, sc->num_ranges, sc->angle_min,
+                                                 sc->angle_increment, sc->angle_max, sc->ftg_thresh, sc->divider,
+                                                 sc->buffer, (f110qp::GapRecord*)gap, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "gap search launch");
+  return F110QP_OK;
+}
+
+int f110qp_half_space_rows_dev(const f110qp_scan_config* sc, int batch, const f110qp_gap_record* gap,
+                               const double* states, float* hs, void* stream) {
+  const int rv = check_scan_config(sc, false, 0);
+  if (rv) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  if (batch == 0) return F110QP_OK;
+  if (!gap || !states || !hs) return fail(F110QP_ERR_INVALID, "gap/states/hs_out must be non-NULL");
+  const hipError_t e = f110qp::launch_half_space_rows(batch, sc->num_ranges, sc->angle_min, sc->angle_increment,
+                                                      (const f110qp::GapRecord*)gap, states, hs,
+                                                      (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "half-space rows launch");
+  return F110QP_OK;
+}
+
+int f110qp_advance_scan_dev(const f110qp_rollout_config* rc, const f110qp_scan_config* sc, int batch,
+                            int horizon, const double* x, const float* u_plan, const int* status,
+                            const f110qp_gap_record* gap, double* x_next, double* u_lin_next,
+                            float* u_applied, float* hs_next, void* stream) {
+  f110qp::AdvanceParams ap;
+  int rv = rollout_params(rc, false, &ap);
+  if (rv) return rv;
+  if ((rv = check_scan_config(sc, false, 0))) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  if (horizon < 1 || horizon > F110QP_MAX_HORIZON) return fail(F110QP_ERR_INVALID, "horizon must be in [1, 48]");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !u_plan || !status || !x_next || !u_lin_next)
+    return fail(F110QP_ERR_INVALID, "x/u_plan/status/x_next/u_lin_next must be non-NULL");
+  if (!gap || !hs_next) return fail(F110QP_ERR_INVALID, "gap/hs_next must be non-NULL");
+  if (x_next == x) return fail(F110QP_ERR_INVALID, "x_next must not alias x");
+  if (!aligned8(u_plan) || !aligned8(u_applied))
+    return fail(F110QP_ERR_INVALID, "u_plan / u_applied must be 8-byte aligned");
+  const hipError_t e = f110qp::launch_advance_scan(ap, batch, horizon, x, u_plan, status, sc->num_ranges,
+                                                   sc->angle_min, sc->angle_increment,
+                                                   (const f110qp::GapRecord*)gap, x_next, u_lin_next, u_applied,
+                                                   hs_next, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "plant step launch");
+  return F110QP_OK;
+}
+
+int f110qp_rollout_scan_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                            int batch, const double* xr, const float* ranges, double* xt, double* ult,
+                            float* ua, int* stt, int* itt, double* cot, float* up, float* xp, float* hst,
+                            void* stream) {
+  f110qp::AdvanceParams ap;
+  const int rv = check_rollout_scan_args(c, rc, sc, batch, xr, ranges, xt, ult, ua, stt, &ap);
+  if (rv || batch == 0) return rv;
+  // gap rows inactive and no rows asked for: nothing reads them, f110qp_rollout_dev's launches
+  const ScanLoop sl{sc, ranges, hst};
+  const bool rows = c->cfg.gap_mode == F110QP_GAP_ACTIVE || hst;
+  return rollout_ticks(c, ap, rc->ticks, batch, xr, nullptr, xt, ult, ua, stt, itt, cot, up, xp,
+                       (hipStream_t)stream, rows ? &sl : nullptr);
+}
+
+int f110qp_rollout_scan(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                        int batch, const double* xr, const float* ranges, double* xt, double* ult, float* ua,
+                        int* stt, int* itt, double* cot, float* up, float* xp, float* hst) {
+  f110qp::AdvanceParams ap;
+  const int rv = check_rollout_scan_args(c, rc, sc, batch, xr, ranges, xt, ult, ua, stt, &ap);
+  if (rv || batch == 0) return rv;
+  return rollout_host(c, rc, ap, batch, xr, nullptr, xt, ult, ua, stt, itt, cot, up, xp, sc, ranges, hst);
+}
+
+}  // extern "C"
+
+static int rollout_host(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp::AdvanceParams& ap,
+                        int batch, const double* xr, const float* hs, double* xt, double* ult, float* ua,
+                        int* stt, int* itt, double* cot, float* up, float* xp,
+                        const f110qp_scan_config* sc, const float* ranges, float* hst) {
   hipError_t e = hipSetDevice(c->cfg.device);
   if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
   if (!c->stream) {
@@ -878,7 +1058,8 @@ int f110qp_rollout(f110qp_ctx* c, const f110qp_rollout_config* rc, int batch, co
     if (e != hipSuccess) return hip_fail(e, "hipStreamCreate");
   }
   hipStream_t s = c->stream;
-  const bool gap = c->cfg.gap_mode == F110QP_GAP_ACTIVE;
+  const bool gap = c->cfg.gap_mode == F110QP_GAP_ACTIVE && !sc;  // held rows (f110qp_rollout)
+  const bool rows = sc && (c->cfg.gap_mode == F110QP_GAP_ACTIVE || hst);  // rows per tick, from the scans
   const size_t B = (size_t)batch, N = (size_t)c->cfg.horizon, S = (size_t)c->kp.xr_stride, T = (size_t)rc->ticks;
   // device layout, the 8-byte fields first: x_ref | x_traj | u_lin_traj | cost | halfspace |
   // u_applied | status | iters | u_plan | x_plan (status and iters padded to 8 bytes; every other
@@ -889,8 +1070,15 @@ int f110qp_rollout(f110qp_ctx* c, const f110qp_rollout_config* rc, int batch, co
   const size_t s_up = up ? T * B * N * 2 * 4 : 0, s_xp = xp ? T * B * (N + 1) * 3 * 4 : 0;
   const size_t o_xt = s_xr, o_ul = o_xt + s_xt, o_co = o_ul + s_ul, o_hs = o_co + s_co, o_ua = o_hs + s_hs;
   const size_t o_st = o_ua + s_ua, o_it = o_st + p_st, o_up = o_it + p_it, o_xp = o_up + s_up;
-  if ((e = c->rdev.ensure(o_xp + s_xp)) != hipSuccess) return hip_fail(e, "hipMalloc rollout staging");
+  // the scan rollout's ranges and recorded rows behind them (4-byte fields)
+  const size_t s_rg = rows ? (size_t)sc->scan_rows * B * (size_t)sc->num_ranges * 4 : 0;
+  const size_t s_ht = rows && hst ? T * B * 6 * 4 : 0;
+  const size_t o_rg = o_xp + s_xp, o_ht = o_rg + s_rg;
+  if ((e = c->rdev.ensure(o_ht + s_ht)) != hipSuccess) return hip_fail(e, "hipMalloc rollout staging");
   char* d = (char*)c->rdev.p;
+  if (rows && (e = hipMemcpyAsync(d + o_rg, ranges, s_rg, hipMemcpyHostToDevice, s)))
+    return hip_fail(e, "hipMemcpyAsync H2D");
+  const ScanLoop sl{sc, (const float*)(d + o_rg), hst ? (float*)(d + o_ht) : nullptr};
   if ((e = hipMemcpyAsync(d, xr, s_xr, hipMemcpyHostToDevice, s)) ||
       (e = hipMemcpyAsync(d + o_xt, xt, B * 3 * 8, hipMemcpyHostToDevice, s)) ||
       (e = hipMemcpyAsync(d + o_ul, ult, B * 2 * 8, hipMemcpyHostToDevice, s)) ||
@@ -899,8 +1087,10 @@ int f110qp_rollout(f110qp_ctx* c, const f110qp_rollout_config* rc, int batch, co
   const int rt = rollout_ticks(c, ap, rc->ticks, batch, (const double*)d, gap ? (const float*)(d + o_hs) : nullptr,
                                (double*)(d + o_xt), (double*)(d + o_ul), (float*)(d + o_ua), (int*)(d + o_st),
                                itt ? (int*)(d + o_it) : nullptr, cot ? (double*)(d + o_co) : nullptr,
-                               up ? (float*)(d + o_up) : nullptr, xp ? (float*)(d + o_xp) : nullptr, s);
+                               up ? (float*)(d + o_up) : nullptr, xp ? (float*)(d + o_xp) : nullptr, s,
+                               rows ? &sl : nullptr);
   if (rt) return rt;
+  if (s_ht && (e = hipMemcpyAsync(hst, d + o_ht, s_ht, hipMemcpyDeviceToHost, s))) return hip_fail(e, "hipMemcpyAsync D2H");
   // rows 1..T of the trajectories (row 0 is the caller's), then every recorded array
   if ((e = hipMemcpyAsync(xt + B * 3, d + o_xt + B * 3 * 8, T * B * 3 * 8, hipMemcpyDeviceToHost, s)) ||
       (e = hipMemcpyAsync(ult + B * 2, d + o_ul + B * 2 * 8, T * B * 2 * 8, hipMemcpyDeviceToHost, s)) ||
@@ -914,8 +1104,6 @@ int f110qp_rollout(f110qp_ctx* c, const f110qp_rollout_config* rc, int batch, co
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
   return F110QP_OK;
 }
-
-}  // extern "C"
 
 template <typename IN>
 static int solve_host(f110qp_ctx* c, int batch, const IN* x0, const IN* ul, const IN* xr,
@@ -1096,6 +1284,21 @@ int f110qp_find_half_spaces_dev(int batch, const float* states, const float* ran
                                 float angle_min, float angle_inc, float angle_max,
                                 float ftg_thresh, float divider, float buffer, float* hs,
                                 int* gap_lo, int* gap_hi, void* stream) {
+  if (batch < 0 || nr <= 0 || nr > 65535) return fail(F110QP_ERR_INVALID, "bad batch / num_ranges (1..65535)");
+  if (batch == 0) return F110QP_OK;
+  if (!states || !ranges || !hs) return fail(F110QP_ERR_INVALID, "NULL pointer argument");
+  if (!(angle_inc > 0.f)) return fail(F110QP_ERR_INVALID, "angle_increment must be > 0");
+  hipError_t e = f110qp::launch_half_spaces(batch, states, ranges, nr, angle_min, angle_inc,
+                                            angle_max, ftg_thresh, divider, buffer, hs, gap_lo,
+                                            gap_hi, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "half-space kernel launch");
+  return F110QP_OK;
+}
+
+int f110qp_find_half_spaces_dev_dbl(int batch, const double* states, const float* ranges, int nr,
+                                    float angle_min, float angle_inc, float angle_max,
+                                    float ftg_thresh, float divider, float buffer, float* hs,
+                                    int* gap_lo, int* gap_hi, void* stream) {
   if (batch < 0 || nr <= 0 || nr > 65535) return fail(F110QP_ERR_INVALID, "bad batch / num_ranges (1..65535)");
   if (batch == 0) return F110QP_OK;
   if (!states || !ranges || !hs) return fail(F110QP_ERR_INVALID, "NULL pointer argument");

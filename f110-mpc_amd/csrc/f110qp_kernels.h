@@ -26,6 +26,8 @@ struct KParams {
   int pdas_max;   // PDAS passes of the wave kernel's box path before its GI loop takes over
   int pass_cap = 0;  // lane kernels: passes per launch (0: max_iter; measurement knob F110QP_LANE_PASSCAP)
   int gap_first = 1;  // wave GI with gap rows: a violated gap row is added before any box row
+  int hs_nan_numerical = 0;  // gap rows: non-finite half-space rows give F110QP_NUMERICAL (the scan
+                             // rollout, where they mean a scan without a gap), not PRIMAL_INFEASIBLE
 };
 
 // Warm-start state of a context (all null = cold solve). Per QP slot b of the batch:
@@ -265,10 +267,31 @@ hipError_t launch_plan(const PlanKParams& K, int B, const double* pose, const fl
                        unsigned char* valid_out, int* best_global, int* best_traj, float* x_ref,
                        float* x0, int* status, hipStream_t stream);
 
-// Batched FindHalfSpaces (constraints.cpp:116-265), one wave per scan.
-hipError_t launch_half_spaces(int B, const float* states, const float* ranges, int num_ranges,
+// Batched FindHalfSpaces (constraints.cpp:116-265), one wave per scan. ST: the scalar of states,
+// float or double (both instantiated in halfspace_kernels.hip).
+template <typename ST>
+hipError_t launch_half_spaces(int B, const ST* states, const float* ranges, int num_ranges,
                               float angle_min, float angle_inc, float angle_max, float thresh,
                               float divider, float buffer, float* hs, int* gap_lo, int* gap_hi,
                               hipStream_t stream);
+
+// FindHalfSpaces split at the point where the pose enters (halfspace_geom.h): the gap search of
+// `count` scans, one wave each, into one GapRecord per scan (constraints.cpp:118-177) ...
+struct GapRecord;
+hipError_t launch_gap_search(int count, const float* ranges, int num_ranges, float angle_min,
+                             float angle_inc, float angle_max, float thresh, float divider, float buffer,
+                             GapRecord* rec, hipStream_t stream);
+// ... and the end-point geometry (:179-264) of B cars, one thread each: gap [B], states [B][3]
+// double -> hs [B][2][3].
+hipError_t launch_half_space_rows(int B, int num_ranges, float angle_min, float angle_inc,
+                                  const GapRecord* gap, const double* states, float* hs,
+                                  hipStream_t stream);
+
+// launch_advance plus that geometry at x_next, written to hs_next [B][2][3] (null: no rows, the plant
+// step alone): one launch. Every other output is bit-identical to launch_advance's.
+hipError_t launch_advance_scan(const AdvanceParams& P, int B, int N, const double* x, const float* u_plan,
+                               const int* status, int num_ranges, float angle_min, float angle_inc,
+                               const GapRecord* gap, double* x_next, double* u_lin_next, float* u_applied,
+                               float* hs_next, hipStream_t stream);
 
 }  // namespace f110qp

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include "f110qp_kernels.h"
+#include "halfspace_geom.h"
 
 namespace f110qp {
 
@@ -42,20 +43,31 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
   return v;
 }
 
-__global__ __launch_bounds__(256) void half_space_kernel(int B, const float* __restrict__ states,
+// ST: the scalar of states, float or double (f110qp_find_half_spaces_dev_dbl: x and y unrounded, ori
+// narrowed to float where the reference narrows it, float current_angle = state.ori()).
+// SEARCH: the gap search alone (f110qp_gap_search_dev): no pose is read and the geometry tail is
+// left out; lane 0 writes the scan's GapRecord (halfspace_geom.h) to rec[b] instead of hs / gap_lo /
+// gap_hi. The search reads only the scan, so it runs once per scan where the pose changes per tick.
+template <typename ST, bool SEARCH>
+__global__ __launch_bounds__(256) void half_space_kernel(int B, const ST* __restrict__ states,
                                                          const float* __restrict__ ranges,
                                                          int nr, float angle_min, float angle_inc,
                                                          float angle_max, float thresh,
                                                          float divider, float buffer,
                                                          float* __restrict__ hs, int* gap_lo,
-                                                         int* gap_hi) {
+                                                         int* gap_hi, GapRecord* __restrict__ rec) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * kHsWaves + (threadIdx.x >> 6);
   if (b >= B) return;  // whole waves only
   const float* r = ranges + (size_t)b * nr;
   // the pose is only needed by the tail: loaded now, its latency hides behind the scan
-  const float st0 = states[3 * b + 0], st1 = states[3 * b + 1], st2 = states[3 * b + 2];
+  ST st0 = 0, st1 = 0, st2 = 0;
+  if constexpr (!SEARCH) {
+    st0 = states[3 * (size_t)b + 0];
+    st1 = states[3 * (size_t)b + 1];
+    st2 = states[3 * (size_t)b + 2];
+  }
   // num_scans = (angle_max - angle_min) / angle_increment + 1 in float, truncated (:118)
   int num_scans = (int)((angle_max - angle_min) / angle_inc + 1.0f);
   if (num_scans > nr) num_scans = nr;
@@ -117,24 +129,33 @@ __global__ __launch_bounds__(256) void half_space_kernel(int B, const float* __r
     best_hi = (int)((float)best_hi - buffer);
     best_lo = (int)((float)best_lo + buffer);
   }
-  if (lane == 0 && gap_lo) gap_lo[b] = best_lo;
-  if (lane == 0 && gap_hi) gap_hi[b] = best_hi;
+  if constexpr (!SEARCH) {
+    if (lane == 0 && gap_lo) gap_lo[b] = best_lo;
+    if (lane == 0 && gap_hi) gap_hi[b] = best_hi;
+  }
   float* o = hs + (size_t)b * 6;
   if (best_lo < 0 || best_hi < 0 || best_lo >= nr || best_hi >= nr) {  // wave-uniform
     const float nanv = __int_as_float(0x7fc00000);
-    if (lane == 0)
-      for (int j = 0; j < 6; j++) o[j] = nanv;
+    if constexpr (SEARCH) {
+      if (lane == 0) rec[b] = GapRecord{best_lo, best_hi, nanv, nanv};
+    } else {
+      if (lane == 0)
+        for (int j = 0; j < 6; j++) o[j] = nanv;
+    }
     return;
   }
   const double poseX = (double)st0, poseY = (double)st1;
-  const float cur = st2;
+  const float cur = (float)st2;
   const float ang1 = angle_min + (float)best_lo * angle_inc + cur;  // :179-180
   const float ang2 = angle_min + (float)best_hi * angle_inc + cur;
   // even lanes evaluate the first end point's cos/sin, odd lanes the second (::cos/::sin(double))
-  double sl, cl;
-  sincos((double)((lane & 1) ? ang2 : ang1), &sl, &cl);
-  const double s1 = __shfl(sl, 0), c1d = __shfl(cl, 0);
-  const double s2 = __shfl(sl, 1), c2d = __shfl(cl, 1);
+  double s1 = 0., c1d = 0., s2 = 0., c2d = 0.;
+  if constexpr (!SEARCH) {
+    double sl, cl;
+    sincos((double)((lane & 1) ? ang2 : ang1), &sl, &cl);
+    s1 = __shfl(sl, 0), c1d = __shfl(cl, 0);
+    s2 = __shfl(sl, 1), c2d = __shfl(cl, 1);
+  }
   // ranges[best_lo], ranges[best_hi]: from the registers of the last batch when the scan fits
   // one batch (1,536 beams), else re-read (L2). An empty window (num_scans <= 0: no block was
   // loaded, (lo, hi) = (0, 0)) reads ranges[0] as the reference does.
@@ -152,6 +173,10 @@ __global__ __launch_bounds__(256) void half_space_kernel(int B, const float* __r
   } else {
     rlo = r[best_lo];
     rhi = r[best_hi];
+  }
+  if constexpr (SEARCH) {
+    if (lane == 0) rec[b] = GapRecord{best_lo, best_hi, rlo, rhi};
+    return;
   }
   const float p1x = (float)((double)rlo * c1d + poseX);  // :181-185
   const float p1y = (float)((double)rlo * s1 + poseY);
@@ -174,14 +199,51 @@ __global__ __launch_bounds__(256) void half_space_kernel(int B, const float* __r
   }
 }
 
-hipError_t launch_half_spaces(int B, const float* states, const float* ranges, int nr,
+template <typename ST>
+hipError_t launch_half_spaces(int B, const ST* states, const float* ranges, int nr,
                               float angle_min, float angle_inc, float angle_max, float thresh,
                               float divider, float buffer, float* hs, int* gap_lo, int* gap_hi,
                               hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  hipLaunchKernelGGL(half_space_kernel, dim3((B + kHsWaves - 1) / kHsWaves), dim3(64 * kHsWaves), 0, s,
-                     B, states, ranges, nr, angle_min, angle_inc, angle_max, thresh, divider,
-                     buffer, hs, gap_lo, gap_hi);
+  hipLaunchKernelGGL((half_space_kernel<ST, false>), dim3((B + kHsWaves - 1) / kHsWaves), dim3(64 * kHsWaves),
+                     0, s, B, states, ranges, nr, angle_min, angle_inc, angle_max, thresh, divider,
+                     buffer, hs, gap_lo, gap_hi, (GapRecord*)nullptr);
+  return hipGetLastError();
+}
+template hipError_t launch_half_spaces<float>(int, const float*, const float*, int, float, float, float, float,
+                                              float, float, float*, int*, int*, hipStream_t);
+template hipError_t launch_half_spaces<double>(int, const double*, const float*, int, float, float, float, float,
+                                               float, float, float*, int*, int*, hipStream_t);
+
+hipError_t launch_gap_search(int count, const float* ranges, int nr, float angle_min, float angle_inc,
+                             float angle_max, float thresh, float divider, float buffer, GapRecord* rec,
+                             hipStream_t s) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL((half_space_kernel<float, true>), dim3((count + kHsWaves - 1) / kHsWaves),
+                     dim3(64 * kHsWaves), 0, s, count, (const float*)nullptr, ranges, nr, angle_min, angle_inc,
+                     angle_max, thresh, divider, buffer, (float*)nullptr, (int*)nullptr, (int*)nullptr, rec);
+  return hipGetLastError();
+}
+
+// One thread per car: a scan's GapRecord and the car's fp64 pose -> its two half-space rows.
+__global__ __launch_bounds__(256) void half_space_rows_kernel(int B, int nr, float angle_min, float angle_inc,
+                                                              const GapRecord* __restrict__ gap,
+                                                              const double* __restrict__ states,
+                                                              float* __restrict__ hs) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  float o[6];
+  half_space_rows(gap[b], nr, states[3 * (size_t)b], states[3 * (size_t)b + 1], states[3 * (size_t)b + 2],
+                  angle_min, angle_inc, o);
+#pragma unroll
+  for (int j = 0; j < 6; j++) hs[6 * (size_t)b + j] = o[j];
+}
+
+hipError_t launch_half_space_rows(int B, int nr, float angle_min, float angle_inc, const GapRecord* gap,
+                                  const double* states, float* hs, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(half_space_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, nr, angle_min,
+                     angle_inc, gap, states, hs);
   return hipGetLastError();
 }
 

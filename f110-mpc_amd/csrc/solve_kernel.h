@@ -903,7 +903,7 @@ __device__ __forceinline__ void solve_qp(Smem<NUM, GAP, IN>& sm, const int b, co
   // gap rows: a*x + b*y >= -(c+0.5) (constraints.cpp:255-264, mpc.cpp:297-298), recentred
   float ga0 = 0.f, ga1 = 0.f, gb0 = 0.f, gb1 = 0.f;
   double gbeta0 = 0.0, gbeta1 = 0.0;
-  bool infeasible0 = false;
+  bool infeasible0 = false, hs_bad = false;
   if (GAP) {
     const float* h6 = hsg + 6 * b;
     ga0 = h6[0]; gb0 = h6[1]; ga1 = h6[3]; gb1 = h6[4];
@@ -912,7 +912,13 @@ __device__ __forceinline__ void solve_qp(Smem<NUM, GAP, IN>& sm, const int b, co
     // the stage-0 rows are constant (x0 lies on both lines): infeasible only if violated
     if (gbeta0 > 1e-9 * (1.0 + fabs((double)h6[2])) || gbeta1 > 1e-9 * (1.0 + fabs((double)h6[5])))
       infeasible0 = true;
-    if (!(isfinite(gbeta0) && isfinite(gbeta1))) infeasible0 = true;
+    // non-finite rows: no pass runs, as for a violated stage-0 row, and the status is that row's
+    // (PRIMAL_INFEASIBLE, the empty-set verdict). The scan rollout, whose rows are NaN for a scan
+    // without a gap, asks for F110QP_NUMERICAL instead (KParams::hs_nan_numerical)
+    if (!(isfinite(gbeta0) && isfinite(gbeta1))) {
+      infeasible0 = true;
+      hs_bad = P.hs_nan_numerical != 0;
+    }
   }
   wsync();
 
@@ -946,7 +952,7 @@ __device__ __forceinline__ void solve_qp(Smem<NUM, GAP, IN>& sm, const int b, co
     // non-finite data -> F110QP_NUMERICAL with NaN outputs (e.g. the NaN x_ref the planning
     // stage emits for a scenario without a valid candidate, where the reference skips
     // MPC::Update)
-    bool bad = !(isfinite(fX0) && isfinite(fY0) && isfinite(fTH0) && isfinite(ul0) && isfinite(ul1));
+    bool bad = hs_bad || !(isfinite(fX0) && isfinite(fY0) && isfinite(fTH0) && isfinite(ul0) && isfinite(ul1));
     if (lane == 0) bad = bad || !(isfinite(x00[0]) && isfinite(x00[1]) && isfinite(x00[2]));
     const Lin M = sm.M;
     double zero[R], px0[R], py0[R], th0s[R], rxd[R], ryd[R], rthd[R], g64[R];

@@ -104,6 +104,13 @@ EXPORTED = (
     "f110qp_advance_dev",
     "f110qp_rollout_dev",
     "f110qp_rollout",
+    "f110qp_find_half_spaces_dev_dbl",
+    "f110qp_default_scan_config",
+    "f110qp_gap_search_dev",
+    "f110qp_half_space_rows_dev",
+    "f110qp_advance_scan_dev",
+    "f110qp_rollout_scan_dev",
+    "f110qp_rollout_scan",
 )
 SCRATCH_NAMES = {0: "none (wave back end)", 1: "LDS fp64", 2: "LDS fp32", 3: "HBM fp64", 4: "HBM fp32"}
 
@@ -150,6 +157,23 @@ class RolloutConfig(C.Structure):
     ]
 
 
+class ScanConfig(C.Structure):
+    _fields_ = [
+        ("num_ranges", C.c_int),
+        ("angle_min", C.c_float),
+        ("angle_increment", C.c_float),
+        ("angle_max", C.c_float),
+        ("ftg_thresh", C.c_float),
+        ("divider", C.c_float),
+        ("buffer", C.c_float),
+        ("scan_rows", C.c_int),
+    ]
+
+
+# f110qp_gap_record (16 bytes) as a numpy record
+GAP_RECORD_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("r_lo", np.float32), ("r_hi", np.float32)])
+
+
 class F110QPError(RuntimeError):
     pass
 
@@ -190,6 +214,14 @@ def load(test: bool = False):
     L.f110qp_advance_dev.argtypes = [C.POINTER(RolloutConfig), C.c_int, C.c_int] + [fp] * 7
     L.f110qp_rollout_dev.argtypes = [C.c_void_p, C.POINTER(RolloutConfig), C.c_int] + [fp] * 11
     L.f110qp_rollout.argtypes = [C.c_void_p, C.POINTER(RolloutConfig), C.c_int] + [fp] * 10
+    L.f110qp_default_scan_config.argtypes = [C.POINTER(ScanConfig)]
+    L.f110qp_find_half_spaces_dev_dbl.argtypes = [C.c_int, fp, fp, C.c_int, C.c_float, C.c_float, C.c_float,
+                                                  C.c_float, C.c_float, C.c_float, fp, fp, fp, fp]
+    L.f110qp_gap_search_dev.argtypes = [C.POINTER(ScanConfig), C.c_int, fp, fp, fp]
+    L.f110qp_half_space_rows_dev.argtypes = [C.POINTER(ScanConfig), C.c_int, fp, fp, fp, fp]
+    L.f110qp_advance_scan_dev.argtypes = [C.POINTER(RolloutConfig), C.POINTER(ScanConfig), C.c_int, C.c_int] + [fp] * 9
+    L.f110qp_rollout_scan_dev.argtypes = [C.c_void_p, C.POINTER(RolloutConfig), C.POINTER(ScanConfig), C.c_int] + [fp] * 12
+    L.f110qp_rollout_scan.argtypes = [C.c_void_p, C.POINTER(RolloutConfig), C.POINTER(ScanConfig), C.c_int] + [fp] * 11
     L.f110qp_select_dev.argtypes = [C.c_int, fp, C.c_int, fp, fp, fp, fp, fp]
     L.f110qp_backend_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
     L.f110qp_lane_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -252,6 +284,16 @@ def default_rollout_config(**over) -> RolloutConfig:
             c.fail_u[0], c.fail_u[1] = v
         else:
             setattr(c, k, v)
+    return c
+
+
+def default_scan_config(**over) -> ScanConfig:
+    """f110qp_default_scan_config: ftg_thresh 3.0, divider 1.5, buffer 3.0, scan_rows 1, the scan's
+    geometry (num_ranges, angle_min, angle_increment, angle_max) zero until the caller sets it."""
+    c = ScanConfig()
+    load().f110qp_default_scan_config(C.byref(c))
+    for k, v in over.items():
+        setattr(c, k, v)
     return c
 
 
@@ -563,6 +605,79 @@ class Solver:
                                           _p(out.get("x_plan"))), "f110qp_rollout")
         return out
 
+    def rollout_scan_dev(self, rc: RolloutConfig, sc: ScanConfig, x_ref, ranges, x_traj, u_lin_traj, u_applied,
+                         status_traj, iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None,
+                         stream=None):
+        """rollout_dev with the half-spaces of every tick computed at that tick's pose
+        (f110qp_rollout_scan_dev): ranges [sc.scan_rows,B,sc.num_ranges] f32 (scan_rows 1 or ticks)
+        replaces halfspace; hs_traj [T,B,2,3] f32 optional, row t the rows tick t solved with."""
+        import torch
+
+        T, N = int(rc.ticks), self.horizon
+        if T < 1:
+            raise F110QPError("ticks must be >= 1")
+        S = self.config.x_ref_points or N
+        B, R, NR = int(x_ref.shape[0]), int(sc.scan_rows), int(sc.num_ranges)
+        if R not in (1, T):
+            raise F110QPError(f"scan_rows must be 1 or ticks = {T}, got {R}")
+        if tuple(x_traj.shape) != (T + 1, B, 3):
+            raise F110QPError(f"x_traj must be [ticks + 1, B, 3] = {(T + 1, B, 3)}, got {tuple(x_traj.shape)}")
+        if tuple(ranges.shape) != (R, B, NR):
+            raise F110QPError(f"ranges must be [scan_rows, B, num_ranges] = {(R, B, NR)}, got {tuple(ranges.shape)}")
+        _devs((x_ref, "f64", 3 * S * B, "x_ref"), (ranges, "f32", R * B * NR, "ranges"),
+              (x_traj, "f64", 3 * B * (T + 1), "x_traj"), (u_lin_traj, "f64", 2 * B * (T + 1), "u_lin_traj"),
+              (u_applied, "f32", 2 * B * T, "u_applied"), (status_traj, "i32", B * T, "status_traj"),
+              (iters_traj, "i32", B * T, "iters_traj", True), (cost_traj, "f64", B * T, "cost_traj", True),
+              (u_plan, "f32", 2 * N * B * T, "u_plan", True), (x_plan, "f32", 3 * (N + 1) * B * T, "x_plan", True),
+              (hs_traj, "f32", 6 * B * T, "hs_traj", True))
+        if stream is None:
+            stream = torch.cuda.current_stream(x_traj.device)
+        self._chk(self.lib.f110qp_rollout_scan_dev(self._h, C.byref(rc), C.byref(sc), B, _tp(x_ref), _tp(ranges),
+                                                   _tp(x_traj), _tp(u_lin_traj), _tp(u_applied), _tp(status_traj),
+                                                   _tp(iters_traj), _tp(cost_traj), _tp(u_plan), _tp(x_plan),
+                                                   _tp(hs_traj), C.c_void_p(stream.cuda_stream)),
+                  "f110qp_rollout_scan_dev")
+
+    def rollout_scan(self, x0, u_lin, x_ref, ranges, sc: ScanConfig, ticks, plans=False, objective=False,
+                     rows=True, rc=None):
+        """rollout() with the half-spaces of every tick computed at that tick's pose
+        (f110qp_rollout_scan, synchronous): ranges [B,R] (sc.scan_rows 1) or [ticks,B,R] (sc.scan_rows
+        ticks) float32. Returns rollout()'s dict; rows=True adds hs_traj [T,B,2,3]."""
+        N, T = self.horizon, int(ticks)
+        if T < 1:
+            raise F110QPError("ticks must be >= 1")
+        x0 = _f64(x0, (-1, 3), "x0")
+        B = x0.shape[0]
+        ul = _f64(u_lin, (B, 2), "u_lin")
+        xr = _f64(x_ref, (B, self.config.x_ref_points or N, 3), "x_ref")
+        R = int(sc.scan_rows)
+        if R not in (1, T):
+            raise F110QPError(f"scan_rows must be 1 or ticks = {T}, got {R}")
+        rg = np.ascontiguousarray(ranges, np.float32)
+        if rg.size != R * B * int(sc.num_ranges):
+            raise F110QPError(f"ranges must hold [scan_rows, B, num_ranges] = {(R, B, int(sc.num_ranges))} values, "
+                              f"got shape {rg.shape}")
+        cfg = RolloutConfig()
+        C.memmove(C.byref(cfg), C.byref(rc if rc is not None else default_rollout_config()), C.sizeof(cfg))
+        cfg.ticks = T
+        out = {"x_traj": np.empty((T + 1, B, 3), np.float64), "u_lin_traj": np.empty((T + 1, B, 2), np.float64),
+               "u_applied": np.empty((T, B, 2), np.float32), "status": np.empty((T, B), np.int32),
+               "iters": np.empty((T, B), np.int32)}
+        out["x_traj"][0], out["u_lin_traj"][0] = x0, ul
+        if objective:
+            out["cost"] = np.empty((T, B), np.float64)
+        if plans:
+            out["u_plan"] = np.empty((T, B, N, 2), np.float32)
+            out["x_plan"] = np.empty((T, B, N + 1, 3), np.float32)
+        if rows:
+            out["hs_traj"] = np.empty((T, B, 2, 3), np.float32)
+        self._chk(self.lib.f110qp_rollout_scan(self._h, C.byref(cfg), C.byref(sc), B, _p(xr), _p(rg),
+                                               _p(out["x_traj"]), _p(out["u_lin_traj"]), _p(out["u_applied"]),
+                                               _p(out["status"]), _p(out["iters"]), _p(out.get("cost")),
+                                               _p(out.get("u_plan")), _p(out.get("x_plan")), _p(out.get("hs_traj"))),
+                  "f110qp_rollout_scan")
+        return out
+
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
         N = self.horizon
@@ -744,6 +859,24 @@ def advance_dev(rc: RolloutConfig, horizon: int, x, u_plan, status, x_next, u_li
            "f110qp_advance_dev")
 
 
+def advance_scan_dev(rc: RolloutConfig, sc: ScanConfig, horizon: int, x, u_plan, status, gap, x_next, u_lin_next,
+                     hs_next, u_applied=None, stream=None):
+    """advance_dev plus, in the same launch, the half-space rows at x_next (f110qp_advance_scan_dev):
+    gap [B] gap records (gap_search_dev) of the scans the next tick reads -> hs_next [B,2,3] f32."""
+    import torch
+
+    B, N = int(x.shape[0]), int(horizon)
+    _devs((x, "f64", 3 * B, "x"), (u_plan, "f32", 2 * N * B, "u_plan"), (status, "i32", B, "status"),
+          (gap, "i32", 4 * B, "gap"), (x_next, "f64", 3 * B, "x_next"), (u_lin_next, "f64", 2 * B, "u_lin_next"),
+          (hs_next, "f32", 6 * B, "hs_next"), (u_applied, "f32", 2 * B, "u_applied", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_advance_scan_dev(C.byref(rc), C.byref(sc), B, N, _tp(x), _tp(u_plan), _tp(status), _tp(gap),
+                                          _tp(x_next), _tp(u_lin_next), _tp(u_applied), _tp(hs_next),
+                                          C.c_void_p(stream.cuda_stream)),
+           "f110qp_advance_scan_dev")
+
+
 def select_dev(group, num_groups, cost, status, winner, best_cost, stream=None):
     """Per-scenario argmin on the device (f110qp_select_dev): group [B] i32, cost [B] f64,
     status [B] i32 -> winner [G] i32 (-1: no solved candidate), best_cost [G] f64."""
@@ -791,6 +924,54 @@ def find_half_spaces_dev(states, ranges, angle_min, angle_inc, angle_max, hs_out
                                          float(angle_max), float(thresh), float(divider), float(buffer),
                                          _tp(hs_out), _tp(gap_lo), _tp(gap_hi), C.c_void_p(stream.cuda_stream)),
            "f110qp_find_half_spaces_dev")
+
+
+def find_half_spaces_dev_dbl(states, ranges, angle_min, angle_inc, angle_max, hs_out, gap_lo=None, gap_hi=None,
+                             thresh=3.0, divider=1.5, buffer=3.0, stream=None):
+    """find_half_spaces_dev on float64 states [B,3] (f110qp_find_half_spaces_dev_dbl): x and y enter
+    the end points unrounded."""
+    import torch
+
+    L = load()
+    B, R = ranges.shape
+    _devs((states, "f64", 3 * B, "states"), (ranges, "f32", B * R, "ranges"), (hs_out, "f32", 6 * B, "hs_out"),
+          (gap_lo, "i32", B, "gap_lo", True), (gap_hi, "i32", B, "gap_hi", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(states.device)
+    _check(L.f110qp_find_half_spaces_dev_dbl(B, _tp(states), _tp(ranges), R, float(angle_min), float(angle_inc),
+                                             float(angle_max), float(thresh), float(divider), float(buffer),
+                                             _tp(hs_out), _tp(gap_lo), _tp(gap_hi), C.c_void_p(stream.cuda_stream)),
+           "f110qp_find_half_spaces_dev_dbl")
+
+
+def gap_search_dev(sc: ScanConfig, ranges, gap_out, stream=None):
+    """The gap search of FindHalfSpaces alone (f110qp_gap_search_dev): ranges [..., sc.num_ranges] f32,
+    every leading index a scan -> gap_out, an int32 tensor of 4 words per scan holding the 16-byte
+    records (lo, hi as int32, r_lo, r_hi as float32 bits: view the host copy as GAP_RECORD_DTYPE)."""
+    import torch
+
+    R = int(sc.num_ranges)
+    if ranges.shape[-1] != R:
+        raise F110QPError(f"ranges must be [..., num_ranges = {R}], got {tuple(ranges.shape)}")
+    count = ranges.numel() // R if R else 0
+    _devs((ranges, "f32", count * R, "ranges"), (gap_out, "i32", 4 * count, "gap_out"))
+    if stream is None:
+        stream = torch.cuda.current_stream(ranges.device)
+    _check(load().f110qp_gap_search_dev(C.byref(sc), count, _tp(ranges), _tp(gap_out),
+                                        C.c_void_p(stream.cuda_stream)), "f110qp_gap_search_dev")
+
+
+def half_space_rows_dev(sc: ScanConfig, gap, states, hs_out, stream=None):
+    """The end-point geometry of FindHalfSpaces (f110qp_half_space_rows_dev): gap [B] records (an
+    int32 tensor of 4 words per car), states [B,3] f64 -> hs_out [B,2,3] f32."""
+    import torch
+
+    B = int(states.shape[0])
+    _devs((gap, "i32", 4 * B, "gap"), (states, "f64", 3 * B, "states"), (hs_out, "f32", 6 * B, "hs_out"))
+    if stream is None:
+        stream = torch.cuda.current_stream(states.device)
+    _check(load().f110qp_half_space_rows_dev(C.byref(sc), B, _tp(gap), _tp(states), _tp(hs_out),
+                                             C.c_void_p(stream.cuda_stream)), "f110qp_half_space_rows_dev")
 
 
 # ---- planning stage (plan_kernels.hip) ---------------------------------------------------------

@@ -336,7 +336,10 @@ int f110qp_advance_dev(const f110qp_rollout_config* rc, int batch, int horizon, 
 /* T closed-loop ticks of B cars (device pointers, asynchronous on `stream`):
  *   x_ref      [B][S][3] double, halfspace [B][2][3] float32 or NULL: held fixed over the T ticks
  *              (the reference passes the same miniPath_ every tick between re-plans,
- *              src/project.cpp:188; the half-spaces are world-frame lines)
+ *              src/project.cpp:188). Holding the half-spaces is a shortcut of this call, not the
+ *              reference's behaviour: MPC::Update recomputes them on every tick from the scan it
+ *              holds and the car's current pose (src/mpc.cpp:73-75), so both lines move and turn
+ *              with the car. f110qp_rollout_scan[_dev] below does that.
  *   x_traj     [T+1][B][3] double, u_lin_traj [T+1][B][2] double: row 0 holds the start on entry,
  *              row t+1 is written by tick t
  *   u_applied  [T][B][2] float32, status_traj [T][B]
@@ -476,6 +479,100 @@ int f110qp_find_half_spaces_dev(int batch, const float* states, const float* ran
                                 int num_ranges, float angle_min, float angle_increment,
                                 float angle_max, float ftg_thresh, float divider, float buffer,
                                 float* hs_out, int* gap_lo, int* gap_hi, void* stream);
+
+/* Same on double states [B][3]: x and y enter the end points unrounded, as the reference reads
+ * poseX / poseY (doubles); ori is narrowed to float where the reference narrows it (float
+ * current_angle = state.ori()). For doubles that are float32 values the output is bit-identical to
+ * the float call's. */
+int f110qp_find_half_spaces_dev_dbl(int batch, const double* states, const float* ranges,
+                                    int num_ranges, float angle_min, float angle_increment,
+                                    float angle_max, float ftg_thresh, float divider, float buffer,
+                                    float* hs_out, int* gap_lo, int* gap_hi, void* stream);
+
+/* ---- closed loop with gap rows: FindHalfSpaces at every tick's pose -----------------------------
+ * MPC::Update calls constraints_.FindHalfSpaces(current_state_, scan_msg_) on every tick
+ * (src/mpc.cpp:73-75) with the scan MPC::UpdateScan stored on the first scan message
+ * (src/project.cpp:45-49) and the car's current pose. FindHalfSpaces splits where the pose enters:
+ *   the gap search (src/constraints.cpp:118-177: window, threshold, first longest run, buffer
+ *   inflation) reads only the scan: one launch per scan set, one wavefront per scan, one 16-byte
+ *   record per scan;
+ *   the end-point geometry (:179-264) reads the record and the pose: one thread per car, fused
+ *   into the plant-step launch, which holds the car's next pose in registers.
+ * Additive: F110QP_API_VERSION stays 6. */
+typedef struct {
+  int   num_ranges;       /* beams per scan, 1..65535                                               */
+  float angle_min;        /* LaserScan.angle_min                                                    */
+  float angle_increment;  /* LaserScan.angle_increment, > 0                                         */
+  float angle_max;        /* LaserScan.angle_max                                                    */
+  float ftg_thresh;       /* 3.0, params.yaml (Constraints::ftg_thresh_)                            */
+  float divider;          /* 1.5: the field-of-view window is +-1.571 / divider                     */
+  float buffer;           /* 3.0: beams the gap shrinks by at either end                            */
+  int   scan_rows;        /* 1: one scan per car, held for the whole call (the reference); T: ranges */
+                          /* [T][B][num_ranges], tick t reads row t (recorded or simulated scans)    */
+} f110qp_scan_config;
+
+/* Zeroes *sc, then ftg_thresh 3.0, divider 1.5, buffer 3.0 and scan_rows 1 (the scan's geometry is
+ * the caller's). */
+void f110qp_default_scan_config(f110qp_scan_config* sc);
+
+/* One record of the gap search: (lo, hi) exactly what f110qp_find_half_spaces_dev reports as
+ * gap_lo / gap_hi (after the buffer inflation; -1 and out-of-range values included), r_lo / r_hi =
+ * ranges[lo], ranges[hi], NaN where lo or hi is no beam of the scan (the rows are NaN then). */
+typedef struct {
+  int   lo, hi;
+  float r_lo, r_hi;
+} f110qp_gap_record;
+
+/* The gap search of `count` scans (device pointers, asynchronous, one launch): ranges
+ * [count][num_ranges] -> gap_out [count]. sc->scan_rows is not read. */
+int f110qp_gap_search_dev(const f110qp_scan_config* sc, int count, const float* ranges,
+                          f110qp_gap_record* gap_out, void* stream);
+
+/* The end-point geometry of B cars (one launch, one thread per car): gap [B], states [B][3] double
+ * -> hs_out [B][2][3] float32. f110qp_gap_search_dev followed by this call is bit-identical to
+ * f110qp_find_half_spaces_dev_dbl. Reads num_ranges, angle_min and angle_increment of sc. */
+int f110qp_half_space_rows_dev(const f110qp_scan_config* sc, int batch, const f110qp_gap_record* gap,
+                               const double* states, float* hs_out, void* stream);
+
+/* f110qp_advance_dev and, in the same launch, f110qp_half_space_rows_dev at x_next into hs_next
+ * [B][2][3]: gap [B] holds the records of the scans the next tick reads. x_next, u_lin_next and
+ * u_applied are bit-identical to f110qp_advance_dev's. The argument rules of f110qp_advance_dev
+ * apply; gap and hs_next must be non-NULL. */
+int f110qp_advance_scan_dev(const f110qp_rollout_config* rc, const f110qp_scan_config* sc, int batch,
+                            int horizon, const double* x, const float* u_plan, const int* status,
+                            const f110qp_gap_record* gap, double* x_next, double* u_lin_next,
+                            float* u_applied, float* hs_next, void* stream);
+
+/* f110qp_rollout_dev with the half-spaces of every tick computed at that tick's pose, as the
+ * reference computes them. Arguments as f110qp_rollout_dev, except:
+ *   ranges   [scan_rows][B][num_ranges] float32 replaces halfspace (scan_rows = 1 or T; any other
+ *            value is F110QP_ERR_INVALID)
+ *   hs_traj  [T][B][2][3] float32: row t holds the rows tick t solved with; may be NULL (the rows
+ *            then live in one buffer of the context of B rows: in stream order tick t's solve has
+ *            read them before tick t's plant step writes the next ones).
+ * Launches: in front of the loop one gap search over scan_rows x B scans and one rows launch for
+ * tick 0; per tick exactly the launches of f110qp_rollout_dev, the plant step being the fused one
+ * (the last tick's the plain one: there is no row T). No host synchronisation, read-back or
+ * allocation inside the loop; every argument is checked before the first launch.
+ * gap_mode INACTIVE: valid. The rows are computed only when hs_traj is given (the shipped reference
+ * computes them and then bounds them by +-INFTY) and the solves ignore them; with hs_traj NULL the
+ * call makes exactly f110qp_rollout_dev's launches.
+ * A scan without a gap gives NaN rows: the tick's solve returns F110QP_NUMERICAL for that car
+ * (non-finite data; in this call only: f110qp_solve_batch* on NaN rows keeps its
+ * F110QP_PRIMAL_INFEASIBLE, with the same NaN outputs) and the car applies fail_u, as any car
+ * without a usable plan. */
+int f110qp_rollout_scan_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc,
+                            const f110qp_scan_config* sc, int batch, const double* x_ref,
+                            const float* ranges, double* x_traj, double* u_lin_traj, float* u_applied,
+                            int* status_traj, int* iters_traj, double* cost_traj, float* u_plan,
+                            float* x_plan, float* hs_traj, void* stream);
+
+/* Same on host pointers (synchronous): ranges staged to and hs_traj copied back from device
+ * buffers of the context, one stream synchronisation at the end, as f110qp_rollout. */
+int f110qp_rollout_scan(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                        int batch, const double* x_ref, const float* ranges, double* x_traj,
+                        double* u_lin_traj, float* u_applied, int* status_traj, int* iters_traj,
+                        double* cost_traj, float* u_plan, float* x_plan, float* hs_traj);
 
 /* ---- planning stage in front of MPC::Update (src/project.cpp:73-152) ----------------------- */
 
