@@ -1,6 +1,10 @@
 // host_demo — drives the ROS-free C++ class surface (MPC / Constraints / Model / Cost / State /
 // Input / LoadParams) for the pytest suite.
 //   host_demo cpu <params.yaml>                         host-only checks, JSON on stdout
+//   host_demo ref <params.yaml> <in.bin> <out.bin>      Model and Constraints on recorded inputs
+//     (host only). in.bin (float64): n, n x (x, y, ori, v, steer, dt), then m, m x (x, y, ori,
+//     angle_min, angle_inc, angle_max, R, ranges[R]). out.bin (float64): n x (A[9], B[6], C[3],
+//     simulate_dynamics[3]), m x (ok, l1[3], l2[3]), u_min[2], u_max[2].
 //   host_demo tick <params.yaml> <in.bin> <out.bin>     MPC::Update over T ticks (GPU)
 //   host_demo batch <params.yaml> <in.bin> <out.bin>    MPC::UpdateBatch over B candidates (GPU)
 //   host_demo project <params.yaml> <in.bin> <out.bin>  the project node's callbacks over T ticks
@@ -72,6 +76,55 @@ static int cpu(const char* params_path) {
   std::printf("\"cost_diag\": [%.17g, %.17g, %.17g, %.17g, %.17g]}\n", cost.q()[0][0], cost.q()[1][1],
               cost.q()[2][2], cost.r()[0][0], cost.r()[1][1]);
   return 0;
+}
+
+static int ref(const char* params_path, const char* in, const char* out) {
+  Params p;
+  if (!LoadParams(params_path, &p)) return 2;
+  std::ifstream f(in, std::ios::binary);
+  f.seekg(0, std::ios::end);
+  std::vector<double> d(static_cast<size_t>(f.tellg()) / 8), res;
+  f.seekg(0);
+  f.read(reinterpret_cast<char*>(d.data()), d.size() * 8);
+  size_t o = 0;
+  const int n = static_cast<int>(d[o++]);
+  Model m;
+  for (int i = 0; i < n; i++, o += 6) {
+    State s(d[o], d[o + 1], d[o + 2]), ns;
+    Input u(d[o + 3], d[o + 4]);
+    m.Linearize(s, u, d[o + 5]);
+    const auto A = m.A();
+    const auto B = m.B();
+    const auto C = m.C();
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) res.push_back(A[r][c]);
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 2; c++) res.push_back(B[r][c]);
+    for (int r = 0; r < 3; r++) res.push_back(C[r]);
+    m.simulate_dynamics(s, u, d[o + 5], ns);
+    res.push_back(ns.x());
+    res.push_back(ns.y());
+    res.push_back(ns.ori());
+  }
+  const int cases = static_cast<int>(d[o++]);
+  Constraints con(p);
+  for (int i = 0; i < cases; i++) {
+    State car(d[o], d[o + 1], d[o + 2]);
+    LaserScan scan;
+    scan.angle_min = static_cast<float>(d[o + 3]);
+    scan.angle_increment = static_cast<float>(d[o + 4]);
+    scan.angle_max = static_cast<float>(d[o + 5]);
+    const int R = static_cast<int>(d[o + 6]);
+    o += 7;
+    scan.ranges.resize(R);
+    for (int k = 0; k < R; k++) scan.ranges[k] = static_cast<float>(d[o++]);
+    res.push_back(con.FindHalfSpaces(car, scan) ? 1.0 : 0.0);
+    for (int k = 0; k < 3; k++) res.push_back(con.l1()[k]);
+    for (int k = 0; k < 3; k++) res.push_back(con.l2()[k]);
+  }
+  for (int k = 0; k < 2; k++) res.push_back(con.u_min()[k]);
+  for (int k = 0; k < 2; k++) res.push_back(con.u_max()[k]);
+  std::ofstream g(out, std::ios::binary);
+  g.write(reinterpret_cast<const char*>(res.data()), res.size() * 8);
+  return g ? 0 : 2;
 }
 
 static int tick(const char* params_path, const char* in, const char* out, bool batch) {
@@ -232,6 +285,7 @@ int main(int argc, char** argv) {
   if (argc >= 4 && !std::strcmp(argv[1], "project_threaded")) return project_threaded(argv[2], argv[3]);
   if (argc >= 5 && !std::strcmp(argv[1], "project")) return project(argv[2], argv[3], argv[4]);
   if (argc >= 3 && !std::strcmp(argv[1], "cpu")) return cpu(argv[2]);
+  if (argc >= 5 && !std::strcmp(argv[1], "ref")) return ref(argv[2], argv[3], argv[4]);
   if (argc >= 5 && !std::strcmp(argv[1], "tick")) return tick(argv[2], argv[3], argv[4], false);
   if (argc >= 5 && !std::strcmp(argv[1], "batch")) return tick(argv[2], argv[3], argv[4], true);
   std::fprintf(stderr, "usage: host_demo cpu|tick|batch ...\n");

@@ -79,8 +79,9 @@ void f110o_simulate_dynamics(const double s[3], const double u[2], double dt, do
  * angle (:182-186) resolves to: 0 = ::cos(double) (the C library function; the restatement's
  * default), 1 = the float overload std::cos(float) (= cosf, the product ranges * cosf in float),
  * which the libstdc++ <math.h> wrapper puts in the global namespace when some header of the ROS /
- * Eigen include chain pulls it in. Which one the reference build gets cannot be checked here
- * (ROS and Eigen are absent); tests/test_halfspace_overload.py measures the difference. */
+ * Eigen include chain pulls it in. Both variants are asserted equal to the reference's source
+ * compiled without and with <math.h> (tests/test_reference_parity.py); which chain the real ROS /
+ * Eigen headers give is open. tests/test_halfspace_overload.py measures the difference. */
 int f110o_find_half_spaces_trig(const double state[3], const float* ranges, int nr, float angle_min,
                                 float angle_inc, float angle_max, float ftg_thresh, float divider,
                                 float buffer, double l1[3], double l2[3], int* out_lo, int* out_hi,

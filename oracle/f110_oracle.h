@@ -9,12 +9,12 @@
  * the float-typed params dt_, L, u bounds). Each function cites the reference
  * file:line it restates (paths relative to the reference repository root).
  *
- * Parity status: the reference publishes no tests, fixtures or solver outputs
- * and cannot be built here (ROS1 + Eigen3 + OsqpEigen + OSQP are absent), so the
- * QP *solution* parity is pinned to the exact optimum, certified by a KKT check
- * on the reference's own sparse formulation (f110o_kkt_residuals), not to
- * OSQP's (eps=1e-3) output. Linearize is pinned to known-answer vectors derived
- * from src/model.cpp:30-59 (tests/golden/linearize_kat.json).
+ * Parity status: Linearize, simulate_dynamics, FindHalfSpaces and the assembly
+ * are asserted equal to the reference's own sources compiled behind stand-in
+ * headers (refshim/, ref_driver.cpp, tests/test_reference_parity.py). OSQP is
+ * absent, so the QP *solution* parity is pinned to the exact optimum, certified
+ * by a KKT check on the reference's own sparse formulation
+ * (f110o_kkt_residuals), not to OSQP's (eps=1e-3) output.
  */
 #ifndef F110_ORACLE_H
 #define F110_ORACLE_H

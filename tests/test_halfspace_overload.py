@@ -1,8 +1,11 @@
-"""Sensitivity of the C3 gap rows to one unverifiable detail of the reference: the unqualified
+"""Sensitivity of the C3 gap rows to one detail of the reference: the unqualified
 cos(angle1) / sin(angle1) on a float angle in Constraints::FindHalfSpaces
-(src/constraints.cpp:182-186 of the reference). It resolves to ::cos(double) unless some header of
-the ROS / Eigen include chain brings the libstdc++ <math.h> wrapper's float overload into the global
-namespace; neither can be built here. The oracle and the device kernel assume the double overload
+(src/constraints.cpp:182-186 of the reference). Observed on the reference's own compiled source
+(tests/golden/ref_halfspace.npz, tests/test_reference_parity.py): with only <cmath> in the include
+chain it calls ::cos(double); with the libstdc++ <math.h> wrapper included as well, the float overload
+is in the global namespace and is chosen, and the rows of 18 of the 82 recorded scans change. Each of
+the oracle's two variants equals one of the two builds. Which chain the real roscpp / Eigen headers
+give is still open (they are not here). The oracle and the device kernel assume the double overload
 (oracle/f110_oracle.c, csrc/halfspace_kernels.hip); this test measures what the float overload
 would change on the committed gap-row fixtures and on the bench's C3 batch (CPU only: the oracle's
 half-spaces and exact optima for both overloads). Measured: about 40% of the QPs get
