@@ -76,8 +76,8 @@ constexpr size_t seg_lds_bytes(int N, int S, bool fst = false, bool f32 = false)
 // The fixed-length kernels (lane_seg_kernel<..., Q > 0>: EVEN, FST, fp64 scratch, Q stages per segment)
 // keep a lane's references, its PDAS state and the first seg_fixedq_reg_gains of a stage's 8 feedback
 // gains (K 6, then k 2) in registers; their LDS holds the lam-gains F (6 per stage), the gains that
-// are not in registers and the two code tables. (The float staging of the references borrows the
-// scratch rows: 3 N (64 / S) + 64 input scalars, 8 KiB at most at N = 20, S = 4, under Q x 6 rows.)
+// are not in registers and the two code tables. (The references are not staged: every lane loads
+// its own 3 Q scalars from global memory.)
 #ifndef F110QP_SEG_QREG
 #define F110QP_SEG_QREG 8  // (knob: 0 .. 8)
 #endif
@@ -144,6 +144,20 @@ __device__ __forceinline__ double seg_dn(double v, int lane) {
   else {  // row_shr:1; segment 0 takes 0: the ring hands it the top segment's x_e, which is 0
     const double b = dpp_d<0x111>(v);
     return (lane & 7) == 0 ? 0.0 : b;
+  }
+}
+
+// the value of the twin sibling's lane (lane ^ S: the other PDAS start of the QP, same segment). At
+// S = 4 the sibling is the neighbouring quad of the lane's DPP row: row_shl:4 reads lane + 4,
+// row_shr:4 lane - 4, and bit 2 of the lane says which one is the sibling (two VALU moves and a
+// select instead of a ds_bpermute round trip); any other S goes through the permute
+template <int S>
+__device__ __forceinline__ int seg_sib(int v, int lane) {
+  if constexpr (S == 4) {
+    const int up = dpp_i<0x104>(v), dn = dpp_i<0x114>(v);
+    return (lane & 4) ? dn : up;
+  } else {
+    return __shfl_xor(v, S, 64);
   }
 }
 
@@ -249,7 +263,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   // 23.1 us, C5 30.9 against 30.4, same box.) Twin starts: row q of the wave is QP (b0 >> 1) + q.
   // Twin starts: the two starts of a QP share its row, staged once ([3N][L / 2] QP rows)
   constexpr int LR = L >> twin;
-  {
+  // Q > 0: no staging. A lane's 3 Q reference scalars are one contiguous run of its QP's row
+  // (elements 3 s0 .. 3 s0 + 3 Q - 1, row stride 3 xr_stride), loaded straight into registers next
+  // to x0 and u_lin: a QP's S lanes read 12 Q S contiguous bytes, twin siblings the same addresses,
+  // and the lanes of a missing QP those of the valid slot they duplicate. Neither LDS round trip
+  // nor the barriers on both sides of it remain.
+  IN fr[Q > 0 ? 3 * Q : 1];
+  if constexpr (Q > 0) {
+    const IN* xrow = xrg + (size_t)b * (3 * (size_t)P.xr_stride) + 3 * s0;
+#pragma unroll
+    for (int e = 0; e < 3 * Q; e++) fr[e] = xrow[e];
+  } else {
     IN* stg = reinterpret_cast<IN*>(lbase + o_sc);
     const int nqr = (nq + twin) >> twin;  // QP rows of the wave (b0 is even with twin starts)
     const int n3 = 3 * N, S3 = 3 * P.xr_stride, tot = nqr * n3;
@@ -345,16 +369,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     if constexpr (Q > 0) {
 #pragma unroll
       for (int t = 0; t < Q; t++) {
-        const int i = s0 + t;
-        const IN fx = stg[(3 * i + 0) * LR + row], fy = stg[(3 * i + 1) * LR + row];
-        const IN ft = stg[(3 * i + 2) * LR + row];
+        const IN fx = fr[3 * t + 0], fy = fr[3 * t + 1], ft = fr[3 * t + 2];
         nonfin |= !(isfinite(fx) && isfinite(fy) && isfinite(ft));
         const double dx = (double)fx - X0, dy = (double)fy - Y0;
         rr[3 * t + 0] = ROT ? cs * dx + sn * dy : dx;
         rr[3 * t + 1] = ROT ? cs * dy - sn * dx : dy;
         rr[3 * t + 2] = (double)ft - th0;
-#pragma unroll
-        for (int e = 0; e < kQReg; e++) gr[t][e] = 0.0;
       }
     } else
     for (int t = 0; t < mM; t++) {
@@ -451,11 +471,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     // per input: 1 lower, 2 upper, 0 free; the lower bound wins. To the wave-uniform mM (rows
     // t >= m of a shorter segment are never read): no EXEC-masked loop exits
     if constexpr (Q > 0) {
+      if (wt) {
 #pragma unroll
-      for (int t = 0; t < Q; t++) {
-        const unsigned l2 = (unsigned)(lw >> (2 * t)) & 3u, h2 = (unsigned)(hw >> (2 * t)) & 3u & ~l2;
-        const unsigned a = (l2 & 1u) | ((h2 & 1u) << 1) | ((l2 & 2u) << 1) | ((h2 & 2u) << 2);
-        apk |= ((tw && 2 * (s0 + t) < N) ? (unsigned)sv : a) << (4 * t);
+        for (int t = 0; t < Q; t++) {
+          const unsigned l2 = (unsigned)(lw >> (2 * t)) & 3u, h2 = (unsigned)(hw >> (2 * t)) & 3u & ~l2;
+          const unsigned a = (l2 & 1u) | ((h2 & 1u) << 1) | ((l2 & 2u) << 1) | ((h2 & 2u) << 2);
+          apk |= ((tw && 2 * (s0 + t) < N) ? (unsigned)sv : a) << (4 * t);
+        }
+      } else {
+        // a call that moves no warm state (wave-uniform): every code is the twin rule's, sv on the
+        // lane's stages t with 2 (s0 + t) < N, that is its first nb = (N + 1) / 2 - s0 (clamped to
+        // 0 .. Q), and free elsewhere; one nibble per stage
+        const int nh = (N + 1) / 2 - s0;
+        const int nb = nh < 0 ? 0 : (nh > Q ? Q : nh);
+        apk = tw ? (unsigned)sv * (0x11111111u & ((1u << (4 * nb)) - 1u)) : 0u;
       }
     } else
     for (int t = 0; t < mM; t++) {
@@ -478,6 +507,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
 
 
   const int max_pass = P.pass_cap > 0 ? P.pass_cap : (P.max_iter > kmax ? P.max_iter : kmax);
+  // Q > 0: the register gains are not initialised: the first backward sweep writes every one before
+  // anything reads them. Only a wave that runs no pass (no budget, or every QP non-finite) reaches
+  // the output sweep without them; it has no solved lane, and its sweep (ran == false, wave-uniform)
+  // stores the NaNs without reading a gain
+  bool ran = false;
 #ifdef F110QP_STAMPS
   t_setup = __builtin_amdgcn_s_memtime() - t_start;
 #endif
@@ -492,6 +526,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
       if (__ballot(!done) == 0ull) break;
     }
     const bool single = pass >= kmax;
+    if constexpr (Q > 0) ran = true;
 #ifdef F110QP_STAMPS
     npass++;
 #endif
@@ -879,8 +914,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   // iteration count while its wave sweeps on), the cold one on a tie or when neither converged
   bool owner = owner0, qowner = qowner0;
   if constexpr (TWIN) {
-    const bool sdone = __shfl_xor((int)done, S, 64) != 0;
-    const int sibit = __shfl_xor(iters, S, 64);
+    // (Q > 0: the sibling's done flag and pass count in one word, one exchange)
+    const int sibw = Q > 0 ? seg_sib<S>((iters << 1) | (int)done, lane) : 0;
+    const bool sdone = Q > 0 ? (sibw & 1) != 0 : __shfl_xor((int)done, S, 64) != 0;
+    const int sibit = Q > 0 ? sibw >> 1 : __shfl_xor(iters, S, 64);
     const bool win = var ? (done && (!sdone || iters < sibit)) : (done ? (!sdone || iters <= sibit) : !sdone);
     owner = owner0 && win;
     qowner = qowner0 && win;
@@ -894,6 +931,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     xo[0] = solved ? (float)fX0 : nanv;
     xo[1] = solved ? (float)fY0 : nanv;
     xo[2] = solved ? (float)fTH0 : nanv;
+    if constexpr (Q > 0) {  // (nothing orders these after the sweep: issued ahead of its arithmetic)
+      status_out[b] = bad ? F110QP_NUMERICAL_ID : (done ? F110QP_SOLVED_ID : F110QP_MAX_ITER_ID);
+      if (iters_out) iters_out[b] = bad ? 0 : (done ? iters : max_pass);
+    }
   }
   const bool want_obj = oo.obj || oo.cost;
   double J = 0.0, Cr = 0.0;
@@ -920,25 +961,44 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     double x0 = xs0, x1 = xs1, x2 = xs2;
     if constexpr (Q > 0) {
       // (the last forward sweep left k + F lam in k's place: no lam-gain is read here)
+      // The objective test is one wave-uniform branch round two copies of the sweep, every output
+      // is selected once (solved or NaN) into registers, and the lane's 5 Q stores go out together
+      // under one owner test: a run of 2 Q floats of u and one of 3 Q of x.
+      float fu[2 * Q], fx[3 * Q];
+      auto sweep = [&](auto obj_tag) {
+        constexpr bool OBJ = decltype(obj_tag)::value != 0;
 #pragma unroll
-      for (int t = 0; t < Q; t++) {
-        const int i = s0 + t;
-        const double u0 = seg_gget<kQReg, NV>(gr, sc, t, 0) * x0 + seg_gget<kQReg, NV>(gr, sc, t, 1) * x1 + seg_gget<kQReg, NV>(gr, sc, t, 2) * x2 + seg_gget<kQReg, NV>(gr, sc, t, 6);
-        const double u1 = seg_gget<kQReg, NV>(gr, sc, t, 3) * x0 + seg_gget<kQReg, NV>(gr, sc, t, 4) * x1 + seg_gget<kQReg, NV>(gr, sc, t, 5) * x2 + seg_gget<kQReg, NV>(gr, sc, t, 7);
-        if (want_obj) {
-          qterm(rr[3 * t], rr[3 * t + 1], rr[3 * t + 2], x0, x1, x2);
-          J += 0.5 * (r0 * (u0 - ud0) * (u0 - ud0) + r1 * (u1 - ud1) * (u1 - ud1));
+        for (int t = 0; t < Q; t++) {
+          const double u0 = seg_gget<kQReg, NV>(gr, sc, t, 0) * x0 + seg_gget<kQReg, NV>(gr, sc, t, 1) * x1 + seg_gget<kQReg, NV>(gr, sc, t, 2) * x2 + seg_gget<kQReg, NV>(gr, sc, t, 6);
+          const double u1 = seg_gget<kQReg, NV>(gr, sc, t, 3) * x0 + seg_gget<kQReg, NV>(gr, sc, t, 4) * x1 + seg_gget<kQReg, NV>(gr, sc, t, 5) * x2 + seg_gget<kQReg, NV>(gr, sc, t, 7);
+          if constexpr (OBJ) {
+            qterm(rr[3 * t], rr[3 * t + 1], rr[3 * t + 2], x0, x1, x2);
+            J += 0.5 * (r0 * (u0 - ud0) * (u0 - ud0) + r1 * (u1 - ud1) * (u1 - ud1));
+          }
+          const double nx0 = x0 + b00 * u0, nx1 = x1 + a12 * x2;  // (ROT)
+          x2 = x2 + b20 * u0 + b21 * u1 + c2;
+          x0 = nx0; x1 = nx1;
+          fu[2 * t] = solved ? (float)u0 : nanv;
+          fu[2 * t + 1] = solved ? (float)u1 : nanv;
+          fx[3 * t + 0] = solved ? (float)(cs * x0 - sn * x1 + X0) : nanv;
+          fx[3 * t + 1] = solved ? (float)(sn * x0 + cs * x1 + Y0) : nanv;
+          fx[3 * t + 2] = solved ? (float)(x2 + th0) : nanv;
         }
-        const double nx0 = x0 + b00 * u0, nx1 = x1 + a12 * x2;  // (ROT)
-        x2 = x2 + b20 * u0 + b21 * u1 + c2;
-        x0 = nx0; x1 = nx1;
-        if (owner) {
-          uo[2 * i] = solved ? (float)u0 : nanv;
-          uo[2 * i + 1] = solved ? (float)u1 : nanv;
-          xo[3 * i + 3] = solved ? (float)(cs * x0 - sn * x1 + X0) : nanv;
-          xo[3 * i + 4] = solved ? (float)(sn * x0 + cs * x1 + Y0) : nanv;
-          xo[3 * i + 5] = solved ? (float)(x2 + th0) : nanv;
-        }
+      };
+      if (!ran) {  // no pass ran: nothing is solved (done == bad), the parent's zero gains gave NaN too
+#pragma unroll
+        for (int e = 0; e < 2 * Q; e++) fu[e] = nanv;
+#pragma unroll
+        for (int e = 0; e < 3 * Q; e++) fx[e] = nanv;
+      } else if (want_obj) sweep(SegMode<1>{});
+      else sweep(SegMode<0>{});
+      if (owner) {
+        float* const ul = uo + 2 * s0;
+        float* const xl = xo + 3 * s0 + 3;
+#pragma unroll
+        for (int e = 0; e < 2 * Q; e++) ul[e] = fu[e];
+#pragma unroll
+        for (int e = 0; e < 3 * Q; e++) xl[e] = fx[e];
       }
     } else
     for (int t = 0; t < m; t++) {
@@ -998,9 +1058,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     const bool ok0 = (ga0 * X0 + gb0 * Y0 >= -gc0 - 1e-9) & (ga1 * X0 + gb1 * Y0 >= -gc1 - 1e-9);
     if (qowner) oo.scr_prio[b] = (!solved || !ok0) ? 1 : (nviol > 0 ? 1 + nviol : 0);
   }
-  if (qowner) {
-    status_out[b] = bad ? F110QP_NUMERICAL_ID : (done ? F110QP_SOLVED_ID : F110QP_MAX_ITER_ID);
-    if (iters_out) iters_out[b] = bad ? 0 : (done ? iters : max_pass);
+  if constexpr (Q == 0) {
+    if (qowner) {
+      status_out[b] = bad ? F110QP_NUMERICAL_ID : (done ? F110QP_SOLVED_ID : F110QP_MAX_ITER_ID);
+      if (iters_out) iters_out[b] = bad ? 0 : (done ? iters : max_pass);
+    }
   }
   if (wt) {  // active set of this solution for the next tick (OR over the segments)
     // the lane's 2m bits (input a of stage t at bit 2t + a), placed at bit 2 s0 of the pair
