@@ -108,6 +108,8 @@ struct f110qp_ctx {
   DevBuf rdev;               // host-pointer rollout: device copies of its arrays
   DevBuf rgap;               // scan rollout: one GapRecord per scan (scan_rows x B)
   DevBuf rhs;                // scan rollout without hs_traj: the current tick's rows (B x 6 floats)
+  DevBuf rstate;             // re-planning rollout: held plans, indices, plan counters and list, and the
+                             // optional per-tick arrays the caller did not give (ReplanWork)
   int lane_kmax = 16;        // lane back end: PDAS passes before single (least-index) flips
   int lane_mode = 0;         // lane scratch placement (LaneWork::mode)
   int lane_qpw = 0;          // lane QPs per wave (LaneWork::qpw, 0 = auto)
@@ -1496,3 +1498,413 @@ extern "C" int f110qp_plan_batch(const f110qp_plan_config* c, int batch, const d
   if ((e = hipStreamSynchronize(s))) return hip_fail(e, "hipStreamSynchronize");
   return F110QP_OK;
 }
+
+// ---- closed loop with re-planning (f110qp_rollout_replan[_dev] and its parts) ----------------------
+
+static int replan_params(const f110qp_replan_config* rp, f110qp::PlanKParams* K) {
+  if (!rp) return fail(F110QP_ERR_INVALID, "replan config is NULL");
+  if (!(rp->replan_dist > 0.0) || !std::isfinite(rp->replan_dist))
+    return fail(F110QP_ERR_INVALID, "replan_dist must be positive and finite");
+  int G;
+  const int rv = validate_plan(&rp->plan, &G);
+  if (rv) return rv;
+  if (rp->num_waypoints < 0) return fail(F110QP_ERR_INVALID, "num_waypoints < 0");
+  K->G = G;
+  K->T = rp->plan.steer_discrete + 1;
+  K->P = rp->plan.traj_discrete;
+  K->discrete = rp->plan.discrete;
+  K->dilation = rp->plan.dilation;
+  K->lookahead = rp->plan.lookahead;
+  return F110QP_OK;
+}
+
+// Argument checks of f110qp_rollout_replan[_dev], all before any device call.
+static int check_replan_args(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                             const f110qp_replan_config* rp, int batch, const void* table, const void* wp,
+                             const void* xr, const void* have, const void* ranges, const void* xt,
+                             const void* ult, const void* ua, const void* stt, f110qp::AdvanceParams* ap,
+                             f110qp::PlanKParams* K) {
+  if (!c) return fail(F110QP_ERR_INVALID, "ctx is NULL");
+  int rv = rollout_params(rc, true, ap);
+  if (rv) return rv;
+  if ((rv = check_scan_config(sc, true, rc->ticks))) return rv;
+  if ((rv = replan_params(rp, K))) return rv;
+  if (c->cfg.horizon < 2) return fail(F110QP_ERR_INVALID, "the re-planning rollout needs horizon >= 2");
+  if (c->kp.xr_stride != rp->plan.traj_discrete)
+    return fail(F110QP_ERR_INVALID, "the context's x_ref_points must equal traj_discrete");
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  if (batch == 0) return F110QP_OK;
+  if (!xr || !xt || !ult || !ua || !stt)
+    return fail(F110QP_ERR_INVALID, "x_ref/x_traj/u_lin_traj/u_applied/status_traj must be non-NULL");
+  if (!have || !table || (rp->num_waypoints > 0 && !wp))
+    return fail(F110QP_ERR_INVALID, "have_path/table/waypoints must be non-NULL");
+  if (!ranges) return fail(F110QP_ERR_INVALID, "ranges must be non-NULL");
+  if (batch > (1 << 30) / 64 || (long long)sc->scan_rows * batch > (1ll << 30))
+    return fail(F110QP_ERR_INVALID, "batch too large");
+  return F110QP_OK;
+}
+
+// The optional per-tick arrays of a re-planning rollout; a null one lives in the context (ReplanWork).
+struct ReplanTraj {
+  float* hs;         // [T][B][6]
+  int* kind;         // [T][B]
+  int* plan_status;  // [T][B]
+  int* best_traj;    // [T][B]
+  int* best_global;  // [T][B]
+  double* pose;      // [T+1][B][4]
+};
+
+// The T ticks of a checked re-planning rollout on device pointers. Every workspace is sized in front
+// of the loop; the loop only launches: the listed plan, the launches of one _dbl solve call, the
+// state machine with the plant step.
+static int replan_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, const f110qp::PlanKParams& K,
+                        const f110qp_scan_config& sc, const f110qp_replan_config& rp, int T, int batch,
+                        const double* table, const double* wp, double* xr, int* have, const float* ranges,
+                        double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up,
+                        float* xp, const ReplanTraj& tr, hipStream_t s) {
+  const size_t B = (size_t)batch, N = (size_t)c->cfg.horizon;
+  const size_t n_up = B * N * 2, n_xp = B * (N + 1) * 3;
+  if (!aligned8(ua) || !aligned8(up)) return fail(F110QP_ERR_INVALID, "u_applied / u_plan must be 8-byte aligned");
+  float* wup = nullptr;
+  float* wxp = nullptr;
+  hipError_t e;
+  if (!up || !xp) {
+    if ((e = c->rplan.ensure((n_up + n_xp) * sizeof(float))) != hipSuccess)
+      return hip_fail(e, "hipMalloc rollout plan workspace");
+    wup = (float*)c->rplan.p;
+    wxp = wup + n_up;
+  }
+  const bool gap = c->cfg.gap_mode == F110QP_GAP_ACTIVE;
+  const bool rows_on = gap || tr.hs;  // as f110qp_rollout_scan_dev: nothing reads them otherwise
+  f110qp::GapRecord* rec = nullptr;
+  float* rows = nullptr;
+  size_t rstep = 0;
+  if (rows_on) {
+    if ((e = c->rgap.ensure((size_t)sc.scan_rows * B * sizeof(f110qp::GapRecord))) != hipSuccess)
+      return hip_fail(e, "hipMalloc gap records");
+    rec = (f110qp::GapRecord*)c->rgap.p;
+    rows = tr.hs;
+    rstep = B * 6;
+    if (!rows) {
+      if ((e = c->rhs.ensure(B * 6 * sizeof(float))) != hipSuccess) return hip_fail(e, "hipMalloc half-space rows");
+      rows = (float*)c->rhs.p;
+      rstep = 0;
+    }
+  }
+  // ReplanWork, the state of the loop in c->rstate: [pose B x 4 doubles unless pose_traj] [u_held B x N
+  // float2] then ints: [held_len B | held_idx B | plan_count T + 1] (zeroed by the one memset), [list B],
+  // [kind 2 B unless kind_traj], [plan_status B], [best_traj B], [best_global B] unless given
+  const size_t o_held = tr.pose ? 0 : B * 4 * 8, o_int = o_held + n_up * 4;
+  const size_t n_zero = 2 * B + (size_t)T + 1;
+  size_t n_int = n_zero + B;
+  const size_t i_kind = n_int;
+  n_int += tr.kind ? 0 : 2 * B;
+  const size_t i_ps = n_int;
+  n_int += tr.plan_status ? 0 : B;
+  const size_t i_bt = n_int;
+  n_int += tr.best_traj ? 0 : B;
+  const size_t i_bg = n_int;
+  n_int += tr.best_global ? 0 : B;
+  if ((e = c->rstate.ensure(o_int + n_int * 4)) != hipSuccess) return hip_fail(e, "hipMalloc re-planning state");
+  char* w = (char*)c->rstate.p;
+  double* wpose = (double*)w;
+  float* held = (float*)(w + o_held);
+  int* wi = (int*)(w + o_int);
+  int* held_len = wi;
+  int* held_idx = wi + B;
+  int* count = wi + 2 * B;
+  int* list = wi + n_zero;
+  int backend;
+  f110qp::LaneWork lw;
+  const int rc = lane_work(c, batch, s, &backend, &lw);
+  if (rc) return rc;
+  if ((e = hipMemsetAsync(wi, 0, n_zero * sizeof(int), s)) != hipSuccess) return hip_fail(e, "hipMemsetAsync plan counters");
+  if (rows_on) {
+    e = f110qp::launch_gap_search(sc.scan_rows * batch, ranges, sc.num_ranges, sc.angle_min, sc.angle_increment,
+                                  sc.angle_max, sc.ftg_thresh, sc.divider, sc.buffer, rec, s);
+    if (e != hipSuccess) return hip_fail(e, "gap search launch");
+  }
+  auto kind_row = [&](size_t t) { return tr.kind ? tr.kind + t * B : wi + i_kind + (t & 1) * B; };
+  auto pose_row = [&](size_t t) { return tr.pose ? tr.pose + t * B * 4 : wpose; };
+  {
+    f110qp::ReplanStart st{};
+    st.x = xt;
+    st.have_path = have;
+    st.x_ref = xr;
+    st.P = K.P;
+    st.replan_dist = rp.replan_dist;
+    st.pose = pose_row(0);
+    st.kind = kind_row(0);
+    st.list = list;
+    st.count = count;
+    st.gap = rec;
+    st.hs = rows;
+    st.nr = sc.num_ranges;
+    st.angle_min = sc.angle_min;
+    st.angle_inc = sc.angle_increment;
+    if ((e = f110qp::launch_replan_start(batch, st, s)) != hipSuccess) return hip_fail(e, "re-planning start launch");
+  }
+  const size_t nr = (size_t)sc.num_ranges;
+  for (size_t t = 0; t < (size_t)T; t++) {
+    int* ps_t = tr.plan_status ? tr.plan_status + t * B : wi + i_ps;
+    e = f110qp::launch_plan_listed(K, batch, list, count + t, pose_row(t),
+                                   ranges + (sc.scan_rows == 1 ? 0 : t * B * nr), sc.num_ranges, sc.angle_min,
+                                   sc.angle_increment, sc.angle_max, table, wp, rp.num_waypoints,
+                                   tr.best_global ? tr.best_global + t * B : wi + i_bg,
+                                   tr.best_traj ? tr.best_traj + t * B : wi + i_bt, xr, ps_t, s);
+    if (e != hipSuccess) return hip_fail(e, "listed plan launch");
+    const float* h = gap ? rows + t * rstep : nullptr;
+    float* u_t = up ? up + t * n_up : wup;
+    float* x_t = xp ? xp + t * n_xp : wxp;
+    int* st_t = stt + t * B;
+    f110qp::ObjOut oo;
+    oo.cost = cot ? cot + t * B : nullptr;
+    e = f110qp::launch_solve(c->kp, batch, (const double*)(xt + t * B * 3), (const double*)(ult + t * B * 2),
+                             (const double*)xr, h, u_t, x_t, st_t, itt ? itt + t * B : nullptr,
+                             f110qp::WarmState(), backend, lw, oo, s);
+    if (e != hipSuccess) return hip_fail(e, "rollout solve launch");
+    const bool last = t + 1 == (size_t)T;  // no tick T: neither its kind and list nor its rows
+    f110qp::ReplanStep S{};
+    S.x = xt + t * B * 3;
+    S.kind = kind_row(t);
+    S.u_plan = u_t;
+    S.status = st_t;
+    S.plan_status = ps_t;
+    S.x_ref = xr;
+    S.P = K.P;
+    S.replan_dist = rp.replan_dist;
+    S.u_held = held;
+    S.held_len = held_len;
+    S.held_idx = held_idx;
+    S.have_path = have;
+    S.x_next = xt + (t + 1) * B * 3;
+    S.u_lin_next = ult + (t + 1) * B * 2;
+    S.u_applied = ua + t * B * 2;
+    S.pose_next = pose_row(t + 1);
+    S.kind_next = last ? nullptr : kind_row(t + 1);
+    S.next_list = last ? nullptr : list;
+    S.next_count = last ? nullptr : count + t + 1;
+    S.gap = rows_on && !last ? rec + (sc.scan_rows == 1 ? 0 : (t + 1) * B) : nullptr;
+    S.hs_next = rows_on && !last ? rows + (t + 1) * rstep : nullptr;
+    S.nr = sc.num_ranges;
+    S.angle_min = sc.angle_min;
+    S.angle_inc = sc.angle_increment;
+    if ((e = f110qp::launch_advance_replan(ap, batch, (int)N, S, s)) != hipSuccess)
+      return hip_fail(e, "plant step launch");
+  }
+  return F110QP_OK;
+}
+
+extern "C" {
+
+void f110qp_default_replan_config(f110qp_replan_config* rp) {
+  if (!rp) return;
+  std::memset(rp, 0, sizeof(*rp));
+  rp->replan_dist = 1.98;  // src/project.cpp:182
+  f110qp_default_plan_config(&rp->plan);
+}
+
+int f110qp_plan_listed_dev(const f110qp_replan_config* rp, const f110qp_scan_config* sc, int batch,
+                           const int* list, const int* count, const double* pose, const float* ranges,
+                           const double* table, const double* wp, double* x_ref, int* plan_status,
+                           int* best_traj, int* best_global, void* stream) {
+  f110qp::PlanKParams K;
+  int rv = replan_params(rp, &K);
+  if (rv) return rv;
+  if ((rv = check_scan_config(sc, false, 0))) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  if (batch == 0) return F110QP_OK;
+  if (!list || !count || !pose || !ranges || !table || (rp->num_waypoints > 0 && !wp) || !x_ref ||
+      !plan_status || !best_traj || !best_global)
+    return fail(F110QP_ERR_INVALID, "NULL pointer argument");
+  const hipError_t e = f110qp::launch_plan_listed(K, batch, list, count, pose, ranges, sc->num_ranges,
+                                                  sc->angle_min, sc->angle_increment, sc->angle_max, table, wp,
+                                                  rp->num_waypoints, best_global, best_traj, x_ref, plan_status,
+                                                  (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "listed plan launch");
+  return F110QP_OK;
+}
+
+int f110qp_replan_start_dev(const f110qp_replan_config* rp, const f110qp_scan_config* sc, int batch,
+                            const double* x, const int* have_path, const double* x_ref,
+                            const f110qp_gap_record* gap, double* pose, int* kind, int* list, int* count,
+                            float* hs, void* stream) {
+  f110qp::PlanKParams K;
+  int rv = replan_params(rp, &K);
+  if (rv) return rv;
+  if (hs && (rv = check_scan_config(sc, false, 0))) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !have_path || !x_ref || !pose || !kind || !list || !count)
+    return fail(F110QP_ERR_INVALID, "x/have_path/x_ref/pose/kind/list/count must be non-NULL");
+  if (hs && !gap) return fail(F110QP_ERR_INVALID, "hs needs the gap records");
+  f110qp::ReplanStart st{};
+  st.x = x;
+  st.have_path = have_path;
+  st.x_ref = x_ref;
+  st.P = K.P;
+  st.replan_dist = rp->replan_dist;
+  st.pose = pose;
+  st.kind = kind;
+  st.list = list;
+  st.count = count;
+  st.gap = (const f110qp::GapRecord*)gap;
+  st.hs = hs;
+  if (hs) {
+    st.nr = sc->num_ranges;
+    st.angle_min = sc->angle_min;
+    st.angle_inc = sc->angle_increment;
+  }
+  const hipError_t e = f110qp::launch_replan_start(batch, st, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "re-planning start launch");
+  return F110QP_OK;
+}
+
+int f110qp_advance_replan_dev(const f110qp_rollout_config* rc, const f110qp_replan_config* rp,
+                              const f110qp_scan_config* sc, int batch, int horizon, const double* x, int* kind,
+                              const float* u_plan, int* status, const int* plan_status, const double* x_ref,
+                              const f110qp_gap_record* gap, float* u_held, int* held_len, int* held_idx,
+                              int* have_path, double* x_next, double* u_lin_next, float* u_applied,
+                              double* pose_next, int* kind_next, int* next_list, int* next_count,
+                              float* hs_next, void* stream) {
+  f110qp::AdvanceParams ap;
+  f110qp::PlanKParams K;
+  int rv = rollout_params(rc, false, &ap);
+  if (rv) return rv;
+  if ((rv = replan_params(rp, &K))) return rv;
+  if (hs_next && (rv = check_scan_config(sc, false, 0))) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  if (horizon < 2 || horizon > F110QP_MAX_HORIZON) return fail(F110QP_ERR_INVALID, "horizon must be in [2, 48]");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !kind || !u_plan || !status || !plan_status || !x_ref || !x_next || !u_lin_next)
+    return fail(F110QP_ERR_INVALID, "x/kind/u_plan/status/plan_status/x_ref/x_next/u_lin_next must be non-NULL");
+  if (!u_held || !held_len || !held_idx || !have_path || !pose_next)
+    return fail(F110QP_ERR_INVALID, "u_held/held_len/held_idx/have_path/pose_next must be non-NULL");
+  if (kind_next && (!next_list || !next_count))
+    return fail(F110QP_ERR_INVALID, "kind_next needs next_list and next_count");
+  if (hs_next && !gap) return fail(F110QP_ERR_INVALID, "hs_next needs the gap records");
+  if (x_next == x) return fail(F110QP_ERR_INVALID, "x_next must not alias x");
+  if (!aligned8(u_plan) || !aligned8(u_applied) || !aligned8(u_held))
+    return fail(F110QP_ERR_INVALID, "u_plan / u_applied / u_held must be 8-byte aligned");
+  f110qp::ReplanStep S{};
+  S.x = x;
+  S.kind = kind;
+  S.u_plan = u_plan;
+  S.status = status;
+  S.plan_status = plan_status;
+  S.x_ref = x_ref;
+  S.P = K.P;
+  S.replan_dist = rp->replan_dist;
+  S.u_held = u_held;
+  S.held_len = held_len;
+  S.held_idx = held_idx;
+  S.have_path = have_path;
+  S.x_next = x_next;
+  S.u_lin_next = u_lin_next;
+  S.u_applied = u_applied;
+  S.pose_next = pose_next;
+  S.kind_next = kind_next;
+  S.next_list = next_list;
+  S.next_count = next_count;
+  S.gap = (const f110qp::GapRecord*)gap;
+  S.hs_next = hs_next;
+  if (hs_next) {
+    S.nr = sc->num_ranges;
+    S.angle_min = sc->angle_min;
+    S.angle_inc = sc->angle_increment;
+  }
+  const hipError_t e = f110qp::launch_advance_replan(ap, batch, horizon, S, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "plant step launch");
+  return F110QP_OK;
+}
+
+int f110qp_rollout_replan_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                              const f110qp_replan_config* rp, int batch, const double* table, const double* wp,
+                              double* xr, int* have, const float* ranges, double* xt, double* ult, float* ua,
+                              int* stt, int* itt, double* cot, float* up, float* xp, float* hst, int* kt,
+                              int* pst, int* btt, int* bgt, double* poset, void* stream) {
+  f110qp::AdvanceParams ap;
+  f110qp::PlanKParams K;
+  const int rv = check_replan_args(c, rc, sc, rp, batch, table, wp, xr, have, ranges, xt, ult, ua, stt, &ap, &K);
+  if (rv || batch == 0) return rv;
+  const ReplanTraj tr{hst, kt, pst, btt, bgt, poset};
+  return replan_ticks(c, ap, K, *sc, *rp, rc->ticks, batch, table, wp, xr, have, ranges, xt, ult, ua, stt, itt,
+                      cot, up, xp, tr, (hipStream_t)stream);
+}
+
+int f110qp_rollout_replan(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                          const f110qp_replan_config* rp, int batch, const double* table, const double* wp,
+                          double* xr, int* have, const float* ranges, double* xt, double* ult, float* ua,
+                          int* stt, int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst,
+                          int* btt, int* bgt, double* poset) {
+  f110qp::AdvanceParams ap;
+  f110qp::PlanKParams K;
+  const int rv = check_replan_args(c, rc, sc, rp, batch, table, wp, xr, have, ranges, xt, ult, ua, stt, &ap, &K);
+  if (rv || batch == 0) return rv;
+  hipError_t e = hipSetDevice(c->cfg.device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  if (!c->stream && (e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
+    return hip_fail(e, "hipStreamCreate");
+  hipStream_t s = c->stream;
+  const size_t B = (size_t)batch, N = (size_t)c->cfg.horizon, T = (size_t)rc->ticks, P = (size_t)K.P;
+  const size_t W = (size_t)rp->num_waypoints, TB = T * B;
+  // device layout in c->rdev: every field padded to 8 bytes, so the doubles and the float2 rows
+  // (u_applied, u_plan) are aligned wherever they stand
+  size_t total = 0;
+  auto field = [&](bool on, size_t bytes) {
+    const size_t o = total;
+    if (on) total += (bytes + 7) & ~(size_t)7;
+    return o;
+  };
+  const size_t s_tab = (size_t)K.T * P * 3 * 8, s_wp = W * 2 * 8, s_xr = B * P * 3 * 8;
+  const size_t s_xt = (T + 1) * B * 3 * 8, s_ul = (T + 1) * B * 2 * 8, s_po = (T + 1) * B * 4 * 8;
+  const size_t s_rg = (size_t)sc->scan_rows * B * (size_t)sc->num_ranges * 4, s_i = TB * 4;
+  const size_t s_up = TB * N * 2 * 4, s_xp = TB * (N + 1) * 3 * 4;
+  const size_t o_tab = field(true, s_tab), o_wp = field(W > 0, s_wp), o_xr = field(true, s_xr);
+  const size_t o_xt = field(true, s_xt), o_ul = field(true, s_ul), o_co = field(cot, TB * 8);
+  const size_t o_po = field(poset, s_po), o_rg = field(true, s_rg), o_hs = field(hst, TB * 6 * 4);
+  const size_t o_ua = field(true, TB * 2 * 4), o_st = field(true, s_i), o_it = field(itt, s_i);
+  const size_t o_up = field(up, s_up), o_xp = field(xp, s_xp), o_hv = field(true, B * 4);
+  const size_t o_kt = field(kt, s_i), o_ps = field(pst, s_i), o_bt = field(btt, s_i), o_bg = field(bgt, s_i);
+  if ((e = c->rdev.ensure(total)) != hipSuccess) return hip_fail(e, "hipMalloc rollout staging");
+  char* d = (char*)c->rdev.p;
+  if ((e = hipMemcpyAsync(d + o_tab, table, s_tab, hipMemcpyHostToDevice, s)) ||
+      (W > 0 && (e = hipMemcpyAsync(d + o_wp, wp, s_wp, hipMemcpyHostToDevice, s))) ||
+      (e = hipMemcpyAsync(d + o_xr, xr, s_xr, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(d + o_xt, xt, B * 3 * 8, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(d + o_ul, ult, B * 2 * 8, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(d + o_rg, ranges, s_rg, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(d + o_hv, have, B * 4, hipMemcpyHostToDevice, s)))
+    return hip_fail(e, "hipMemcpyAsync H2D");
+  const ReplanTraj tr{hst ? (float*)(d + o_hs) : nullptr, kt ? (int*)(d + o_kt) : nullptr,
+                      pst ? (int*)(d + o_ps) : nullptr,   btt ? (int*)(d + o_bt) : nullptr,
+                      bgt ? (int*)(d + o_bg) : nullptr,   poset ? (double*)(d + o_po) : nullptr};
+  const int rt = replan_ticks(c, ap, K, *sc, *rp, rc->ticks, batch, (const double*)(d + o_tab),
+                              W > 0 ? (const double*)(d + o_wp) : nullptr, (double*)(d + o_xr), (int*)(d + o_hv),
+                              (const float*)(d + o_rg), (double*)(d + o_xt), (double*)(d + o_ul), (float*)(d + o_ua),
+                              (int*)(d + o_st), itt ? (int*)(d + o_it) : nullptr, cot ? (double*)(d + o_co) : nullptr,
+                              up ? (float*)(d + o_up) : nullptr, xp ? (float*)(d + o_xp) : nullptr, tr, s);
+  if (rt) return rt;
+  // the state that carries over, rows 1..T of the trajectories (row 0 is the caller's), every record
+  if ((e = hipMemcpyAsync(xr, d + o_xr, s_xr, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(have, d + o_hv, B * 4, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(xt + B * 3, d + o_xt + B * 3 * 8, T * B * 3 * 8, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(ult + B * 2, d + o_ul + B * 2 * 8, T * B * 2 * 8, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(ua, d + o_ua, TB * 2 * 4, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(stt, d + o_st, s_i, hipMemcpyDeviceToHost, s)) ||
+      (itt && (e = hipMemcpyAsync(itt, d + o_it, s_i, hipMemcpyDeviceToHost, s))) ||
+      (cot && (e = hipMemcpyAsync(cot, d + o_co, TB * 8, hipMemcpyDeviceToHost, s))) ||
+      (up && (e = hipMemcpyAsync(up, d + o_up, s_up, hipMemcpyDeviceToHost, s))) ||
+      (xp && (e = hipMemcpyAsync(xp, d + o_xp, s_xp, hipMemcpyDeviceToHost, s))) ||
+      (hst && (e = hipMemcpyAsync(hst, d + o_hs, TB * 6 * 4, hipMemcpyDeviceToHost, s))) ||
+      (kt && (e = hipMemcpyAsync(kt, d + o_kt, s_i, hipMemcpyDeviceToHost, s))) ||
+      (pst && (e = hipMemcpyAsync(pst, d + o_ps, s_i, hipMemcpyDeviceToHost, s))) ||
+      (btt && (e = hipMemcpyAsync(btt, d + o_bt, s_i, hipMemcpyDeviceToHost, s))) ||
+      (bgt && (e = hipMemcpyAsync(bgt, d + o_bg, s_i, hipMemcpyDeviceToHost, s))) ||
+      (poset && (e = hipMemcpyAsync(poset, d + o_po, s_po, hipMemcpyDeviceToHost, s))))
+    return hip_fail(e, "hipMemcpyAsync D2H");
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+  return F110QP_OK;
+}
+
+}  // extern "C"

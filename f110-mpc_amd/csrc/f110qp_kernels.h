@@ -294,4 +294,68 @@ hipError_t launch_advance_scan(const AdvanceParams& P, int B, int N, const doubl
                                const GapRecord* gap, double* x_next, double* u_lin_next, float* u_applied,
                                float* hs_next, hipStream_t stream);
 
+// ---- closed loop with re-planning (rollout_kernels.hip, plan_kernels.hip) -------------------------
+// tick kinds (== F110QP_TICK_* in include/f110qp.h)
+constexpr int TICK_MPC = 0, TICK_PLAN = 1, TICK_HOLD = 2, TICK_PLAN_FAILED = 3;
+
+// launch_plan for the cars of a device-side list: workgroups stride over list[0 .. min(*count, B)),
+// at most plan_listed_grid(B) of them; a workgroup past the count exits at its first load. pose is
+// the pose row [B][4] (x, y, sin(ori/2), cos(ori/2)), ranges [B][nr]. Per listed car: status,
+// best_global, best_traj, and on status 0 its path as doubles (widened floats, ori 0) into x_ref
+// [B][P][3]; a car without a path keeps the one it has. Unlisted cars are not touched.
+int plan_listed_grid(int B);
+hipError_t launch_plan_listed(const PlanKParams& K, int B, const int* list, const int* count,
+                              const double* pose, const float* ranges, int nr, float angle_min,
+                              float angle_inc, float angle_max, const double* table, const double* wp,
+                              int W, int* best_global, int* best_traj, double* x_ref, int* status,
+                              hipStream_t stream);
+
+// The per-car OdomCallback state around one plant step (advance_replan_kernel), all [B] unless said.
+struct ReplanStep {
+  const double* x;         // [B][3] this tick's pose
+  int* kind;               // this tick's kind; a PLAN tick whose plan failed is rewritten PLAN_FAILED
+  const float* u_plan;     // [B][N][2] this tick's solve (read on MPC ticks)
+  int* status;             // the solve's status; set to 0 on ticks that are not MPC ticks
+  const int* plan_status;  // the listed plan's status (read on PLAN ticks)
+  const double* x_ref;     // [B][P][3] the paths (the end point is read)
+  int P;
+  double replan_dist;
+  float* u_held;           // [B][N][2] the published plan
+  int* held_len;           // N or 0
+  int* held_idx;           // inputs_idx_
+  int* have_path;          // get_mini_path_
+  double* x_next;          // [B][3]
+  double* u_lin_next;      // [B][2]
+  float* u_applied;        // [B][2] or null
+  double* pose_next;       // [B][4] the pose row the next tick's plan reads
+  int* kind_next;          // the next tick's kind, or null (then no list either)
+  int* next_list;          // the cars whose next tick is a PLAN tick, in any order
+  int* next_count;         // their count (one atomicAdd per wave; zero on entry)
+  const GapRecord* gap;    // the records of the scans the next tick reads (with hs_next)
+  float* hs_next;          // [B][2][3] or null
+  int nr;
+  float angle_min, angle_inc;
+};
+hipError_t launch_advance_replan(const AdvanceParams& P, int B, int N, const ReplanStep& S,
+                                 hipStream_t stream);
+
+// The launch in front of the loop: pose row 0, kind 0, list 0 (count zero on entry) and, with hs0,
+// the half-space rows of tick 0.
+struct ReplanStart {
+  const double* x;       // [B][3]
+  const int* have_path;
+  const double* x_ref;   // [B][P][3]
+  int P;
+  double replan_dist;
+  double* pose;          // [B][4]
+  int* kind;
+  int* list;
+  int* count;
+  const GapRecord* gap;
+  float* hs;             // [B][2][3] or null
+  int nr;
+  float angle_min, angle_inc;
+};
+hipError_t launch_replan_start(int B, const ReplanStart& S, hipStream_t stream);
+
 }  // namespace f110qp

@@ -110,23 +110,25 @@ __device__ unsigned long long g_pstamps[4096 * kPlanStampSlots];
 #define PSTAMP(k)
 #endif
 
-__global__ __launch_bounds__(256) void plan_kernel(const PlanKParams K, const int B,
-                                                   const double* __restrict__ pose,
-                                                   const float* __restrict__ ranges, const int nr,
-                                                   const float angle_min, const float angle_inc,
-                                                   const float angle_max,
-                                                   const double* __restrict__ table,
-                                                   const double* __restrict__ wp, const int W,
-                                                   unsigned char* __restrict__ grid_out,
-                                                   unsigned char* __restrict__ valid_out,
-                                                   int* __restrict__ best_global,
-                                                   int* __restrict__ best_traj,
-                                                   float* __restrict__ xref_out,
-                                                   float* __restrict__ x0_out,
-                                                   int* __restrict__ status_out) {
+// The planning branch for car b on one 256-thread workgroup. LISTED (the re-planning closed loop,
+// launch_plan_listed): the path goes to xref_d as doubles, and only on status 0; x0 is not written.
+template <bool LISTED>
+__device__ __forceinline__ void plan_one(const PlanKParams& K, const int b, unsigned char* plds,
+                                         const double* __restrict__ pose,
+                                         const float* __restrict__ ranges, const int nr,
+                                         const float angle_min, const float angle_inc,
+                                         const float angle_max,
+                                         const double* __restrict__ table,
+                                         const double* __restrict__ wp, const int W,
+                                         unsigned char* __restrict__ grid_out,
+                                         unsigned char* __restrict__ valid_out,
+                                         int* __restrict__ best_global,
+                                         int* __restrict__ best_traj,
+                                         float* __restrict__ xref_out,
+                                         double* __restrict__ xref_d,
+                                         float* __restrict__ x0_out,
+                                         int* __restrict__ status_out) {
 #pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) unsigned char plds[];
-  const int b = blockIdx.x;
   const int tid = threadIdx.x;
 #ifdef F110QP_STAMPS
   const unsigned long long t_start = __builtin_amdgcn_s_memtime();
@@ -315,19 +317,37 @@ __global__ __launch_bounds__(256) void plan_kernel(const PlanKParams K, const in
     status_out[b] = status;
     best_global[b] = !any_valid ? -1 : closest;
     best_traj[b] = best;
-    x0_out[3 * b + 0] = (float)px;  // State(position.x, position.y, GetCarOrientation) (:162)
-    x0_out[3 * b + 1] = (float)py;
-    x0_out[3 * b + 2] = cur;
-  }
-  float* xo = xref_out + (size_t)b * P * 3;
-  for (int j = tid; j < P; j += 256) {
-    float wx = __int_as_float(0x7fc00000), wy = wx, wo = wx;  // NaN when no candidate is taken
-    if (best >= 0) {
-      const double* pt = table + ((size_t)best * P + j) * 3;
-      car_to_world(R, px, py, (float)pt[0], (float)pt[1], wx, wy);
-      wo = 0.0f;
+    if constexpr (!LISTED) {
+      x0_out[3 * b + 0] = (float)px;  // State(position.x, position.y, GetCarOrientation) (:162)
+      x0_out[3 * b + 1] = (float)py;
+      x0_out[3 * b + 2] = cur;
     }
-    xo[3 * j] = wx; xo[3 * j + 1] = wy; xo[3 * j + 2] = wo;
+  }
+  if constexpr (LISTED) {
+    // miniPath_ as the State doubles it holds (:149-152), stored only when the branch stores it
+    if (status == 0) {
+      double* xo = xref_d + (size_t)b * P * 3;
+      for (int j = tid; j < P; j += 256) {
+        float wx = __int_as_float(0x7fc00000), wy = wx, wo = wx;
+        if (best >= 0) {
+          const double* pt = table + ((size_t)best * P + j) * 3;
+          car_to_world(R, px, py, (float)pt[0], (float)pt[1], wx, wy);
+          wo = 0.0f;
+        }
+        xo[3 * j] = (double)wx; xo[3 * j + 1] = (double)wy; xo[3 * j + 2] = (double)wo;
+      }
+    }
+  } else {
+    float* xo = xref_out + (size_t)b * P * 3;
+    for (int j = tid; j < P; j += 256) {
+      float wx = __int_as_float(0x7fc00000), wy = wx, wo = wx;  // NaN when no candidate is taken
+      if (best >= 0) {
+        const double* pt = table + ((size_t)best * P + j) * 3;
+        car_to_world(R, px, py, (float)pt[0], (float)pt[1], wx, wy);
+        wo = 0.0f;
+      }
+      xo[3 * j] = wx; xo[3 * j + 1] = wy; xo[3 * j + 2] = wo;
+    }
   }
   if (valid_out)
     for (int i = tid; i < T; i += 256) valid_out[(size_t)b * T + i] = (unsigned char)vflag[i];
@@ -338,13 +358,63 @@ __global__ __launch_bounds__(256) void plan_kernel(const PlanKParams K, const in
   PSTAMP(6);
 }
 
+__global__ __launch_bounds__(256) void plan_kernel(const PlanKParams K, const int B,
+                                                   const double* __restrict__ pose,
+                                                   const float* __restrict__ ranges, const int nr,
+                                                   const float angle_min, const float angle_inc,
+                                                   const float angle_max,
+                                                   const double* __restrict__ table,
+                                                   const double* __restrict__ wp, const int W,
+                                                   unsigned char* __restrict__ grid_out,
+                                                   unsigned char* __restrict__ valid_out,
+                                                   int* __restrict__ best_global,
+                                                   int* __restrict__ best_traj,
+                                                   float* __restrict__ xref_out,
+                                                   float* __restrict__ x0_out,
+                                                   int* __restrict__ status_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char plds[];
+  plan_one<false>(K, blockIdx.x, plds, pose, ranges, nr, angle_min, angle_inc, angle_max, table, wp, W,
+                  grid_out, valid_out, best_global, best_traj, xref_out, nullptr, x0_out, status_out);
+}
+
+// plan_kernel for the cars of a device-side list (the PLAN ticks of the re-planning closed loop):
+// workgroup w takes list[w], list[w + nwg], ... below min(*count, B); one past the count leaves at
+// that load. The barrier at the end of a car keeps its LDS reads ahead of the next car's set-up.
+__global__ __launch_bounds__(256) void plan_listed_kernel(const PlanKParams K, const int B, const int nwg,
+                                                          const int* __restrict__ list,
+                                                          const int* __restrict__ count,
+                                                          const double* __restrict__ pose,
+                                                          const float* __restrict__ ranges, const int nr,
+                                                          const float angle_min, const float angle_inc,
+                                                          const float angle_max,
+                                                          const double* __restrict__ table,
+                                                          const double* __restrict__ wp, const int W,
+                                                          int* __restrict__ best_global,
+                                                          int* __restrict__ best_traj,
+                                                          double* __restrict__ xref_d,
+                                                          int* __restrict__ status_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char plds[];
+  const int n = min(*count, B);
+  for (int k = blockIdx.x; k < n; k += nwg) {
+    const int b = list[k];
+    if (b >= 0 && b < B)  // uniform over the workgroup
+      plan_one<true>(K, b, plds, pose, ranges, nr, angle_min, angle_inc, angle_max, table, wp, W, nullptr,
+                     nullptr, best_global, best_traj, nullptr, xref_d, nullptr, status_out);
+    __syncthreads();
+  }
+}
+
+static size_t plan_lds_bytes(const PlanKParams& K) {
+  return 32 + 4 * (size_t)K.T + 4 * (size_t)((K.G * K.G + 3) / 4);
+}
+
 hipError_t launch_plan(const PlanKParams& K, int B, const double* pose, const float* ranges,
                        int nr, float angle_min, float angle_inc, float angle_max,
                        const double* table, const double* wp, int W, unsigned char* grid_out,
                        unsigned char* valid_out, int* best_global, int* best_traj, float* x_ref,
                        float* x0, int* status, hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  const size_t lds = 32 + 4 * (size_t)K.T + 4 * (size_t)((K.G * K.G + 3) / 4);
+  const size_t lds = plan_lds_bytes(K);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&plan_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -353,6 +423,35 @@ hipError_t launch_plan(const PlanKParams& K, int B, const double* pose, const fl
   hipLaunchKernelGGL(plan_kernel, dim3(B), dim3(256), lds, s, K, B, pose, ranges, nr, angle_min,
                      angle_inc, angle_max, table, wp, W, grid_out, valid_out, best_global,
                      best_traj, x_ref, x0, status);
+  return hipGetLastError();
+}
+
+// Grid of the listed launch: one workgroup per car up to 768. The listed kernel holds 148 VGPRs (the
+// code-object metadata; plan_kernel 80), so a SIMD keeps three of its waves and a CU three of its
+// four-wave workgroups (10 KB of LDS each is no limit): 768 is what the MI355X's 256 CUs hold at
+// once. A full list of up to 768 cars is planned in one resident round, a longer one strides without
+// a second dispatch round, and on a tick on which few cars plan (the common one: a car plans about
+// every sixth tick) a workgroup past the count costs its dispatch and one scalar load. Derived from
+// the occupancy, not from a sweep of caps.
+constexpr int kPlanListedMaxGrid = 768;
+int plan_listed_grid(int B) { return B < kPlanListedMaxGrid ? B : kPlanListedMaxGrid; }
+
+hipError_t launch_plan_listed(const PlanKParams& K, int B, const int* list, const int* count,
+                              const double* pose, const float* ranges, int nr, float angle_min,
+                              float angle_inc, float angle_max, const double* table, const double* wp,
+                              int W, int* best_global, int* best_traj, double* x_ref, int* status,
+                              hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  const size_t lds = plan_lds_bytes(K);
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&plan_listed_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  const int nwg = plan_listed_grid(B);
+  hipLaunchKernelGGL(plan_listed_kernel, dim3(nwg), dim3(256), lds, s, K, B, nwg, list, count, pose, ranges,
+                     nr, angle_min, angle_inc, angle_max, table, wp, W, best_global, best_traj, x_ref,
+                     status);
   return hipGetLastError();
 }
 

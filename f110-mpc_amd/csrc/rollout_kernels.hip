@@ -6,7 +6,8 @@
 // a solve's plan, and the next linearisation input as project::OdomCallback forms it (GetNextInput()
 // with v forced, src/project.cpp:169-170,210-218). 56 bytes in and 40 (48 with u_applied) out per
 // car, three fp64 trig calls: the launch is the cost, so there is no LDS, no cross-lane traffic and
-// no atomic here.
+// no atomic in these two. The re-planning loop's step (advance_replan_kernel, below) adds the per-car
+// OdomCallback state and one ballot and one atomic per wave for the next tick's plan list.
 #include <hip/hip_runtime.h>
 
 #include "f110qp_kernels.h"
@@ -111,6 +112,173 @@ hipError_t launch_advance_scan(const AdvanceParams& P, int B, int N, const doubl
   if (B <= 0) return hipSuccess;
   hipLaunchKernelGGL(advance_scan_kernel, dim3((B + 255) / 256), dim3(256), 0, s, P, B, N, x, u_plan, status,
                      nr, angle_min, angle_inc, gap, x_next, u_lin_next, u_applied, hs_next);
+  return hipGetLastError();
+}
+
+// ---- closed loop with re-planning -----------------------------------------------------------------
+// The next tick's kind at the pose the plant step has just formed (host/src/project.cpp:35,76-82):
+// PLAN without a path; with one, HOLD when Transforms::CalcDist(car, path end) < replan_dist, else
+// MPC. CalcDist (transforms.cpp:20-22) subtracts in float, squares and adds in double (std::pow of a
+// float promotes), takes the double root and narrows it to float; the reference compares that float
+// with the double 1.98.
+__device__ __forceinline__ int tick_kind(const int have, const double x, const double y, const double ex,
+                                         const double ey, const double replan_dist) {
+#pragma clang fp contract(off)
+  if (!have) return TICK_PLAN;
+  const float dx = (float)x - (float)ex, dy = (float)y - (float)ey;
+  const float dist = (float)sqrt((double)dx * (double)dx + (double)dy * (double)dy);
+  return (double)dist < replan_dist ? TICK_HOLD : TICK_MPC;
+}
+
+// Append the cars of this wave whose next tick plans to the next tick's list: one ballot, one vector
+// atomicAdd per wave that holds such a car (lane 0, every lane of the wave is still here), the
+// position of each car its rank among the wave's set bits. A position past the list (a counter that
+// was not zero on entry) is dropped.
+__device__ __forceinline__ void append_plan_list(const bool plans, const int b, const int B,
+                                                 int* __restrict__ list, int* __restrict__ count) {
+  const unsigned long long m = __ballot(plans);
+  if (m == 0ull) return;  // wave-uniform
+  const int lane = threadIdx.x & 63;
+  int base = 0;
+  if (lane == 0) base = atomicAdd(count, __popcll(m));
+  base = __shfl(base, 0, 64);
+  const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+  if (plans && pos >= 0 && pos < B) list[pos] = b;
+}
+
+// advance_scan_kernel plus the per-car state machine of Project::OdomCallback + Project::DriveStep
+// (host/src/project.cpp:31-100; include/f110qp.h, "closed loop with re-planning"). One thread per car.
+// The tick's action on (u_held, len, idx, have_path), DriveStep's input, the plant step in
+// advance_kernel's expressions (for the same applied input x_next, u_lin_next, u_applied and hs_next
+// have advance_scan_kernel's bits), the pose row of the next tick's plan, the next tick's kind and
+// its plan list. The N float2 of a plan move only on a usable MPC tick; every other tick reads at most
+// two of the held inputs.
+__global__ __launch_bounds__(256) void advance_replan_kernel(const AdvanceParams P, const int B, const int N,
+                                                             const ReplanStep S) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  const bool live = b < B;  // no early return: the ballot below wants whole waves
+  int knext = TICK_MPC;
+  if (live) {
+    int kind = S.kind[b];
+    int have = S.have_path[b], len = S.held_len[b], idx = S.held_idx[b];
+    const GapRecord g = S.hs_next ? S.gap[b] : GapRecord{-1, -1, 0.f, 0.f};
+    const double px = S.x[3 * (size_t)b], py = S.x[3 * (size_t)b + 1], th = S.x[3 * (size_t)b + 2];
+    float2* held = reinterpret_cast<float2*>(S.u_held) + (size_t)b * N;
+    float2 a0 = make_float2(0.f, 0.f), a1 = a0;  // the inputs at idx and idx + 1 after the action
+    bool fresh = false;                          // ... already in registers (a usable MPC tick)
+    if (kind == TICK_PLAN) {
+      if (S.plan_status[b] == 0) {
+        have = 1;
+      } else {
+        kind = TICK_PLAN_FAILED;
+        S.kind[b] = kind;
+      }
+    } else if (kind == TICK_HOLD) {
+      have = 0;  // miniPath_ dropped; MPC::Update keeps its solution, re-published at index 0
+      idx = 0;
+    } else {
+      const int st = S.status[b];
+      const bool usable = st == F110QP_SOLVED_ID || st == F110QP_SOLVED_INACCURATE_ID;
+      idx = 0;
+      len = 0;
+      if (usable) {
+        const float2* row = reinterpret_cast<const float2*>(S.u_plan) + (size_t)b * N;
+        for (int k = 0; k < N; k++) {
+          const float2 u = row[k];
+          held[k] = u;
+          if (k == 0) a0 = u;
+          if (k == 1) a1 = u;
+        }
+        len = N;
+        fresh = true;
+      }
+    }
+    if (kind != TICK_MPC) S.status[b] = 0;
+    // DriveStep: the input at the index, fail_u past the end; then the index moves
+    const bool has0 = idx < len, has1 = idx + 1 < len;
+    if (!fresh) {
+      if (has0) a0 = held[idx];
+      if (has1) a1 = held[idx + 1];
+    }
+    idx++;
+    const double v = has0 ? (double)a0.x : P.fail_u[0];
+    const double delta = has0 ? (double)a0.y : P.fail_u[1];
+    const double d0 = v * cos(th);
+    const double d1 = v * sin(th);
+    const double d2 = tan(delta) * v / P.car_length;
+    const double nx = px + d0 * P.plant_dt;
+    const double ny = py + d1 * P.plant_dt;
+    const double nth = th + d2 * P.plant_dt;
+    S.x_next[3 * (size_t)b] = nx;
+    S.x_next[3 * (size_t)b + 1] = ny;
+    S.x_next[3 * (size_t)b + 2] = nth;
+    S.u_lin_next[2 * (size_t)b] = P.v_lin;
+    S.u_lin_next[2 * (size_t)b + 1] = has1 ? (double)a1.y : P.fail_u[1];
+    if (S.u_applied)
+      reinterpret_cast<float2*>(S.u_applied)[b] = has0 ? a0 : make_float2((float)v, (float)delta);
+    S.have_path[b] = have;
+    S.held_len[b] = len;
+    S.held_idx[b] = idx;
+    // the planar quaternion a simulator's odometry would carry
+    double sh, ch;
+    sincos(nth * 0.5, &sh, &ch);
+    S.pose_next[4 * (size_t)b] = nx;
+    S.pose_next[4 * (size_t)b + 1] = ny;
+    S.pose_next[4 * (size_t)b + 2] = sh;
+    S.pose_next[4 * (size_t)b + 3] = ch;
+    if (S.kind_next) {
+      const double* end = S.x_ref + ((size_t)b * S.P + (S.P - 1)) * 3;
+      knext = tick_kind(have, nx, ny, have ? end[0] : 0.0, have ? end[1] : 0.0, S.replan_dist);
+      S.kind_next[b] = knext;
+    }
+    if (S.hs_next) {
+      float o[6];
+      half_space_rows(g, S.nr, nx, ny, nth, S.angle_min, S.angle_inc, o);
+#pragma unroll
+      for (int j = 0; j < 6; j++) S.hs_next[6 * (size_t)b + j] = o[j];
+    }
+  }
+  if (S.kind_next) append_plan_list(live && knext == TICK_PLAN, b, B, S.next_list, S.next_count);
+}
+
+hipError_t launch_advance_replan(const AdvanceParams& P, int B, int N, const ReplanStep& S, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(advance_replan_kernel, dim3((B + 255) / 256), dim3(256), 0, s, P, B, N, S);
+  return hipGetLastError();
+}
+
+// In front of the loop: the pose row, kind and plan list of tick 0 and (hs) its half-space rows.
+__global__ __launch_bounds__(256) void replan_start_kernel(const int B, const ReplanStart S) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  const bool live = b < B;
+  int kind = TICK_MPC;
+  if (live) {
+    const double px = S.x[3 * (size_t)b], py = S.x[3 * (size_t)b + 1], th = S.x[3 * (size_t)b + 2];
+    const int have = S.have_path[b];
+    double sh, ch;
+    sincos(th * 0.5, &sh, &ch);
+    S.pose[4 * (size_t)b] = px;
+    S.pose[4 * (size_t)b + 1] = py;
+    S.pose[4 * (size_t)b + 2] = sh;
+    S.pose[4 * (size_t)b + 3] = ch;
+    const double* end = S.x_ref + ((size_t)b * S.P + (S.P - 1)) * 3;
+    kind = tick_kind(have, px, py, have ? end[0] : 0.0, have ? end[1] : 0.0, S.replan_dist);
+    S.kind[b] = kind;
+    if (S.hs) {
+      float o[6];
+      half_space_rows(S.gap[b], S.nr, px, py, th, S.angle_min, S.angle_inc, o);
+#pragma unroll
+      for (int j = 0; j < 6; j++) S.hs[6 * (size_t)b + j] = o[j];
+    }
+  }
+  append_plan_list(live && kind == TICK_PLAN, b, B, S.list, S.count);
+}
+
+hipError_t launch_replan_start(int B, const ReplanStart& S, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(replan_start_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, S);
   return hipGetLastError();
 }
 

@@ -39,6 +39,11 @@ LANE_MIN_BATCH_GROUPED = LANE_MIN_BATCH
 LANE_MIN_BATCH_GROUPED_WIDE = LANE_MIN_BATCH_WIDE
 LANE_MAX_SMALL_BATCH = 8
 GAP_SCREEN_MIN_BATCH = 1024
+TICK_MPC = 0
+TICK_PLAN = 1
+TICK_HOLD = 2
+TICK_PLAN_FAILED = 3
+NO_SOLVE = 0
 
 
 def auto_backend(horizon: int, batch: int, gap: bool, grouped: bool = False) -> int:
@@ -111,6 +116,12 @@ EXPORTED = (
     "f110qp_advance_scan_dev",
     "f110qp_rollout_scan_dev",
     "f110qp_rollout_scan",
+    "f110qp_default_replan_config",
+    "f110qp_plan_listed_dev",
+    "f110qp_replan_start_dev",
+    "f110qp_advance_replan_dev",
+    "f110qp_rollout_replan_dev",
+    "f110qp_rollout_replan",
 )
 SCRATCH_NAMES = {0: "none (wave back end)", 1: "LDS fp64", 2: "LDS fp32", 3: "HBM fp64", 4: "HBM fp32"}
 
@@ -170,6 +181,14 @@ class ScanConfig(C.Structure):
     ]
 
 
+class ReplanConfig(C.Structure):
+    _fields_ = [
+        ("replan_dist", C.c_double),
+        ("plan", PlanConfig),
+        ("num_waypoints", C.c_int),
+    ]
+
+
 # f110qp_gap_record (16 bytes) as a numpy record
 GAP_RECORD_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("r_lo", np.float32), ("r_hi", np.float32)])
 
@@ -222,6 +241,13 @@ def load(test: bool = False):
     L.f110qp_advance_scan_dev.argtypes = [C.POINTER(RolloutConfig), C.POINTER(ScanConfig), C.c_int, C.c_int] + [fp] * 9
     L.f110qp_rollout_scan_dev.argtypes = [C.c_void_p, C.POINTER(RolloutConfig), C.POINTER(ScanConfig), C.c_int] + [fp] * 12
     L.f110qp_rollout_scan.argtypes = [C.c_void_p, C.POINTER(RolloutConfig), C.POINTER(ScanConfig), C.c_int] + [fp] * 11
+    rp, sp, rop = C.POINTER(ReplanConfig), C.POINTER(ScanConfig), C.POINTER(RolloutConfig)
+    L.f110qp_default_replan_config.argtypes = [rp]
+    L.f110qp_plan_listed_dev.argtypes = [rp, sp, C.c_int] + [fp] * 11
+    L.f110qp_replan_start_dev.argtypes = [rp, sp, C.c_int] + [fp] * 10
+    L.f110qp_advance_replan_dev.argtypes = [rop, rp, sp, C.c_int, C.c_int] + [fp] * 20
+    L.f110qp_rollout_replan_dev.argtypes = [C.c_void_p, rop, sp, rp, C.c_int] + [fp] * 20
+    L.f110qp_rollout_replan.argtypes = [C.c_void_p, rop, sp, rp, C.c_int] + [fp] * 19
     L.f110qp_select_dev.argtypes = [C.c_int, fp, C.c_int, fp, fp, fp, fp, fp]
     L.f110qp_backend_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
     L.f110qp_lane_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -294,6 +320,23 @@ def default_scan_config(**over) -> ScanConfig:
     load().f110qp_default_scan_config(C.byref(c))
     for k, v in over.items():
         setattr(c, k, v)
+    return c
+
+
+def default_replan_config(**over) -> ReplanConfig:
+    """f110qp_default_replan_config: replan_dist 1.98, the default plan config, num_waypoints 0. Keys of
+    the plan config (size, discrete, ..., traj_discrete) set rp.plan's fields; plan=PlanConfig replaces
+    it."""
+    c = ReplanConfig()
+    load().f110qp_default_replan_config(C.byref(c))
+    names = {f[0] for f in PlanConfig._fields_}
+    for k, v in over.items():
+        if k == "plan":
+            C.memmove(C.byref(c.plan), C.byref(v), C.sizeof(PlanConfig))
+        elif k in names:
+            setattr(c.plan, k, v)
+        else:
+            setattr(c, k, v)
     return c
 
 
@@ -678,6 +721,101 @@ class Solver:
                   "f110qp_rollout_scan")
         return out
 
+    def rollout_replan_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, table, waypoints, x_ref,
+                           have_path, ranges, x_traj, u_lin_traj, u_applied, status_traj, iters_traj=None,
+                           cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
+                           plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
+                           stream=None):
+        """rc.ticks ticks of the closed loop with re-planning on device tensors (f110qp_rollout_replan_dev),
+        asynchronous: rollout_scan_dev's arguments plus table [Tc,P,3] f64, waypoints [W,2] f64, x_ref
+        [B,P,3] f64 and have_path [B] i32 (both in/out), and the optional kind_traj, plan_status_traj,
+        best_traj_traj, best_global_traj [T,B] i32 and pose_traj [T+1,B,4] f64."""
+        import torch
+
+        T, N = int(rc.ticks), self.horizon
+        if T < 1:
+            raise F110QPError("ticks must be >= 1")
+        P, Tc, W = int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
+        B, R, NR = int(x_ref.shape[0]), int(sc.scan_rows), int(sc.num_ranges)
+        if R not in (1, T):
+            raise F110QPError(f"scan_rows must be 1 or ticks = {T}, got {R}")
+        if tuple(x_traj.shape) != (T + 1, B, 3):
+            raise F110QPError(f"x_traj must be [ticks + 1, B, 3] = {(T + 1, B, 3)}, got {tuple(x_traj.shape)}")
+        if tuple(ranges.shape) != (R, B, NR):
+            raise F110QPError(f"ranges must be [scan_rows, B, num_ranges] = {(R, B, NR)}, got {tuple(ranges.shape)}")
+        _devs((table, "f64", 3 * P * Tc, "table"), (waypoints, "f64", 2 * W, "waypoints", W == 0),
+              (x_ref, "f64", 3 * P * B, "x_ref"), (have_path, "i32", B, "have_path"),
+              (ranges, "f32", R * B * NR, "ranges"),
+              (x_traj, "f64", 3 * B * (T + 1), "x_traj"), (u_lin_traj, "f64", 2 * B * (T + 1), "u_lin_traj"),
+              (u_applied, "f32", 2 * B * T, "u_applied"), (status_traj, "i32", B * T, "status_traj"),
+              (iters_traj, "i32", B * T, "iters_traj", True), (cost_traj, "f64", B * T, "cost_traj", True),
+              (u_plan, "f32", 2 * N * B * T, "u_plan", True), (x_plan, "f32", 3 * (N + 1) * B * T, "x_plan", True),
+              (hs_traj, "f32", 6 * B * T, "hs_traj", True), (kind_traj, "i32", B * T, "kind_traj", True),
+              (plan_status_traj, "i32", B * T, "plan_status_traj", True),
+              (best_traj_traj, "i32", B * T, "best_traj_traj", True),
+              (best_global_traj, "i32", B * T, "best_global_traj", True),
+              (pose_traj, "f64", 4 * B * (T + 1), "pose_traj", True))
+        if stream is None:
+            stream = torch.cuda.current_stream(x_traj.device)
+        self._chk(self.lib.f110qp_rollout_replan_dev(
+            self._h, C.byref(rc), C.byref(sc), C.byref(rp), B, _tp(table), _tp(waypoints), _tp(x_ref), _tp(have_path),
+            _tp(ranges), _tp(x_traj), _tp(u_lin_traj), _tp(u_applied), _tp(status_traj), _tp(iters_traj),
+            _tp(cost_traj), _tp(u_plan), _tp(x_plan), _tp(hs_traj), _tp(kind_traj), _tp(plan_status_traj),
+            _tp(best_traj_traj), _tp(best_global_traj), _tp(pose_traj), C.c_void_p(stream.cuda_stream)),
+            "f110qp_rollout_replan_dev")
+
+    def rollout_replan(self, x0, u_lin, ranges, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
+                       x_ref=None, have_path=None, plans=False, objective=False, rows=True, rc=None):
+        """`ticks` ticks of the closed loop with re-planning from host arrays (f110qp_rollout_replan,
+        synchronous): x0 [B,3], u_lin [B,2] float64, ranges as rollout_scan, table [Tc,P,3] and waypoints
+        [W,2] float64. x_ref [B,P,3] float64 / have_path [B] int32: the paths the cars hold (default: none,
+        every car plans on tick 0); copies of both come back updated, so a second call can continue.
+        Returns rollout_scan()'s dict plus x_ref, have_path, kind, plan_status, best_traj, best_global
+        [T,B] and pose_traj [T+1,B,4]."""
+        N, T = self.horizon, int(ticks)
+        if T < 1:
+            raise F110QPError("ticks must be >= 1")
+        x0 = _f64(x0, (-1, 3), "x0")
+        B = x0.shape[0]
+        ul = _f64(u_lin, (B, 2), "u_lin")
+        P, Tc, W = int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
+        xr = np.full((B, P, 3), np.nan) if x_ref is None else _f64(x_ref, (B, P, 3), "x_ref").copy()
+        hv = np.zeros(B, np.int32) if have_path is None else np.array(have_path, np.int32).reshape(B)
+        tab = _f64(table, (Tc, P, 3), "table")
+        wp = np.ascontiguousarray(np.asarray(waypoints, np.float64)[:, :2])
+        if wp.shape[0] != W:
+            raise F110QPError(f"waypoints must hold num_waypoints = {W} rows, got {wp.shape[0]}")
+        R = int(sc.scan_rows)
+        if R not in (1, T):
+            raise F110QPError(f"scan_rows must be 1 or ticks = {T}, got {R}")
+        rg = np.ascontiguousarray(ranges, np.float32)
+        if rg.size != R * B * int(sc.num_ranges):
+            raise F110QPError(f"ranges must hold [scan_rows, B, num_ranges] = {(R, B, int(sc.num_ranges))} values, "
+                              f"got shape {rg.shape}")
+        cfg = RolloutConfig()
+        C.memmove(C.byref(cfg), C.byref(rc if rc is not None else default_rollout_config()), C.sizeof(cfg))
+        cfg.ticks = T
+        i32 = lambda: np.empty((T, B), np.int32)  # noqa: E731
+        out = {"x_traj": np.empty((T + 1, B, 3), np.float64), "u_lin_traj": np.empty((T + 1, B, 2), np.float64),
+               "u_applied": np.empty((T, B, 2), np.float32), "status": i32(), "iters": i32(), "x_ref": xr,
+               "have_path": hv, "kind": i32(), "plan_status": i32(), "best_traj": i32(), "best_global": i32(),
+               "pose_traj": np.empty((T + 1, B, 4), np.float64)}
+        out["x_traj"][0], out["u_lin_traj"][0] = x0, ul
+        if objective:
+            out["cost"] = np.empty((T, B), np.float64)
+        if plans:
+            out["u_plan"] = np.empty((T, B, N, 2), np.float32)
+            out["x_plan"] = np.empty((T, B, N + 1, 3), np.float32)
+        if rows:
+            out["hs_traj"] = np.empty((T, B, 2, 3), np.float32)
+        self._chk(self.lib.f110qp_rollout_replan(
+            self._h, C.byref(cfg), C.byref(sc), C.byref(rp), B, _p(tab), _p(wp) if W else None, _p(xr), _p(hv), _p(rg),
+            _p(out["x_traj"]), _p(out["u_lin_traj"]), _p(out["u_applied"]), _p(out["status"]), _p(out["iters"]),
+            _p(out.get("cost")), _p(out.get("u_plan")), _p(out.get("x_plan")), _p(out.get("hs_traj")),
+            _p(out["kind"]), _p(out["plan_status"]), _p(out["best_traj"]), _p(out["best_global"]),
+            _p(out["pose_traj"])), "f110qp_rollout_replan")
+        return out
+
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
         N = self.horizon
@@ -875,6 +1013,68 @@ def advance_scan_dev(rc: RolloutConfig, sc: ScanConfig, horizon: int, x, u_plan,
                                           _tp(x_next), _tp(u_lin_next), _tp(u_applied), _tp(hs_next),
                                           C.c_void_p(stream.cuda_stream)),
            "f110qp_advance_scan_dev")
+
+
+def plan_listed_dev(rp: ReplanConfig, sc: ScanConfig, list_, count, pose, ranges, table, waypoints, x_ref,
+                    plan_status, best_traj, best_global, stream=None):
+    """The planning stage for the cars of a device-side list (f110qp_plan_listed_dev): list_ [B] i32 and
+    count [1] i32 on the device, pose [B,4] f64, ranges [B,R] f32 -> per listed car plan_status,
+    best_traj, best_global [B] i32 and, on status 0, its path into x_ref [B,P,3] f64."""
+    import torch
+
+    B, P, Tc, W = int(pose.shape[0]), int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
+    _devs((list_, "i32", B, "list"), (count, "i32", 1, "count"), (pose, "f64", 4 * B, "pose"),
+          (ranges, "f32", B * int(sc.num_ranges), "ranges"), (table, "f64", 3 * P * Tc, "table"),
+          (waypoints, "f64", 2 * W, "waypoints", W == 0), (x_ref, "f64", 3 * P * B, "x_ref"),
+          (plan_status, "i32", B, "plan_status"), (best_traj, "i32", B, "best_traj"),
+          (best_global, "i32", B, "best_global"))
+    if stream is None:
+        stream = torch.cuda.current_stream(pose.device)
+    _check(load().f110qp_plan_listed_dev(C.byref(rp), C.byref(sc), B, _tp(list_), _tp(count), _tp(pose), _tp(ranges),
+                                         _tp(table), _tp(waypoints), _tp(x_ref), _tp(plan_status), _tp(best_traj),
+                                         _tp(best_global), C.c_void_p(stream.cuda_stream)), "f110qp_plan_listed_dev")
+
+
+def replan_start_dev(rp: ReplanConfig, sc, x, have_path, x_ref, gap, pose, kind, list_, count, hs=None, stream=None):
+    """The launch in front of the re-planning loop (f110qp_replan_start_dev): x [B,3] f64, have_path [B]
+    i32, x_ref [B,P,3] f64 -> pose [B,4] f64, kind [B] i32, the PLAN cars appended to list_ [B] / count
+    [1] (zero on entry) and, with hs [B,2,3] f32, the half-space rows at x from gap (sc required)."""
+    import torch
+
+    B, P = int(x.shape[0]), int(rp.plan.traj_discrete)
+    _devs((x, "f64", 3 * B, "x"), (have_path, "i32", B, "have_path"), (x_ref, "f64", 3 * P * B, "x_ref"),
+          (gap, "i32", 4 * B, "gap", hs is None), (pose, "f64", 4 * B, "pose"), (kind, "i32", B, "kind"),
+          (list_, "i32", B, "list"), (count, "i32", 1, "count"), (hs, "f32", 6 * B, "hs", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_replan_start_dev(C.byref(rp), C.byref(sc) if sc is not None else None, B, _tp(x),
+                                          _tp(have_path), _tp(x_ref), _tp(gap), _tp(pose), _tp(kind), _tp(list_),
+                                          _tp(count), _tp(hs), C.c_void_p(stream.cuda_stream)),
+           "f110qp_replan_start_dev")
+
+
+def advance_replan_dev(rc: RolloutConfig, rp: ReplanConfig, sc, horizon: int, x, kind, u_plan, status, plan_status,
+                       x_ref, u_held, held_len, held_idx, have_path, x_next, u_lin_next, pose_next, u_applied=None,
+                       kind_next=None, next_list=None, next_count=None, gap=None, hs_next=None, stream=None):
+    """One tick's state machine and plant step (f110qp_advance_replan_dev); see include/f110qp.h."""
+    import torch
+
+    B, N, P = int(x.shape[0]), int(horizon), int(rp.plan.traj_discrete)
+    _devs((x, "f64", 3 * B, "x"), (kind, "i32", B, "kind"), (u_plan, "f32", 2 * N * B, "u_plan"),
+          (status, "i32", B, "status"), (plan_status, "i32", B, "plan_status"), (x_ref, "f64", 3 * P * B, "x_ref"),
+          (gap, "i32", 4 * B, "gap", hs_next is None), (u_held, "f32", 2 * N * B, "u_held"),
+          (held_len, "i32", B, "held_len"), (held_idx, "i32", B, "held_idx"), (have_path, "i32", B, "have_path"),
+          (x_next, "f64", 3 * B, "x_next"), (u_lin_next, "f64", 2 * B, "u_lin_next"),
+          (u_applied, "f32", 2 * B, "u_applied", True), (pose_next, "f64", 4 * B, "pose_next"),
+          (kind_next, "i32", B, "kind_next", True), (next_list, "i32", B, "next_list", kind_next is None),
+          (next_count, "i32", 1, "next_count", kind_next is None), (hs_next, "f32", 6 * B, "hs_next", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_advance_replan_dev(
+        C.byref(rc), C.byref(rp), C.byref(sc) if sc is not None else None, B, N, _tp(x), _tp(kind), _tp(u_plan),
+        _tp(status), _tp(plan_status), _tp(x_ref), _tp(gap), _tp(u_held), _tp(held_len), _tp(held_idx),
+        _tp(have_path), _tp(x_next), _tp(u_lin_next), _tp(u_applied), _tp(pose_next), _tp(kind_next),
+        _tp(next_list), _tp(next_count), _tp(hs_next), C.c_void_p(stream.cuda_stream)), "f110qp_advance_replan_dev")
 
 
 def select_dev(group, num_groups, cost, status, winner, best_cost, stream=None):

@@ -626,6 +626,133 @@ int f110qp_plan_batch(const f110qp_plan_config* cfg, int batch, const double* po
                       int num_waypoints, unsigned char* grid, unsigned char* valid,
                       int* best_global, int* best_traj, float* x_ref, float* x0, int* status);
 
+/* ---- closed loop with re-planning: project::OdomCallback's per-car state on the device ----------
+ * f110qp_rollout[_scan][_dev] hold x_ref for the whole call. The reference does not: a mini path of
+ * traj_discrete = 50 points at dt 0.01 and umax 4.5 is 2.205 m long, project::OdomCallback drops it
+ * once the car is within 1.98 m of its end (src/project.cpp:180-186), and the next callback plans
+ * again (a re-plan about every 0.225 m driven, derived from those parameters). The calls below run
+ * that loop for B cars and T ticks on one stream, without a host round trip. Additive:
+ * F110QP_API_VERSION stays 6.
+ *
+ * Specification: per car, one tick is one Project::OdomCallback followed by one Project::DriveStep of
+ * the host mirror (f110-mpc_amd/host/src/project.cpp:31-100), including its choice for the tick on
+ * which the reference reads an emptied miniPath_: MPC::Update refuses the path, keeps its previous
+ * solution, and that solution is re-published with the input index reset to 0.
+ * Per-car state: have_path (get_mini_path_), the path x_ref[b] ([P][3] doubles that are widened
+ * floats, ori 0, as miniPath_), the published plan u_held[b] ([N][2] float32), its length len (N or
+ * 0) and the index idx (inputs_idx_).
+ * A tick's kind is decided at the tick's pose:
+ *   PLAN  have_path == 0. The planning branch (f110qp_plan_batch_dev's kernel) runs at this pose on
+ *         this tick's scan row. Status 0: the path is stored, have_path = 1. Any other status
+ *         (reported as F110QP_TICK_PLAN_FAILED): path and flag stay. No solve result is used;
+ *         u_held, len, idx are untouched.
+ *   HOLD  have_path == 1 and Transforms::CalcDist((float)x, (float)y, path end) < replan_dist (its
+ *         float expression, compared as the reference compares a float with the double 1.98):
+ *         have_path = 0, idx = 0; no solve result is used.
+ *   MPC   have_path == 1 otherwise. The solve's plan is published: a usable status (F110QP_SOLVED,
+ *         F110QP_SOLVED_INACCURATE) gives u_held = u*, len = N, idx = 0, any other len = 0, idx = 0
+ *         (f110qp_advance_dev's choices).
+ * Then, on every tick: DriveStep applies idx < len ? u_held[idx] : fail_u and idx++; the plant step
+ * is f110qp_advance_dev's; u_lin_next = (v_lin, idx < len ? u_held[idx].steer : fail_u[1]). On an
+ * uninterrupted run of MPC ticks this is f110qp_rollout_scan_dev for N >= 2; the calls below refuse
+ * horizon < 2 (f110qp_advance_dev's N = 1 rule has no counterpart in the index model).
+ * Modelling choices, next to the two of f110qp_advance_dev: the pose the planner reads is (x, y,
+ * sin(ori / 2), cos(ori / 2)), the planar quaternion a simulator's odometry would carry, formed in
+ * fp64 by the plant-step launch.
+ * The solve runs for all B cars on every tick, unmasked, with the launch policy of
+ * f110qp_solve_batch_dev_dbl at batch B (f110qp_backend_info, ... answer for it) and bit-identical to
+ * that call (NaN half-space rows keep its F110QP_PRIMAL_INFEASIBLE). On PLAN, PLAN_FAILED and HOLD
+ * ticks status_traj holds F110QP_NO_SOLVE and the car's rows of iters_traj, cost_traj, u_plan and
+ * x_plan are unspecified (whatever the stale path gave, NaN for a caller's NaN path at tick 0);
+ * nothing reads them. plan_status_traj, best_traj_traj and best_global_traj are written on PLAN /
+ * PLAN_FAILED ticks only (unspecified elsewhere). */
+#define F110QP_TICK_MPC 0
+#define F110QP_TICK_PLAN 1
+#define F110QP_TICK_HOLD 2
+#define F110QP_TICK_PLAN_FAILED 3
+#define F110QP_NO_SOLVE 0         /* status_traj on a tick whose solve result is not used */
+
+typedef struct {
+  double replan_dist;       /* 1.98, src/project.cpp:182; positive and finite                        */
+  f110qp_plan_config plan;  /* the planning stage; traj_discrete must equal the context's x_ref_points */
+  int num_waypoints;        /* rows of `waypoints`                                                    */
+} f110qp_replan_config;
+
+/* replan_dist 1.98, f110qp_default_plan_config, num_waypoints 0 (the caller's). */
+void f110qp_default_replan_config(f110qp_replan_config* rp);
+
+/* f110qp_plan_batch_dev for the cars of a device-side list (one launch): list[0 .. min(*count,
+ * batch)) names the cars, in any order; count is read on the device. pose is a pose row [B][4]
+ * doubles, ranges [B][num_ranges] (sc: num_ranges, angle_min, angle_increment, angle_max). Per listed
+ * car: plan_status, best_traj, best_global, and on status 0 the path into x_ref [B][P][3] as doubles
+ * (the float32 values f110qp_plan_batch_dev writes, widened). A listed car with another status keeps
+ * the path it has (no NaN is written); unlisted cars are not touched; count 0 changes nothing.
+ * Workgroups stride over the list, at most min(batch, 768) of them (what the device holds at once);
+ * one past the count exits at its first load. */
+int f110qp_plan_listed_dev(const f110qp_replan_config* rp, const f110qp_scan_config* sc, int batch,
+                           const int* list, const int* count, const double* pose, const float* ranges,
+                           const double* table, const double* waypoints, double* x_ref,
+                           int* plan_status, int* best_traj, int* best_global, void* stream);
+
+/* The launch in front of the loop: pose [B][4] = (x, y, sin(ori/2), cos(ori/2)) of x [B][3], kind [B]
+ * at that pose from have_path [B] and the path ends of x_ref [B][P][3], the cars whose kind is PLAN
+ * appended to list [B] (one atomic per wavefront on *count, which must be zero on entry), and, with
+ * hs non-NULL, f110qp_half_space_rows_dev(gap, x) into hs [B][2][3] (sc may be NULL when hs is). */
+int f110qp_replan_start_dev(const f110qp_replan_config* rp, const f110qp_scan_config* sc, int batch,
+                            const double* x, const int* have_path, const double* x_ref,
+                            const f110qp_gap_record* gap, double* pose, int* kind, int* list,
+                            int* count, float* hs, void* stream);
+
+/* One tick's state machine and plant step (one launch, one thread per car): f110qp_advance_scan_dev
+ * plus the rules above. Reads kind [B] (a PLAN tick with plan_status != 0 is rewritten
+ * F110QP_TICK_PLAN_FAILED), plan_status [B] on PLAN ticks, status [B] and u_plan [B][N][2] on MPC
+ * ticks, the path ends of x_ref; updates u_held [B][N][2], held_len, held_idx, have_path [B]; sets
+ * status to F110QP_NO_SOLVE on ticks that are not MPC ticks; writes x_next, u_lin_next, u_applied (may
+ * be NULL) with f110qp_advance_scan_dev's bits for the same applied input, pose_next [B][4], and,
+ * unless kind_next is NULL, the next tick's kind and its PLAN cars appended to next_list [B] /
+ * *next_count (zero on entry). hs_next [B][2][3] non-NULL: the rows at x_next from gap (sc required).
+ * horizon >= 2; the argument rules of f110qp_advance_dev apply, u_held 8-byte aligned. */
+int f110qp_advance_replan_dev(const f110qp_rollout_config* rc, const f110qp_replan_config* rp,
+                              const f110qp_scan_config* sc, int batch, int horizon, const double* x,
+                              int* kind, const float* u_plan, int* status, const int* plan_status,
+                              const double* x_ref, const f110qp_gap_record* gap, float* u_held,
+                              int* held_len, int* held_idx, int* have_path, double* x_next,
+                              double* u_lin_next, float* u_applied, double* pose_next, int* kind_next,
+                              int* next_list, int* next_count, float* hs_next, void* stream);
+
+/* T ticks of that loop (device pointers, asynchronous on `stream`). f110qp_rollout_scan_dev's
+ * arguments, except:
+ *   table      [T_c][P][3] doubles (f110qp_traj_table), waypoints [num_waypoints][2] doubles
+ *   x_ref      [B][P][3] doubles, in/out: the paths the cars hold (read only where have_path is 1)
+ *   have_path  [B], in/out: with x_ref it lets a call continue the previous one. The held plan does
+ *              not carry over: it starts empty on every call, like a fresh node.
+ *   kind_traj, plan_status_traj, best_traj_traj, best_global_traj [T][B], pose_traj [T+1][B][4]: each
+ *              may be NULL (workspaces of the context then).
+ * The context's x_ref_points must equal rp->plan.traj_discrete, its horizon be >= 2.
+ * Stream order: one memset of the per-tick plan counters, the gap search (when rows are computed, as
+ * f110qp_rollout_scan_dev), f110qp_replan_start_dev; then per tick the listed plan on that tick's
+ * list and scan row, the launches of f110qp_solve_batch_dev_dbl, and f110qp_advance_replan_dev. No
+ * host synchronisation, read-back or allocation inside the loop; every argument is checked before
+ * the first launch. */
+int f110qp_rollout_replan_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc,
+                              const f110qp_scan_config* sc, const f110qp_replan_config* rp, int batch,
+                              const double* table, const double* waypoints, double* x_ref,
+                              int* have_path, const float* ranges, double* x_traj, double* u_lin_traj,
+                              float* u_applied, int* status_traj, int* iters_traj, double* cost_traj,
+                              float* u_plan, float* x_plan, float* hs_traj, int* kind_traj,
+                              int* plan_status_traj, int* best_traj_traj, int* best_global_traj,
+                              double* pose_traj, void* stream);
+
+/* Same on host pointers (synchronous): staged through device buffers of the context, one stream
+ * synchronisation at the end, as f110qp_rollout_scan. */
+int f110qp_rollout_replan(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                          const f110qp_replan_config* rp, int batch, const double* table,
+                          const double* waypoints, double* x_ref, int* have_path, const float* ranges,
+                          double* x_traj, double* u_lin_traj, float* u_applied, int* status_traj,
+                          int* iters_traj, double* cost_traj, float* u_plan, float* x_plan,
+                          float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
+                          int* best_global_traj, double* pose_traj);
+
 #ifdef __cplusplus
 }
 #endif
