@@ -108,6 +108,7 @@ struct f110qp_ctx {
   DevBuf rdev;               // host-pointer rollout: device copies of its arrays
   DevBuf rgap;               // scan rollout: one GapRecord per scan (scan_rows x B)
   DevBuf rhs;                // scan rollout without hs_traj: the current tick's rows (B x 6 floats)
+  DevBuf rscan;              // world rollout without ranges_traj: the current tick's scans (B x num_ranges)
   DevBuf rstate;             // re-planning rollout: held plans, indices, plan counters and list, and the
                              // optional per-tick arrays the caller did not give (ReplanWork)
   int lane_kmax = 16;        // lane back end: PDAS passes before single (least-index) flips
@@ -1518,16 +1519,17 @@ static int replan_params(const f110qp_replan_config* rp, f110qp::PlanKParams* K)
   return F110QP_OK;
 }
 
-// Argument checks of f110qp_rollout_replan[_dev], all before any device call.
+// Argument checks of f110qp_rollout_replan[_dev], all before any device call. world (the world
+// rollouts): the scans are cast, so neither `ranges` nor sc->scan_rows is read.
 static int check_replan_args(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
                              const f110qp_replan_config* rp, int batch, const void* table, const void* wp,
                              const void* xr, const void* have, const void* ranges, const void* xt,
                              const void* ult, const void* ua, const void* stt, f110qp::AdvanceParams* ap,
-                             f110qp::PlanKParams* K) {
+                             f110qp::PlanKParams* K, bool world = false) {
   if (!c) return fail(F110QP_ERR_INVALID, "ctx is NULL");
   int rv = rollout_params(rc, true, ap);
   if (rv) return rv;
-  if ((rv = check_scan_config(sc, true, rc->ticks))) return rv;
+  if ((rv = check_scan_config(sc, !world, rc->ticks))) return rv;
   if ((rv = replan_params(rp, K))) return rv;
   if (c->cfg.horizon < 2) return fail(F110QP_ERR_INVALID, "the re-planning rollout needs horizon >= 2");
   if (c->kp.xr_stride != rp->plan.traj_discrete)
@@ -1538,8 +1540,8 @@ static int check_replan_args(f110qp_ctx* c, const f110qp_rollout_config* rc, con
     return fail(F110QP_ERR_INVALID, "x_ref/x_traj/u_lin_traj/u_applied/status_traj must be non-NULL");
   if (!have || !table || (rp->num_waypoints > 0 && !wp))
     return fail(F110QP_ERR_INVALID, "have_path/table/waypoints must be non-NULL");
-  if (!ranges) return fail(F110QP_ERR_INVALID, "ranges must be non-NULL");
-  if (batch > (1 << 30) / 64 || (long long)sc->scan_rows * batch > (1ll << 30))
+  if (!world && !ranges) return fail(F110QP_ERR_INVALID, "ranges must be non-NULL");
+  if (batch > (1 << 30) / 64 || (!world && (long long)sc->scan_rows * batch > (1ll << 30)))
     return fail(F110QP_ERR_INVALID, "batch too large");
   return F110QP_OK;
 }
@@ -1554,15 +1556,27 @@ struct ReplanTraj {
   double* pose;      // [T+1][B][4]
 };
 
+// f110qp_rollout_world[_dev]: tick t's scans are cast at tick t's pose instead of read from `ranges`.
+struct WorldLoop {
+  f110qp::CastParams P;
+  const double* circles;  // [world_rows][C][3]
+  float* ranges_traj;     // [T][B][num_ranges] or null: one row set in the context, listed cars only
+};
+
 // The T ticks of a checked re-planning rollout on device pointers. Every workspace is sized in front
 // of the loop; the loop only launches: the listed plan, the launches of one _dbl solve call, the
 // state machine with the plant step.
+// wl (the world rollout; ranges is not read): per tick the cast in front of the listed plan, on that
+// plan's list or, with ranges_traj, for all cars into row t. The gap records are those of one all-cars
+// cast at row 0 in front of the loop, held as at scan_rows = 1.
 static int replan_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, const f110qp::PlanKParams& K,
                         const f110qp_scan_config& sc, const f110qp_replan_config& rp, int T, int batch,
                         const double* table, const double* wp, double* xr, int* have, const float* ranges,
                         double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up,
-                        float* xp, const ReplanTraj& tr, hipStream_t s) {
+                        float* xp, const ReplanTraj& tr, hipStream_t s, const WorldLoop* wl = nullptr) {
   const size_t B = (size_t)batch, N = (size_t)c->cfg.horizon;
+  const size_t nr = (size_t)sc.num_ranges;
+  const int scan_rows = wl ? 1 : sc.scan_rows;
   const size_t n_up = B * N * 2, n_xp = B * (N + 1) * 3;
   if (!aligned8(ua) || !aligned8(up)) return fail(F110QP_ERR_INVALID, "u_applied / u_plan must be 8-byte aligned");
   float* wup = nullptr;
@@ -1580,7 +1594,7 @@ static int replan_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, const f1
   float* rows = nullptr;
   size_t rstep = 0;
   if (rows_on) {
-    if ((e = c->rgap.ensure((size_t)sc.scan_rows * B * sizeof(f110qp::GapRecord))) != hipSuccess)
+    if ((e = c->rgap.ensure((size_t)scan_rows * B * sizeof(f110qp::GapRecord))) != hipSuccess)
       return hip_fail(e, "hipMalloc gap records");
     rec = (f110qp::GapRecord*)c->rgap.p;
     rows = tr.hs;
@@ -1591,6 +1605,12 @@ static int replan_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, const f1
       rstep = 0;
     }
   }
+  float* wscan = nullptr;  // the world rollout's one row set
+  if (wl && !wl->ranges_traj) {
+    if ((e = c->rscan.ensure(B * nr * sizeof(float))) != hipSuccess) return hip_fail(e, "hipMalloc scan rows");
+    wscan = (float*)c->rscan.p;
+  }
+  auto scan_row = [&](size_t t) { return wscan ? wscan : wl->ranges_traj + t * B * nr; };
   // ReplanWork, the state of the loop in c->rstate: [pose B x 4 doubles unless pose_traj] [u_held B x N
   // float2] then ints: [held_len B | held_idx B | plan_count T + 1] (zeroed by the one memset), [list B],
   // [kind 2 B unless kind_traj], [plan_status B], [best_traj B], [best_global B] unless given
@@ -1620,7 +1640,12 @@ static int replan_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, const f1
   if (rc) return rc;
   if ((e = hipMemsetAsync(wi, 0, n_zero * sizeof(int), s)) != hipSuccess) return hip_fail(e, "hipMemsetAsync plan counters");
   if (rows_on) {
-    e = f110qp::launch_gap_search(sc.scan_rows * batch, ranges, sc.num_ranges, sc.angle_min, sc.angle_increment,
+    if (wl) {  // MPC's scan is the first one (src/project.cpp:45-49): every car's, at row 0
+      ranges = scan_row(0);
+      e = f110qp::launch_cast_scans(wl->P, batch, nullptr, nullptr, xt, wl->circles, scan_row(0), s);
+      if (e != hipSuccess) return hip_fail(e, "scan cast launch");
+    }
+    e = f110qp::launch_gap_search(scan_rows * batch, ranges, sc.num_ranges, sc.angle_min, sc.angle_increment,
                                   sc.angle_max, sc.ftg_thresh, sc.divider, sc.buffer, rec, s);
     if (e != hipSuccess) return hip_fail(e, "gap search launch");
   }
@@ -1644,11 +1669,16 @@ static int replan_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, const f1
     st.angle_inc = sc.angle_increment;
     if ((e = f110qp::launch_replan_start(batch, st, s)) != hipSuccess) return hip_fail(e, "re-planning start launch");
   }
-  const size_t nr = (size_t)sc.num_ranges;
   for (size_t t = 0; t < (size_t)T; t++) {
     int* ps_t = tr.plan_status ? tr.plan_status + t * B : wi + i_ps;
-    e = f110qp::launch_plan_listed(K, batch, list, count + t, pose_row(t),
-                                   ranges + (sc.scan_rows == 1 ? 0 : t * B * nr), sc.num_ranges, sc.angle_min,
+    const float* scan_t = wl ? scan_row(t) : ranges + (scan_rows == 1 ? 0 : t * B * nr);
+    if (wl) {
+      const bool all = wl->ranges_traj != nullptr;
+      e = f110qp::launch_cast_scans(wl->P, batch, all ? nullptr : list, all ? nullptr : count + t, xt + t * B * 3,
+                                    wl->circles, scan_row(t), s);
+      if (e != hipSuccess) return hip_fail(e, "scan cast launch");
+    }
+    e = f110qp::launch_plan_listed(K, batch, list, count + t, pose_row(t), scan_t, sc.num_ranges, sc.angle_min,
                                    sc.angle_increment, sc.angle_max, table, wp, rp.num_waypoints,
                                    tr.best_global ? tr.best_global + t * B : wi + i_bg,
                                    tr.best_traj ? tr.best_traj + t * B : wi + i_bt, xr, ps_t, s);
@@ -1684,7 +1714,7 @@ static int replan_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, const f1
     S.kind_next = last ? nullptr : kind_row(t + 1);
     S.next_list = last ? nullptr : list;
     S.next_count = last ? nullptr : count + t + 1;
-    S.gap = rows_on && !last ? rec + (sc.scan_rows == 1 ? 0 : (t + 1) * B) : nullptr;
+    S.gap = rows_on && !last ? rec + (scan_rows == 1 ? 0 : (t + 1) * B) : nullptr;
     S.hs_next = rows_on && !last ? rows + (t + 1) * rstep : nullptr;
     S.nr = sc.num_ranges;
     S.angle_min = sc.angle_min;
@@ -1832,15 +1862,17 @@ int f110qp_rollout_replan_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, co
                       cot, up, xp, tr, (hipStream_t)stream);
 }
 
-int f110qp_rollout_replan(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
-                          const f110qp_replan_config* rp, int batch, const double* table, const double* wp,
-                          double* xr, int* have, const float* ranges, double* xt, double* ult, float* ua,
-                          int* stt, int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst,
-                          int* btt, int* bgt, double* poset) {
-  f110qp::AdvanceParams ap;
-  f110qp::PlanKParams K;
-  const int rv = check_replan_args(c, rc, sc, rp, batch, table, wp, xr, have, ranges, xt, ult, ua, stt, &ap, &K);
-  if (rv || batch == 0) return rv;
+}  // extern "C"
+
+// The host-pointer re-planning rollouts on checked arguments: f110qp_rollout_replan (wl null: ranges
+// [scan_rows][B][num_ranges]) and f110qp_rollout_world (wl: its host circles staged in, its host
+// ranges_traj, when given, copied back), staged through c->rdev.
+static int replan_host(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                       const f110qp_replan_config* rp, const f110qp::AdvanceParams& ap,
+                       const f110qp::PlanKParams& K, int batch, const double* table, const double* wp,
+                       double* xr, int* have, const float* ranges, double* xt, double* ult, float* ua,
+                       int* stt, int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst,
+                       int* btt, int* bgt, double* poset, const WorldLoop* wl) {
   hipError_t e = hipSetDevice(c->cfg.device);
   if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
   if (!c->stream && (e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
@@ -1858,11 +1890,14 @@ int f110qp_rollout_replan(f110qp_ctx* c, const f110qp_rollout_config* rc, const 
   };
   const size_t s_tab = (size_t)K.T * P * 3 * 8, s_wp = W * 2 * 8, s_xr = B * P * 3 * 8;
   const size_t s_xt = (T + 1) * B * 3 * 8, s_ul = (T + 1) * B * 2 * 8, s_po = (T + 1) * B * 4 * 8;
-  const size_t s_rg = (size_t)sc->scan_rows * B * (size_t)sc->num_ranges * 4, s_i = TB * 4;
+  const size_t s_rg = (wl ? T : (size_t)sc->scan_rows) * B * (size_t)sc->num_ranges * 4, s_i = TB * 4;
+  const size_t s_ci = wl ? (size_t)wl->P.world_rows * (size_t)wl->P.C * 3 * 8 : 0;
+  float* const rgt = wl ? wl->ranges_traj : nullptr;
   const size_t s_up = TB * N * 2 * 4, s_xp = TB * (N + 1) * 3 * 4;
   const size_t o_tab = field(true, s_tab), o_wp = field(W > 0, s_wp), o_xr = field(true, s_xr);
   const size_t o_xt = field(true, s_xt), o_ul = field(true, s_ul), o_co = field(cot, TB * 8);
-  const size_t o_po = field(poset, s_po), o_rg = field(true, s_rg), o_hs = field(hst, TB * 6 * 4);
+  const size_t o_po = field(poset, s_po), o_rg = field(!wl || rgt, s_rg), o_hs = field(hst, TB * 6 * 4);
+  const size_t o_ci = field(s_ci > 0, s_ci);
   const size_t o_ua = field(true, TB * 2 * 4), o_st = field(true, s_i), o_it = field(itt, s_i);
   const size_t o_up = field(up, s_up), o_xp = field(xp, s_xp), o_hv = field(true, B * 4);
   const size_t o_kt = field(kt, s_i), o_ps = field(pst, s_i), o_bt = field(btt, s_i), o_bg = field(bgt, s_i);
@@ -1873,17 +1908,21 @@ int f110qp_rollout_replan(f110qp_ctx* c, const f110qp_rollout_config* rc, const 
       (e = hipMemcpyAsync(d + o_xr, xr, s_xr, hipMemcpyHostToDevice, s)) ||
       (e = hipMemcpyAsync(d + o_xt, xt, B * 3 * 8, hipMemcpyHostToDevice, s)) ||
       (e = hipMemcpyAsync(d + o_ul, ult, B * 2 * 8, hipMemcpyHostToDevice, s)) ||
-      (e = hipMemcpyAsync(d + o_rg, ranges, s_rg, hipMemcpyHostToDevice, s)) ||
+      (!wl && (e = hipMemcpyAsync(d + o_rg, ranges, s_rg, hipMemcpyHostToDevice, s))) ||
+      (s_ci > 0 && (e = hipMemcpyAsync(d + o_ci, wl->circles, s_ci, hipMemcpyHostToDevice, s))) ||
       (e = hipMemcpyAsync(d + o_hv, have, B * 4, hipMemcpyHostToDevice, s)))
     return hip_fail(e, "hipMemcpyAsync H2D");
   const ReplanTraj tr{hst ? (float*)(d + o_hs) : nullptr, kt ? (int*)(d + o_kt) : nullptr,
                       pst ? (int*)(d + o_ps) : nullptr,   btt ? (int*)(d + o_bt) : nullptr,
                       bgt ? (int*)(d + o_bg) : nullptr,   poset ? (double*)(d + o_po) : nullptr};
+  WorldLoop dwl{};
+  if (wl) dwl = WorldLoop{wl->P, s_ci > 0 ? (const double*)(d + o_ci) : nullptr, rgt ? (float*)(d + o_rg) : nullptr};
   const int rt = replan_ticks(c, ap, K, *sc, *rp, rc->ticks, batch, (const double*)(d + o_tab),
                               W > 0 ? (const double*)(d + o_wp) : nullptr, (double*)(d + o_xr), (int*)(d + o_hv),
                               (const float*)(d + o_rg), (double*)(d + o_xt), (double*)(d + o_ul), (float*)(d + o_ua),
                               (int*)(d + o_st), itt ? (int*)(d + o_it) : nullptr, cot ? (double*)(d + o_co) : nullptr,
-                              up ? (float*)(d + o_up) : nullptr, xp ? (float*)(d + o_xp) : nullptr, tr, s);
+                              up ? (float*)(d + o_up) : nullptr, xp ? (float*)(d + o_xp) : nullptr, tr, s,
+                              wl ? &dwl : nullptr);
   if (rt) return rt;
   // the state that carries over, rows 1..T of the trajectories (row 0 is the caller's), every record
   if ((e = hipMemcpyAsync(xr, d + o_xr, s_xr, hipMemcpyDeviceToHost, s)) ||
@@ -1901,10 +1940,109 @@ int f110qp_rollout_replan(f110qp_ctx* c, const f110qp_rollout_config* rc, const 
       (pst && (e = hipMemcpyAsync(pst, d + o_ps, s_i, hipMemcpyDeviceToHost, s))) ||
       (btt && (e = hipMemcpyAsync(btt, d + o_bt, s_i, hipMemcpyDeviceToHost, s))) ||
       (bgt && (e = hipMemcpyAsync(bgt, d + o_bg, s_i, hipMemcpyDeviceToHost, s))) ||
-      (poset && (e = hipMemcpyAsync(poset, d + o_po, s_po, hipMemcpyDeviceToHost, s))))
+      (poset && (e = hipMemcpyAsync(poset, d + o_po, s_po, hipMemcpyDeviceToHost, s))) ||
+      (rgt && (e = hipMemcpyAsync(rgt, d + o_rg, s_rg, hipMemcpyDeviceToHost, s))))
     return hip_fail(e, "hipMemcpyAsync D2H");
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
   return F110QP_OK;
+}
+
+// The world of f110qp_cast_scans_dev and the world rollouts, checked; with sc's geometry into *P.
+static int world_params(const f110qp_scan_config* sc, const f110qp_world_config* wc, int batch,
+                        const void* circles, f110qp::CastParams* P) {
+  if (!wc) return fail(F110QP_ERR_INVALID, "world config is NULL");
+  if (wc->num_circles < 0) return fail(F110QP_ERR_INVALID, "num_circles < 0");
+  if (!std::isfinite(wc->lidar_offset)) return fail(F110QP_ERR_INVALID, "lidar_offset must be finite");
+  if (!(wc->max_range > 0.0) || !std::isfinite(wc->max_range))
+    return fail(F110QP_ERR_INVALID, "max_range must be positive and finite");
+  if (wc->world_rows != 1 && wc->world_rows != batch)
+    return fail(F110QP_ERR_INVALID, "world_rows must be 1 or batch");
+  if (wc->num_circles > 0 && !circles) return fail(F110QP_ERR_INVALID, "num_circles > 0 needs the circles");
+  P->nr = sc->num_ranges;
+  P->angle_min = sc->angle_min;
+  P->angle_inc = sc->angle_increment;
+  P->C = wc->num_circles;
+  P->world_rows = wc->world_rows;
+  P->lidar_offset = wc->lidar_offset;
+  P->max_range = wc->max_range;
+  return F110QP_OK;
+}
+
+extern "C" {
+
+int f110qp_rollout_replan(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                          const f110qp_replan_config* rp, int batch, const double* table, const double* wp,
+                          double* xr, int* have, const float* ranges, double* xt, double* ult, float* ua,
+                          int* stt, int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst,
+                          int* btt, int* bgt, double* poset) {
+  f110qp::AdvanceParams ap;
+  f110qp::PlanKParams K;
+  const int rv = check_replan_args(c, rc, sc, rp, batch, table, wp, xr, have, ranges, xt, ult, ua, stt, &ap, &K);
+  if (rv || batch == 0) return rv;
+  return replan_host(c, rc, sc, rp, ap, K, batch, table, wp, xr, have, ranges, xt, ult, ua, stt, itt, cot, up, xp,
+                     hst, kt, pst, btt, bgt, poset, nullptr);
+}
+
+void f110qp_default_world_config(f110qp_world_config* wc) {
+  if (!wc) return;
+  std::memset(wc, 0, sizeof(*wc));
+  wc->world_rows = 1;
+  wc->lidar_offset = 0.275;  // occupancy_grid.cpp:63-64
+  wc->max_range = 10.0;
+}
+
+int f110qp_cast_scans_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc, int batch, const int* list,
+                          const int* count, const double* x, const double* circles, float* ranges,
+                          void* stream) {
+  int rv = check_scan_config(sc, false, 0);
+  if (rv) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  f110qp::CastParams P;
+  if ((rv = world_params(sc, wc, batch, circles, &P))) return rv;
+  if ((list != nullptr) != (count != nullptr))
+    return fail(F110QP_ERR_INVALID, "list and count must be given together");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !ranges) return fail(F110QP_ERR_INVALID, "x/ranges must be non-NULL");
+  const hipError_t e = f110qp::launch_cast_scans(P, batch, list, count, x, circles, ranges, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "scan cast launch");
+  return F110QP_OK;
+}
+
+int f110qp_rollout_world_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                             const f110qp_replan_config* rp, const f110qp_world_config* wc, int batch,
+                             const double* table, const double* wp, double* xr, int* have, const double* circles,
+                             double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up,
+                             float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset,
+                             float* rgt, void* stream) {
+  f110qp::AdvanceParams ap;
+  f110qp::PlanKParams K;
+  WorldLoop wl{};
+  int rv = check_replan_args(c, rc, sc, rp, batch, table, wp, xr, have, nullptr, xt, ult, ua, stt, &ap, &K, true);
+  if (rv) return rv;
+  if ((rv = world_params(sc, wc, batch, circles, &wl.P)) || batch == 0) return rv;
+  wl.circles = circles;
+  wl.ranges_traj = rgt;
+  const ReplanTraj tr{hst, kt, pst, btt, bgt, poset};
+  return replan_ticks(c, ap, K, *sc, *rp, rc->ticks, batch, table, wp, xr, have, nullptr, xt, ult, ua, stt, itt,
+                      cot, up, xp, tr, (hipStream_t)stream, &wl);
+}
+
+int f110qp_rollout_world(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                         const f110qp_replan_config* rp, const f110qp_world_config* wc, int batch,
+                         const double* table, const double* wp, double* xr, int* have, const double* circles,
+                         double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up,
+                         float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset,
+                         float* rgt) {
+  f110qp::AdvanceParams ap;
+  f110qp::PlanKParams K;
+  WorldLoop wl{};
+  int rv = check_replan_args(c, rc, sc, rp, batch, table, wp, xr, have, nullptr, xt, ult, ua, stt, &ap, &K, true);
+  if (rv) return rv;
+  if ((rv = world_params(sc, wc, batch, circles, &wl.P)) || batch == 0) return rv;
+  wl.circles = circles;
+  wl.ranges_traj = rgt;
+  return replan_host(c, rc, sc, rp, ap, K, batch, table, wp, xr, have, nullptr, xt, ult, ua, stt, itt, cot, up, xp,
+                     hst, kt, pst, btt, bgt, poset, &wl);
 }
 
 }  // extern "C"

@@ -358,4 +358,22 @@ struct ReplanStart {
 };
 hipError_t launch_replan_start(int B, const ReplanStart& S, hipStream_t stream);
 
+// ---- simulated LiDAR (scan_kernels.hip) -----------------------------------------------------------
+// Ray casting against circles, workload._ray_circles on the device: per car the scan of nr beams at
+// pose x [B][3] from the LiDAR lidar_offset ahead, circles [world_rows][C][3] = (cx, cy, r), ranges
+// [B][nr] float32. One workgroup per car, at most cast_scans_grid(B) of them striding over all B cars
+// (list and count null) or over list[0 .. min(*count, B)) as launch_plan_listed; unlisted cars are
+// not touched. Circles are processed kCastCircleTile at a time (== F110QP_CAST_CIRCLE_TILE).
+constexpr int kCastCircleTile = 256;
+struct CastParams {
+  int nr;
+  float angle_min, angle_inc;
+  int C;
+  int world_rows;  // 1 or B
+  double lidar_offset, max_range;
+};
+int cast_scans_grid(int B);
+hipError_t launch_cast_scans(const CastParams& P, int B, const int* list, const int* count, const double* x,
+                             const double* circles, float* ranges, hipStream_t stream);
+
 }  // namespace f110qp

@@ -1,0 +1,194 @@
+// scan_kernels.hip — the simulated LiDAR of the closed loop: 2-D ray casting against circles.
+//
+// The project's world model (f110qp/workload.py, _ray_circles: every scan of make_scenes, drive_stream,
+// the tests and bench.py) on the device, so that a rollout can take tick t's scan at tick t's pose.
+// Per car: the LiDAR origin o = (x + off cos(ori), y + off sin(ori)) (occupancy_grid.cpp:63-64), beam
+// i along ori + ((double)angle_min + (double)angle_increment i), and per circle (c, r)
+//   p = c - o, t = p.d, d2 = p.p - t t, hit: d2 <= r^2 && t > 0, th = t - sqrt(max(r^2 - d2, 0)),
+// which counts when th > 0; range = (float)min(min over circles of th, max_range). All fp64 in the
+// numpy expression order with FP contraction off, sincos(double) and the correctly rounded sqrt: per
+// (beam, circle) pair the value is fixed by the beam's direction, so the minimum does not depend on
+// the order the circles are visited in (or on which thread visits them).
+//
+// Mapping: one 256-thread workgroup per car, striding over the cars (all B, or a device-side list as
+// plan_listed_kernel). Brute force is C x R pair tests per car; here the work is circle-parallel
+// behind a cull. Per beam tile (kCastBeamTile beams: their directions and running minima in LDS) and
+// per circle tile (kCastCircleTile circles, one per thread):
+//   A  thread j reads circle j, drops it when |p| - |r| is past max_range (a NaN or inf field fails or
+//      passes that compare like any other number: no branch looks for it), and turns it into a beam
+//      interval: the circle subtends atan2(p) -+ asin(|r| / |p|), a beam can hit it only inside that
+//      arc, so the beams are floor(f_lo) - 1 .. floor(f_lo) + ceil(2w / inc) + 2 with f_lo the arc's
+//      low edge in beam units: at least one beam more than the arc at either end, repeated every
+//      2 pi / inc beams for a scan that wraps. The LiDAR inside (or on) a circle, an arc that with its
+//      margin closes the turn, or an increment too small for the margin: every beam.
+//   B  eight lanes per kept circle run the exact test above on its beams only and fold th into the
+//      beam's minimum with an unsigned 64-bit LDS atomic min (positive doubles order as their bits).
+// A beam outside an interval cannot hit, one inside is decided by the exact test, so the interval
+// changes the work and not the result.
+#include <hip/hip_runtime.h>
+
+#include "f110qp_kernels.h"
+
+namespace f110qp {
+
+namespace {
+
+constexpr int kCastThreads = 256;
+constexpr int kCastBeamTile = 1152;  // beams per LDS tile (a 1,080-beam scan is one tile)
+constexpr int kCastLanes = 8;        // lanes that share one circle's interval
+constexpr int kCastGroups = kCastThreads / kCastLanes;
+static_assert(kCastCircleTile == kCastThreads, "phase A: one circle per thread");
+
+constexpr double kTwoPi = 6.283185307179586476925286766559;
+// relative slack of the two culls (range and inside-the-circle) and absolute slack of the arc: far
+// above the rounding of dist, asin and atan2, far below a beam
+constexpr double kCastRel = 1.000001;
+constexpr double kCastArcSlack = 1e-9;
+// below this increment the one-beam margin is not safely above the rounding of the arc: every beam
+constexpr double kCastMinInc = 1e-9;
+
+// A circle of the current tile as phase B reads it. nd: beams per interval less one (0: culled, < 0:
+// every beam of the scan).
+struct CastSlot {
+  double px, py, r2, flo, nd;
+};
+
+// The exact hit test of circle (px, py, pp, r2) on beams lo .. hi of the scan (clipped to the beam tile
+// [cb, cb + nb)), lanes striding by kCastLanes.
+#pragma clang fp contract(off)
+__device__ __forceinline__ void cast_beams(const double px, const double py, const double pp, const double r2,
+                                           int lo, int hi, const int cb, const int nb, const int sub,
+                                           const double* s_dx, const double* s_dy,
+                                           unsigned long long* s_min) {
+  lo = max(lo, cb) - cb;
+  hi = min(hi, cb + nb - 1) - cb;
+  for (int i = lo + sub; i <= hi; i += kCastLanes) {
+    const double t = px * s_dx[i] + py * s_dy[i];
+    const double d2 = pp - t * t;
+    if (d2 <= r2 && t > 0.0) {
+      const double th = t - __dsqrt_rn(fmax(r2 - d2, 0.0));
+      if (th > 0.0) atomicMin(&s_min[i], (unsigned long long)__double_as_longlong(th));
+    }
+  }
+}
+
+#pragma clang fp contract(off)
+__device__ __forceinline__ void cast_one(const CastParams& P, const int b, const double* __restrict__ x,
+                                         const double* __restrict__ circles, float* __restrict__ ranges,
+                                         double* s_dx, double* s_dy, unsigned long long* s_min,
+                                         CastSlot* s_slot) {
+  const int tid = threadIdx.x;
+  const double ori = x[(size_t)b * 3 + 2];
+  double so, co;
+  sincos(ori, &so, &co);
+  const double ox = x[(size_t)b * 3 + 0] + P.lidar_offset * co;
+  const double oy = x[(size_t)b * 3 + 1] + P.lidar_offset * so;
+  const double amin = (double)P.angle_min, ainc = (double)P.angle_inc;
+  const double per = kTwoPi / ainc;  // beams per turn
+  const double* cw = circles + (P.world_rows == 1 ? (size_t)0 : (size_t)b * (size_t)P.C * 3);
+  const int nr = P.nr;
+  const double last = (double)(nr - 1);
+  for (int cb = 0; cb < nr; cb += kCastBeamTile) {
+    const int nb = min(kCastBeamTile, nr - cb);
+    for (int i = tid; i < nb; i += kCastThreads) {
+      double sa, ca;
+      sincos(ori + (amin + ainc * (double)(cb + i)), &sa, &ca);
+      s_dx[i] = ca;
+      s_dy[i] = sa;
+      s_min[i] = (unsigned long long)__double_as_longlong(P.max_range);
+    }
+    __syncthreads();
+    for (int c0 = 0; c0 < P.C; c0 += kCastCircleTile) {
+      {  // A: circle c0 + tid -> slot tid
+        CastSlot sl{0.0, 0.0, 0.0, 0.0, 0.0};
+        const int j = c0 + tid;
+        if (j < P.C) {
+          const double r = cw[(size_t)j * 3 + 2];
+          const double px = cw[(size_t)j * 3 + 0] - ox, py = cw[(size_t)j * 3 + 1] - oy;
+          const double ra = fabs(r), dist = __dsqrt_rn(px * px + py * py);
+          if (dist - ra <= P.max_range * kCastRel) {
+            sl.px = px;
+            sl.py = py;
+            sl.r2 = r * r;
+            const double w = asin(fmin(ra / dist, 1.0)) + kCastArcSlack;
+            const bool arc = dist > ra * kCastRel && 2.0 * w + 4.0 * ainc < kTwoPi && ainc >= kCastMinInc;
+            if (arc) {
+              double rel = atan2(py, px) - ori - amin - w;  // the arc's low edge from beam 0
+              rel -= kTwoPi * floor(rel / kTwoPi);
+              sl.flo = rel / ainc;
+              sl.nd = ceil(2.0 * w / ainc) + 3.0;
+            } else {
+              sl.nd = -1.0;
+            }
+          }
+        }
+        s_slot[tid] = sl;
+      }
+      __syncthreads();
+      {  // B: kCastLanes lanes per kept circle
+        const int nt = min(kCastCircleTile, P.C - c0), sub = tid % kCastLanes;
+        for (int j = tid / kCastLanes; j < nt; j += kCastGroups) {
+          const CastSlot sl = s_slot[j];
+          if (sl.nd == 0.0) continue;
+          const double pp = sl.px * sl.px + sl.py * sl.py;
+          if (sl.nd < 0.0) {
+            cast_beams(sl.px, sl.py, pp, sl.r2, 0, nr - 1, cb, nb, sub, s_dx, s_dy, s_min);
+            continue;
+          }
+          // the interval and its copies a turn apart; the first starts below beam 0 (flo < per)
+          for (double k = -1.0;; k += 1.0) {
+            const double s = floor(sl.flo + k * per) - 1.0;
+            if (!(s <= last)) break;
+            const double lo = fmax(s, 0.0), hi = fmin(s + sl.nd, last);
+            if (lo <= hi) cast_beams(sl.px, sl.py, pp, sl.r2, (int)lo, (int)hi, cb, nb, sub, s_dx, s_dy, s_min);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    float* out = ranges + (size_t)b * (size_t)nr + cb;
+    for (int i = tid; i < nb; i += kCastThreads) out[i] = (float)__longlong_as_double((long long)s_min[i]);
+    __syncthreads();  // the next tile (or car) resets the minima
+  }
+}
+
+}  // namespace
+
+// Workgroup w takes cars w, w + nwg, ... below B, or with a list the cars list[w], list[w + nwg], ...
+// below min(*count, B) (plan_listed_kernel's rule: one past the count leaves at that load).
+__global__ __launch_bounds__(kCastThreads) void cast_scans_kernel(const CastParams P, const int B, const int nwg,
+                                                                  const int* __restrict__ list,
+                                                                  const int* __restrict__ count,
+                                                                  const double* __restrict__ x,
+                                                                  const double* __restrict__ circles,
+                                                                  float* __restrict__ ranges) {
+  __shared__ double s_dx[kCastBeamTile];
+  __shared__ double s_dy[kCastBeamTile];
+  __shared__ unsigned long long s_min[kCastBeamTile];
+  __shared__ CastSlot s_slot[kCastCircleTile];
+  const int n = list ? min(*count, B) : B;
+  for (int k = blockIdx.x; k < n; k += nwg) {
+    const int b = list ? list[k] : k;
+    if (b >= 0 && b < B)  // uniform over the workgroup
+      cast_one(P, b, x, circles, ranges, s_dx, s_dy, s_min, s_slot);
+  }
+}
+
+// Grid: one workgroup per car up to 768. The kernel holds 155 VGPRs (the code-object metadata,
+// DESIGN.md 2i; the fp64 sincos, asin and atan2 set that figure), so a SIMD keeps three of its waves
+// and a CU three of its four-wave workgroups (37,888 B of LDS each would allow four): 768 is what the
+// MI355X's 256 CUs hold at once, the same figure as plan_listed_grid's and derived the same way, from
+// the occupancy and not from a sweep of caps. Forcing four waves per SIMD spills 17 VGPRs to scratch.
+constexpr int kCastMaxGrid = 768;
+int cast_scans_grid(int B) { return B < kCastMaxGrid ? B : kCastMaxGrid; }
+
+hipError_t launch_cast_scans(const CastParams& P, int B, const int* list, const int* count, const double* x,
+                             const double* circles, float* ranges, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  const int nwg = cast_scans_grid(B);
+  hipLaunchKernelGGL(cast_scans_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, B, nwg, list, count, x, circles,
+                     ranges);
+  return hipGetLastError();
+}
+
+}  // namespace f110qp

@@ -122,7 +122,12 @@ EXPORTED = (
     "f110qp_advance_replan_dev",
     "f110qp_rollout_replan_dev",
     "f110qp_rollout_replan",
+    "f110qp_default_world_config",
+    "f110qp_cast_scans_dev",
+    "f110qp_rollout_world_dev",
+    "f110qp_rollout_world",
 )
+CAST_CIRCLE_TILE = 256  # F110QP_CAST_CIRCLE_TILE: circles per LDS tile of the ray-cast kernel
 SCRATCH_NAMES = {0: "none (wave back end)", 1: "LDS fp64", 2: "LDS fp32", 3: "HBM fp64", 4: "HBM fp32"}
 
 
@@ -189,6 +194,15 @@ class ReplanConfig(C.Structure):
     ]
 
 
+class WorldConfig(C.Structure):
+    _fields_ = [
+        ("num_circles", C.c_int),
+        ("world_rows", C.c_int),
+        ("lidar_offset", C.c_double),
+        ("max_range", C.c_double),
+    ]
+
+
 # f110qp_gap_record (16 bytes) as a numpy record
 GAP_RECORD_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("r_lo", np.float32), ("r_hi", np.float32)])
 
@@ -248,6 +262,11 @@ def load(test: bool = False):
     L.f110qp_advance_replan_dev.argtypes = [rop, rp, sp, C.c_int, C.c_int] + [fp] * 20
     L.f110qp_rollout_replan_dev.argtypes = [C.c_void_p, rop, sp, rp, C.c_int] + [fp] * 20
     L.f110qp_rollout_replan.argtypes = [C.c_void_p, rop, sp, rp, C.c_int] + [fp] * 19
+    wcp = C.POINTER(WorldConfig)
+    L.f110qp_default_world_config.argtypes = [wcp]
+    L.f110qp_cast_scans_dev.argtypes = [sp, wcp, C.c_int] + [fp] * 6
+    L.f110qp_rollout_world_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, C.c_int] + [fp] * 21
+    L.f110qp_rollout_world.argtypes = [C.c_void_p, rop, sp, rp, wcp, C.c_int] + [fp] * 20
     L.f110qp_select_dev.argtypes = [C.c_int, fp, C.c_int, fp, fp, fp, fp, fp]
     L.f110qp_backend_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
     L.f110qp_lane_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -337,6 +356,16 @@ def default_replan_config(**over) -> ReplanConfig:
             setattr(c.plan, k, v)
         else:
             setattr(c, k, v)
+    return c
+
+
+def default_world_config(**over) -> WorldConfig:
+    """f110qp_default_world_config: world_rows 1, lidar_offset 0.275, max_range 10.0, num_circles 0 (the
+    caller's)."""
+    c = WorldConfig()
+    load().f110qp_default_world_config(C.byref(c))
+    for k, v in over.items():
+        setattr(c, k, v)
     return c
 
 
@@ -816,6 +845,103 @@ class Solver:
             _p(out["pose_traj"])), "f110qp_rollout_replan")
         return out
 
+    def rollout_world_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, table,
+                          waypoints, x_ref, have_path, circles, x_traj, u_lin_traj, u_applied, status_traj,
+                          iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
+                          plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
+                          ranges_traj=None, stream=None):
+        """rollout_replan_dev with every tick's scan cast at that tick's pose (f110qp_rollout_world_dev): wc
+        and circles [world_rows,C,3] f64 replace ranges, sc.scan_rows is not read, and the optional
+        ranges_traj [T,B,num_ranges] f32 records every car's scan of every tick."""
+        import torch
+
+        T, N = int(rc.ticks), self.horizon
+        if T < 1:
+            raise F110QPError("ticks must be >= 1")
+        P, Tc, W = int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
+        B, NR = int(x_ref.shape[0]), int(sc.num_ranges)
+        Cn, WR = int(wc.num_circles), int(wc.world_rows)
+        if tuple(x_traj.shape) != (T + 1, B, 3):
+            raise F110QPError(f"x_traj must be [ticks + 1, B, 3] = {(T + 1, B, 3)}, got {tuple(x_traj.shape)}")
+        if WR not in (1, B):
+            raise F110QPError(f"world_rows must be 1 or B = {B}, got {WR}")
+        _devs((table, "f64", 3 * P * Tc, "table"), (waypoints, "f64", 2 * W, "waypoints", W == 0),
+              (x_ref, "f64", 3 * P * B, "x_ref"), (have_path, "i32", B, "have_path"),
+              (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
+              (x_traj, "f64", 3 * B * (T + 1), "x_traj"), (u_lin_traj, "f64", 2 * B * (T + 1), "u_lin_traj"),
+              (u_applied, "f32", 2 * B * T, "u_applied"), (status_traj, "i32", B * T, "status_traj"),
+              (iters_traj, "i32", B * T, "iters_traj", True), (cost_traj, "f64", B * T, "cost_traj", True),
+              (u_plan, "f32", 2 * N * B * T, "u_plan", True), (x_plan, "f32", 3 * (N + 1) * B * T, "x_plan", True),
+              (hs_traj, "f32", 6 * B * T, "hs_traj", True), (kind_traj, "i32", B * T, "kind_traj", True),
+              (plan_status_traj, "i32", B * T, "plan_status_traj", True),
+              (best_traj_traj, "i32", B * T, "best_traj_traj", True),
+              (best_global_traj, "i32", B * T, "best_global_traj", True),
+              (pose_traj, "f64", 4 * B * (T + 1), "pose_traj", True),
+              (ranges_traj, "f32", T * B * NR, "ranges_traj", True))
+        if stream is None:
+            stream = torch.cuda.current_stream(x_traj.device)
+        self._chk(self.lib.f110qp_rollout_world_dev(
+            self._h, C.byref(rc), C.byref(sc), C.byref(rp), C.byref(wc), B, _tp(table), _tp(waypoints), _tp(x_ref),
+            _tp(have_path), _tp(circles), _tp(x_traj), _tp(u_lin_traj), _tp(u_applied), _tp(status_traj),
+            _tp(iters_traj), _tp(cost_traj), _tp(u_plan), _tp(x_plan), _tp(hs_traj), _tp(kind_traj),
+            _tp(plan_status_traj), _tp(best_traj_traj), _tp(best_global_traj), _tp(pose_traj), _tp(ranges_traj),
+            C.c_void_p(stream.cuda_stream)), "f110qp_rollout_world_dev")
+
+    def rollout_world(self, x0, u_lin, circles, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
+                      wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
+                      scans=False, rc=None):
+        """rollout_replan() in a world of circles (f110qp_rollout_world, synchronous): circles [C,3] (one world
+        for all cars) or [B,C,3] float64 replace ranges; wc defaults to f110qp_default_world_config with
+        num_circles and world_rows taken from the array. scans=True adds ranges_traj [T,B,num_ranges]."""
+        N, T = self.horizon, int(ticks)
+        if T < 1:
+            raise F110QPError("ticks must be >= 1")
+        x0 = _f64(x0, (-1, 3), "x0")
+        B = x0.shape[0]
+        ul = _f64(u_lin, (B, 2), "u_lin")
+        P, Tc, W = int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
+        xr = np.full((B, P, 3), np.nan) if x_ref is None else _f64(x_ref, (B, P, 3), "x_ref").copy()
+        hv = np.zeros(B, np.int32) if have_path is None else np.array(have_path, np.int32).reshape(B)
+        tab = _f64(table, (Tc, P, 3), "table")
+        wp = np.ascontiguousarray(np.asarray(waypoints, np.float64)[:, :2])
+        if wp.shape[0] != W:
+            raise F110QPError(f"waypoints must hold num_waypoints = {W} rows, got {wp.shape[0]}")
+        if not isinstance(circles, np.ndarray) or circles.dtype != np.float64 or circles.ndim not in (2, 3) \
+                or circles.shape[-1] != 3:
+            raise F110QPError("circles must be a float64 numpy array [C, 3] or [B, C, 3]")
+        ci = np.ascontiguousarray(circles)
+        w = WorldConfig()
+        C.memmove(C.byref(w), C.byref(wc if wc is not None else default_world_config()), C.sizeof(w))
+        w.num_circles = ci.shape[-2]
+        w.world_rows = 1 if ci.ndim == 2 else ci.shape[0]
+        if w.world_rows not in (1, B):
+            raise F110QPError(f"circles must hold one world or B = {B} worlds, got {w.world_rows}")
+        cfg = RolloutConfig()
+        C.memmove(C.byref(cfg), C.byref(rc if rc is not None else default_rollout_config()), C.sizeof(cfg))
+        cfg.ticks = T
+        i32 = lambda: np.empty((T, B), np.int32)  # noqa: E731
+        out = {"x_traj": np.empty((T + 1, B, 3), np.float64), "u_lin_traj": np.empty((T + 1, B, 2), np.float64),
+               "u_applied": np.empty((T, B, 2), np.float32), "status": i32(), "iters": i32(), "x_ref": xr,
+               "have_path": hv, "kind": i32(), "plan_status": i32(), "best_traj": i32(), "best_global": i32(),
+               "pose_traj": np.empty((T + 1, B, 4), np.float64)}
+        out["x_traj"][0], out["u_lin_traj"][0] = x0, ul
+        if objective:
+            out["cost"] = np.empty((T, B), np.float64)
+        if plans:
+            out["u_plan"] = np.empty((T, B, N, 2), np.float32)
+            out["x_plan"] = np.empty((T, B, N + 1, 3), np.float32)
+        if rows:
+            out["hs_traj"] = np.empty((T, B, 2, 3), np.float32)
+        if scans:
+            out["ranges_traj"] = np.empty((T, B, int(sc.num_ranges)), np.float32)
+        self._chk(self.lib.f110qp_rollout_world(
+            self._h, C.byref(cfg), C.byref(sc), C.byref(rp), C.byref(w), B, _p(tab), _p(wp) if W else None, _p(xr),
+            _p(hv), _p(ci) if ci.size else None, _p(out["x_traj"]), _p(out["u_lin_traj"]), _p(out["u_applied"]),
+            _p(out["status"]), _p(out["iters"]), _p(out.get("cost")), _p(out.get("u_plan")), _p(out.get("x_plan")),
+            _p(out.get("hs_traj")), _p(out["kind"]), _p(out["plan_status"]), _p(out["best_traj"]),
+            _p(out["best_global"]), _p(out["pose_traj"]), _p(out.get("ranges_traj"))), "f110qp_rollout_world")
+        return out
+
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
         N = self.horizon
@@ -1033,6 +1159,22 @@ def plan_listed_dev(rp: ReplanConfig, sc: ScanConfig, list_, count, pose, ranges
     _check(load().f110qp_plan_listed_dev(C.byref(rp), C.byref(sc), B, _tp(list_), _tp(count), _tp(pose), _tp(ranges),
                                          _tp(table), _tp(waypoints), _tp(x_ref), _tp(plan_status), _tp(best_traj),
                                          _tp(best_global), C.c_void_p(stream.cuda_stream)), "f110qp_plan_listed_dev")
+
+
+def cast_scans_dev(sc: ScanConfig, wc: WorldConfig, x, circles, ranges, list_=None, count=None, stream=None):
+    """The simulated LiDAR (f110qp_cast_scans_dev): x [B,3] f64, circles [world_rows,C,3] f64 (None for
+    C = 0) -> ranges [B,num_ranges] f32, for all B cars or, with list_ [B] i32 and count [1] i32 on the
+    device, for the listed ones."""
+    import torch
+
+    B, Cn, WR = int(x.shape[0]), int(wc.num_circles), int(wc.world_rows)
+    _devs((x, "f64", 3 * B, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
+          (ranges, "f32", B * int(sc.num_ranges), "ranges"), (list_, "i32", B, "list", True),
+          (count, "i32", 1, "count", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_cast_scans_dev(C.byref(sc), C.byref(wc), B, _tp(list_), _tp(count), _tp(x), _tp(circles),
+                                        _tp(ranges), C.c_void_p(stream.cuda_stream)), "f110qp_cast_scans_dev")
 
 
 def replan_start_dev(rp: ReplanConfig, sc, x, have_path, x_ref, gap, pose, kind, list_, count, hs=None, stream=None):

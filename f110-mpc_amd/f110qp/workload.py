@@ -296,3 +296,21 @@ def drive_stream(ticks: int, seed: int = 0, step: float = 0.09, beams: int = SCA
     near = np.argsort(d, axis=1)[:, :200]
     ranges = _ray_circles(lx, ly, ang, cxs[near], cys[near], rads[near], max_range).astype(np.float32)
     return dict(pose=pose, ranges=ranges, angle_min=amin, angle_inc=ainc, angle_max=amax, waypoints=wp)
+
+
+def make_world(seed: int = 0, obstacles: int = 40) -> np.ndarray:
+    """The static world drive_stream(seed=seed, obstacles=obstacles) builds internally, as circles [C, 3]
+    float64 = (cx, cy, r): the two track walls (radius 0.12 at +-1.6 m of every waypoint) followed by the
+    `obstacles` circles beside the path, drawn from the same generator in the same order. The input of
+    the device ray casting (f110qp_cast_scans_dev, f110qp_rollout_world[_dev])."""
+    rng = np.random.default_rng(seed)
+    wp = track_waypoints()
+    W = wp.shape[0]
+    rng.uniform(0, np.hypot(*(np.roll(wp, -1, 0) - wp).T).sum())  # drive_stream draws its start first
+    hw = np.arctan2(np.roll(wp[:, 1], -1) - wp[:, 1], np.roll(wp[:, 0], -1) - wp[:, 0])
+    nrm = np.stack([-np.sin(hw), np.cos(hw)], 1)
+    wall = np.concatenate([wp + 1.6 * nrm, wp - 1.6 * nrm])
+    oi = rng.integers(0, W, obstacles)
+    obst = wp[oi] + nrm[oi] * rng.choice([-0.9, 0.9], obstacles)[:, None]
+    rads = np.concatenate([np.full(len(wall), 0.12), rng.uniform(0.15, 0.3, obstacles)])
+    return np.ascontiguousarray(np.concatenate([np.concatenate([wall, obst]), rads[:, None]], 1))

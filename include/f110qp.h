@@ -753,6 +753,87 @@ int f110qp_rollout_replan(f110qp_ctx* ctx, const f110qp_rollout_config* rc, cons
                           float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
                           int* best_global_traj, double* pose_traj);
 
+/* ---- closed loop with a simulated LiDAR: scans ray-cast at every tick's pose ---------------------
+ * f110qp_rollout_replan[_dev] reads scans made before the call: one per car held while the car
+ * drives on (scan_rows = 1), or T rows taken at poses the loop has not produced yet. The reference
+ * runs inside the f1tenth simulator, which publishes a fresh scan at every pose: ScanCallback fills
+ * the occupancy grid from each of them (src/project.cpp:56), MPC keeps the first for its gap rows
+ * (src/project.cpp:45-49). The calls below put that simulator's part on the device for a static world
+ * of circles (cx, cy, r): walls and obstacles. Additive: F110QP_API_VERSION stays 6. */
+typedef struct {
+  int    num_circles;   /* C >= 0 circles per world                                                  */
+  int    world_rows;    /* 1: one world for all cars; B: circles [B][C][3], car b reads row b        */
+  double lidar_offset;  /* 0.275: LiDAR ahead of the pose along the heading (occupancy_grid.cpp:63-64) */
+  double max_range;     /* 10.0; positive, finite                                                    */
+} f110qp_world_config;
+
+/* Zeroes *wc, then world_rows 1, lidar_offset 0.275, max_range 10.0 (the circles are the caller's). */
+void f110qp_default_world_config(f110qp_world_config* wc);
+
+/* Circles per LDS tile of the ray-cast kernel. No limit on num_circles: a larger world is processed
+ * tile after tile. */
+#define F110QP_CAST_CIRCLE_TILE 256
+
+/* The scans of B cars in a world of circles (device pointers, asynchronous on `stream`, one launch):
+ *   x [B][3] double, circles [world_rows][C][3] double = (cx, cy, r) -> ranges [B][num_ranges] float32
+ * (sc: num_ranges, angle_min, angle_increment; sc->scan_rows is not read).
+ * list / count both NULL: all B cars. Both given: the cars list[0 .. min(*count, B)), in any order,
+ * count read on the device as in f110qp_plan_listed_dev; the rows of unlisted cars are not touched,
+ * count 0 changes nothing. One of the two alone is F110QP_ERR_INVALID.
+ * Arithmetic, all fp64, every product and sum rounded (no fused multiply-add):
+ *   LiDAR origin o = (x + lidar_offset cos(ori), y + lidar_offset sin(ori));
+ *   beam i along ori + ((double)angle_min + (double)angle_increment i), d = (cos, sin) of it;
+ *   per circle p = c - o, t = p.d, d2 = p.p - t t; the beam hits when d2 <= r^2 && t > 0, at
+ *   th = t - sqrt(max(r^2 - d2, 0)), which counts only when th > 0;
+ *   range = (float)min(min over the circles of th, max_range).
+ * Consequences: a LiDAR inside a circle sees through it (th <= 0 on every beam); only r^2 enters, so
+ * a negative radius acts as its absolute value; a circle with a NaN or infinite field hits nothing
+ * (every compare is false) and does not disturb its neighbours; C = 0 gives max_range everywhere.
+ * The result is a minimum of per-pair values that do not depend on the other circles: it is
+ * bit-identical for every order of the circle list. */
+int f110qp_cast_scans_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc, int batch,
+                          const int* list, const int* count, const double* x, const double* circles,
+                          float* ranges, void* stream);
+
+/* f110qp_rollout_replan_dev with tick t's scan cast at tick t's pose. The per-car specification is
+ * that call's, word for word; only the source of the planner's scan row changes. Arguments as
+ * f110qp_rollout_replan_dev, except:
+ *   wc, circles  replace ranges (f110qp_cast_scans_dev's world); sc->scan_rows is not read
+ *   ranges_traj  [T][B][num_ranges] float32, may be NULL: row t holds every car's scan at x_traj row t.
+ * Planner scan: tick t's planning stage reads the scan cast at x_traj row t. With ranges_traj NULL
+ * the cast runs on tick t's plan list only (the list and counter the listed plan reads next, in
+ * stream order) into one buffer of the context of B rows; with ranges_traj it runs for all B cars
+ * into row t. Trajectories, kinds and statuses are bit-identical either way.
+ * Gap rows are the reference's: MPC sees the first scan only. When rows are computed (gap_mode
+ * ACTIVE, or hs_traj given) one all-cars cast at x_traj row 0 and one f110qp_gap_search_dev on it run
+ * in front of the loop; the records are held and the rows follow the car inside
+ * f110qp_advance_replan_dev exactly as in f110qp_rollout_replan_dev at scan_rows = 1. A fresh gap
+ * search per tick is not part of this call.
+ * Stream order: the memset of the plan counters, then (rows computed) the cast at row 0 and the gap
+ * search, f110qp_replan_start_dev; per tick the cast, the listed plan, the launches of
+ * f110qp_solve_batch_dev_dbl, f110qp_advance_replan_dev. No host synchronisation, read-back or
+ * allocation inside the loop; every argument is checked before the first launch (the checks of
+ * f110qp_rollout_replan_dev and of f110qp_cast_scans_dev's world). */
+int f110qp_rollout_world_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc,
+                             const f110qp_scan_config* sc, const f110qp_replan_config* rp,
+                             const f110qp_world_config* wc, int batch, const double* table,
+                             const double* waypoints, double* x_ref, int* have_path, const double* circles,
+                             double* x_traj, double* u_lin_traj, float* u_applied, int* status_traj,
+                             int* iters_traj, double* cost_traj, float* u_plan, float* x_plan,
+                             float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
+                             int* best_global_traj, double* pose_traj, float* ranges_traj, void* stream);
+
+/* Same on host pointers (synchronous): staged through device buffers of the context, one stream
+ * synchronisation at the end, as f110qp_rollout_replan. */
+int f110qp_rollout_world(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                         const f110qp_replan_config* rp, const f110qp_world_config* wc, int batch,
+                         const double* table, const double* waypoints, double* x_ref, int* have_path,
+                         const double* circles, double* x_traj, double* u_lin_traj, float* u_applied,
+                         int* status_traj, int* iters_traj, double* cost_traj, float* u_plan,
+                         float* x_plan, float* hs_traj, int* kind_traj, int* plan_status_traj,
+                         int* best_traj_traj, int* best_global_traj, double* pose_traj,
+                         float* ranges_traj);
+
 #ifdef __cplusplus
 }
 #endif
