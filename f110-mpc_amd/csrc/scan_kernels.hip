@@ -20,7 +20,11 @@
 //      arc, so the beams are floor(f_lo) - 1 .. floor(f_lo) + ceil(2w / inc) + 2 with f_lo the arc's
 //      low edge in beam units: at least one beam more than the arc at either end, repeated every
 //      2 pi / inc beams for a scan that wraps. The LiDAR inside (or on) a circle, an arc that with its
-//      margin closes the turn, or an increment too small for the margin: every beam.
+//      margin closes the turn, or an increment too small for the margin: every beam. The low edge
+//      atan2(p) - ori - angle_min - w carries a few ulp(|ori| + |angle_min| + pi) of rounding against
+//      that one-beam margin: the interval is safe while this ulp is far below one increment. For the
+//      1,080-beam scan (5.8e-3 rad a beam) it reaches a thousandth of a beam at |ori| ~ 2.6e10 rad
+//      (1.2e-10 rad at 1e6 rad), where the beam directions ori + angle are quantised just as coarsely.
 //   B  eight lanes per kept circle run the exact test above on its beams only and fold th into the
 //      beam's minimum with an unsigned 64-bit LDS atomic min (positive doubles order as their bits).
 // A beam outside an interval cannot hit, one inside is decided by the exact test, so the interval

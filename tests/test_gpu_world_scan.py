@@ -13,7 +13,8 @@ TILE = wc_.TILE
 SENTINEL = np.float32(-7.0)
 
 
-def cast(capi, cuda, x, circles, geom, beams, listed=None, count=None, max_range=wc_.MAX_RANGE):
+def cast(capi, cuda, x, circles, geom, beams, listed=None, count=None, max_range=wc_.MAX_RANGE,
+         lidar_offset=wc_.LIDAR_OFFSET):
     """f110qp_cast_scans_dev on host arrays into rows pre-filled with the sentinel -> ranges [B, R]."""
     import torch
 
@@ -21,7 +22,7 @@ def cast(capi, cuda, x, circles, geom, beams, listed=None, count=None, max_range
     B = x.shape[0]
     C = circles.shape[-2]
     w = capi.default_world_config(num_circles=C, world_rows=1 if circles.ndim == 2 else circles.shape[0],
-                                  max_range=max_range)
+                                  max_range=max_range, lidar_offset=lidar_offset)
     out = torch.full((B, beams), float(SENTINEL), dtype=torch.float32, device=cuda)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(cuda)  # noqa: E731
     capi.cast_scans_dev(scan_config(capi, beams, geom), w, dev(x), dev(circles) if C else None, out,

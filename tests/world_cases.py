@@ -8,6 +8,17 @@ A beam is grazing if, in the oracle, some circle has t > 0 and |d2 - r^2| < 1e-9
 1.6e-9 m, and the float rounding can then differ by one ulp and no more. A case may skip at most 0.1 % of
 its beams; the check asserts that cap.
 
+check_scan_strict judges the grazing beams too (no cap, no skip). Per beam the circles are firm hits, firm
+misses or flippable (one of the three conditions above, per circle); firm is the least th of the firm hits,
+clipped to max_range. A grazing beam's range is at most firm + bound, and it is firm (no flippable circle
+counted) or the th of a flippable circle that did count: within [t - sqrt(2 GRAZE), t] when that circle is
+flippable by |d2 - r^2| < GRAZE (the root term is sqrt(r^2 - d2) < sqrt(GRAZE) in the oracle, and at most
+sqrt(2 GRAZE) with the device's own d2), or th itself when the circle is flippable by |th| or |t| < GRAZE
+(the value is firm there, only its sign test can flip).
+
+Cases whose kept circles lie past the 20 m the absolute term was derived for (abs_tol): the same formula,
+2 |p|^2 eps64 / (2 sqrt(GRAZE)), scaled from 20 m to the case's own largest |p|, headroom and all.
+
     python tests/world_cases.py      # the grazing count of every hand-made case and of the track world
 """
 import os
@@ -28,6 +39,12 @@ TILE = 256            # F110QP_CAST_CIRCLE_TILE
 GRAZE = 1e-9          # the three grazing thresholds
 ABS_TOL = 4e-9        # metres, next to one float32 ulp
 SKIP_CAP = 1e-3       # grazing beams a case may skip
+P_ENVELOPE = 20.0     # metres: the largest |p| of a kept circle ABS_TOL was derived for
+
+
+def abs_tol(pmax):
+    """The absolute term for kept circles up to pmax metres from the LiDAR (module docstring)."""
+    return ABS_TOL * max(1.0, (pmax / P_ENVELOPE) ** 2)
 
 
 def geometry(beams, kind="2pi"):
@@ -58,17 +75,19 @@ def _terms(x, circles, geom, beams, lidar_offset=LIDAR_OFFSET):
     return ox, oy, ang, ci, t, d2, r2, th
 
 
-def _per_car(fn, x, circles, *a):
+def _per_car(fn, x, circles, *a, max_range=MAX_RANGE, lidar_offset=LIDAR_OFFSET):
     """fn car by car (its [R, C] intermediates of a 1,040-circle world are 9 MB a car), stacked. A finite
-    circle whose near face is more than max_range + 1 m from the pose is left out: its th exceeds max_range
-    by 0.7 m at least (the LiDAR is 0.275 m from the pose), so it changes neither the minimum nor a hit
-    below max_range; dropping it from the classifier can only keep more beams in the comparison."""
+    circle whose near face is more than max_range + |lidar_offset| + 0.725 m from the pose (11 m with the
+    defaults) is left out: its th exceeds max_range by 0.7 m at least (the LiDAR is |lidar_offset| from the
+    pose), so it changes neither the minimum nor a hit below max_range; dropping it from the classifier can
+    only keep more beams in the comparison."""
     x = np.asarray(x, np.float64)
+    reach = max_range + abs(lidar_offset) + 0.725
     out = []
     for b in range(len(x)):
         ci = circles if circles.ndim == 2 else circles[b]
         with np.errstate(invalid="ignore", over="ignore"):
-            far = np.hypot(ci[:, 0] - x[b, 0], ci[:, 1] - x[b, 1]) - np.abs(ci[:, 2]) > MAX_RANGE + 1.0
+            far = np.hypot(ci[:, 0] - x[b, 0], ci[:, 1] - x[b, 1]) - np.abs(ci[:, 2]) > reach
         out.append(fn(x[b:b + 1], ci[~(far & np.isfinite(ci).all(axis=1))][None], *a))
     return np.concatenate(out)
 
@@ -76,7 +95,8 @@ def _per_car(fn, x, circles, *a):
 def oracle_scan(x, circles, geom, beams, max_range=MAX_RANGE, lidar_offset=LIDAR_OFFSET):
     """ranges [B, R] float32 of poses x [B, 3] in circles [C, 3] or [B, C, 3]: workload._ray_circles."""
     if len(x) > 1:
-        return _per_car(oracle_scan, x, circles, geom, beams, max_range, lidar_offset)
+        return _per_car(oracle_scan, x, circles, geom, beams, max_range, lidar_offset, max_range=max_range,
+                        lidar_offset=lidar_offset)
     ox, oy, ang, ci, *_ = _terms(x, circles, geom, beams, lidar_offset)
     if ci.shape[1] == 0:
         return np.full((len(ox), beams), np.float32(max_range))
@@ -84,10 +104,11 @@ def oracle_scan(x, circles, geom, beams, max_range=MAX_RANGE, lidar_offset=LIDAR
         return workload._ray_circles(ox, oy, ang, ci[:, :, 0], ci[:, :, 1], ci[:, :, 2], max_range).astype(np.float32)
 
 
-def grazing(x, circles, geom, beams, lidar_offset=LIDAR_OFFSET):
+def grazing(x, circles, geom, beams, lidar_offset=LIDAR_OFFSET, max_range=MAX_RANGE):
     """[B, R] bool: the beams on which a hit can flip under a few ulp of sincos (module docstring)."""
     if len(x) > 1:
-        return _per_car(grazing, x, circles, geom, beams, lidar_offset)
+        return _per_car(grazing, x, circles, geom, beams, lidar_offset, max_range, max_range=max_range,
+                        lidar_offset=lidar_offset)
     *_, ci, t, d2, r2, th = _terms(x, circles, geom, beams, lidar_offset)
     if ci.shape[1] == 0:
         return np.zeros(t.shape[:2], bool)
@@ -96,12 +117,12 @@ def grazing(x, circles, geom, beams, lidar_offset=LIDAR_OFFSET):
     return g.any(axis=2)
 
 
-def check_scan(got, x, circles, geom, beams, what="", max_range=MAX_RANGE):
+def check_scan(got, x, circles, geom, beams, what="", max_range=MAX_RANGE, lidar_offset=LIDAR_OFFSET):
     """got [B, R] float32 against the oracle on every non-grazing beam, and the cap on the skipped ones.
     Returns (skipped, worst error in units of the bound)."""
-    want = oracle_scan(x, circles, geom, beams, max_range)
+    want = oracle_scan(x, circles, geom, beams, max_range, lidar_offset)
     assert got.dtype == np.float32 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
-    skip = grazing(x, circles, geom, beams)
+    skip = grazing(x, circles, geom, beams, lidar_offset, max_range)
     assert skip.sum() <= SKIP_CAP * skip.size, f"{what}: {int(skip.sum())} of {skip.size} beams are grazing"
     w = want.astype(np.float64)
     bound = np.spacing(want).astype(np.float64) + ABS_TOL
@@ -109,6 +130,55 @@ def check_scan(got, x, circles, geom, beams, what="", max_range=MAX_RANGE):
     bad = (err > bound) & ~skip
     assert not bad.any(), (what, np.argwhere(bad)[:5].tolist(), got[bad][:5], want[bad][:5])
     return int(skip.sum()), float((err / bound)[~skip].max())
+
+
+def _ulp32(v):
+    return np.spacing(np.abs(v).astype(np.float32)).astype(np.float64)
+
+
+def check_scan_strict(got, x, circles, geom, beams, what="", max_range=MAX_RANGE, lidar_offset=LIDAR_OFFSET,
+                      tol=ABS_TOL):
+    """got [B, R] float32 against the oracle on every beam: the non-grazing ones as check_scan, the grazing
+    ones by the firm / flippable rule of the module docstring. No beam is skipped and there is no cap.
+    Returns (grazing beams, worst error of a non-grazing beam in units of the bound)."""
+    x = np.asarray(x, np.float64)
+    assert got.dtype == np.float32 and got.shape == (len(x), beams), (what, got.dtype, got.shape)
+    assert np.isfinite(got).all(), what
+    n_graze, worst, root = 0, 0.0, np.sqrt(2.0 * GRAZE)
+    for b in range(len(x)):
+        ci = circles if circles.ndim == 2 else circles[b]
+        want = oracle_scan(x[b:b + 1], ci, geom, beams, max_range, lidar_offset)[0]
+        g = got[b].astype(np.float64)
+        bound = _ulp32(want) + tol
+        err = np.abs(g - want.astype(np.float64))
+        if ci.shape[0] == 0:
+            assert (err <= bound).all(), (what, b)
+            continue
+        *_, t, d2, r2, th = (v[0] for v in _terms(x[b:b + 1], ci, geom, beams, lidar_offset))
+        with np.errstate(invalid="ignore"):
+            by_d2 = (t > 0) & (np.abs(d2 - r2) < GRAZE)
+            flip = by_d2 | (np.abs(th) < GRAZE) | (np.abs(t) < GRAZE)
+            hit = (d2 <= r2) & (t > 0) & (th > 0)
+        firm = np.minimum(np.where(hit & ~flip, th, np.inf).min(axis=1), max_range)
+        graze = flip.any(axis=1)
+        bad = (err > bound) & ~graze
+        assert not bad.any(), (what, b, np.flatnonzero(bad)[:5].tolist(), got[b][bad][:5], want[bad][:5])
+        if (~graze).any():
+            worst = max(worst, float((err / bound)[~graze].max()))
+        n_graze += int(graze.sum())
+        for i in np.flatnonzero(graze):
+            fb = _ulp32(np.float64(firm[i])) + tol
+            assert g[i] <= firm[i] + fb, (what, b, int(i), "past the firm hit", got[b, i], firm[i])
+            if abs(g[i] - firm[i]) <= fb:
+                continue
+            c = np.flatnonzero(flip[i])
+            with np.errstate(invalid="ignore"):
+                in_root = by_d2[i, c] & (t[i, c] - root - _ulp32(t[i, c]) - tol <= g[i]) & \
+                    (g[i] <= t[i, c] + _ulp32(t[i, c]) + tol)
+                at_th = np.abs(g[i] - th[i, c]) <= _ulp32(th[i, c]) + tol
+            assert (in_root | at_th).any(), (what, b, int(i), "neither firm nor a flippable circle's",
+                                             got[b, i], firm[i], t[i, c][:5], th[i, c][:5])
+    return n_graze, worst
 
 
 # ---- worlds ------------------------------------------------------------------------------------------
@@ -146,9 +216,9 @@ def poses_near_origin(B, seed, yaws=()):
 YAWS = (np.pi, -np.pi, np.pi / 2, -np.pi / 2)
 
 
-def _ahead(x, dist, r, bearing=0.0):
+def _ahead(x, dist, r, bearing=0.0, lidar_offset=LIDAR_OFFSET):
     """A circle whose centre is `dist` from the LiDAR of pose x at `bearing` from the heading."""
-    ox, oy = x[0] + LIDAR_OFFSET * np.cos(x[2]), x[1] + LIDAR_OFFSET * np.sin(x[2])
+    ox, oy = x[0] + lidar_offset * np.cos(x[2]), x[1] + lidar_offset * np.sin(x[2])
     return [ox + dist * np.cos(x[2] + bearing), oy + dist * np.sin(x[2] + bearing), r]
 
 
@@ -181,6 +251,200 @@ def hand_cases(geom, beams):
     alt = [_ahead(x[0], 3.0 + 0.05 * (k % 2), 0.02, -0.5 + k * 0.0117) for k in range(86)]
     cases["alternating"] = (x, np.array(alt), "two rows whose nearer hit alternates from beam to beam")
     return cases
+
+
+# ---- the edge suite (test_gpu_world_scan_edges.py on the device, test_world_cases.py on the oracle) ----
+
+class Case:
+    """One scan of the edge suite: poses x [B, 3], circles [C, 3] or [B, C, 3], the scan and world settings,
+    the |p| envelope `pmax` of the kept circles with the absolute term `tol` derived for it, and what the
+    oracle must show: `target` (index of the circle the case is about), `hits` (the number of beams of car
+    0 that hit it, or a tuple of allowed numbers where rounding decides) and `seen` (the least number of
+    beams below max_range)."""
+
+    def __init__(self, name, x, ci, geom, R, max_range=MAX_RANGE, lidar_offset=LIDAR_OFFSET, pmax=P_ENVELOPE,
+                 target=None, hits=None, seen=1):
+        self.name, self.x, self.ci, self.geom, self.R = name, np.atleast_2d(np.asarray(x, np.float64)), ci, geom, R
+        self.max_range, self.lidar_offset, self.pmax, self.tol = max_range, lidar_offset, pmax, abs_tol(pmax)
+        self.target, self.hits, self.seen = target, hits, seen
+
+    @property
+    def kw(self):
+        return dict(max_range=self.max_range, lidar_offset=self.lidar_offset)
+
+
+def _geom(amin, ainc, R):
+    amin, ainc = np.float32(amin), np.float32(ainc)
+    return amin, ainc, np.float32(amin + ainc * (R - 1))
+
+
+# name -> [(R, angle_min, angle_increment)]; what each reaches in the kernel's interval code
+EDGE_GEOMETRIES = {
+    # per = 5, 4 inc = 1.6 pi: a circle of half-width w >= pi / 5 takes every beam, a narrower one an
+    # interval of at least 4 of the 5 beams of a turn
+    "coarse5": [(5, -np.pi, 2 * np.pi / 5)],
+    "coarse7": [(7, -np.pi, 0.8)],                         # per = 7.85: copies at a non-integer period
+    "turn_edge": [(9, -np.pi, 0.78), (9, -np.pi, 0.79)],   # the wall of _extras: arc at 0.78, every beam at 0.79
+    "turns3": [(200, -np.pi, 0.1)],                        # 3.2 turns, per = 62.83
+    "turns4_tiles": [(1300, -np.pi, 0.02)],                # 4.1 turns, a copy across beam 1,152
+    "amin_pos": [(300, 2.5, 0.01)],                        # across the +-pi seam
+    "amin_low": [(300, -7.0, 0.01)],                       # rel reduced by more than a turn
+    # float32(5e-10) and float32(1e-9) = 9.9999997e-10 are below kCastMinInc (every beam), float32(2e-9)
+    # is above (an interval of about 1e8 beams, clipped to the 64 there are)
+    "inc_min": [(64, -0.5, 5e-10), (64, -0.5, 1e-9), (64, -0.5, 2e-9)],
+    "one_beam": [(1, 0.3, 0.01)],
+}
+EDGE_OFFSETS = (0.0, -0.3, 0.275)
+THRESHOLD_GEOMETRIES = (("2pi", 256), ("270", 257))
+X0 = np.array([0.3, -0.2, 0.4])
+
+
+def _extras(x0, geom, R, off, fine):
+    """Threshold circles of a geometry case, placed from pose x0: a wall (r = 5 m, the LiDAR 0.1 mm off its
+    face: w = pi / 2 - 6.3e-3), a 1 mm circle along beam 0, a circle along the last beam, a negative radius.
+    fine (inc_min: all beams within 1e-7 rad): instead of the wall a circle tangent to the middle beam, so
+    that the beams differ."""
+    a0, inc = float(geom[0]), float(geom[1])
+    first = _ahead(x0, 3.0, 0.3, a0 + inc * (R // 2) - np.arcsin(0.1), off) if fine else \
+        _ahead(x0, 5.0 * (1 + 2e-5), 5.0, a0 + inc * (R // 2) + 0.3, off)
+    return [first, _ahead(x0, 3.0, 1e-3, a0, off), _ahead(x0, 2.5, 0.2, a0 + inc * (R - 1), off),
+            _ahead(x0, 4.0, -0.3, a0 + inc * (R // 3), off)]
+
+
+def geometry_cases(name):
+    """The cases of one row of EDGE_GEOMETRIES: worlds of 40 and TILE + 1 random circles plus _extras, three
+    LiDAR offsets, 3 poses (two heading +-pi)."""
+    out = []
+    for n, (R, amin, ainc) in enumerate(EDGE_GEOMETRIES[name]):
+        g = _geom(amin, ainc, R)
+        x = poses_near_origin(3, 40 + R + n, YAWS[:2])
+        for C in (40, TILE + 1):
+            for off in EDGE_OFFSETS:
+                ci = np.concatenate([random_world(C, 11 * R + C + n), _extras(x[0], g, R, off, name == "inc_min")])
+                out.append(Case(f"{name} inc {float(g[1]):.3g} C {C} off {off}", x, ci, g, R, lidar_offset=off))
+    return out
+
+
+def _ordinary(x0, clear=(), off=LIDAR_OFFSET, seed=17, inc=0.0):
+    """30 random circles, none of them within three beams of the bearings (from the heading) in `clear`."""
+    w = random_world(60, seed)
+    ox, oy = x0[0] + off * np.cos(x0[2]), x0[1] + off * np.sin(x0[2])
+    px, py = w[:, 0] - ox, w[:, 1] - oy
+    half = np.arcsin(np.minimum(w[:, 2] / np.hypot(px, py), 1.0)) + 3 * inc
+    keep = np.ones(len(w), bool)
+    for c in clear:
+        d = np.arctan2(py, px) - x0[2] - c
+        keep &= np.abs(d - 2 * np.pi * np.round(d / (2 * np.pi))) > half
+    assert keep.sum() >= 30
+    return w[keep][:30]
+
+
+def threshold_cases(family):
+    """The circles at the kernel's thresholds, by family, on the 2 pi scan at 256 beams and the 270 degree
+    scan at 257, each among 30 ordinary circles. The target is the last circle but where said."""
+    out = []
+    for kind, R in THRESHOLD_GEOMETRIES:
+        g = geometry(R, kind)
+        a0, inc = float(g[0]), float(g[1])
+        beam = lambda k: a0 + inc * k  # noqa: E731  (the bearing of beam k, the oracle's expression)
+        tag = f"{family} {kind}"
+        if family == "sub_beam":
+            # at 3 m, along beam k (one beam meets it head-on) and half a beam off (0.037 m and 0.028 m to
+            # the nearest beam's line: no radius here reaches it). r = 0 and 1e-9: r^2 is below the
+            # rounding of d2 (2e-15 m^2), the head-on hit is decided by that rounding, 0 or 1
+            k = R // 2 + 7
+            for r in (0.0, 1e-9, 1e-6, 1e-3, 1e-2):
+                for where, b, hits in (("on", beam(k), 1 if r >= 1e-6 else (0, 1)), ("off", beam(k) + inc / 2, 0)):
+                    ci = np.concatenate([_ordinary(X0, (b,), inc=inc), [_ahead(X0, 3.0, r, b)]])
+                    out.append(Case(f"{tag} r {r:g} {where} the beam", X0, ci, g, R, target=30, hits=hits))
+        elif family == "negative":
+            # 0.3 is some eight beams wide at 3 m; rn is three and a half: an interval sized from r in place
+            # of |r| comes out negative (which reads as every beam) for the wide one and empty for rn
+            b, rn = beam(R // 2 - 9), 3.0 * np.sin(1.75 * inc)
+            for near, far in ((-0.3, 0.3), (0.3, -0.3), (-rn, rn), (rn, -rn)):
+                ci = np.concatenate([_ordinary(X0), [_ahead(X0, 3.0, near, b), _ahead(X0, 4.0, far, b + 0.05)]])
+                out.append(Case(f"{tag} r {near:+g} in front of {far:+g}", X0, ci, g, R, target=30, seen=10))
+        elif family == "on_circle":
+            # the LiDAR at ra (1 + e) from the centre. e > 0: the centre is placed so that the circle's
+            # upper tangent is beam k, which then grazes (d2 = r^2 to rounding); e = 0: th = 0 to rounding
+            # on every beam of the covered half. A circle 4 m off in the covered half, one in the free half.
+            k = R // 2 + 20
+            for ra in (0.5, 50.0):
+                for e in (-1e-6, 0.0, 5e-7, 1e-6, 2e-6, 1e-3):
+                    dist = ra * (1 + e)
+                    mid = beam(k) - np.arcsin(min(ra / dist, 1.0))
+                    ci = np.concatenate([_ordinary(X0), [_ahead(X0, 4.0, 0.3, mid + 0.02), _ahead(X0, 4.0, 0.3, mid + np.pi),
+                                                         _ahead(X0, dist, ra, mid)]])
+                    out.append(Case(f"{tag} ra {ra:g} e {e:g}", X0, ci, g, R, pmax=max(P_ENVELOPE, dist + 0.1),
+                                    target=32))
+        elif family == "centre":
+            for r in (0.4, 0.0):
+                ci = np.concatenate([_ordinary(X0, off=0.0), [[X0[0], X0[1], r]]])
+                out.append(Case(f"{tag} dist 0 r {r:g}", X0, ci, g, R, lidar_offset=0.0, target=30, hits=0))
+        elif family == "seam":
+            xs = np.array([0.3, 0.0, 0.0])  # yaw 0, no offset: py = cy - 0.0 keeps the sign of the zero
+            for cy in (0.0, -0.0):
+                ci = np.concatenate([_ordinary(xs, off=0.0), [[0.3 - 3.0, cy, 2.5]]])
+                assert ci[30, 1] == 0 and np.signbit(ci[30, 1]) == np.signbit(cy)
+                out.append(Case(f"{tag} py {cy:+g}", xs, ci, g, R, lidar_offset=0.0, target=30, seen=10))
+            for what, b in (("beam 0", beam(0)), ("the last beam", beam(R - 1))):
+                ci = np.concatenate([_ordinary(X0, (b,), inc=inc), [_ahead(X0, 3.0, 0.4, b)]])
+                out.append(Case(f"{tag} centre along {what}", X0, ci, g, R, target=30, seen=5))
+        elif family == "near_face":
+            # r = 0.5 with its near face at m (1 + e), a third of a beam off beam k. Its tangent beams are at
+            # sqrt(m^2 + 2 m r) > m: this circle has no grazing beam below max_range, and a third of a beam
+            # off no tangent falls on a beam at all. So that the family has grazing beams, a twin is moved to
+            # have its upper tangent exactly on beam k + 40; a small circle at 0.6 m is in range of every m.
+            k = R // 2 - 30
+            for m in (0.5, 10.0, 30.0):
+                for e in (-2e-6, -5e-7, 0.0, 5e-7, 2e-6):
+                    D = m * (1 + e) + 0.5
+                    ci = np.concatenate([_ordinary(X0), [_ahead(X0, 0.6 * m, 0.1 * m, beam(R // 4)),
+                                                         _ahead(X0, D, 0.5, beam(k + 40) - np.arcsin(0.5 / D)),
+                                                         _ahead(X0, D, 0.5, beam(k) + inc / 3)]])
+                    # pmax: m = 30 keeps circles up to 30.5 m; 2 * 31^2 * eps64 / (2 sqrt(1e-9)) = 6.7e-9 m
+                    # by the formula, abs_tol(31) = 9.6e-9 m with ABS_TOL's own headroom
+                    out.append(Case(f"{tag} max_range {m:g} e {e:g}", X0, ci, g, R, max_range=m,
+                                    pmax=max(P_ENVELOPE, D + 0.6), target=32))
+        else:
+            raise KeyError(family)
+    return out
+
+
+THRESHOLD_FAMILIES = ("sub_beam", "negative", "on_circle", "centre", "seam", "near_face")
+# the headings inside the kernel's bound (ulp(|ori| + |angle_min| + pi) far below an increment): at 1e6 rad
+# the ulp is 1.2e-10 rad against 0.0245 rad a beam
+HEADINGS = [s * v for v in (1e3, 1e6) + tuple(2 * np.pi * k + 1e-12 for k in (0, 1, 100)) for s in (1.0, -1.0)]
+
+
+def heading_case():
+    R = 256
+    x = np.array([[0.1, -0.2, yaw] for yaw in HEADINGS])
+    return Case("headings", x, random_world(40, 23), geometry(R), R, seen=10 * len(HEADINGS))
+
+
+def per_car_case(B=800):
+    """One world of three circles per car, more cars than the kernel's 768 workgroups."""
+    R = 16
+    return Case(f"per-car worlds B {B}", poses_near_origin(B, 77), random_world(3, 78, B, spread=3.0), geometry(R), R,
+                seen=B)
+
+
+def case_facts(c):
+    """From the oracle alone: (ranges [B, R], beams of car 0 that hit the target or None, the largest |p|
+    of a circle the range cull keeps)."""
+    want = oracle_scan(c.x, c.ci, c.geom, c.R, c.max_range, c.lidar_offset)
+    hits = None
+    if c.target is not None:
+        *_, t, d2, r2, th = _terms(c.x[:1], c.ci, c.geom, c.R, c.lidar_offset)
+        with np.errstate(invalid="ignore"):
+            hits = int(((d2 <= r2) & (t > 0) & (th > 0))[0, :, c.target].sum())
+    ci = np.broadcast_to(c.ci, (len(c.x),) + c.ci.shape[-2:])
+    ox = c.x[:, 0] + c.lidar_offset * np.cos(c.x[:, 2])
+    oy = c.x[:, 1] + c.lidar_offset * np.sin(c.x[:, 2])
+    p = np.hypot(ci[:, :, 0] - ox[:, None], ci[:, :, 1] - oy[:, None])
+    kept = p - np.abs(ci[:, :, 2]) <= c.max_range * 1.000001
+    return want, hits, float(p[kept].max()) if kept.any() else 0.0
 
 
 if __name__ == "__main__":
