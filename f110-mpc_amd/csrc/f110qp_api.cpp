@@ -1557,11 +1557,20 @@ struct ReplanTraj {
 };
 
 // f110qp_rollout_world[_dev]: tick t's scans are cast at tick t's pose instead of read from `ranges`.
+// race (f110qp_rollout_race[_dev]): every cast also sees the race-mates at the poses it casts from.
 struct WorldLoop {
   f110qp::CastParams P;
   const double* circles;  // [world_rows][C][3]
   float* ranges_traj;     // [T][B][num_ranges] or null: one row set in the context, listed cars only
+  bool race;
+  f110qp::RaceParams Q;
 };
+
+static hipError_t world_cast(const WorldLoop& wl, int batch, const int* list, const int* count, const double* x,
+                             float* ranges, hipStream_t s) {
+  return wl.race ? f110qp::launch_cast_scans_race(wl.P, wl.Q, batch, list, count, x, wl.circles, ranges, s)
+                 : f110qp::launch_cast_scans(wl.P, batch, list, count, x, wl.circles, ranges, s);
+}
 
 // The T ticks of a checked re-planning rollout on device pointers. Every workspace is sized in front
 // of the loop; the loop only launches: the listed plan, the launches of one _dbl solve call, the
@@ -1642,7 +1651,7 @@ static int replan_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, const f1
   if (rows_on) {
     if (wl) {  // MPC's scan is the first one (src/project.cpp:45-49): every car's, at row 0
       ranges = scan_row(0);
-      e = f110qp::launch_cast_scans(wl->P, batch, nullptr, nullptr, xt, wl->circles, scan_row(0), s);
+      e = world_cast(*wl, batch, nullptr, nullptr, xt, scan_row(0), s);
       if (e != hipSuccess) return hip_fail(e, "scan cast launch");
     }
     e = f110qp::launch_gap_search(scan_rows * batch, ranges, sc.num_ranges, sc.angle_min, sc.angle_increment,
@@ -1674,8 +1683,7 @@ static int replan_ticks(f110qp_ctx* c, const f110qp::AdvanceParams& ap, const f1
     const float* scan_t = wl ? scan_row(t) : ranges + (scan_rows == 1 ? 0 : t * B * nr);
     if (wl) {
       const bool all = wl->ranges_traj != nullptr;
-      e = f110qp::launch_cast_scans(wl->P, batch, all ? nullptr : list, all ? nullptr : count + t, xt + t * B * 3,
-                                    wl->circles, scan_row(t), s);
+      e = world_cast(*wl, batch, all ? nullptr : list, all ? nullptr : count + t, xt + t * B * 3, scan_row(t), s);
       if (e != hipSuccess) return hip_fail(e, "scan cast launch");
     }
     e = f110qp::launch_plan_listed(K, batch, list, count + t, pose_row(t), scan_t, sc.num_ranges, sc.angle_min,
@@ -1916,7 +1924,11 @@ static int replan_host(f110qp_ctx* c, const f110qp_rollout_config* rc, const f11
                       pst ? (int*)(d + o_ps) : nullptr,   btt ? (int*)(d + o_bt) : nullptr,
                       bgt ? (int*)(d + o_bg) : nullptr,   poset ? (double*)(d + o_po) : nullptr};
   WorldLoop dwl{};
-  if (wl) dwl = WorldLoop{wl->P, s_ci > 0 ? (const double*)(d + o_ci) : nullptr, rgt ? (float*)(d + o_rg) : nullptr};
+  if (wl) {
+    dwl = *wl;
+    dwl.circles = s_ci > 0 ? (const double*)(d + o_ci) : nullptr;
+    dwl.ranges_traj = rgt ? (float*)(d + o_rg) : nullptr;
+  }
   const int rt = replan_ticks(c, ap, K, *sc, *rp, rc->ticks, batch, (const double*)(d + o_tab),
                               W > 0 ? (const double*)(d + o_wp) : nullptr, (double*)(d + o_xr), (int*)(d + o_hv),
                               (const float*)(d + o_rg), (double*)(d + o_xt), (double*)(d + o_ul), (float*)(d + o_ua),
@@ -1965,6 +1977,22 @@ static int world_params(const f110qp_scan_config* sc, const f110qp_world_config*
   P->world_rows = wc->world_rows;
   P->lidar_offset = wc->lidar_offset;
   P->max_range = wc->max_range;
+  return F110QP_OK;
+}
+
+// The races of f110qp_cast_scans_race_dev and the race rollouts, checked, into *Q.
+static int race_params(const f110qp_race_config* race, int batch, int num_circles, f110qp::RaceParams* Q) {
+  if (!race) return fail(F110QP_ERR_INVALID, "race config is NULL");
+  if (race->group_size < 1) return fail(F110QP_ERR_INVALID, "group_size < 1");
+  if (batch % race->group_size != 0) return fail(F110QP_ERR_INVALID, "batch must be a multiple of group_size");
+  if (!(race->car_radius > 0.0) || !std::isfinite(race->car_radius))
+    return fail(F110QP_ERR_INVALID, "car_radius must be positive and finite");
+  if (!std::isfinite(race->center_offset)) return fail(F110QP_ERR_INVALID, "center_offset must be finite");
+  if ((long long)num_circles + race->group_size - 1 > 0x7fffffffll)
+    return fail(F110QP_ERR_INVALID, "num_circles + group_size - 1 does not fit an int");
+  Q->G = race->group_size;
+  Q->car_radius = race->car_radius;
+  Q->center_offset = race->center_offset;
   return F110QP_OK;
 }
 
@@ -2041,6 +2069,75 @@ int f110qp_rollout_world(f110qp_ctx* c, const f110qp_rollout_config* rc, const f
   if ((rv = world_params(sc, wc, batch, circles, &wl.P)) || batch == 0) return rv;
   wl.circles = circles;
   wl.ranges_traj = rgt;
+  return replan_host(c, rc, sc, rp, ap, K, batch, table, wp, xr, have, nullptr, xt, ult, ua, stt, itt, cot, up, xp,
+                     hst, kt, pst, btt, bgt, poset, &wl);
+}
+
+void f110qp_default_race_config(f110qp_race_config* race) {
+  if (!race) return;
+  std::memset(race, 0, sizeof(*race));
+  race->group_size = 1;
+  race->car_radius = 0.3;        // covers a 0.58 x 0.31 m car
+  race->center_offset = 0.1651;  // half the 0.3302 wheelbase of Model::Linearize
+}
+
+int f110qp_cast_scans_race_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
+                               const f110qp_race_config* race, int batch, const int* list, const int* count,
+                               const double* x, const double* circles, float* ranges, void* stream) {
+  int rv = check_scan_config(sc, false, 0);
+  if (rv) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  f110qp::CastParams P;
+  f110qp::RaceParams Q;
+  if ((rv = world_params(sc, wc, batch, circles, &P))) return rv;
+  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
+  if ((list != nullptr) != (count != nullptr))
+    return fail(F110QP_ERR_INVALID, "list and count must be given together");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !ranges) return fail(F110QP_ERR_INVALID, "x/ranges must be non-NULL");
+  const hipError_t e =
+      f110qp::launch_cast_scans_race(P, Q, batch, list, count, x, circles, ranges, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "race scan cast launch");
+  return F110QP_OK;
+}
+
+int f110qp_rollout_race_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                            const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                            const f110qp_race_config* race, int batch, const double* table, const double* wp,
+                            double* xr, int* have, const double* circles, double* xt, double* ult, float* ua,
+                            int* stt, int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst,
+                            int* btt, int* bgt, double* poset, float* rgt, void* stream) {
+  f110qp::AdvanceParams ap;
+  f110qp::PlanKParams K;
+  WorldLoop wl{};
+  int rv = check_replan_args(c, rc, sc, rp, batch, table, wp, xr, have, nullptr, xt, ult, ua, stt, &ap, &K, true);
+  if (rv) return rv;
+  if ((rv = world_params(sc, wc, batch, circles, &wl.P))) return rv;
+  if ((rv = race_params(race, batch, wc->num_circles, &wl.Q)) || batch == 0) return rv;
+  wl.circles = circles;
+  wl.ranges_traj = rgt;
+  wl.race = true;
+  const ReplanTraj tr{hst, kt, pst, btt, bgt, poset};
+  return replan_ticks(c, ap, K, *sc, *rp, rc->ticks, batch, table, wp, xr, have, nullptr, xt, ult, ua, stt, itt,
+                      cot, up, xp, tr, (hipStream_t)stream, &wl);
+}
+
+int f110qp_rollout_race(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                        const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                        const f110qp_race_config* race, int batch, const double* table, const double* wp,
+                        double* xr, int* have, const double* circles, double* xt, double* ult, float* ua, int* stt,
+                        int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst, int* btt,
+                        int* bgt, double* poset, float* rgt) {
+  f110qp::AdvanceParams ap;
+  f110qp::PlanKParams K;
+  WorldLoop wl{};
+  int rv = check_replan_args(c, rc, sc, rp, batch, table, wp, xr, have, nullptr, xt, ult, ua, stt, &ap, &K, true);
+  if (rv) return rv;
+  if ((rv = world_params(sc, wc, batch, circles, &wl.P))) return rv;
+  if ((rv = race_params(race, batch, wc->num_circles, &wl.Q)) || batch == 0) return rv;
+  wl.circles = circles;
+  wl.ranges_traj = rgt;
+  wl.race = true;
   return replan_host(c, rc, sc, rp, ap, K, batch, table, wp, xr, have, nullptr, xt, ult, ua, stt, itt, cot, up, xp,
                      hst, kt, pst, btt, bgt, poset, &wl);
 }

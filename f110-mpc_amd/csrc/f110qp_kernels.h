@@ -375,5 +375,14 @@ struct CastParams {
 int cast_scans_grid(int B);
 hipError_t launch_cast_scans(const CastParams& P, int B, const int* list, const int* count, const double* x,
                              const double* circles, float* ranges, hipStream_t stream);
+// Races: the B cars are B / G races of G consecutive cars (B % G == 0), and every car also sees each of
+// its G - 1 race-mates as the circle (x_m + center_offset cos(ori_m), y_m + center_offset sin(ori_m),
+// car_radius) at the mate's pose in x. Same grid, same list rule; circles may be null when C = 0.
+struct RaceParams {
+  int G;
+  double car_radius, center_offset;
+};
+hipError_t launch_cast_scans_race(const CastParams& P, const RaceParams& Q, int B, const int* list, const int* count,
+                                  const double* x, const double* circles, float* ranges, hipStream_t stream);
 
 }  // namespace f110qp

@@ -29,6 +29,16 @@
 //      beam's minimum with an unsigned 64-bit LDS atomic min (positive doubles order as their bits).
 // A beam outside an interval cannot hit, one inside is decided by the exact test, so the interval
 // changes the work and not the result.
+//
+// Races (RACE, cast_scans_race_kernel): the B cars are B / G races of G consecutive cars, and car b also
+// sees each race-mate m as the circle (x_m + off cos(ori_m), y_m + off sin(ori_m), car_radius), the
+// LiDAR origin's own expressions. The mates are a virtual tail of the circle list: index j in
+// [C, C + G - 1) is mate k = j - C of the race, stepped over the car's own slot, built by the thread
+// that takes j in phase A with one sincos; from there on it is a circle like any other (the same
+// cull, inside test, interval and phase B), so what holds per circle holds per opponent: a non-finite
+// pose fails the range compare and hits nothing, and the minimum is the same for every order of the
+// race's cars. The tile loop runs to C + G - 1: no cap on G. The plain kernel is the RACE = false
+// instantiation; every race statement is behind `if constexpr`.
 #include <hip/hip_runtime.h>
 
 #include "f110qp_kernels.h"
@@ -77,10 +87,11 @@ __device__ __forceinline__ void cast_beams(const double px, const double py, con
 }
 
 #pragma clang fp contract(off)
-__device__ __forceinline__ void cast_one(const CastParams& P, const int b, const double* __restrict__ x,
-                                         const double* __restrict__ circles, float* __restrict__ ranges,
-                                         double* s_dx, double* s_dy, unsigned long long* s_min,
-                                         CastSlot* s_slot) {
+template <bool RACE>
+__device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& Q, const int b,
+                                         const double* __restrict__ x, const double* __restrict__ circles,
+                                         float* __restrict__ ranges, double* s_dx, double* s_dy,
+                                         unsigned long long* s_min, CastSlot* s_slot) {
   const int tid = threadIdx.x;
   const double ori = x[(size_t)b * 3 + 2];
   double so, co;
@@ -92,6 +103,13 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const int b, const
   const double* cw = circles + (P.world_rows == 1 ? (size_t)0 : (size_t)b * (size_t)P.C * 3);
   const int nr = P.nr;
   const double last = (double)(nr - 1);
+  int nc = P.C;  // the circles and, in a race, the G - 1 mates behind them
+  int own = 0, first = 0;
+  if constexpr (RACE) {
+    nc += Q.G - 1;
+    own = b % Q.G;
+    first = b - own;
+  }
   for (int cb = 0; cb < nr; cb += kCastBeamTile) {
     const int nb = min(kCastBeamTile, nr - cb);
     for (int i = tid; i < nb; i += kCastThreads) {
@@ -102,13 +120,28 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const int b, const
       s_min[i] = (unsigned long long)__double_as_longlong(P.max_range);
     }
     __syncthreads();
-    for (int c0 = 0; c0 < P.C; c0 += kCastCircleTile) {
+    for (int c0 = 0; c0 < nc; c0 += kCastCircleTile) {
       {  // A: circle c0 + tid -> slot tid
         CastSlot sl{0.0, 0.0, 0.0, 0.0, 0.0};
         const int j = c0 + tid;
-        if (j < P.C) {
-          const double r = cw[(size_t)j * 3 + 2];
-          const double px = cw[(size_t)j * 3 + 0] - ox, py = cw[(size_t)j * 3 + 1] - oy;
+        if (j < nc) {
+          double cx, cy, r;
+          bool mate = false;
+          if constexpr (RACE) mate = j >= P.C;
+          if (mate) {  // mate k of the race, stepped over the own slot
+            const int k = j - P.C;
+            const double* xm = x + (size_t)(first + k + (k >= own ? 1 : 0)) * 3;
+            double sm, cm;
+            sincos(xm[2], &sm, &cm);
+            cx = xm[0] + Q.center_offset * cm;
+            cy = xm[1] + Q.center_offset * sm;
+            r = Q.car_radius;
+          } else {
+            r = cw[(size_t)j * 3 + 2];
+            cx = cw[(size_t)j * 3 + 0];
+            cy = cw[(size_t)j * 3 + 1];
+          }
+          const double px = cx - ox, py = cy - oy;
           const double ra = fabs(r), dist = __dsqrt_rn(px * px + py * py);
           if (dist - ra <= P.max_range * kCastRel) {
             sl.px = px;
@@ -130,7 +163,7 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const int b, const
       }
       __syncthreads();
       {  // B: kCastLanes lanes per kept circle
-        const int nt = min(kCastCircleTile, P.C - c0), sub = tid % kCastLanes;
+        const int nt = min(kCastCircleTile, nc - c0), sub = tid % kCastLanes;
         for (int j = tid / kCastLanes; j < nt; j += kCastGroups) {
           const CastSlot sl = s_slot[j];
           if (sl.nd == 0.0) continue;
@@ -156,16 +189,13 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const int b, const
   }
 }
 
-}  // namespace
-
 // Workgroup w takes cars w, w + nwg, ... below B, or with a list the cars list[w], list[w + nwg], ...
 // below min(*count, B) (plan_listed_kernel's rule: one past the count leaves at that load).
-__global__ __launch_bounds__(kCastThreads) void cast_scans_kernel(const CastParams P, const int B, const int nwg,
-                                                                  const int* __restrict__ list,
-                                                                  const int* __restrict__ count,
-                                                                  const double* __restrict__ x,
-                                                                  const double* __restrict__ circles,
-                                                                  float* __restrict__ ranges) {
+template <bool RACE>
+__device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams& Q, const int B, const int nwg,
+                                           const int* __restrict__ list, const int* __restrict__ count,
+                                           const double* __restrict__ x, const double* __restrict__ circles,
+                                           float* __restrict__ ranges) {
   __shared__ double s_dx[kCastBeamTile];
   __shared__ double s_dy[kCastBeamTile];
   __shared__ unsigned long long s_min[kCastBeamTile];
@@ -174,8 +204,27 @@ __global__ __launch_bounds__(kCastThreads) void cast_scans_kernel(const CastPara
   for (int k = blockIdx.x; k < n; k += nwg) {
     const int b = list ? list[k] : k;
     if (b >= 0 && b < B)  // uniform over the workgroup
-      cast_one(P, b, x, circles, ranges, s_dx, s_dy, s_min, s_slot);
+      cast_one<RACE>(P, Q, b, x, circles, ranges, s_dx, s_dy, s_min, s_slot);
   }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kCastThreads) void cast_scans_kernel(const CastParams P, const int B, const int nwg,
+                                                                  const int* __restrict__ list,
+                                                                  const int* __restrict__ count,
+                                                                  const double* __restrict__ x,
+                                                                  const double* __restrict__ circles,
+                                                                  float* __restrict__ ranges) {
+  cast_scans<false>(P, RaceParams{}, B, nwg, list, count, x, circles, ranges);
+}
+
+// The same with the race-mates of every car behind its circles (x is also the opponents' poses).
+__global__ __launch_bounds__(kCastThreads) void cast_scans_race_kernel(
+    const CastParams P, const RaceParams Q, const int B, const int nwg, const int* __restrict__ list,
+    const int* __restrict__ count, const double* __restrict__ x, const double* __restrict__ circles,
+    float* __restrict__ ranges) {
+  cast_scans<true>(P, Q, B, nwg, list, count, x, circles, ranges);
 }
 
 // Grid: one workgroup per car up to 768. The kernel holds 155 VGPRs (the code-object metadata,
@@ -183,6 +232,7 @@ __global__ __launch_bounds__(kCastThreads) void cast_scans_kernel(const CastPara
 // and a CU three of its four-wave workgroups (37,888 B of LDS each would allow four): 768 is what the
 // MI355X's 256 CUs hold at once, the same figure as plan_listed_grid's and derived the same way, from
 // the occupancy and not from a sweep of caps. Forcing four waves per SIMD spills 17 VGPRs to scratch.
+// The race instantiation holds 155 VGPRs too (no scratch): the same cap.
 constexpr int kCastMaxGrid = 768;
 int cast_scans_grid(int B) { return B < kCastMaxGrid ? B : kCastMaxGrid; }
 
@@ -192,6 +242,15 @@ hipError_t launch_cast_scans(const CastParams& P, int B, const int* list, const 
   const int nwg = cast_scans_grid(B);
   hipLaunchKernelGGL(cast_scans_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, B, nwg, list, count, x, circles,
                      ranges);
+  return hipGetLastError();
+}
+
+hipError_t launch_cast_scans_race(const CastParams& P, const RaceParams& Q, int B, const int* list, const int* count,
+                                  const double* x, const double* circles, float* ranges, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  const int nwg = cast_scans_grid(B);
+  hipLaunchKernelGGL(cast_scans_race_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, Q, B, nwg, list, count, x,
+                     circles, ranges);
   return hipGetLastError();
 }
 

@@ -126,6 +126,10 @@ EXPORTED = (
     "f110qp_cast_scans_dev",
     "f110qp_rollout_world_dev",
     "f110qp_rollout_world",
+    "f110qp_default_race_config",
+    "f110qp_cast_scans_race_dev",
+    "f110qp_rollout_race_dev",
+    "f110qp_rollout_race",
 )
 CAST_CIRCLE_TILE = 256  # F110QP_CAST_CIRCLE_TILE: circles per LDS tile of the ray-cast kernel
 SCRATCH_NAMES = {0: "none (wave back end)", 1: "LDS fp64", 2: "LDS fp32", 3: "HBM fp64", 4: "HBM fp32"}
@@ -203,6 +207,14 @@ class WorldConfig(C.Structure):
     ]
 
 
+class RaceConfig(C.Structure):
+    _fields_ = [
+        ("group_size", C.c_int),
+        ("car_radius", C.c_double),
+        ("center_offset", C.c_double),
+    ]
+
+
 # f110qp_gap_record (16 bytes) as a numpy record
 GAP_RECORD_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("r_lo", np.float32), ("r_hi", np.float32)])
 
@@ -267,6 +279,11 @@ def load(test: bool = False):
     L.f110qp_cast_scans_dev.argtypes = [sp, wcp, C.c_int] + [fp] * 6
     L.f110qp_rollout_world_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, C.c_int] + [fp] * 21
     L.f110qp_rollout_world.argtypes = [C.c_void_p, rop, sp, rp, wcp, C.c_int] + [fp] * 20
+    rcp = C.POINTER(RaceConfig)
+    L.f110qp_default_race_config.argtypes = [rcp]
+    L.f110qp_cast_scans_race_dev.argtypes = [sp, wcp, rcp, C.c_int] + [fp] * 6
+    L.f110qp_rollout_race_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, C.c_int] + [fp] * 21
+    L.f110qp_rollout_race.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, C.c_int] + [fp] * 20
     L.f110qp_select_dev.argtypes = [C.c_int, fp, C.c_int, fp, fp, fp, fp, fp]
     L.f110qp_backend_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
     L.f110qp_lane_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -367,6 +384,21 @@ def default_world_config(**over) -> WorldConfig:
     for k, v in over.items():
         setattr(c, k, v)
     return c
+
+
+def default_race_config(**over) -> RaceConfig:
+    """f110qp_default_race_config: group_size 1, car_radius 0.3, center_offset 0.1651."""
+    c = RaceConfig()
+    load().f110qp_default_race_config(C.byref(c))
+    for k, v in over.items():
+        setattr(c, k, v)
+    return c
+
+
+def _check_race(race, B):
+    G = int(race.group_size)
+    if G < 1 or B % G:
+        raise F110QPError(f"group_size must be >= 1 and divide B = {B}, got {G}")
 
 
 def qp_dims(horizon: int):
@@ -849,7 +881,7 @@ class Solver:
                           waypoints, x_ref, have_path, circles, x_traj, u_lin_traj, u_applied, status_traj,
                           iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
                           plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
-                          ranges_traj=None, stream=None):
+                          ranges_traj=None, stream=None, _race=None):
         """rollout_replan_dev with every tick's scan cast at that tick's pose (f110qp_rollout_world_dev): wc
         and circles [world_rows,C,3] f64 replace ranges, sc.scan_rows is not read, and the optional
         ranges_traj [T,B,num_ranges] f32 records every car's scan of every tick."""
@@ -865,6 +897,8 @@ class Solver:
             raise F110QPError(f"x_traj must be [ticks + 1, B, 3] = {(T + 1, B, 3)}, got {tuple(x_traj.shape)}")
         if WR not in (1, B):
             raise F110QPError(f"world_rows must be 1 or B = {B}, got {WR}")
+        if _race is not None:
+            _check_race(_race, B)
         _devs((table, "f64", 3 * P * Tc, "table"), (waypoints, "f64", 2 * W, "waypoints", W == 0),
               (x_ref, "f64", 3 * P * B, "x_ref"), (have_path, "i32", B, "have_path"),
               (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
@@ -880,16 +914,33 @@ class Solver:
               (ranges_traj, "f32", T * B * NR, "ranges_traj", True))
         if stream is None:
             stream = torch.cuda.current_stream(x_traj.device)
-        self._chk(self.lib.f110qp_rollout_world_dev(
-            self._h, C.byref(rc), C.byref(sc), C.byref(rp), C.byref(wc), B, _tp(table), _tp(waypoints), _tp(x_ref),
+        name = "f110qp_rollout_world_dev" if _race is None else "f110qp_rollout_race_dev"
+        self._chk(getattr(self.lib, name)(
+            self._h, C.byref(rc), C.byref(sc), C.byref(rp), C.byref(wc), *([] if _race is None else [C.byref(_race)]),
+            B, _tp(table), _tp(waypoints), _tp(x_ref),
             _tp(have_path), _tp(circles), _tp(x_traj), _tp(u_lin_traj), _tp(u_applied), _tp(status_traj),
             _tp(iters_traj), _tp(cost_traj), _tp(u_plan), _tp(x_plan), _tp(hs_traj), _tp(kind_traj),
             _tp(plan_status_traj), _tp(best_traj_traj), _tp(best_global_traj), _tp(pose_traj), _tp(ranges_traj),
-            C.c_void_p(stream.cuda_stream)), "f110qp_rollout_world_dev")
+            C.c_void_p(stream.cuda_stream)), name)
+
+    def rollout_race_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
+                         table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj, u_applied, status_traj,
+                         iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
+                         plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
+                         ranges_traj=None, stream=None):
+        """rollout_world_dev with the cars of a race in each other's scans (f110qp_rollout_race_dev): the B cars
+        are B / race.group_size races of consecutive cars; every cast reads x_traj row t as the casting poses
+        and as the opponents'. circles may be None when wc.num_circles is 0."""
+        if not isinstance(race, RaceConfig):
+            raise F110QPError("race must be a RaceConfig")
+        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
+                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
+                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
+                               _race=race)
 
     def rollout_world(self, x0, u_lin, circles, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
                       wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
-                      scans=False, rc=None):
+                      scans=False, rc=None, _race=None):
         """rollout_replan() in a world of circles (f110qp_rollout_world, synchronous): circles [C,3] (one world
         for all cars) or [B,C,3] float64 replace ranges; wc defaults to f110qp_default_world_config with
         num_circles and world_rows taken from the array. scans=True adds ranges_traj [T,B,num_ranges]."""
@@ -916,6 +967,8 @@ class Solver:
         w.world_rows = 1 if ci.ndim == 2 else ci.shape[0]
         if w.world_rows not in (1, B):
             raise F110QPError(f"circles must hold one world or B = {B} worlds, got {w.world_rows}")
+        if _race is not None:
+            _check_race(_race, B)
         cfg = RolloutConfig()
         C.memmove(C.byref(cfg), C.byref(rc if rc is not None else default_rollout_config()), C.sizeof(cfg))
         cfg.ticks = T
@@ -934,13 +987,25 @@ class Solver:
             out["hs_traj"] = np.empty((T, B, 2, 3), np.float32)
         if scans:
             out["ranges_traj"] = np.empty((T, B, int(sc.num_ranges)), np.float32)
-        self._chk(self.lib.f110qp_rollout_world(
-            self._h, C.byref(cfg), C.byref(sc), C.byref(rp), C.byref(w), B, _p(tab), _p(wp) if W else None, _p(xr),
+        name = "f110qp_rollout_world" if _race is None else "f110qp_rollout_race"
+        self._chk(getattr(self.lib, name)(
+            self._h, C.byref(cfg), C.byref(sc), C.byref(rp), C.byref(w), *([] if _race is None else [C.byref(_race)]),
+            B, _p(tab), _p(wp) if W else None, _p(xr),
             _p(hv), _p(ci) if ci.size else None, _p(out["x_traj"]), _p(out["u_lin_traj"]), _p(out["u_applied"]),
             _p(out["status"]), _p(out["iters"]), _p(out.get("cost")), _p(out.get("u_plan")), _p(out.get("x_plan")),
             _p(out.get("hs_traj")), _p(out["kind"]), _p(out["plan_status"]), _p(out["best_traj"]),
-            _p(out["best_global"]), _p(out["pose_traj"]), _p(out.get("ranges_traj"))), "f110qp_rollout_world")
+            _p(out["best_global"]), _p(out["pose_traj"]), _p(out.get("ranges_traj"))), name)
         return out
+
+    def rollout_race(self, x0, u_lin, circles, race: RaceConfig, sc: ScanConfig, rp: ReplanConfig, table, waypoints,
+                     ticks, wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False,
+                     rows=True, scans=False, rc=None):
+        """rollout_world() with the cars of a race in each other's scans (f110qp_rollout_race, synchronous):
+        circles [C,3] or [B,C,3] float64, C = 0 allowed (the world is then the opponents only)."""
+        if not isinstance(race, RaceConfig):
+            raise F110QPError("race must be a RaceConfig")
+        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
+                                  objective, rows, scans, rc, _race=race)
 
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
@@ -1175,6 +1240,24 @@ def cast_scans_dev(sc: ScanConfig, wc: WorldConfig, x, circles, ranges, list_=No
         stream = torch.cuda.current_stream(x.device)
     _check(load().f110qp_cast_scans_dev(C.byref(sc), C.byref(wc), B, _tp(list_), _tp(count), _tp(x), _tp(circles),
                                         _tp(ranges), C.c_void_p(stream.cuda_stream)), "f110qp_cast_scans_dev")
+
+
+def cast_scans_race_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, x, circles, ranges, list_=None, count=None,
+                        stream=None):
+    """cast_scans_dev with the race-mates in every scan (f110qp_cast_scans_race_dev): the B cars are
+    B / race.group_size races of consecutive cars, x [B,3] f64 is both the casting poses and the opponents'."""
+    import torch
+
+    B, Cn, WR = int(x.shape[0]), int(wc.num_circles), int(wc.world_rows)
+    _check_race(race, B)
+    _devs((x, "f64", 3 * B, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
+          (ranges, "f32", B * int(sc.num_ranges), "ranges"), (list_, "i32", B, "list", True),
+          (count, "i32", 1, "count", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_cast_scans_race_dev(C.byref(sc), C.byref(wc), C.byref(race), B, _tp(list_), _tp(count), _tp(x),
+                                             _tp(circles), _tp(ranges), C.c_void_p(stream.cuda_stream)),
+           "f110qp_cast_scans_race_dev")
 
 
 def replan_start_dev(rp: ReplanConfig, sc, x, have_path, x_ref, gap, pose, kind, list_, count, hs=None, stream=None):

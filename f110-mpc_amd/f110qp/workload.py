@@ -314,3 +314,44 @@ def make_world(seed: int = 0, obstacles: int = 40) -> np.ndarray:
     obst = wp[oi] + nrm[oi] * rng.choice([-0.9, 0.9], obstacles)[:, None]
     rads = np.concatenate([np.full(len(wall), 0.12), rng.uniform(0.15, 0.3, obstacles)])
     return np.ascontiguousarray(np.concatenate([np.concatenate([wall, obst]), rads[:, None]], 1))
+
+
+# ---- head-to-head races (f110qp_cast_scans_race_dev, f110qp_rollout_race[_dev]) ------------------------
+
+def race_circles(x, group_size: int, car_radius: float = 0.3, center_offset: float = 0.1651) -> np.ndarray:
+    """The opponent circles of include/f110qp.h's race model, [B, G - 1, 3] float64: the B poses x [B, 3] are
+    B / G races of G consecutive cars, and row b holds, for every other car m of b's race in the order of
+    the car index (the own car left out), (x_m + center_offset cos(ori_m), y_m + center_offset sin(ori_m),
+    car_radius). The oracle of what the device builds; at center_offset = 0 the centres are the poses' bits."""
+    x = np.asarray(x, np.float64)
+    B, G = x.shape[0], int(group_size)
+    if G < 1 or B % G:
+        raise ValueError(f"group_size must be >= 1 and divide B = {B}, got {G}")
+    with np.errstate(invalid="ignore"):
+        c = np.stack([x[:, 0] + center_offset * np.cos(x[:, 2]), x[:, 1] + center_offset * np.sin(x[:, 2]),
+                      np.full(B, float(car_radius))], 1)
+    own = np.arange(B) % G
+    k = np.arange(G - 1)[None, :]
+    mate = (np.arange(B) - own)[:, None] + k + (k >= own[:, None])
+    return np.ascontiguousarray(c[mate].reshape(B, G - 1, 3))
+
+
+def make_race_grid(races: int, group_size: int, seed: int = 0, spacing: float = 1.2, lateral: float = 0.4) -> np.ndarray:
+    """Start states [races * group_size, 3] float64 (x, y, yaw) of `races` races on track_waypoints(): a race
+    starts at a seeded position on the path; its car i stands i * spacing metres behind car 0 along the path,
+    alternately +lateral and -lateral off it, heading along the path."""
+    rng = np.random.default_rng(seed)
+    wp = track_waypoints()
+    W, G = wp.shape[0], int(group_size)
+    seg = np.hypot(*(np.roll(wp, -1, 0) - wp).T)
+    s_along = np.concatenate([[0.0], np.cumsum(seg)])
+    total = s_along[-1]
+    s0 = rng.uniform(0, total, races)
+    i = np.arange(G)
+    s = ((s0[:, None] - spacing * i[None, :]) % total).reshape(-1)
+    k = np.minimum(np.searchsorted(s_along, s, side="right") - 1, W - 1)
+    nxt = wp[(k + 1) % W]
+    base = wp[k] + (nxt - wp[k]) * ((s - s_along[k]) / seg[k])[:, None]
+    hd = np.arctan2(nxt[:, 1] - wp[k, 1], nxt[:, 0] - wp[k, 0])
+    lat = np.tile(np.where(i % 2 == 0, lateral, -lateral), races)
+    return np.ascontiguousarray(np.stack([base[:, 0] - np.sin(hd) * lat, base[:, 1] + np.cos(hd) * lat, hd], 1))

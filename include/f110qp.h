@@ -834,6 +834,73 @@ int f110qp_rollout_world(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const
                          int* best_traj_traj, int* best_global_traj, double* pose_traj,
                          float* ranges_traj);
 
+/* ---- head-to-head races: the cars of a race see each other in the simulated LiDAR -----------------
+ * In the world calls above every car drives alone. The reference is a racing controller: its gap rows
+ * and its occupancy-grid planner exist to get past an opponent, and the simulator it runs in
+ * publishes a scan that contains the other car. Model:
+ *   - the B cars form B / G races of G consecutive cars: race g is cars gG .. gG + G - 1. Cars of
+ *     different races never see each other;
+ *   - at the tick whose poses are x [B][3], car b's LiDAR sees the static circles exactly as before
+ *     (world_rows 1 or B stays orthogonal) and, for every other car m of its race, one more circle
+ *       (x_m + center_offset cos(ori_m), y_m + center_offset sin(ori_m), car_radius),
+ *     in fp64, each product and sum rounded, sincos(double): the expressions of the LiDAR origin;
+ *   - a car never sees itself.
+ * Opponent circles enter the same per-pair test and the same minimum as the static circles, so every
+ * consequence stated at f110qp_cast_scans_dev carries over: a LiDAR inside an opponent's circle sees
+ * through it; an opponent with a non-finite pose hits nothing and disturbs nobody; the result is
+ * bit-identical for every order of the race's cars and of the static circles.
+ * car_radius 0.3 covers a 0.58 x 0.31 m car and center_offset 0.1651 is half the 0.3302 wheelbase of
+ * Model::Linearize (the circle sits over the middle of the car, the pose at its rear axle): both are
+ * modelling choices of this library, not values of the reference. Additive: F110QP_API_VERSION stays 6. */
+typedef struct {
+  int    group_size;     /* G >= 1; batch % G == 0                                          */
+  double car_radius;     /* finite, > 0                                                     */
+  double center_offset;  /* finite: circle centre ahead of the pose along the heading       */
+} f110qp_race_config;
+
+/* Zeroes *race, then group_size 1, car_radius 0.3, center_offset 0.1651. */
+void f110qp_default_race_config(f110qp_race_config* race);
+
+/* f110qp_cast_scans_dev with the race-mates in every scan (one launch). Arguments and list / count
+ * rules as there; x is read both as the casting poses and as the opponents' poses, so a listed car
+ * reads the poses of its unlisted race-mates from x. num_circles == 0 with circles == NULL is valid:
+ * the world is then the opponents only. group_size 1 gives f110qp_cast_scans_dev's bits.
+ * F110QP_ERR_INVALID before any HIP call: a NULL race, group_size < 1, batch not a multiple of
+ * group_size, a non-finite or non-positive car_radius, a non-finite center_offset, and every rule of
+ * f110qp_cast_scans_dev. */
+int f110qp_cast_scans_race_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
+                               const f110qp_race_config* race, int batch, const int* list,
+                               const int* count, const double* x, const double* circles, float* ranges,
+                               void* stream);
+
+/* f110qp_rollout_world_dev, word for word, with every cast passing the race: the all-cars cast at row
+ * 0 in front of the loop and the per-tick listed or all-cars cast read x_traj row t as the casting
+ * poses and as the opponents' poses (row t is complete for every car when tick t's cast runs). The
+ * gap records come from the first scan, so they hold the opponents where they stood at tick 0: the
+ * reference keeps its first scan too (src/project.cpp:45-49), so this is its behaviour and not a
+ * shortcut. Launches per tick, stream order and the absence of host synchronisation, read-back and
+ * allocation inside the loop are f110qp_rollout_world_dev's; every argument is checked before the
+ * first launch (that call's checks and f110qp_cast_scans_race_dev's race rules). */
+int f110qp_rollout_race_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc,
+                            const f110qp_scan_config* sc, const f110qp_replan_config* rp,
+                            const f110qp_world_config* wc, const f110qp_race_config* race, int batch,
+                            const double* table, const double* waypoints, double* x_ref, int* have_path,
+                            const double* circles, double* x_traj, double* u_lin_traj, float* u_applied,
+                            int* status_traj, int* iters_traj, double* cost_traj, float* u_plan,
+                            float* x_plan, float* hs_traj, int* kind_traj, int* plan_status_traj,
+                            int* best_traj_traj, int* best_global_traj, double* pose_traj,
+                            float* ranges_traj, void* stream);
+
+/* Same on host pointers (synchronous), staged as f110qp_rollout_world. */
+int f110qp_rollout_race(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                        const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                        const f110qp_race_config* race, int batch, const double* table,
+                        const double* waypoints, double* x_ref, int* have_path, const double* circles,
+                        double* x_traj, double* u_lin_traj, float* u_applied, int* status_traj,
+                        int* iters_traj, double* cost_traj, float* u_plan, float* x_plan, float* hs_traj,
+                        int* kind_traj, int* plan_status_traj, int* best_traj_traj, int* best_global_traj,
+                        double* pose_traj, float* ranges_traj);
+
 #ifdef __cplusplus
 }
 #endif
