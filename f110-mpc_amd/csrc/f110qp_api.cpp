@@ -261,11 +261,22 @@ static int validate_config(const f110qp_config* c) {
     return fail(F110QP_ERR_INVALID, "horizon must be in [1, 48] (one wave holds 2N inputs in <= 2 register rows)");
   if (!(c->dt > 0.f) || !std::isfinite(c->dt)) return fail(F110QP_ERR_INVALID, "dt must be > 0");
   for (int i = 0; i < 3; i++)
-    if (!(c->q[i] >= 0.0)) return fail(F110QP_ERR_INVALID, "Q must be >= 0");
+    if (!(c->q[i] >= 0.0) || !std::isfinite(c->q[i])) return fail(F110QP_ERR_INVALID, "Q must be >= 0 and finite");
   for (int i = 0; i < 2; i++) {
-    if (!(c->r[i] > 0.0)) return fail(F110QP_ERR_INVALID, "R must be > 0 (strictly convex QP)");
+    if (!(c->r[i] > 0.0) || !std::isfinite(c->r[i]))
+      return fail(F110QP_ERR_INVALID, "R must be > 0 (strictly convex QP) and finite");
+    if (!std::isfinite(c->u_des[i])) return fail(F110QP_ERR_INVALID, "u_des must be finite");
+    if (std::isnan(c->u_min[i]) || std::isnan(c->u_max[i])) return fail(F110QP_ERR_INVALID, "u_min / u_max is NaN");
     if (!(c->u_min[i] <= c->u_max[i])) return fail(F110QP_ERR_INVALID, "u_min > u_max");
+    if (c->u_min[i] == INFINITY || c->u_max[i] == -INFINITY)
+      return fail(F110QP_ERR_INVALID, "u_min = +inf / u_max = -inf leaves no input");
   }
+  // stiff weights: the wave kernel works on the fp32 inverse of H = R + G'QG, and from
+  // max(q) / min(r) = 1e5 (N = 48) it returned points off the optimum as SOLVED; from 1e4 both back
+  // ends give up on QPs that have a solution (tests/test_gpu_config_corners.py). Up to 1e3 is tested.
+  const double qmax = std::fmax(c->q[0], std::fmax(c->q[1], c->q[2])), rmin = std::fmin(c->r[0], c->r[1]);
+  if (qmax > F110QP_MAX_WEIGHT_RATIO * rmin)
+    return fail(F110QP_ERR_INVALID, "max(q) / min(r) must be <= 1e3 (the weight ratio limit of f110qp.h)");
   if (c->gap_mode != F110QP_GAP_INACTIVE && c->gap_mode != F110QP_GAP_ACTIVE)
     return fail(F110QP_ERR_INVALID, "gap_mode must be 0 (gap rows inactive) or 1 (active)");
   if (c->max_iter < 0) return fail(F110QP_ERR_INVALID, "max_iter must be >= 0");

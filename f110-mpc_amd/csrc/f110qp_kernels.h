@@ -30,6 +30,20 @@ struct KParams {
                              // rollout, where they mean a scan without a gap), not PRIMAL_INFEASIBLE
 };
 
+// 1 + |lb| + |ub| as it enters the scale of a multiplier (flip) tolerance of the lane kernels,
+// gtol = tol (1 + r scale): the bounds stand for the size of the inputs there. A bound far beyond
+// the inputs (a "no bound" of 1e30, OSQP's INFTY: constraints.cpp:15; 1e20 or inf elsewhere) does
+// not: with u_min = (3, -1e30), u_max = (1e30, 0.43) the plain sum made gtol 1e19, and an input once
+// fixed on its finite bound never left it (a wrong point returned as SOLVED). Each |bound| counts
+// up to m = 1 + |u_des| + the smaller |bound|, which is where the inputs of such a QP live. Where
+// the larger |bound| is within m (the shipped box, every box around or next to u_des) this is
+// the plain sum, bit for bit.
+__host__ __device__ inline double bound_scale(double lb, double ub, double ud) {
+  const double al = fabs(lb), au = fabs(ub);
+  const double m = 1.0 + fabs(ud) + fmin(al, au);
+  return 1.0 + fmin(al, m) + fmin(au, m);
+}
+
 // Warm-start state of a context (all null = cold solve). Per QP slot b of the batch:
 //   W[b]   the cached W = H^-1 (2N x 2N, fp32) of the last solve of slot b,
 //   key[b] the float bits of (theta0, v_lin, delta_lin) it was built for + a valid flag,

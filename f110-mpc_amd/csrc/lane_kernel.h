@@ -264,8 +264,8 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
     const double pt = loose ? kPtL : kPtT, gt = loose ? kGtL : kGtT;
     l0 = lb0 - pt * (1.0 + fabs(lb0)); u0 = ub0 + pt * (1.0 + fabs(ub0));
     l1 = lb1 - pt * (1.0 + fabs(lb1)); u1 = ub1 + pt * (1.0 + fabs(ub1));
-    g0 = gt * (1.0 + r0 * (1.0 + fabs(lb0) + fabs(ub0)));
-    g1 = gt * (1.0 + r1 * (1.0 + fabs(lb1) + fabs(ub1)));
+    g0 = gt * (1.0 + r0 * bound_scale(lb0, ub0, ud0));
+    g1 = gt * (1.0 + r1 * bound_scale(lb1, ub1, ud1));
   };
 
   // scratch slot (i, e) of this QP: sp[8 L i + e ES] (LDS [stage][8][L]: ES = L; HBM

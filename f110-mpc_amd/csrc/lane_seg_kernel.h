@@ -344,12 +344,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   const double ptL = F32 ? 1e-6 : 1e-10, gtL = F32 ? 1e-5 : 1e-10;
   const double lbe0 = lb0 - ptT * (1.0 + fabs(lb0)), ube0 = ub0 + ptT * (1.0 + fabs(ub0));
   const double lbe1 = lb1 - ptT * (1.0 + fabs(lb1)), ube1 = ub1 + ptT * (1.0 + fabs(ub1));
-  const double gtol0 = gtT * (1.0 + r0 * (1.0 + fabs(lb0) + fabs(ub0)));
-  const double gtol1 = gtT * (1.0 + r1 * (1.0 + fabs(lb1) + fabs(ub1)));
+  const double gtol0 = gtT * (1.0 + r0 * bound_scale(lb0, ub0, ud0));
+  const double gtol1 = gtT * (1.0 + r1 * bound_scale(lb1, ub1, ud1));
   const double lbl0 = lb0 - ptL * (1.0 + fabs(lb0)), ubl0 = ub0 + ptL * (1.0 + fabs(ub0));
   const double lbl1 = lb1 - ptL * (1.0 + fabs(lb1)), ubl1 = ub1 + ptL * (1.0 + fabs(ub1));
-  const double gtoll0 = gtL * (1.0 + r0 * (1.0 + fabs(lb0) + fabs(ub0)));
-  const double gtoll1 = gtL * (1.0 + r1 * (1.0 + fabs(lb1) + fabs(ub1)));
+  const double gtoll0 = gtL * (1.0 + r0 * bound_scale(lb0, ub0, ud0));
+  const double gtoll1 = gtL * (1.0 + r1 * bound_scale(lb1, ub1, ud1));
 
   SSTAMP(t_lin);
   // references of the lane's stages: recentred (ROT: rotated) fp64, lane-major; a non-finite

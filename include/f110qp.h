@@ -128,6 +128,13 @@ extern "C" {
 #define F110QP_LANE_MIN_BATCH_GROUPED F110QP_LANE_MIN_BATCH
 #define F110QP_LANE_MIN_BATCH_GROUPED_WIDE F110QP_LANE_MIN_BATCH_WIDE
 
+/* Largest max(q) / min(r) f110qp_create accepts. The wave back end holds the inverse of the condensed
+ * Hessian H = R + G'QG in fp32: measured on an MI355X against the exact optimum, it returned points
+ * off the optimum as SOLVED from a ratio of 1e5 (N = 48, dt 0.01; from 1e6 at N = 20), and from 1e4
+ * both back ends gave up (SOLVED_INACCURATE, NUMERICAL, MAX_ITER) on QPs that have a solution. The
+ * shipped weights are at 100; the parity tests reach 1e3. */
+#define F110QP_MAX_WEIGHT_RATIO 1e3
+
 #define F110QP_MAX_HORIZON 48  /* 2N <= 96 decision variables: two register rows per lane */
 
 typedef struct f110qp_ctx f110qp_ctx;
@@ -140,8 +147,29 @@ typedef struct {
   double u_des[2];  /* des_vel, des_steer (params.yaml:42-43; mpc.cpp:18-19)              */
   float u_min[2];   /* (umin, -0.43f) constraints.cpp:21                                  */
   float u_max[2];   /* (umax,  0.43f) constraints.cpp:19                                  */
+                    /* q, r and u_des are finite, max(q) <= F110QP_MAX_WEIGHT_RATIO min(r), */
+                    /* u_min <= u_max (equal: the input is                                  */
+                    /* fixed); u_des and u_lin may lie outside the box. "No bound" is       */
+                    /* -+1e30, OSQP's INFTY (constraints.cpp:15), or -+inf, on either side. */
   int gap_mode;     /* F110QP_GAP_INACTIVE | F110QP_GAP_ACTIVE                            */
-  int max_iter;     /* active-set iteration cap per QP (0 = default 8*(2N+2N))             */
+  int max_iter;     /* active-set iteration cap per QP; 0 = the default 8 * 2N + 16, with   */
+                    /* gap rows 8 * (2N + 2N) + 16. A QP the cap stops has status           */
+                    /* F110QP_MAX_ITER and NaN outputs, never a point off the optimum; a QP */
+                    /* solved under a cap is solved under every larger one (box rows: bit   */
+                    /* for bit alike, iters included).                                      */
+                    /* What the cap counts depends on the back end a call runs on (AUTO     */
+                    /* chooses by batch size, so one context may meet both meanings):       */
+                    /*  - wave: one count over the box PDAS passes, the fp64 passes behind  */
+                    /*    them and the dual active-set (GI) steps. The first fp32 PDAS      */
+                    /*    passes (up to 10) always run: a QP they solve is SOLVED under any */
+                    /*    cap, with iters up to 10.                                         */
+                    /*  - lane (sequential and partitioned-horizon kernels): PDAS passes,   */
+                    /*    and never fewer than the 16 multi-flip passes: the cap in effect  */
+                    /*    is max(max_iter, 16).                                             */
+                    /* Gap rows: a QP the wave kernel does not certify (stopped by the cap  */
+                    /* included) is answered by the fp64 re-check, whose cap is its own,    */
+                    /* whatever max_iter says: there a small max_iter costs time, not       */
+                    /* answers.                                                             */
   int device;       /* HIP device ordinal used by the host-pointer entry points            */
   int warm_start;   /* 1: keep per-slot state across calls (OsqpEigen setWarmStart(true),   */
                     /*    mpc.cpp:98): the factor W = H^-1 is reused when a slot's          */

@@ -93,17 +93,44 @@ def test_version_and_defaults(capi):
     (dict(gap_mode=7), "gap_mode"),
     (dict(dt=0.0), "dt"),
     (dict(max_iter=-1), "max_iter"),
+    # non-finite values: !(x >= 0) and !(a <= b) alone let +inf and some NaNs through
+    (dict(q=[np.inf, 10.0, 0.0]), "Q must be"),
+    (dict(q=[10.0, 10.0, np.nan]), "Q must be"),
+    (dict(r=[0.1, np.inf]), "R must be > 0"),
+    (dict(r=[np.nan, 5.0]), "R must be > 0"),
+    (dict(u_des=[np.nan, 0.0]), "u_des"),
+    (dict(u_des=[4.5, np.inf]), "u_des"),
+    (dict(u_des=[-np.inf, 0.0]), "u_des"),
+    (dict(u_min=[np.nan, -0.43]), "NaN"),
+    (dict(u_max=[4.5, np.nan]), "NaN"),
+    (dict(u_min=[np.nan, -0.43], u_max=[np.nan, 0.43]), "NaN"),
+    # stiff weights: max(q) / min(r) above F110QP_MAX_WEIGHT_RATIO = 1e3 (the wave kernel returned points
+    # off the optimum as SOLVED at 1e5 and above)
+    (dict(q=[1e4, 1e4, 0.0], r=[1e-3, 1e-3]), "weight ratio"),
+    (dict(q=[10.0, 10.0, 101.0]), "weight ratio"),
+    (dict(r=[0.1, 0.009]), "weight ratio"),
+    (dict(u_min=[np.inf, -0.43], u_max=[np.inf, 0.43]), "leaves no input"),
+    (dict(u_min=[3.0, -np.inf], u_max=[4.5, -np.inf]), "leaves no input"),
 ])
 def test_create_rejects_bad_config(capi, over, msg):
     c = capi.default_config(20)
     for k, v in over.items():
-        if k in ("q", "r", "u_min", "u_max"):
+        if k in ("q", "r", "u_des", "u_min", "u_max"):
             for i, x in enumerate(v):
                 getattr(c, k)[i] = x
         else:
             setattr(c, k, v)
     with pytest.raises(capi.F110QPError, match=msg):
         capi.Solver(c)
+
+
+def test_create_accepts_the_corners_of_the_config(capi):
+    """What validate_config lets through on purpose: the weight ratio at its limit, a zero-width box,
+    u_des outside the box, "no bound" as +-1e30 and +-inf."""
+    for over in (dict(q=[1e2, 1e2, 0.0], r=[0.1, 0.1]), dict(q=[0.0, 0.0, 5.0]), dict(u_min=[4.0, 0.1], u_max=[4.0, 0.1]),
+                 dict(u_des=[6.0, 0.8]), dict(u_min=[-1e30, -1e30], u_max=[1e30, 1e30]),
+                 dict(u_min=[3.0, -np.inf], u_max=[np.inf, 0.43])):
+        capi.Solver(capi.default_config(20, **over)).close()
 
 
 def test_solve_argument_validation_without_gpu(capi):
