@@ -648,112 +648,69 @@ class Solver:
                                                       _tp(cost), C.c_void_p(stream.cuda_stream)),
                   "f110qp_solve_batch_dev_dbl")
 
-    def rollout_dev(self, rc: RolloutConfig, x_ref, halfspace, x_traj, u_lin_traj, u_applied, status_traj,
-                    iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, stream=None):
-        """rc.ticks closed-loop ticks on device (torch) tensors, enqueued on `stream`, asynchronous
-        and without a host synchronisation (f110qp_rollout_dev): x_ref [B,S,3] f64 and halfspace
-        [B,2,3] f32 held fixed; x_traj [T+1,B,3] / u_lin_traj [T+1,B,2] f64 with row 0 the start;
-        u_applied [T,B,2] f32, status_traj [T,B] i32; iters_traj [T,B] i32, cost_traj [T,B] f64,
-        u_plan [T,B,N,2] and x_plan [T,B,N+1,3] f32 optional."""
-        import torch
+    # ---- the closed-loop families: what their nine bindings share --------------------------------------
 
-        T, N = int(rc.ticks), self.horizon
+    @staticmethod
+    def _dev_loop(rc, x_ref, x_traj, scan=None):
+        """(T, B) of a rollout_*_dev call, checked: ticks, x_traj's shape and, with scan = (sc, ranges),
+        scan_rows and the shape of ranges."""
+        T = int(rc.ticks)
         if T < 1:
             raise F110QPError("ticks must be >= 1")
-        S = self.config.x_ref_points or N
         B = int(x_ref.shape[0])
+        if scan is not None:
+            sc, ranges = scan
+            R, NR = int(sc.scan_rows), int(sc.num_ranges)
+            if R not in (1, T):
+                raise F110QPError(f"scan_rows must be 1 or ticks = {T}, got {R}")
         if tuple(x_traj.shape) != (T + 1, B, 3):
             raise F110QPError(f"x_traj must be [ticks + 1, B, 3] = {(T + 1, B, 3)}, got {tuple(x_traj.shape)}")
-        _devs((x_ref, "f64", 3 * S * B, "x_ref"),
-              (halfspace, "f32", 6 * B, "halfspace", self.config.gap_mode == GAP_INACTIVE),
-              (x_traj, "f64", 3 * B * (T + 1), "x_traj"), (u_lin_traj, "f64", 2 * B * (T + 1), "u_lin_traj"),
-              (u_applied, "f32", 2 * B * T, "u_applied"), (status_traj, "i32", B * T, "status_traj"),
-              (iters_traj, "i32", B * T, "iters_traj", True), (cost_traj, "f64", B * T, "cost_traj", True),
-              (u_plan, "f32", 2 * N * B * T, "u_plan", True), (x_plan, "f32", 3 * (N + 1) * B * T, "x_plan", True))
-        if stream is None:
-            stream = torch.cuda.current_stream(x_traj.device)
-        self._chk(self.lib.f110qp_rollout_dev(self._h, C.byref(rc), B, _tp(x_ref), _tp(halfspace), _tp(x_traj),
-                                              _tp(u_lin_traj), _tp(u_applied), _tp(status_traj), _tp(iters_traj),
-                                              _tp(cost_traj), _tp(u_plan), _tp(x_plan),
-                                              C.c_void_p(stream.cuda_stream)), "f110qp_rollout_dev")
+        if scan is not None and tuple(ranges.shape) != (R, B, NR):
+            raise F110QPError(f"ranges must be [scan_rows, B, num_ranges] = {(R, B, NR)}, got {tuple(ranges.shape)}")
+        return T, B
 
-    def rollout(self, x0, u_lin, x_ref, ticks, halfspace=None, plans=False, objective=False, rc=None):
-        """`ticks` closed-loop ticks from float64 host arrays x0 [B,3], u_lin [B,2], x_ref [B,S,3]
-        (f110qp_rollout, synchronous). rc: a RolloutConfig whose plant parameters to use (its ticks
-        is replaced). Returns a dict of numpy arrays: x_traj [T+1,B,3], u_lin_traj [T+1,B,2],
-        u_applied [T,B,2], status [T,B], iters [T,B]; plans=True adds u_plan [T,B,N,2] and x_plan
-        [T,B,N+1,3], objective=True adds cost [T,B]."""
-        N, T = self.horizon, int(ticks)
-        if T < 1:
-            raise F110QPError("ticks must be >= 1")
-        x0 = _f64(x0, (-1, 3), "x0")
-        B = x0.shape[0]
-        ul = _f64(u_lin, (B, 2), "u_lin")
-        xr = _f64(x_ref, (B, self.config.x_ref_points or N, 3), "x_ref")
-        hs = None if halfspace is None else np.ascontiguousarray(halfspace, np.float32).reshape(B, 6)
-        cfg = RolloutConfig()
-        C.memmove(C.byref(cfg), C.byref(rc if rc is not None else default_rollout_config()), C.sizeof(cfg))
-        cfg.ticks = T
-        out = {"x_traj": np.empty((T + 1, B, 3), np.float64), "u_lin_traj": np.empty((T + 1, B, 2), np.float64),
-               "u_applied": np.empty((T, B, 2), np.float32), "status": np.empty((T, B), np.int32),
-               "iters": np.empty((T, B), np.int32)}
-        out["x_traj"][0], out["u_lin_traj"][0] = x0, ul
-        if objective:
-            out["cost"] = np.empty((T, B), np.float64)
-        if plans:
-            out["u_plan"] = np.empty((T, B, N, 2), np.float32)
-            out["x_plan"] = np.empty((T, B, N + 1, 3), np.float32)
-        self._chk(self.lib.f110qp_rollout(self._h, C.byref(cfg), B, _p(xr), _p(hs), _p(out["x_traj"]),
-                                          _p(out["u_lin_traj"]), _p(out["u_applied"]), _p(out["status"]),
-                                          _p(out["iters"]), _p(out.get("cost")), _p(out.get("u_plan")),
-                                          _p(out.get("x_plan"))), "f110qp_rollout")
-        return out
+    def _traj_specs(self, T, B, x_traj, u_lin_traj, u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan):
+        """The _devs specs of the arrays every family records (a new per-tick array: one spec here or in
+        _record_specs)."""
+        N = self.horizon
+        return [(x_traj, "f64", 3 * B * (T + 1), "x_traj"), (u_lin_traj, "f64", 2 * B * (T + 1), "u_lin_traj"),
+                (u_applied, "f32", 2 * B * T, "u_applied"), (status_traj, "i32", B * T, "status_traj"),
+                (iters_traj, "i32", B * T, "iters_traj", True), (cost_traj, "f64", B * T, "cost_traj", True),
+                (u_plan, "f32", 2 * N * B * T, "u_plan", True), (x_plan, "f32", 3 * (N + 1) * B * T, "x_plan", True)]
 
-    def rollout_scan_dev(self, rc: RolloutConfig, sc: ScanConfig, x_ref, ranges, x_traj, u_lin_traj, u_applied,
-                         status_traj, iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None,
-                         stream=None):
-        """rollout_dev with the half-spaces of every tick computed at that tick's pose
-        (f110qp_rollout_scan_dev): ranges [sc.scan_rows,B,sc.num_ranges] f32 (scan_rows 1 or ticks)
-        replaces halfspace; hs_traj [T,B,2,3] f32 optional, row t the rows tick t solved with."""
+    @staticmethod
+    def _plan_specs(rp, B, table, waypoints, x_ref, have_path):
+        """The _devs specs of what a re-planning family reads and carries over."""
+        P, Tc, W = int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
+        return [(table, "f64", 3 * P * Tc, "table"), (waypoints, "f64", 2 * W, "waypoints", W == 0),
+                (x_ref, "f64", 3 * P * B, "x_ref"), (have_path, "i32", B, "have_path")]
+
+    @staticmethod
+    def _record_specs(T, B, hs_traj, kind_traj, plan_status_traj, best_traj_traj, best_global_traj, pose_traj):
+        """The _devs specs of a re-planning family's optional records."""
+        return [(hs_traj, "f32", 6 * B * T, "hs_traj", True), (kind_traj, "i32", B * T, "kind_traj", True),
+                (plan_status_traj, "i32", B * T, "plan_status_traj", True),
+                (best_traj_traj, "i32", B * T, "best_traj_traj", True),
+                (best_global_traj, "i32", B * T, "best_global_traj", True),
+                (pose_traj, "f64", 4 * B * (T + 1), "pose_traj", True)]
+
+    @staticmethod
+    def _stream(stream, x_traj):
         import torch
 
-        T, N = int(rc.ticks), self.horizon
-        if T < 1:
-            raise F110QPError("ticks must be >= 1")
-        S = self.config.x_ref_points or N
-        B, R, NR = int(x_ref.shape[0]), int(sc.scan_rows), int(sc.num_ranges)
-        if R not in (1, T):
-            raise F110QPError(f"scan_rows must be 1 or ticks = {T}, got {R}")
-        if tuple(x_traj.shape) != (T + 1, B, 3):
-            raise F110QPError(f"x_traj must be [ticks + 1, B, 3] = {(T + 1, B, 3)}, got {tuple(x_traj.shape)}")
-        if tuple(ranges.shape) != (R, B, NR):
-            raise F110QPError(f"ranges must be [scan_rows, B, num_ranges] = {(R, B, NR)}, got {tuple(ranges.shape)}")
-        _devs((x_ref, "f64", 3 * S * B, "x_ref"), (ranges, "f32", R * B * NR, "ranges"),
-              (x_traj, "f64", 3 * B * (T + 1), "x_traj"), (u_lin_traj, "f64", 2 * B * (T + 1), "u_lin_traj"),
-              (u_applied, "f32", 2 * B * T, "u_applied"), (status_traj, "i32", B * T, "status_traj"),
-              (iters_traj, "i32", B * T, "iters_traj", True), (cost_traj, "f64", B * T, "cost_traj", True),
-              (u_plan, "f32", 2 * N * B * T, "u_plan", True), (x_plan, "f32", 3 * (N + 1) * B * T, "x_plan", True),
-              (hs_traj, "f32", 6 * B * T, "hs_traj", True))
-        if stream is None:
-            stream = torch.cuda.current_stream(x_traj.device)
-        self._chk(self.lib.f110qp_rollout_scan_dev(self._h, C.byref(rc), C.byref(sc), B, _tp(x_ref), _tp(ranges),
-                                                   _tp(x_traj), _tp(u_lin_traj), _tp(u_applied), _tp(status_traj),
-                                                   _tp(iters_traj), _tp(cost_traj), _tp(u_plan), _tp(x_plan),
-                                                   _tp(hs_traj), C.c_void_p(stream.cuda_stream)),
-                  "f110qp_rollout_scan_dev")
+        return C.c_void_p((stream if stream is not None else torch.cuda.current_stream(x_traj.device)).cuda_stream)
 
-    def rollout_scan(self, x0, u_lin, x_ref, ranges, sc: ScanConfig, ticks, plans=False, objective=False,
-                     rows=True, rc=None):
-        """rollout() with the half-spaces of every tick computed at that tick's pose
-        (f110qp_rollout_scan, synchronous): ranges [B,R] (sc.scan_rows 1) or [ticks,B,R] (sc.scan_rows
-        ticks) float32. Returns rollout()'s dict; rows=True adds hs_traj [T,B,2,3]."""
-        N, T = self.horizon, int(ticks)
+    @staticmethod
+    def _host_start(x0, u_lin, ticks):
+        """(T, B, x0, u_lin) of a host rollout: float64 x0 [B,3] and u_lin [B,2]."""
+        T = int(ticks)
         if T < 1:
             raise F110QPError("ticks must be >= 1")
         x0 = _f64(x0, (-1, 3), "x0")
-        B = x0.shape[0]
-        ul = _f64(u_lin, (B, 2), "u_lin")
-        xr = _f64(x_ref, (B, self.config.x_ref_points or N, 3), "x_ref")
+        return T, x0.shape[0], x0, _f64(u_lin, (x0.shape[0], 2), "u_lin")
+
+    @staticmethod
+    def _host_ranges(ranges, sc, T, B):
         R = int(sc.scan_rows)
         if R not in (1, T):
             raise F110QPError(f"scan_rows must be 1 or ticks = {T}, got {R}")
@@ -761,12 +718,39 @@ class Solver:
         if rg.size != R * B * int(sc.num_ranges):
             raise F110QPError(f"ranges must hold [scan_rows, B, num_ranges] = {(R, B, int(sc.num_ranges))} values, "
                               f"got shape {rg.shape}")
+        return rg
+
+    @staticmethod
+    def _host_plan(rp, B, table, waypoints, x_ref, have_path):
+        """(x_ref, have_path, table, waypoints) of a host re-planning rollout: the paths the cars hold (copies:
+        the call updates them; default none) and the checked table and waypoints."""
+        P, Tc, W = int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
+        xr = np.full((B, P, 3), np.nan) if x_ref is None else _f64(x_ref, (B, P, 3), "x_ref").copy()
+        hv = np.zeros(B, np.int32) if have_path is None else np.array(have_path, np.int32).reshape(B)
+        tab = _f64(table, (Tc, P, 3), "table")
+        wp = np.ascontiguousarray(np.asarray(waypoints, np.float64)[:, :2])
+        if wp.shape[0] != W:
+            raise F110QPError(f"waypoints must hold num_waypoints = {W} rows, got {wp.shape[0]}")
+        return xr, hv, tab, wp
+
+    @staticmethod
+    def _ticks_config(rc, T):
+        """A copy of rc (default: f110qp_default_rollout_config) with its ticks replaced."""
         cfg = RolloutConfig()
         C.memmove(C.byref(cfg), C.byref(rc if rc is not None else default_rollout_config()), C.sizeof(cfg))
         cfg.ticks = T
+        return cfg
+
+    def _host_out(self, T, B, x0, ul, objective, plans, rows=False, scans=0, paths=None):
+        """The result dict of a host rollout, row 0 of the trajectories set. paths = (x_ref, have_path): a
+        re-planning family, with its records; scans: num_ranges of ranges_traj, 0 for none."""
+        N = self.horizon
+        i32 = lambda: np.empty((T, B), np.int32)  # noqa: E731
         out = {"x_traj": np.empty((T + 1, B, 3), np.float64), "u_lin_traj": np.empty((T + 1, B, 2), np.float64),
-               "u_applied": np.empty((T, B, 2), np.float32), "status": np.empty((T, B), np.int32),
-               "iters": np.empty((T, B), np.int32)}
+               "u_applied": np.empty((T, B, 2), np.float32), "status": i32(), "iters": i32()}
+        if paths is not None:
+            out.update({"x_ref": paths[0], "have_path": paths[1], "kind": i32(), "plan_status": i32(),
+                        "best_traj": i32(), "best_global": i32(), "pose_traj": np.empty((T + 1, B, 4), np.float64)})
         out["x_traj"][0], out["u_lin_traj"][0] = x0, ul
         if objective:
             out["cost"] = np.empty((T, B), np.float64)
@@ -775,10 +759,76 @@ class Solver:
             out["x_plan"] = np.empty((T, B, N + 1, 3), np.float32)
         if rows:
             out["hs_traj"] = np.empty((T, B, 2, 3), np.float32)
-        self._chk(self.lib.f110qp_rollout_scan(self._h, C.byref(cfg), C.byref(sc), B, _p(xr), _p(rg),
-                                               _p(out["x_traj"]), _p(out["u_lin_traj"]), _p(out["u_applied"]),
-                                               _p(out["status"]), _p(out["iters"]), _p(out.get("cost")),
-                                               _p(out.get("u_plan")), _p(out.get("x_plan")), _p(out.get("hs_traj"))),
+        if scans:
+            out["ranges_traj"] = np.empty((T, B, scans), np.float32)
+        return out
+
+    @staticmethod
+    def _out_args(out):
+        """The result dict's arrays in the ABI's order (the nine's seven outputs, then hs_traj and, for a
+        re-planning family, its records)."""
+        a = [_p(out["x_traj"]), _p(out["u_lin_traj"]), _p(out["u_applied"]), _p(out["status"]), _p(out["iters"]),
+             _p(out.get("cost")), _p(out.get("u_plan")), _p(out.get("x_plan"))]
+        if "kind" in out:
+            a += [_p(out.get("hs_traj")), _p(out["kind"]), _p(out["plan_status"]), _p(out["best_traj"]),
+                  _p(out["best_global"]), _p(out["pose_traj"])]
+        return a
+
+    def rollout_dev(self, rc: RolloutConfig, x_ref, halfspace, x_traj, u_lin_traj, u_applied, status_traj,
+                    iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, stream=None):
+        """rc.ticks closed-loop ticks on device (torch) tensors, enqueued on `stream`, asynchronous
+        and without a host synchronisation (f110qp_rollout_dev): x_ref [B,S,3] f64 and halfspace
+        [B,2,3] f32 held fixed; x_traj [T+1,B,3] / u_lin_traj [T+1,B,2] f64 with row 0 the start;
+        u_applied [T,B,2] f32, status_traj [T,B] i32; iters_traj [T,B] i32, cost_traj [T,B] f64,
+        u_plan [T,B,N,2] and x_plan [T,B,N+1,3] f32 optional."""
+        T, B = self._dev_loop(rc, x_ref, x_traj)
+        traj = (x_traj, u_lin_traj, u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan)
+        _devs((x_ref, "f64", 3 * (self.config.x_ref_points or self.horizon) * B, "x_ref"),
+              (halfspace, "f32", 6 * B, "halfspace", self.config.gap_mode == GAP_INACTIVE),
+              *self._traj_specs(T, B, *traj))
+        self._chk(self.lib.f110qp_rollout_dev(self._h, C.byref(rc), B, _tp(x_ref), _tp(halfspace), *map(_tp, traj),
+                                              self._stream(stream, x_traj)), "f110qp_rollout_dev")
+
+    def rollout(self, x0, u_lin, x_ref, ticks, halfspace=None, plans=False, objective=False, rc=None):
+        """`ticks` closed-loop ticks from float64 host arrays x0 [B,3], u_lin [B,2], x_ref [B,S,3]
+        (f110qp_rollout, synchronous). rc: a RolloutConfig whose plant parameters to use (its ticks
+        is replaced). Returns a dict of numpy arrays: x_traj [T+1,B,3], u_lin_traj [T+1,B,2],
+        u_applied [T,B,2], status [T,B], iters [T,B]; plans=True adds u_plan [T,B,N,2] and x_plan
+        [T,B,N+1,3], objective=True adds cost [T,B]."""
+        T, B, x0, ul = self._host_start(x0, u_lin, ticks)
+        xr = _f64(x_ref, (B, self.config.x_ref_points or self.horizon, 3), "x_ref")
+        hs = None if halfspace is None else np.ascontiguousarray(halfspace, np.float32).reshape(B, 6)
+        out = self._host_out(T, B, x0, ul, objective, plans)
+        self._chk(self.lib.f110qp_rollout(self._h, C.byref(self._ticks_config(rc, T)), B, _p(xr), _p(hs),
+                                          *self._out_args(out)), "f110qp_rollout")
+        return out
+
+    def rollout_scan_dev(self, rc: RolloutConfig, sc: ScanConfig, x_ref, ranges, x_traj, u_lin_traj, u_applied,
+                         status_traj, iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None,
+                         stream=None):
+        """rollout_dev with the half-spaces of every tick computed at that tick's pose
+        (f110qp_rollout_scan_dev): ranges [sc.scan_rows,B,sc.num_ranges] f32 (scan_rows 1 or ticks)
+        replaces halfspace; hs_traj [T,B,2,3] f32 optional, row t the rows tick t solved with."""
+        T, B = self._dev_loop(rc, x_ref, x_traj, (sc, ranges))
+        traj = (x_traj, u_lin_traj, u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan)
+        _devs((x_ref, "f64", 3 * (self.config.x_ref_points or self.horizon) * B, "x_ref"),
+              (ranges, "f32", int(sc.scan_rows) * B * int(sc.num_ranges), "ranges"),
+              *self._traj_specs(T, B, *traj), (hs_traj, "f32", 6 * B * T, "hs_traj", True))
+        self._chk(self.lib.f110qp_rollout_scan_dev(self._h, C.byref(rc), C.byref(sc), B, _tp(x_ref), _tp(ranges),
+                                                   *map(_tp, traj), _tp(hs_traj), self._stream(stream, x_traj)),
+                  "f110qp_rollout_scan_dev")
+
+    def rollout_scan(self, x0, u_lin, x_ref, ranges, sc: ScanConfig, ticks, plans=False, objective=False,
+                     rows=True, rc=None):
+        """rollout() with the half-spaces of every tick computed at that tick's pose
+        (f110qp_rollout_scan, synchronous): ranges [B,R] (sc.scan_rows 1) or [ticks,B,R] (sc.scan_rows
+        ticks) float32. Returns rollout()'s dict; rows=True adds hs_traj [T,B,2,3]."""
+        T, B, x0, ul = self._host_start(x0, u_lin, ticks)
+        xr = _f64(x_ref, (B, self.config.x_ref_points or self.horizon, 3), "x_ref")
+        rg = self._host_ranges(ranges, sc, T, B)
+        out = self._host_out(T, B, x0, ul, objective, plans, rows)
+        self._chk(self.lib.f110qp_rollout_scan(self._h, C.byref(self._ticks_config(rc, T)), C.byref(sc), B, _p(xr),
+                                               _p(rg), *self._out_args(out), _p(out.get("hs_traj"))),
                   "f110qp_rollout_scan")
         return out
 
@@ -791,39 +841,16 @@ class Solver:
         asynchronous: rollout_scan_dev's arguments plus table [Tc,P,3] f64, waypoints [W,2] f64, x_ref
         [B,P,3] f64 and have_path [B] i32 (both in/out), and the optional kind_traj, plan_status_traj,
         best_traj_traj, best_global_traj [T,B] i32 and pose_traj [T+1,B,4] f64."""
-        import torch
-
-        T, N = int(rc.ticks), self.horizon
-        if T < 1:
-            raise F110QPError("ticks must be >= 1")
-        P, Tc, W = int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
-        B, R, NR = int(x_ref.shape[0]), int(sc.scan_rows), int(sc.num_ranges)
-        if R not in (1, T):
-            raise F110QPError(f"scan_rows must be 1 or ticks = {T}, got {R}")
-        if tuple(x_traj.shape) != (T + 1, B, 3):
-            raise F110QPError(f"x_traj must be [ticks + 1, B, 3] = {(T + 1, B, 3)}, got {tuple(x_traj.shape)}")
-        if tuple(ranges.shape) != (R, B, NR):
-            raise F110QPError(f"ranges must be [scan_rows, B, num_ranges] = {(R, B, NR)}, got {tuple(ranges.shape)}")
-        _devs((table, "f64", 3 * P * Tc, "table"), (waypoints, "f64", 2 * W, "waypoints", W == 0),
-              (x_ref, "f64", 3 * P * B, "x_ref"), (have_path, "i32", B, "have_path"),
-              (ranges, "f32", R * B * NR, "ranges"),
-              (x_traj, "f64", 3 * B * (T + 1), "x_traj"), (u_lin_traj, "f64", 2 * B * (T + 1), "u_lin_traj"),
-              (u_applied, "f32", 2 * B * T, "u_applied"), (status_traj, "i32", B * T, "status_traj"),
-              (iters_traj, "i32", B * T, "iters_traj", True), (cost_traj, "f64", B * T, "cost_traj", True),
-              (u_plan, "f32", 2 * N * B * T, "u_plan", True), (x_plan, "f32", 3 * (N + 1) * B * T, "x_plan", True),
-              (hs_traj, "f32", 6 * B * T, "hs_traj", True), (kind_traj, "i32", B * T, "kind_traj", True),
-              (plan_status_traj, "i32", B * T, "plan_status_traj", True),
-              (best_traj_traj, "i32", B * T, "best_traj_traj", True),
-              (best_global_traj, "i32", B * T, "best_global_traj", True),
-              (pose_traj, "f64", 4 * B * (T + 1), "pose_traj", True))
-        if stream is None:
-            stream = torch.cuda.current_stream(x_traj.device)
+        T, B = self._dev_loop(rc, x_ref, x_traj, (sc, ranges))
+        plan = (table, waypoints, x_ref, have_path)
+        traj = (x_traj, u_lin_traj, u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan)
+        rec = (hs_traj, kind_traj, plan_status_traj, best_traj_traj, best_global_traj, pose_traj)
+        _devs(*self._plan_specs(rp, B, *plan),
+              (ranges, "f32", int(sc.scan_rows) * B * int(sc.num_ranges), "ranges"),
+              *self._traj_specs(T, B, *traj), *self._record_specs(T, B, *rec))
         self._chk(self.lib.f110qp_rollout_replan_dev(
-            self._h, C.byref(rc), C.byref(sc), C.byref(rp), B, _tp(table), _tp(waypoints), _tp(x_ref), _tp(have_path),
-            _tp(ranges), _tp(x_traj), _tp(u_lin_traj), _tp(u_applied), _tp(status_traj), _tp(iters_traj),
-            _tp(cost_traj), _tp(u_plan), _tp(x_plan), _tp(hs_traj), _tp(kind_traj), _tp(plan_status_traj),
-            _tp(best_traj_traj), _tp(best_global_traj), _tp(pose_traj), C.c_void_p(stream.cuda_stream)),
-            "f110qp_rollout_replan_dev")
+            self._h, C.byref(rc), C.byref(sc), C.byref(rp), B, *map(_tp, plan), _tp(ranges), *map(_tp, traj),
+            *map(_tp, rec), self._stream(stream, x_traj)), "f110qp_rollout_replan_dev")
 
     def rollout_replan(self, x0, u_lin, ranges, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
                        x_ref=None, have_path=None, plans=False, objective=False, rows=True, rc=None):
@@ -833,48 +860,13 @@ class Solver:
         every car plans on tick 0); copies of both come back updated, so a second call can continue.
         Returns rollout_scan()'s dict plus x_ref, have_path, kind, plan_status, best_traj, best_global
         [T,B] and pose_traj [T+1,B,4]."""
-        N, T = self.horizon, int(ticks)
-        if T < 1:
-            raise F110QPError("ticks must be >= 1")
-        x0 = _f64(x0, (-1, 3), "x0")
-        B = x0.shape[0]
-        ul = _f64(u_lin, (B, 2), "u_lin")
-        P, Tc, W = int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
-        xr = np.full((B, P, 3), np.nan) if x_ref is None else _f64(x_ref, (B, P, 3), "x_ref").copy()
-        hv = np.zeros(B, np.int32) if have_path is None else np.array(have_path, np.int32).reshape(B)
-        tab = _f64(table, (Tc, P, 3), "table")
-        wp = np.ascontiguousarray(np.asarray(waypoints, np.float64)[:, :2])
-        if wp.shape[0] != W:
-            raise F110QPError(f"waypoints must hold num_waypoints = {W} rows, got {wp.shape[0]}")
-        R = int(sc.scan_rows)
-        if R not in (1, T):
-            raise F110QPError(f"scan_rows must be 1 or ticks = {T}, got {R}")
-        rg = np.ascontiguousarray(ranges, np.float32)
-        if rg.size != R * B * int(sc.num_ranges):
-            raise F110QPError(f"ranges must hold [scan_rows, B, num_ranges] = {(R, B, int(sc.num_ranges))} values, "
-                              f"got shape {rg.shape}")
-        cfg = RolloutConfig()
-        C.memmove(C.byref(cfg), C.byref(rc if rc is not None else default_rollout_config()), C.sizeof(cfg))
-        cfg.ticks = T
-        i32 = lambda: np.empty((T, B), np.int32)  # noqa: E731
-        out = {"x_traj": np.empty((T + 1, B, 3), np.float64), "u_lin_traj": np.empty((T + 1, B, 2), np.float64),
-               "u_applied": np.empty((T, B, 2), np.float32), "status": i32(), "iters": i32(), "x_ref": xr,
-               "have_path": hv, "kind": i32(), "plan_status": i32(), "best_traj": i32(), "best_global": i32(),
-               "pose_traj": np.empty((T + 1, B, 4), np.float64)}
-        out["x_traj"][0], out["u_lin_traj"][0] = x0, ul
-        if objective:
-            out["cost"] = np.empty((T, B), np.float64)
-        if plans:
-            out["u_plan"] = np.empty((T, B, N, 2), np.float32)
-            out["x_plan"] = np.empty((T, B, N + 1, 3), np.float32)
-        if rows:
-            out["hs_traj"] = np.empty((T, B, 2, 3), np.float32)
+        T, B, x0, ul = self._host_start(x0, u_lin, ticks)
+        xr, hv, tab, wp = self._host_plan(rp, B, table, waypoints, x_ref, have_path)
+        rg = self._host_ranges(ranges, sc, T, B)
+        out = self._host_out(T, B, x0, ul, objective, plans, rows, paths=(xr, hv))
         self._chk(self.lib.f110qp_rollout_replan(
-            self._h, C.byref(cfg), C.byref(sc), C.byref(rp), B, _p(tab), _p(wp) if W else None, _p(xr), _p(hv), _p(rg),
-            _p(out["x_traj"]), _p(out["u_lin_traj"]), _p(out["u_applied"]), _p(out["status"]), _p(out["iters"]),
-            _p(out.get("cost")), _p(out.get("u_plan")), _p(out.get("x_plan")), _p(out.get("hs_traj")),
-            _p(out["kind"]), _p(out["plan_status"]), _p(out["best_traj"]), _p(out["best_global"]),
-            _p(out["pose_traj"])), "f110qp_rollout_replan")
+            self._h, C.byref(self._ticks_config(rc, T)), C.byref(sc), C.byref(rp), B, _p(tab),
+            _p(wp) if wp.shape[0] else None, _p(xr), _p(hv), _p(rg), *self._out_args(out)), "f110qp_rollout_replan")
         return out
 
     def rollout_world_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, table,
@@ -885,43 +877,23 @@ class Solver:
         """rollout_replan_dev with every tick's scan cast at that tick's pose (f110qp_rollout_world_dev): wc
         and circles [world_rows,C,3] f64 replace ranges, sc.scan_rows is not read, and the optional
         ranges_traj [T,B,num_ranges] f32 records every car's scan of every tick."""
-        import torch
-
-        T, N = int(rc.ticks), self.horizon
-        if T < 1:
-            raise F110QPError("ticks must be >= 1")
-        P, Tc, W = int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
-        B, NR = int(x_ref.shape[0]), int(sc.num_ranges)
+        T, B = self._dev_loop(rc, x_ref, x_traj)
         Cn, WR = int(wc.num_circles), int(wc.world_rows)
-        if tuple(x_traj.shape) != (T + 1, B, 3):
-            raise F110QPError(f"x_traj must be [ticks + 1, B, 3] = {(T + 1, B, 3)}, got {tuple(x_traj.shape)}")
         if WR not in (1, B):
             raise F110QPError(f"world_rows must be 1 or B = {B}, got {WR}")
         if _race is not None:
             _check_race(_race, B)
-        _devs((table, "f64", 3 * P * Tc, "table"), (waypoints, "f64", 2 * W, "waypoints", W == 0),
-              (x_ref, "f64", 3 * P * B, "x_ref"), (have_path, "i32", B, "have_path"),
-              (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
-              (x_traj, "f64", 3 * B * (T + 1), "x_traj"), (u_lin_traj, "f64", 2 * B * (T + 1), "u_lin_traj"),
-              (u_applied, "f32", 2 * B * T, "u_applied"), (status_traj, "i32", B * T, "status_traj"),
-              (iters_traj, "i32", B * T, "iters_traj", True), (cost_traj, "f64", B * T, "cost_traj", True),
-              (u_plan, "f32", 2 * N * B * T, "u_plan", True), (x_plan, "f32", 3 * (N + 1) * B * T, "x_plan", True),
-              (hs_traj, "f32", 6 * B * T, "hs_traj", True), (kind_traj, "i32", B * T, "kind_traj", True),
-              (plan_status_traj, "i32", B * T, "plan_status_traj", True),
-              (best_traj_traj, "i32", B * T, "best_traj_traj", True),
-              (best_global_traj, "i32", B * T, "best_global_traj", True),
-              (pose_traj, "f64", 4 * B * (T + 1), "pose_traj", True),
-              (ranges_traj, "f32", T * B * NR, "ranges_traj", True))
-        if stream is None:
-            stream = torch.cuda.current_stream(x_traj.device)
+        plan = (table, waypoints, x_ref, have_path)
+        traj = (x_traj, u_lin_traj, u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan)
+        rec = (hs_traj, kind_traj, plan_status_traj, best_traj_traj, best_global_traj, pose_traj)
+        _devs(*self._plan_specs(rp, B, *plan), (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
+              *self._traj_specs(T, B, *traj), *self._record_specs(T, B, *rec),
+              (ranges_traj, "f32", T * B * int(sc.num_ranges), "ranges_traj", True))
         name = "f110qp_rollout_world_dev" if _race is None else "f110qp_rollout_race_dev"
         self._chk(getattr(self.lib, name)(
             self._h, C.byref(rc), C.byref(sc), C.byref(rp), C.byref(wc), *([] if _race is None else [C.byref(_race)]),
-            B, _tp(table), _tp(waypoints), _tp(x_ref),
-            _tp(have_path), _tp(circles), _tp(x_traj), _tp(u_lin_traj), _tp(u_applied), _tp(status_traj),
-            _tp(iters_traj), _tp(cost_traj), _tp(u_plan), _tp(x_plan), _tp(hs_traj), _tp(kind_traj),
-            _tp(plan_status_traj), _tp(best_traj_traj), _tp(best_global_traj), _tp(pose_traj), _tp(ranges_traj),
-            C.c_void_p(stream.cuda_stream)), name)
+            B, *map(_tp, plan), _tp(circles), *map(_tp, traj), *map(_tp, rec), _tp(ranges_traj),
+            self._stream(stream, x_traj)), name)
 
     def rollout_race_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
                          table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj, u_applied, status_traj,
@@ -944,19 +916,8 @@ class Solver:
         """rollout_replan() in a world of circles (f110qp_rollout_world, synchronous): circles [C,3] (one world
         for all cars) or [B,C,3] float64 replace ranges; wc defaults to f110qp_default_world_config with
         num_circles and world_rows taken from the array. scans=True adds ranges_traj [T,B,num_ranges]."""
-        N, T = self.horizon, int(ticks)
-        if T < 1:
-            raise F110QPError("ticks must be >= 1")
-        x0 = _f64(x0, (-1, 3), "x0")
-        B = x0.shape[0]
-        ul = _f64(u_lin, (B, 2), "u_lin")
-        P, Tc, W = int(rp.plan.traj_discrete), int(rp.plan.steer_discrete) + 1, int(rp.num_waypoints)
-        xr = np.full((B, P, 3), np.nan) if x_ref is None else _f64(x_ref, (B, P, 3), "x_ref").copy()
-        hv = np.zeros(B, np.int32) if have_path is None else np.array(have_path, np.int32).reshape(B)
-        tab = _f64(table, (Tc, P, 3), "table")
-        wp = np.ascontiguousarray(np.asarray(waypoints, np.float64)[:, :2])
-        if wp.shape[0] != W:
-            raise F110QPError(f"waypoints must hold num_waypoints = {W} rows, got {wp.shape[0]}")
+        T, B, x0, ul = self._host_start(x0, u_lin, ticks)
+        xr, hv, tab, wp = self._host_plan(rp, B, table, waypoints, x_ref, have_path)
         if not isinstance(circles, np.ndarray) or circles.dtype != np.float64 or circles.ndim not in (2, 3) \
                 or circles.shape[-1] != 3:
             raise F110QPError("circles must be a float64 numpy array [C, 3] or [B, C, 3]")
@@ -969,32 +930,12 @@ class Solver:
             raise F110QPError(f"circles must hold one world or B = {B} worlds, got {w.world_rows}")
         if _race is not None:
             _check_race(_race, B)
-        cfg = RolloutConfig()
-        C.memmove(C.byref(cfg), C.byref(rc if rc is not None else default_rollout_config()), C.sizeof(cfg))
-        cfg.ticks = T
-        i32 = lambda: np.empty((T, B), np.int32)  # noqa: E731
-        out = {"x_traj": np.empty((T + 1, B, 3), np.float64), "u_lin_traj": np.empty((T + 1, B, 2), np.float64),
-               "u_applied": np.empty((T, B, 2), np.float32), "status": i32(), "iters": i32(), "x_ref": xr,
-               "have_path": hv, "kind": i32(), "plan_status": i32(), "best_traj": i32(), "best_global": i32(),
-               "pose_traj": np.empty((T + 1, B, 4), np.float64)}
-        out["x_traj"][0], out["u_lin_traj"][0] = x0, ul
-        if objective:
-            out["cost"] = np.empty((T, B), np.float64)
-        if plans:
-            out["u_plan"] = np.empty((T, B, N, 2), np.float32)
-            out["x_plan"] = np.empty((T, B, N + 1, 3), np.float32)
-        if rows:
-            out["hs_traj"] = np.empty((T, B, 2, 3), np.float32)
-        if scans:
-            out["ranges_traj"] = np.empty((T, B, int(sc.num_ranges)), np.float32)
+        out = self._host_out(T, B, x0, ul, objective, plans, rows, int(sc.num_ranges) if scans else 0, (xr, hv))
         name = "f110qp_rollout_world" if _race is None else "f110qp_rollout_race"
         self._chk(getattr(self.lib, name)(
-            self._h, C.byref(cfg), C.byref(sc), C.byref(rp), C.byref(w), *([] if _race is None else [C.byref(_race)]),
-            B, _p(tab), _p(wp) if W else None, _p(xr),
-            _p(hv), _p(ci) if ci.size else None, _p(out["x_traj"]), _p(out["u_lin_traj"]), _p(out["u_applied"]),
-            _p(out["status"]), _p(out["iters"]), _p(out.get("cost")), _p(out.get("u_plan")), _p(out.get("x_plan")),
-            _p(out.get("hs_traj")), _p(out["kind"]), _p(out["plan_status"]), _p(out["best_traj"]),
-            _p(out["best_global"]), _p(out["pose_traj"]), _p(out.get("ranges_traj"))), name)
+            self._h, C.byref(self._ticks_config(rc, T)), C.byref(sc), C.byref(rp), C.byref(w),
+            *([] if _race is None else [C.byref(_race)]), B, _p(tab), _p(wp) if wp.shape[0] else None, _p(xr), _p(hv),
+            _p(ci) if ci.size else None, *self._out_args(out), _p(out.get("ranges_traj"))), name)
         return out
 
     def rollout_race(self, x0, u_lin, circles, race: RaceConfig, sc: ScanConfig, rp: ReplanConfig, table, waypoints,
