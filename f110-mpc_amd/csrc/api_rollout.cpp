@@ -1,7 +1,8 @@
 // api_rollout.cpp — the C ABI's closed loops on the device (include/f110qp.h): the plant step and the
 // rollout (f110qp_advance_dev, f110qp_rollout[_dev]), the rollout with gap rows from the scans
 // (f110qp_rollout_scan[_dev]), with re-planning (f110qp_rollout_replan[_dev]), in a world of circles
-// (f110qp_rollout_world[_dev]) and with race-mates (f110qp_rollout_race[_dev]), and the parts of each.
+// (f110qp_rollout_world[_dev]), with race-mates (f110qp_rollout_race[_dev]) and with contact
+// (f110qp_clearance_dev, f110qp_rollout_contact[_dev]), and the parts of each.
 // Host-side responsibilities only: argument validation, workspaces, H2D/D2H of the host-pointer calls
 // (the staging table of api_stage.h). No C++ exception crosses this boundary.
 #include <cmath>
@@ -50,7 +51,8 @@ static int replan_params(const f110qp_replan_config* rp, f110qp::PlanKParams* K)
   return F110QP_OK;
 }
 
-// The world of f110qp_cast_scans_dev and the world rollouts, checked; with sc's geometry into *P.
+// The world of f110qp_cast_scans_dev, f110qp_clearance_dev and the world rollouts, checked; with sc's
+// geometry (sc null: none) into *P.
 static int world_params(const f110qp_scan_config* sc, const f110qp_world_config* wc, int batch,
                         const void* circles, f110qp::CastParams* P) {
   if (!wc) return fail(F110QP_ERR_INVALID, "world config is NULL");
@@ -61,9 +63,11 @@ static int world_params(const f110qp_scan_config* sc, const f110qp_world_config*
   if (wc->world_rows != 1 && wc->world_rows != batch)
     return fail(F110QP_ERR_INVALID, "world_rows must be 1 or batch");
   if (wc->num_circles > 0 && !circles) return fail(F110QP_ERR_INVALID, "num_circles > 0 needs the circles");
-  P->nr = sc->num_ranges;
-  P->angle_min = sc->angle_min;
-  P->angle_inc = sc->angle_increment;
+  if (sc) {
+    P->nr = sc->num_ranges;
+    P->angle_min = sc->angle_min;
+    P->angle_inc = sc->angle_increment;
+  }
   P->C = wc->num_circles;
   P->world_rows = wc->world_rows;
   P->lidar_offset = wc->lidar_offset;
@@ -87,6 +91,15 @@ static int race_params(const f110qp_race_config* race, int batch, int num_circle
   return F110QP_OK;
 }
 
+// The contact config of f110qp_rollout_contact[_dev], checked.
+static int contact_params(const f110qp_contact_config* cc) {
+  if (!cc) return fail(F110QP_ERR_INVALID, "contact config is NULL");
+  if (cc->stop_on_contact != 0 && cc->stop_on_contact != 1)
+    return fail(F110QP_ERR_INVALID, "stop_on_contact must be 0 or 1");
+  if (!std::isfinite(cc->margin)) return fail(F110QP_ERR_INVALID, "margin must be finite");
+  return F110QP_OK;
+}
+
 // The scan geometry of the re-planning kernels' argument records (ReplanStart, ReplanStep).
 template <typename S>
 static void scan_geometry(S* s, const f110qp_scan_config& sc) {
@@ -99,8 +112,8 @@ static void scan_geometry(S* s, const f110qp_scan_config& sc) {
 
 // The family of a rollout call, in the order each was built on the one before: from kScan a scan
 // config is read, from kReplan the loop re-plans, from kWorld the scans are cast (so neither `ranges`
-// nor sc->scan_rows is read), and kRace casts see the race-mates.
-enum Family { kPlain, kScan, kReplan, kWorld, kRace };
+// nor sc->scan_rows is read), kRace casts see the race-mates, and kContact records every row's clearance.
+enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact };
 
 // The configs of a rollout call as the caller gave them and, once check_args has passed, the
 // kernels' parameters.
@@ -251,6 +264,14 @@ struct WorldLoop {
   f110qp::RaceParams Q;
 };
 
+// f110qp_rollout_contact[_dev]: the race rollout with one clearance launch per row of x_traj, which also
+// keeps crash_tick; stop: the plant step is the parking one. The arrays are device pointers here.
+struct ContactLoop {
+  bool stop;
+  double margin;
+  ContactIO io;
+};
+
 static hipError_t world_cast(const WorldLoop& wl, int batch, const int* list, const int* count, const double* x,
                              float* ranges, hipStream_t s) {
   return wl.race ? f110qp::launch_cast_scans_race(wl.P, wl.Q, batch, list, count, x, wl.circles, ranges, s)
@@ -263,8 +284,10 @@ static hipError_t world_cast(const WorldLoop& wl, int batch, const int* list, co
 // wl (the world rollout; r.ranges is not read): per tick the cast in front of the listed plan, on that
 // plan's list or, with ranges_traj, for all cars into row t. The gap records are those of one all-cars
 // cast at row 0 in front of the loop, held as at scan_rows = 1.
+// cl (the contact rollout, with wl): one clearance launch on row 0 behind the start kernel and one on row
+// t + 1 behind tick t's plant step, each marking crash_tick; with cl->stop the plant step parks.
 static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, const ReplanIO& r, hipStream_t s,
-                        const WorldLoop* wl) {
+                        const WorldLoop* wl, const ContactLoop* cl = nullptr) {
   const f110qp_scan_config& sc = *cfg.sc;
   const f110qp_replan_config& rp = *cfg.rp;
   const ReplanTraj& tr = r.tr;
@@ -335,6 +358,14 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
     scan_geometry(&st, sc);
     if ((e = f110qp::launch_replan_start(io.B, st, s)) != hipSuccess) return hip_fail(e, "re-planning start launch");
   }
+  // row t's clearances into clear_traj / nearest_traj, crash_tick started (row 0) or kept up
+  auto clearance_row = [&](size_t t) {
+    const f110qp::ClearParams cp{wl->P.C, wl->P.world_rows};
+    const f110qp::ContactMark mk{cl->io.crash_tick, (int)t, t == 0, cl->margin};
+    return f110qp::launch_clearance(cp, wl->Q, io.B, 1, io.x(t), wl->circles, cl->io.clear_traj + t * B,
+                                    cl->io.nearest_traj ? cl->io.nearest_traj + t * B : nullptr, mk, s);
+  };
+  if (cl && (e = clearance_row(0)) != hipSuccess) return hip_fail(e, "clearance launch");
   for (size_t t = 0; t < T; t++) {
     int* ps_t = tr.plan_status ? tr.plan_status + t * B : wi + i_ps;
     const float* scan_t = wl ? scan_row(t) : ranges + (scan_rows == 1 ? 0 : t * B * nr);
@@ -380,8 +411,16 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
     S.gap = rows_on && !last ? w.rec + (scan_rows == 1 ? 0 : (t + 1) * B) : nullptr;
     S.hs_next = rows_on && !last ? w.rows + (t + 1) * w.rstep : nullptr;
     scan_geometry(&S, sc);
-    if ((e = f110qp::launch_advance_replan(cfg.ap, io.B, io.N, S, s)) != hipSuccess)
-      return hip_fail(e, "plant step launch");
+    if (cl && cl->stop) {
+      S.crash_tick = cl->io.crash_tick;
+      S.u_lin = io.ul(t);
+      S.pose = pose_row(t);
+      e = f110qp::launch_advance_replan_park(cfg.ap, io.B, io.N, S, s);
+    } else {
+      e = f110qp::launch_advance_replan(cfg.ap, io.B, io.N, S, s);
+    }
+    if (e != hipSuccess) return hip_fail(e, "plant step launch");
+    if (cl && (e = clearance_row(t + 1)) != hipSuccess) return hip_fail(e, "clearance launch");
   }
   return F110QP_OK;
 }
@@ -441,9 +480,10 @@ static int rollout_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
   return stage_out(c, L, s);
 }
 
-// f110qp_rollout_replan (wl null) and f110qp_rollout_world / _race (wl, its circles and ranges_traj the
-// host's) on checked host pointers.
-static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, const ReplanIO& r, const WorldLoop* wl) {
+// f110qp_rollout_replan (wl null), f110qp_rollout_world / _race (wl, its circles and ranges_traj the
+// host's) and f110qp_rollout_contact (wl and cl, its three records the host's) on checked host pointers.
+static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, const ReplanIO& r, const WorldLoop* wl,
+                       const ContactLoop* cl = nullptr) {
   hipStream_t s;
   int rv = host_stream(c, &s);
   if (rv) return rv;
@@ -451,9 +491,11 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
   RolloutIO d;
   ReplanIO dr;
   WorldIO hw{}, dw{};
+  ContactLoop dcl{};
   if (wl) hw = WorldIO{wl->circles, (size_t)wl->P.world_rows * (size_t)wl->P.C * 3 * 8, wl->ranges_traj};
+  if (cl) dcl = *cl;
   stage::replan_fields(L, io, &d, r, &dr, *cfg.sc, (size_t)cfg.K.T, (size_t)cfg.K.P, (size_t)cfg.rp->num_waypoints,
-                       wl ? &hw : nullptr, &dw);
+                       wl ? &hw : nullptr, &dw, cl ? &cl->io : nullptr, &dcl.io);
   if ((rv = stage_in(c, L, s))) return rv;
   WorldLoop dwl{};
   if (wl) {
@@ -461,7 +503,7 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
     dwl.circles = dw.circles;
     dwl.ranges_traj = dw.ranges_traj;
   }
-  if ((rv = replan_ticks(c, cfg, d, dr, s, wl ? &dwl : nullptr))) return rv;
+  if ((rv = replan_ticks(c, cfg, d, dr, s, wl ? &dwl : nullptr, cl ? &dcl : nullptr))) return rv;
   return stage_out(c, L, s);
 }
 
@@ -485,19 +527,28 @@ static int replan_call(f110qp_ctx* c, LoopCfg cfg, RolloutIO io, const ReplanIO&
   return w.host ? replan_host(c, cfg, io, r, nullptr) : replan_ticks(c, cfg, io, r, w.stream, nullptr);
 }
 
-// f110qp_rollout_world[_dev] (kWorld; race not read) and f110qp_rollout_race[_dev] (kRace).
+// f110qp_rollout_world[_dev] (kWorld; race not read), f110qp_rollout_race[_dev] (kRace) and
+// f110qp_rollout_contact[_dev] (kContact: cc and the records k).
 static int world_call(f110qp_ctx* c, LoopCfg cfg, const f110qp_world_config* wc, const f110qp_race_config* race,
-                      RolloutIO io, const ReplanIO& r, const double* circles, float* rgt, Where w) {
+                      RolloutIO io, const ReplanIO& r, const double* circles, float* rgt, Where w,
+                      const f110qp_contact_config* cc = nullptr, const ContactIO* k = nullptr) {
   WorldLoop wl{};
   int rv = check_args(c, &cfg, &io, nullptr, nullptr, &r);
   if (rv) return rv;
   if ((rv = world_params(cfg.sc, wc, io.B, circles, &wl.P))) return rv;
-  wl.race = cfg.fam == kRace;
+  wl.race = cfg.fam >= kRace;
   if (wl.race && (rv = race_params(race, io.B, wc->num_circles, &wl.Q))) return rv;
+  const bool contact = cfg.fam == kContact;
+  if (contact && (rv = contact_params(cc))) return rv;
   if (io.B == 0) return F110QP_OK;
+  if (contact && (!k->clear_traj || !k->crash_tick))
+    return fail(F110QP_ERR_INVALID, "clear_traj/crash_tick must be non-NULL");
   wl.circles = circles;
   wl.ranges_traj = rgt;
-  return w.host ? replan_host(c, cfg, io, r, &wl) : replan_ticks(c, cfg, io, r, w.stream, &wl);
+  ContactLoop cl{};
+  if (contact) cl = ContactLoop{cc->stop_on_contact == 1, cc->margin, *k};
+  const ContactLoop* clp = contact ? &cl : nullptr;
+  return w.host ? replan_host(c, cfg, io, r, &wl, clp) : replan_ticks(c, cfg, io, r, w.stream, &wl, clp);
 }
 
 extern "C" {
@@ -860,6 +911,61 @@ int f110qp_rollout_race(f110qp_ctx* c, const f110qp_rollout_config* rc, const f1
   const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
   const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
   return world_call(c, LoopCfg{kRace, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host());
+}
+
+// ---- contact: clearance to walls and race-mates, crashed cars park (f110qp_clearance_dev, ----------------
+// ---- f110qp_rollout_contact[_dev]) ---------------------------------------------------------------------
+
+void f110qp_default_contact_config(f110qp_contact_config* cc) {
+  if (!cc) return;
+  std::memset(cc, 0, sizeof(*cc));
+  cc->stop_on_contact = 0;
+  cc->margin = 0.0;
+}
+
+int f110qp_clearance_dev(const f110qp_world_config* wc, const f110qp_race_config* race, int batch, int rows,
+                         const double* x, const double* circles, double* clearance, int* nearest, void* stream) {
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  f110qp::CastParams P;
+  f110qp::RaceParams Q;
+  int rv = world_params(nullptr, wc, batch, circles, &P);
+  if (rv) return rv;
+  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
+  if (rows < 1) return fail(F110QP_ERR_INVALID, "rows must be >= 1");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !clearance) return fail(F110QP_ERR_INVALID, "x/clearance must be non-NULL");
+  if ((long long)rows * batch > (1ll << 30)) return fail(F110QP_ERR_INVALID, "rows x batch too large");
+  const hipError_t e = f110qp::launch_clearance(f110qp::ClearParams{P.C, P.world_rows}, Q, batch, rows, x, circles,
+                                                clearance, nearest, f110qp::ContactMark{nullptr, 0, 0, 0.0},
+                                                (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "clearance launch");
+  return F110QP_OK;
+}
+
+int f110qp_rollout_contact_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                               const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                               const f110qp_race_config* race, const f110qp_contact_config* cc, int batch,
+                               const double* table, const double* wp, double* xr, int* have, const double* circles,
+                               double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up,
+                               float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset,
+                               float* rgt, double* clt, int* nrt, int* crash, void* stream) {
+  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
+  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
+  const ContactIO k{clt, nrt, crash};
+  return world_call(c, LoopCfg{kContact, rc, sc, rp}, wc, race, io, r, circles, rgt, on_stream(stream), cc, &k);
+}
+
+int f110qp_rollout_contact(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                           const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                           const f110qp_race_config* race, const f110qp_contact_config* cc, int batch,
+                           const double* table, const double* wp, double* xr, int* have, const double* circles,
+                           double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up, float* xp,
+                           float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset, float* rgt, double* clt,
+                           int* nrt, int* crash) {
+  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
+  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
+  const ContactIO k{clt, nrt, crash};
+  return world_call(c, LoopCfg{kContact, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k);
 }
 
 }  // extern "C"

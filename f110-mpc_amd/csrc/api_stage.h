@@ -69,6 +69,13 @@ struct WorldIO {
   float* ranges_traj;     // [T][B][num_ranges] or null
 };
 
+// What the contact rollout records on top of the race rollout's arrays.
+struct ContactIO {
+  double* clear_traj;  // [T+1][B]
+  int* nearest_traj;   // [T+1][B] or null
+  int* crash_tick;     // [B]
+};
+
 namespace stage {
 
 enum Dir { kIn = 1, kOut = 2, kInOut = 3 };
@@ -143,10 +150,11 @@ inline void rollout_fields(Layout& L, const RolloutIO& h, RolloutIO* d, size_t x
 }
 
 // f110qp_rollout_replan (w null: r.ranges read) and f110qp_rollout_world / _race (w: its circles staged
-// in, its ranges_traj, when given, copied back). table_rows = steer_discrete + 1.
+// in, its ranges_traj, when given, copied back) and f110qp_rollout_contact (w and k: its three records,
+// every row of them the device's). table_rows = steer_discrete + 1.
 inline void replan_fields(Layout& L, const RolloutIO& h, RolloutIO* d, const ReplanIO& r, ReplanIO* dr,
                           const f110qp_scan_config& sc, size_t table_rows, size_t xr_points, size_t num_waypoints,
-                          const WorldIO* w, WorldIO* dw) {
+                          const WorldIO* w, WorldIO* dw, const ContactIO* k = nullptr, ContactIO* dk = nullptr) {
   const size_t B = (size_t)h.B, T = (size_t)h.T, TB = T * B, nr = (size_t)sc.num_ranges;
   io_fields(L, h, d, xr_points, kInOut);
   *dr = r;
@@ -164,6 +172,11 @@ inline void replan_fields(Layout& L, const RolloutIO& h, RolloutIO* d, const Rep
   *dw = *w;
   L.add(w->circles, &dw->circles, w->circle_bytes, true, kIn);
   L.add(w->ranges_traj, &dw->ranges_traj, TB * nr * 4, w->ranges_traj, kOut);
+  if (!k) return;
+  *dk = *k;
+  L.add(k->clear_traj, &dk->clear_traj, (T + 1) * B * 8, true, kOut);
+  L.add(k->nearest_traj, &dk->nearest_traj, (T + 1) * B * 4, k->nearest_traj, kOut);
+  L.add(k->crash_tick, &dk->crash_tick, B * 4, true, kOut);
 }
 
 }  // namespace stage

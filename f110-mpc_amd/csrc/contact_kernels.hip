@@ -1,0 +1,171 @@
+// contact_kernels.hip — contact in the closed loop's world of circles: every car's clearance to the static
+// circles and to its race-mates (f110qp_clearance_dev, f110qp_rollout_contact[_dev] of include/f110qp.h).
+//
+// The body of a car is the race model's circle: centre q = (x + off cos(ori), y + off sin(ori)) with
+// off = center_offset, radius R = car_radius. Per pose and obstacle, all fp64 with FP contraction off and the
+// correctly rounded square root (the cast kernel's discipline):
+//   static circle j = (cx, cy, r):  dx = cx - qx, dy = cy - qy, d = sqrt(dx dx + dy dy), v = (d - |r|) - R
+//   race-mate m (centre q_m built as q is, at the same row of x):   dx = q_m.x - qx, ...,  v = (d - R) - R
+// clearance = the minimum of the v, nearest = its index (j, or C + i for the mate with index i inside the
+// race), the lowest index on equal values. A candidate replaces the running (best, idx) only when v < best, or
+// v == best with a lower index, from the start (+inf, -1): a NaN v never passes a compare, so a NaN circle or
+// mate is never chosen and a car with a non-finite pose keeps the start value. Per pair the value depends on
+// nothing else, and the (value, index) minimum is associative and commutative: the result does not depend on
+// which thread visits which obstacle, or on the order of the list.
+//
+// Mapping: one 256-thread workgroup per car, striding over the cars; the car's rows in passes of
+// kClearPoses. Per pass the first threads build the body centres into LDS (one sincos each), then the
+// obstacle list is walked kCastCircleTile at a time, one obstacle per thread: the thread reads its circle
+// once (or, in the virtual tail behind the C circles as in cast_one<RACE>, builds mate k of the race at every
+// pose's row, stepped over the own slot) and tests it against every pose of the pass, (best, idx) per pose
+// in registers. A car's circles are read once per pass straight from global memory, 24 contiguous bytes a
+// thread: there is no reuse inside a pass that an LDS copy would serve. The pass ends with a lexicographic
+// (value, index) minimum over xor shuffles inside each wave and over the four waves' results in LDS. Every
+// loop bound is uniform over the workgroup, so whole waves reach every shuffle and barrier. No atomic. No cull:
+// every pair takes its square root (clearances are negative on contact, so a cheaper sign test has nothing
+// to stand on), and the result is the exact minimum by construction. No cap on C or G.
+#include <hip/hip_runtime.h>
+
+#include "f110qp_kernels.h"
+
+namespace f110qp {
+
+namespace {
+
+constexpr int kClearThreads = 256;
+constexpr int kClearWaves = kClearThreads / 64;
+constexpr int kClearPoses = 8;  // poses (rows of one car) per pass
+static_assert(kCastCircleTile == kClearThreads, "one obstacle of the tile per thread");
+
+// (v, i) into (best, idx): the update rule above.
+__device__ __forceinline__ void take_min(double& best, int& idx, const double v, const int i) {
+  if (v < best || (v == best && i < idx)) {
+    best = v;
+    idx = i;
+  }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kClearThreads) void clearance_kernel(const ClearParams P, const RaceParams Q, const int B,
+                                                                  const int rows, const int nwg,
+                                                                  const double* __restrict__ x,
+                                                                  const double* __restrict__ circles,
+                                                                  double* __restrict__ clearance,
+                                                                  int* __restrict__ nearest, const ContactMark M) {
+#pragma clang fp contract(off)
+  __shared__ double s_qx[kClearPoses], s_qy[kClearPoses];
+  __shared__ double s_best[kClearWaves][kClearPoses];
+  __shared__ int s_idx[kClearWaves][kClearPoses];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double inf = __longlong_as_double(0x7ff0000000000000ll);
+  const int nc = P.C + Q.G - 1;  // the circles and the G - 1 mates behind them
+  for (int b = blockIdx.x; b < B; b += nwg) {
+    const double* cw = circles + (P.world_rows == 1 ? (size_t)0 : (size_t)b * (size_t)P.C * 3);
+    const int own = b % Q.G, first = b - own;
+    int crash = -1;  // thread 0: the first row at or under the margin
+    if (M.crash_tick && !M.init && tid == 0) crash = M.crash_tick[b];
+    for (int r0 = 0; r0 < rows; r0 += kClearPoses) {
+      const int np = min(kClearPoses, rows - r0);
+      if (tid < np) {  // the body centre of pose tid of the pass
+        const double* xp = x + ((size_t)(r0 + tid) * (size_t)B + (size_t)b) * 3;
+        double so, co;
+        sincos(xp[2], &so, &co);
+        s_qx[tid] = xp[0] + Q.center_offset * co;
+        s_qy[tid] = xp[1] + Q.center_offset * so;
+      }
+      __syncthreads();
+      double best[kClearPoses];
+      int idx[kClearPoses];
+#pragma unroll
+      for (int p = 0; p < kClearPoses; p++) {
+        best[p] = inf;
+        idx[p] = -1;
+      }
+      for (int c0 = 0; c0 < nc; c0 += kCastCircleTile) {
+        const int j = c0 + tid;
+        if (j < P.C) {
+          const double cx = cw[(size_t)j * 3 + 0], cy = cw[(size_t)j * 3 + 1];
+          const double ra = fabs(cw[(size_t)j * 3 + 2]);
+#pragma unroll
+          for (int p = 0; p < kClearPoses; p++) {
+            if (p < np) {
+              const double dx = cx - s_qx[p], dy = cy - s_qy[p];
+              const double d = __dsqrt_rn(dx * dx + dy * dy);
+              take_min(best[p], idx[p], (d - ra) - Q.car_radius, j);
+            }
+          }
+        } else if (j < nc) {  // mate k of the race, stepped over the own slot: index i inside the race
+          const int k = j - P.C, i = k + (k >= own ? 1 : 0);
+#pragma unroll
+          for (int p = 0; p < kClearPoses; p++) {
+            if (p < np) {
+              const double* xm = x + ((size_t)(r0 + p) * (size_t)B + (size_t)(first + i)) * 3;
+              double sm, cm;
+              sincos(xm[2], &sm, &cm);
+              const double mx = xm[0] + Q.center_offset * cm, my = xm[1] + Q.center_offset * sm;
+              const double dx = mx - s_qx[p], dy = my - s_qy[p];
+              const double d = __dsqrt_rn(dx * dx + dy * dy);
+              take_min(best[p], idx[p], (d - Q.car_radius) - Q.car_radius, P.C + i);
+            }
+          }
+        }
+      }
+      // the wave's (value, index) minimum per pose, then the four waves' through LDS
+#pragma unroll
+      for (int p = 0; p < kClearPoses; p++) {
+        if (p < np) {  // uniform
+#pragma unroll
+          for (int m = 32; m >= 1; m >>= 1) {
+            const double ov = __shfl_xor(best[p], m, 64);
+            const int oi = __shfl_xor(idx[p], m, 64);
+            take_min(best[p], idx[p], ov, oi);
+          }
+          if (lane == 0) {
+            s_best[wave][p] = best[p];
+            s_idx[wave][p] = idx[p];
+          }
+        }
+      }
+      __syncthreads();
+      if (tid < np) {
+        double v = s_best[0][tid];
+        int i = s_idx[0][tid];
+#pragma unroll
+        for (int w = 1; w < kClearWaves; w++) take_min(v, i, s_best[w][tid], s_idx[w][tid]);
+        const size_t o = (size_t)(r0 + tid) * (size_t)B + (size_t)b;
+        clearance[o] = v;
+        if (nearest) nearest[o] = i;
+        s_best[0][tid] = v;  // for the mark below (read by thread 0 behind the barrier)
+      }
+      if (M.crash_tick) {  // uniform
+        __syncthreads();
+        if (tid == 0)
+          for (int p = 0; p < np; p++)
+            if (crash < 0 && s_best[0][p] <= M.margin) crash = M.row0 + r0 + p;
+      }
+      __syncthreads();  // the next pass (or car) rewrites the centres and the waves' results
+    }
+    if (M.crash_tick && tid == 0) M.crash_tick[b] = crash;
+  }
+}
+
+// Grid: one workgroup per car up to 1,024. The kernel holds 127 VGPRs (the code-object metadata, DESIGN.md
+// 2i; the fp64 sincos and the eight poses' running minima set that figure), so a SIMD keeps four of its
+// waves; a workgroup is one wave on each of a CU's four SIMDs and 512 B of LDS, so a CU holds four
+// workgroups and the MI355X's 256 CUs hold 1,024 at once: derived from the occupancy, as cast_scans_grid's
+// 768 is, and not from a sweep of caps (none was measured).
+constexpr int kClearMaxGrid = 1024;
+int clearance_grid(int B) { return B < kClearMaxGrid ? B : kClearMaxGrid; }
+
+hipError_t launch_clearance(const ClearParams& P, const RaceParams& Q, int B, int rows, const double* x,
+                            const double* circles, double* clearance, int* nearest, const ContactMark& M,
+                            hipStream_t s) {
+  if (B <= 0 || rows <= 0) return hipSuccess;
+  const int nwg = clearance_grid(B);
+  hipLaunchKernelGGL(clearance_kernel, dim3(nwg), dim3(kClearThreads), 0, s, P, Q, B, rows, nwg, x, circles, clearance,
+                     nearest, M);
+  return hipGetLastError();
+}
+
+}  // namespace f110qp

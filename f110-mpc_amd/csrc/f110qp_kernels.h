@@ -310,7 +310,7 @@ hipError_t launch_advance_scan(const AdvanceParams& P, int B, int N, const doubl
 
 // ---- closed loop with re-planning (rollout_kernels.hip, plan_kernels.hip) -------------------------
 // tick kinds (== F110QP_TICK_* in include/f110qp.h)
-constexpr int TICK_MPC = 0, TICK_PLAN = 1, TICK_HOLD = 2, TICK_PLAN_FAILED = 3;
+constexpr int TICK_MPC = 0, TICK_PLAN = 1, TICK_HOLD = 2, TICK_PLAN_FAILED = 3, TICK_CRASHED = 4;
 
 // launch_plan for the cars of a device-side list: workgroups stride over list[0 .. min(*count, B)),
 // at most plan_listed_grid(B) of them; a workgroup past the count exits at its first load. pose is
@@ -349,9 +349,21 @@ struct ReplanStep {
   float* hs_next;          // [B][2][3] or null
   int nr;
   float angle_min, angle_inc;
+  // launch_advance_replan_park only: a car with crash_tick[b] >= 0 parks, and repeats its rows
+  const int* crash_tick;   // the first row in contact or -1 (launch_clearance's mark)
+  const double* u_lin;     // [B][2] this tick's linearisation input
+  const double* pose;      // [B][4] this tick's pose row
 };
 hipError_t launch_advance_replan(const AdvanceParams& P, int B, int N, const ReplanStep& S,
                                  hipStream_t stream);
+// The same with parking (f110qp_rollout_contact[_dev] at stop_on_contact = 1): a car whose crash_tick is
+// not -1 takes no action on its state (path flag, held plan and index stay), applies (0, 0), repeats the
+// bits of its x, u_lin and pose rows into the next ones, has its kind rewritten TICK_CRASHED and its
+// status F110QP_NO_SOLVE, is announced TICK_CRASHED in kind_next and is not appended to the plan list; its
+// half-space rows are those of the unchanged pose. Every other car is launch_advance_replan's, bit for
+// bit. The kernel is advance_replan_kernel's template with PARK = true; the plain launch is PARK = false.
+hipError_t launch_advance_replan_park(const AdvanceParams& P, int B, int N, const ReplanStep& S,
+                                      hipStream_t stream);
 
 // The launch in front of the loop: pose row 0, kind 0, list 0 (count zero on entry) and, with hs0,
 // the half-space rows of tick 0.
@@ -398,5 +410,29 @@ struct RaceParams {
 };
 hipError_t launch_cast_scans_race(const CastParams& P, const RaceParams& Q, int B, const int* list, const int* count,
                                   const double* x, const double* circles, float* ranges, hipStream_t stream);
+
+// ---- contact (contact_kernels.hip) ----------------------------------------------------------------
+// The clearance of rows x B poses x [rows][B][3] to everything each car can touch: the C circles of its
+// world (circles [world_rows][C][3], null when C = 0) and the G - 1 mates of its race at the same row of x,
+// the car's body being the race model's circle. clearance [rows][B], nearest [rows][B] or null (the index
+// of the minimum: j, C + i for mate i of the race, -1 for none). One workgroup per car, at most
+// clearance_grid(B) of them striding over the cars; one launch.
+struct ClearParams {
+  int C;
+  int world_rows;  // 1 or B
+};
+// The rollout's crash record, updated by the same launch (crash_tick null: no record): crash_tick[b] is the
+// first row whose clearance is <= margin, counted from row0, or -1. init: the launch starts every car
+// from -1; otherwise from what crash_tick holds (a car that has crashed keeps its row).
+struct ContactMark {
+  int* crash_tick;  // [B] or null
+  int row0;         // the row of x_traj that row 0 of this launch is
+  int init;
+  double margin;
+};
+int clearance_grid(int B);
+hipError_t launch_clearance(const ClearParams& P, const RaceParams& Q, int B, int rows, const double* x,
+                            const double* circles, double* clearance, int* nearest, const ContactMark& M,
+                            hipStream_t stream);
 
 }  // namespace f110qp

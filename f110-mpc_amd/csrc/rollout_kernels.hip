@@ -7,7 +7,8 @@
 // with v forced, src/project.cpp:169-170,210-218). 56 bytes in and 40 (48 with u_applied) out per
 // car, three fp64 trig calls: the launch is the cost, so there is no LDS, no cross-lane traffic and
 // no atomic in these two. The re-planning loop's step (advance_replan_kernel, below) adds the per-car
-// OdomCallback state and one ballot and one atomic per wave for the next tick's plan list.
+// OdomCallback state and one ballot and one atomic per wave for the next tick's plan list; its PARK
+// instantiation (advance_replan_park_kernel) parks the cars that contact_kernels.hip has marked crashed.
 #include <hip/hip_runtime.h>
 
 #include "f110qp_kernels.h"
@@ -146,6 +147,32 @@ __device__ __forceinline__ void append_plan_list(const bool plans, const int b, 
   if (plans && pos >= 0 && pos < B) list[pos] = b;
 }
 
+// A parked car's tick (advance_replan<true>): no action on (u_held, len, idx, have_path); the applied input
+// is (0, 0); the next x, u_lin and pose rows repeat this tick's bits; this tick's kind is rewritten CRASHED
+// over what the previous tick announced (as PLAN_FAILED is over PLAN) and the next one announced CRASHED;
+// the status is F110QP_NO_SOLVE; the half-space rows are those of the unchanged pose.
+__device__ __forceinline__ void park_car(const int b, const ReplanStep& S) {
+#pragma clang fp contract(off)
+  const double px = S.x[3 * (size_t)b], py = S.x[3 * (size_t)b + 1], th = S.x[3 * (size_t)b + 2];
+  S.kind[b] = TICK_CRASHED;
+  S.status[b] = 0;
+  S.x_next[3 * (size_t)b] = px;
+  S.x_next[3 * (size_t)b + 1] = py;
+  S.x_next[3 * (size_t)b + 2] = th;
+  S.u_lin_next[2 * (size_t)b] = S.u_lin[2 * (size_t)b];
+  S.u_lin_next[2 * (size_t)b + 1] = S.u_lin[2 * (size_t)b + 1];
+  if (S.u_applied) reinterpret_cast<float2*>(S.u_applied)[b] = make_float2(0.f, 0.f);
+#pragma unroll
+  for (int j = 0; j < 4; j++) S.pose_next[4 * (size_t)b + j] = S.pose[4 * (size_t)b + j];
+  if (S.kind_next) S.kind_next[b] = TICK_CRASHED;
+  if (S.hs_next) {
+    float o[6];
+    half_space_rows(S.gap[b], S.nr, px, py, th, S.angle_min, S.angle_inc, o);
+#pragma unroll
+    for (int j = 0; j < 6; j++) S.hs_next[6 * (size_t)b + j] = o[j];
+  }
+}
+
 // advance_scan_kernel plus the per-car state machine of Project::OdomCallback + Project::DriveStep
 // (host/src/project.cpp:31-100; include/f110qp.h, "closed loop with re-planning"). One thread per car.
 // The tick's action on (u_held, len, idx, have_path), DriveStep's input, the plant step in
@@ -153,13 +180,25 @@ __device__ __forceinline__ void append_plan_list(const bool plans, const int b, 
 // have advance_scan_kernel's bits), the pose row of the next tick's plan, the next tick's kind and
 // its plan list. The N float2 of a plan move only on a usable MPC tick; every other tick reads at most
 // two of the held inputs.
-__global__ __launch_bounds__(256) void advance_replan_kernel(const AdvanceParams P, const int B, const int N,
-                                                             const ReplanStep S) {
+//
+// PARK (advance_replan_park_kernel, f110qp_rollout_contact[_dev] at stop_on_contact = 1): a car whose
+// crash_tick is not -1 takes park_car instead of the tick. Every parking statement is behind `if constexpr`;
+// the plain kernel is the PARK = false instantiation.
+template <bool PARK>
+__device__ __forceinline__ void advance_replan(const AdvanceParams& P, const int B, const int N, const ReplanStep& S) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x * 256 + threadIdx.x;
   const bool live = b < B;  // no early return: the ballot below wants whole waves
   int knext = TICK_MPC;
-  if (live) {
+  bool parked = false;
+  if constexpr (PARK) {
+    if (live && S.crash_tick[b] >= 0) {
+      parked = true;
+      knext = TICK_CRASHED;  // not a PLAN tick: the car is not appended to the list
+      park_car(b, S);
+    }
+  }
+  if (live && !parked) {
     int kind = S.kind[b];
     int have = S.have_path[b], len = S.held_len[b], idx = S.held_idx[b];
     const GapRecord g = S.hs_next ? S.gap[b] : GapRecord{-1, -1, 0.f, 0.f};
@@ -242,9 +281,25 @@ __global__ __launch_bounds__(256) void advance_replan_kernel(const AdvanceParams
   if (S.kind_next) append_plan_list(live && knext == TICK_PLAN, b, B, S.next_list, S.next_count);
 }
 
+__global__ __launch_bounds__(256) void advance_replan_kernel(const AdvanceParams P, const int B, const int N,
+                                                             const ReplanStep S) {
+  advance_replan<false>(P, B, N, S);
+}
+
+__global__ __launch_bounds__(256) void advance_replan_park_kernel(const AdvanceParams P, const int B, const int N,
+                                                                  const ReplanStep S) {
+  advance_replan<true>(P, B, N, S);
+}
+
 hipError_t launch_advance_replan(const AdvanceParams& P, int B, int N, const ReplanStep& S, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   hipLaunchKernelGGL(advance_replan_kernel, dim3((B + 255) / 256), dim3(256), 0, s, P, B, N, S);
+  return hipGetLastError();
+}
+
+hipError_t launch_advance_replan_park(const AdvanceParams& P, int B, int N, const ReplanStep& S, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(advance_replan_park_kernel, dim3((B + 255) / 256), dim3(256), 0, s, P, B, N, S);
   return hipGetLastError();
 }
 

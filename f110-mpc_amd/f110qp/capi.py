@@ -43,6 +43,7 @@ TICK_MPC = 0
 TICK_PLAN = 1
 TICK_HOLD = 2
 TICK_PLAN_FAILED = 3
+TICK_CRASHED = 4
 NO_SOLVE = 0
 
 
@@ -130,6 +131,10 @@ EXPORTED = (
     "f110qp_cast_scans_race_dev",
     "f110qp_rollout_race_dev",
     "f110qp_rollout_race",
+    "f110qp_clearance_dev",
+    "f110qp_default_contact_config",
+    "f110qp_rollout_contact_dev",
+    "f110qp_rollout_contact",
 )
 CAST_CIRCLE_TILE = 256  # F110QP_CAST_CIRCLE_TILE: circles per LDS tile of the ray-cast kernel
 SCRATCH_NAMES = {0: "none (wave back end)", 1: "LDS fp64", 2: "LDS fp32", 3: "HBM fp64", 4: "HBM fp32"}
@@ -215,6 +220,13 @@ class RaceConfig(C.Structure):
     ]
 
 
+class ContactConfig(C.Structure):
+    _fields_ = [
+        ("stop_on_contact", C.c_int),
+        ("margin", C.c_double),
+    ]
+
+
 # f110qp_gap_record (16 bytes) as a numpy record
 GAP_RECORD_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("r_lo", np.float32), ("r_hi", np.float32)])
 
@@ -284,6 +296,11 @@ def load(test: bool = False):
     L.f110qp_cast_scans_race_dev.argtypes = [sp, wcp, rcp, C.c_int] + [fp] * 6
     L.f110qp_rollout_race_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, C.c_int] + [fp] * 21
     L.f110qp_rollout_race.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, C.c_int] + [fp] * 20
+    ccp = C.POINTER(ContactConfig)
+    L.f110qp_default_contact_config.argtypes = [ccp]
+    L.f110qp_clearance_dev.argtypes = [wcp, rcp, C.c_int, C.c_int] + [fp] * 5
+    L.f110qp_rollout_contact_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, C.c_int] + [fp] * 24
+    L.f110qp_rollout_contact.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, C.c_int] + [fp] * 23
     L.f110qp_select_dev.argtypes = [C.c_int, fp, C.c_int, fp, fp, fp, fp, fp]
     L.f110qp_backend_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
     L.f110qp_lane_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -390,6 +407,15 @@ def default_race_config(**over) -> RaceConfig:
     """f110qp_default_race_config: group_size 1, car_radius 0.3, center_offset 0.1651."""
     c = RaceConfig()
     load().f110qp_default_race_config(C.byref(c))
+    for k, v in over.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_contact_config(**over) -> ContactConfig:
+    """f110qp_default_contact_config: stop_on_contact 0, margin 0.0."""
+    c = ContactConfig()
+    load().f110qp_default_contact_config(C.byref(c))
     for k, v in over.items():
         setattr(c, k, v)
     return c
@@ -873,7 +899,7 @@ class Solver:
                           waypoints, x_ref, have_path, circles, x_traj, u_lin_traj, u_applied, status_traj,
                           iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
                           plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
-                          ranges_traj=None, stream=None, _race=None):
+                          ranges_traj=None, stream=None, _race=None, _contact=None):
         """rollout_replan_dev with every tick's scan cast at that tick's pose (f110qp_rollout_world_dev): wc
         and circles [world_rows,C,3] f64 replace ranges, sc.scan_rows is not read, and the optional
         ranges_traj [T,B,num_ranges] f32 records every car's scan of every tick."""
@@ -886,13 +912,20 @@ class Solver:
         plan = (table, waypoints, x_ref, have_path)
         traj = (x_traj, u_lin_traj, u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan)
         rec = (hs_traj, kind_traj, plan_status_traj, best_traj_traj, best_global_traj, pose_traj)
+        name = "f110qp_rollout_world_dev" if _race is None else "f110qp_rollout_race_dev"
+        cfgs, tail, more = ([] if _race is None else [C.byref(_race)]), [], []
+        if _contact is not None:  # (cc, clear_traj, nearest_traj, crash_tick) behind the race rollout's arrays
+            cc, clear_traj, nearest_traj, crash_tick = _contact
+            more = [(clear_traj, "f64", (T + 1) * B, "clear_traj"), (nearest_traj, "i32", (T + 1) * B, "nearest_traj", True),
+                    (crash_tick, "i32", B, "crash_tick")]
+            name, cfgs, tail = "f110qp_rollout_contact_dev", cfgs + [C.byref(cc)], [_tp(clear_traj), _tp(nearest_traj),
+                                                                                   _tp(crash_tick)]
         _devs(*self._plan_specs(rp, B, *plan), (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
               *self._traj_specs(T, B, *traj), *self._record_specs(T, B, *rec),
-              (ranges_traj, "f32", T * B * int(sc.num_ranges), "ranges_traj", True))
-        name = "f110qp_rollout_world_dev" if _race is None else "f110qp_rollout_race_dev"
+              (ranges_traj, "f32", T * B * int(sc.num_ranges), "ranges_traj", True), *more)
         self._chk(getattr(self.lib, name)(
-            self._h, C.byref(rc), C.byref(sc), C.byref(rp), C.byref(wc), *([] if _race is None else [C.byref(_race)]),
-            B, *map(_tp, plan), _tp(circles), *map(_tp, traj), *map(_tp, rec), _tp(ranges_traj),
+            self._h, C.byref(rc), C.byref(sc), C.byref(rp), C.byref(wc), *cfgs,
+            B, *map(_tp, plan), _tp(circles), *map(_tp, traj), *map(_tp, rec), _tp(ranges_traj), *tail,
             self._stream(stream, x_traj)), name)
 
     def rollout_race_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
@@ -910,9 +943,24 @@ class Solver:
                                plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
                                _race=race)
 
+    def rollout_contact_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig,
+                            race: RaceConfig, cc: ContactConfig, table, waypoints, x_ref, have_path, circles, x_traj,
+                            u_lin_traj, u_applied, status_traj, clear_traj, crash_tick, nearest_traj=None, iters_traj=None,
+                            cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None, plan_status_traj=None,
+                            best_traj_traj=None, best_global_traj=None, pose_traj=None, ranges_traj=None, stream=None):
+        """rollout_race_dev with every row's clearance recorded and, with cc.stop_on_contact, crashed cars parked
+        (f110qp_rollout_contact_dev): clear_traj [T+1,B] f64, crash_tick [B] i32, nearest_traj [T+1,B] i32
+        optional; a parked car's kind is TICK_CRASHED."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig):
+            raise F110QPError("race must be a RaceConfig and cc a ContactConfig")
+        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
+                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
+                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
+                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick))
+
     def rollout_world(self, x0, u_lin, circles, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
                       wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
-                      scans=False, rc=None, _race=None):
+                      scans=False, rc=None, _race=None, _contact=None):
         """rollout_replan() in a world of circles (f110qp_rollout_world, synchronous): circles [C,3] (one world
         for all cars) or [B,C,3] float64 replace ranges; wc defaults to f110qp_default_world_config with
         num_circles and world_rows taken from the array. scans=True adds ranges_traj [T,B,num_ranges]."""
@@ -932,10 +980,18 @@ class Solver:
             _check_race(_race, B)
         out = self._host_out(T, B, x0, ul, objective, plans, rows, int(sc.num_ranges) if scans else 0, (xr, hv))
         name = "f110qp_rollout_world" if _race is None else "f110qp_rollout_race"
+        cfgs, tail = ([] if _race is None else [C.byref(_race)]), []
+        if _contact is not None:  # (cc, nearest): the three records behind the race rollout's arrays
+            out["clear_traj"] = np.empty((T + 1, B), np.float64)
+            if _contact[1]:
+                out["nearest_traj"] = np.empty((T + 1, B), np.int32)
+            out["crash_tick"] = np.empty(B, np.int32)
+            name, cfgs = "f110qp_rollout_contact", cfgs + [C.byref(_contact[0])]
+            tail = [_p(out["clear_traj"]), _p(out.get("nearest_traj")), _p(out["crash_tick"])]
         self._chk(getattr(self.lib, name)(
             self._h, C.byref(self._ticks_config(rc, T)), C.byref(sc), C.byref(rp), C.byref(w),
-            *([] if _race is None else [C.byref(_race)]), B, _p(tab), _p(wp) if wp.shape[0] else None, _p(xr), _p(hv),
-            _p(ci) if ci.size else None, *self._out_args(out), _p(out.get("ranges_traj"))), name)
+            *cfgs, B, _p(tab), _p(wp) if wp.shape[0] else None, _p(xr), _p(hv),
+            _p(ci) if ci.size else None, *self._out_args(out), _p(out.get("ranges_traj")), *tail), name)
         return out
 
     def rollout_race(self, x0, u_lin, circles, race: RaceConfig, sc: ScanConfig, rp: ReplanConfig, table, waypoints,
@@ -947,6 +1003,16 @@ class Solver:
             raise F110QPError("race must be a RaceConfig")
         return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
                                   objective, rows, scans, rc, _race=race)
+
+    def rollout_contact(self, x0, u_lin, circles, race: RaceConfig, cc: ContactConfig, sc: ScanConfig, rp: ReplanConfig,
+                        table, waypoints, ticks, wc: WorldConfig = None, x_ref=None, have_path=None, plans=False,
+                        objective=False, rows=True, scans=False, nearest=True, rc=None):
+        """rollout_race() with contact (f110qp_rollout_contact, synchronous): adds clear_traj [T+1,B], crash_tick
+        [B] and, with nearest=True, nearest_traj [T+1,B]; with cc.stop_on_contact crashed cars park."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig):
+            raise F110QPError("race must be a RaceConfig and cc a ContactConfig")
+        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
+                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest))
 
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
@@ -1199,6 +1265,27 @@ def cast_scans_race_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, x, ci
     _check(load().f110qp_cast_scans_race_dev(C.byref(sc), C.byref(wc), C.byref(race), B, _tp(list_), _tp(count), _tp(x),
                                              _tp(circles), _tp(ranges), C.c_void_p(stream.cuda_stream)),
            "f110qp_cast_scans_race_dev")
+
+
+def clearance_dev(wc: WorldConfig, race: RaceConfig, x, circles, clearance, nearest=None, stream=None):
+    """Every car's clearance to its world's circles and its race-mates (f110qp_clearance_dev): x [rows,B,3] f64
+    (or [B,3]: one row), circles [world_rows,C,3] f64 (None for C = 0) -> clearance [rows,B] f64 and, optionally,
+    nearest [rows,B] i32."""
+    import torch
+
+    if x.dim() not in (2, 3) or x.shape[-1] != 3:
+        raise F110QPError(f"x must be [rows, B, 3] or [B, 3], got {tuple(x.shape)}")
+    rows, B = (1, int(x.shape[0])) if x.dim() == 2 else (int(x.shape[0]), int(x.shape[1]))
+    if rows < 1:
+        raise F110QPError("x must hold at least one row")
+    Cn, WR = int(wc.num_circles), int(wc.world_rows)
+    _check_race(race, B)
+    _devs((x, "f64", 3 * B * rows, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
+          (clearance, "f64", B * rows, "clearance"), (nearest, "i32", B * rows, "nearest", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_clearance_dev(C.byref(wc), C.byref(race), B, rows, _tp(x), _tp(circles), _tp(clearance),
+                                       _tp(nearest), C.c_void_p(stream.cuda_stream)), "f110qp_clearance_dev")
 
 
 def replan_start_dev(rp: ReplanConfig, sc, x, have_path, x_ref, gap, pose, kind, list_, count, hs=None, stream=None):

@@ -336,6 +336,49 @@ def race_circles(x, group_size: int, car_radius: float = 0.3, center_offset: flo
     return np.ascontiguousarray(c[mate].reshape(B, G - 1, 3))
 
 
+def clearance(x, circles, group_size: int = 1, car_radius: float = 0.3, center_offset: float = 0.1651):
+    """The contact model of include/f110qp.h (f110qp_clearance_dev) in numpy, the device kernel's expressions in
+    its order: poses x [rows, B, 3] (or [B, 3]) in circles [C, 3], [B, C, 3] or None -> (clearance [rows, B]
+    float64, nearest [rows, B] int32). Body centre q = (x + off cos(ori), y + off sin(ori)); per static circle
+    v = (sqrt(dx dx + dy dy) - |r|) - R with d = c - q; per race-mate (race_circles at the same row, its centre
+    minus q) v = (d - R) - R; the minimum, the lowest index on equal values (j, or C + i for the mate with index
+    i inside the race), NaN values never chosen, +inf and -1 without a candidate."""
+    x = np.asarray(x, np.float64)
+    one = x.ndim == 2
+    x = x[None] if one else x
+    rows, B = x.shape[:2]
+    G, R = int(group_size), float(car_radius)
+    ci = np.zeros((0, 3)) if circles is None else np.asarray(circles, np.float64)
+    Cn = ci.shape[-2]
+    own = np.arange(B) % G
+    k = np.arange(G - 1)[None, :]
+    mate_idx = Cn + k + (k >= own[:, None])                      # [B, G - 1]: C + index inside the race
+    clear = np.full((rows, B), np.inf)
+    near = np.full((rows, B), -1, np.int32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r in range(rows):
+            qx = x[r, :, 0] + center_offset * np.cos(x[r, :, 2])
+            qy = x[r, :, 1] + center_offset * np.sin(x[r, :, 2])
+            cw = np.broadcast_to(ci, (B, Cn, 3)) if ci.ndim == 2 else ci
+            dx, dy = cw[:, :, 0] - qx[:, None], cw[:, :, 1] - qy[:, None]
+            v = (np.sqrt(dx * dx + dy * dy) - np.abs(cw[:, :, 2])) - R
+            idx = np.broadcast_to(np.arange(Cn)[None, :], (B, Cn))
+            if G > 1:
+                m = race_circles(x[r], G, car_radius, center_offset)
+                dx, dy = m[:, :, 0] - qx[:, None], m[:, :, 1] - qy[:, None]
+                v = np.concatenate([v, (np.sqrt(dx * dx + dy * dy) - R) - R], 1)
+                idx = np.concatenate([idx, mate_idx], 1)
+            if v.shape[1] == 0:
+                continue
+            v = np.where(np.isnan(v), np.inf, v)
+            a = np.argmin(v, axis=1)                             # the first of equal values: the lowest index
+            best = v[np.arange(B), a]
+            hit = best < np.inf
+            clear[r] = np.where(hit, best, np.inf)
+            near[r] = np.where(hit, idx[np.arange(B), a], -1)
+    return (clear[0], near[0]) if one else (clear, near)
+
+
 def make_race_grid(races: int, group_size: int, seed: int = 0, spacing: float = 1.2, lateral: float = 0.4) -> np.ndarray:
     """Start states [races * group_size, 3] float64 (x, y, yaw) of `races` races on track_waypoints(): a race
     starts at a seeded position on the path; its car i stands i * spacing metres behind car 0 along the path,

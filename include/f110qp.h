@@ -698,6 +698,7 @@ int f110qp_plan_batch(const f110qp_plan_config* cfg, int batch, const double* po
 #define F110QP_TICK_PLAN 1
 #define F110QP_TICK_HOLD 2
 #define F110QP_TICK_PLAN_FAILED 3
+#define F110QP_TICK_CRASHED 4     /* f110qp_rollout_contact[_dev] with stop_on_contact only: a parked car */
 #define F110QP_NO_SOLVE 0         /* status_traj on a tick whose solve result is not used */
 
 typedef struct {
@@ -928,6 +929,102 @@ int f110qp_rollout_race(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const 
                         int* iters_traj, double* cost_traj, float* u_plan, float* x_plan, float* hs_traj,
                         int* kind_traj, int* plan_status_traj, int* best_traj_traj, int* best_global_traj,
                         double* pose_traj, float* ranges_traj);
+
+/* ---- contact: car-to-wall and car-to-car clearance, crashed cars park -------------------------------
+ * In the calls above nothing can touch anything: a car that meets a wall drives through it, and in a race it
+ * stays a moving circle in its race-mates' scans while it does. The f1tenth simulator the reference runs in
+ * stops a car on collision; the calls below give this library's stand-in the same. Model: the body of a car
+ * is the race model's circle, centre (x + center_offset cos(ori), y + center_offset sin(ori)), radius
+ * car_radius (f110qp_race_config); a car touches the static circles of its world and the other cars of its
+ * race, never a car of another race. A circle body and both numbers are modelling choices of this library, not
+ * the reference's. There is no swept test between ticks: contact is judged at the poses of the rows only. At
+ * 4.5 m/s and the default plant_dt a car moves 0.045 m per tick, against a body radius of 0.3 m plus the
+ * walls' 0.12 m, so a car cannot step over a wall circle or a race-mate between two rows; a world of circles
+ * thinner than a tick's travel, or a much larger plant_dt, is outside what this model detects.
+ * Additive: F110QP_API_VERSION stays 6, and no call above changes its results. */
+
+/* The clearance of rows x B poses (device pointers, asynchronous on `stream`, one launch):
+ *   x [rows][B][3] double, circles [world_rows][C][3] double = (cx, cy, r)
+ *   -> clearance [rows][B] double, nearest [rows][B] int (may be NULL).
+ * The B cars of every row are B / G races as in f110qp_cast_scans_race_dev (G = race->group_size), the world
+ * is f110qp_cast_scans_dev's (wc->lidar_offset and wc->max_range are checked as there and not read).
+ * Arithmetic, all fp64, every product and sum rounded (no fused multiply-add), with off = race->center_offset
+ * and R = race->car_radius:
+ *   body centre q = (x + off cos(ori), y + off sin(ori)), one sincos(double): the LiDAR origin's and the race
+ *   circle's expressions;
+ *   static circle j = (cx, cy, r) of car b's world: dx = cx - qx, dy = cy - qy, d = sqrt(dx dx + dy dy) (the
+ *   correctly rounded square root), v_j = (d - |r|) - R;
+ *   race-mate m, every other car of b's race at the same row of x, with q_m built as q is: dx = q_m.x - q.x,
+ *   dy = q_m.y - q.y, v = (d - R) - R;
+ *   clearance[row][b] = the minimum of these values, nearest[row][b] = the index of the minimum: j for a static
+ *   circle, C + i for the race-mate whose index inside the race is i; the lowest index wins on equal values.
+ *   A candidate replaces the running minimum only when v < best, or when v == best with a lower index; the
+ *   start value is +inf and -1, which is also the answer for C = 0, G = 1.
+ * Consequences: a circle or mate with a NaN field gives a NaN v, which passes no compare: it is never chosen
+ * and does not disturb the others (the same holds for an infinite centre coordinate: v = +inf never replaces
+ * the start value; an infinite radius is, by the arithmetic, contact with everything: v = -inf). A car whose
+ * own pose is non-finite keeps +inf and -1. A negative radius acts as its absolute value. Because the squares
+ * are the same bits either way, car a's value against b is bit-identical to b's against a. The result is a
+ * minimum of per-pair values that do not depend on the other obstacles: bit-identical for every order of the
+ * circle list and of the race's cars, apart from nearest mapping through the permutation. Negative on
+ * overlap, zero at touch.
+ * F110QP_ERR_INVALID before any HIP call: every world rule of f110qp_cast_scans_dev, every race rule of
+ * f110qp_cast_scans_race_dev, rows < 1, a NULL x or clearance. num_circles == 0 with circles == NULL is valid.
+ * Workgroups stride over the cars, one car each, at most min(batch, 1024) of them (what the device holds at
+ * once). */
+int f110qp_clearance_dev(const f110qp_world_config* wc, const f110qp_race_config* race, int batch, int rows,
+                         const double* x, const double* circles, double* clearance, int* nearest, void* stream);
+
+typedef struct {
+  int    stop_on_contact;  /* 0: record only; 1: a crashed car parks                       */
+  double margin;           /* contact when clearance <= margin; default 0.0; finite        */
+} f110qp_contact_config;
+
+/* Zeroes *cc: stop_on_contact 0, margin 0.0. */
+void f110qp_default_contact_config(f110qp_contact_config* cc);
+
+/* f110qp_rollout_race_dev with every row's clearance recorded and, optionally, crashed cars parked.
+ * Arguments as f110qp_rollout_race_dev, plus cc and
+ *   clear_traj    [T+1][B] double: row t is f110qp_clearance_dev at x_traj row t
+ *   nearest_traj  [T+1][B] int, may be NULL
+ *   crash_tick    [B] int: the first row whose clearance is <= cc->margin, or -1 if there is none.
+ * Stream order: f110qp_rollout_race_dev's, with one clearance launch on x_traj row 0 behind
+ * f110qp_replan_start_dev (it also initialises crash_tick) and one on row t + 1 behind tick t's plant step:
+ * one launch more per tick, no memset of its own inside the loop, no host synchronisation, read-back or
+ * allocation inside the loop; every argument is checked before the first launch (that call's checks, a NULL
+ * cc, a stop_on_contact other than 0 or 1, a non-finite margin, a NULL clear_traj or crash_tick).
+ * stop_on_contact = 0: every array f110qp_rollout_race_dev writes is bit-identical to that call's.
+ * stop_on_contact = 1: a car with crash_tick[b] = k parks from tick k on. At every tick t >= k: x_traj,
+ * u_lin_traj and pose_traj row t + 1 repeat row t's bits; u_applied[t] = (0, 0); kind_traj[t] =
+ * F110QP_TICK_CRASHED, written over the kind the previous tick announced, the way PLAN_FAILED is written over
+ * PLAN; status_traj[t] = F110QP_NO_SOLVE (the car's rows of iters_traj, cost_traj, u_plan and x_plan are
+ * unspecified, as on any tick without a solve); the car is not appended to the next plan list; its path flag
+ * and held plan stay as they are; its half-space rows follow the unchanged pose; it stays where it stands as
+ * a circle in its race-mates' scans and clearances. The car may have been listed for planning at tick k
+ * itself, because that list was built before the crash was known: that plan is wasted and harmless (it may
+ * rewrite the car's row of x_ref and of the plan records of tick k; nothing reads them again). Cars of a race
+ * in which nobody has crashed yet are bit-identical to the stop_on_contact = 0 run. */
+int f110qp_rollout_contact_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc,
+                               const f110qp_scan_config* sc, const f110qp_replan_config* rp,
+                               const f110qp_world_config* wc, const f110qp_race_config* race,
+                               const f110qp_contact_config* cc, int batch, const double* table,
+                               const double* waypoints, double* x_ref, int* have_path, const double* circles,
+                               double* x_traj, double* u_lin_traj, float* u_applied, int* status_traj,
+                               int* iters_traj, double* cost_traj, float* u_plan, float* x_plan,
+                               float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
+                               int* best_global_traj, double* pose_traj, float* ranges_traj,
+                               double* clear_traj, int* nearest_traj, int* crash_tick, void* stream);
+
+/* Same on host pointers (synchronous), staged as f110qp_rollout_race; the three records are copied back. */
+int f110qp_rollout_contact(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                           const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                           const f110qp_race_config* race, const f110qp_contact_config* cc, int batch,
+                           const double* table, const double* waypoints, double* x_ref, int* have_path,
+                           const double* circles, double* x_traj, double* u_lin_traj, float* u_applied,
+                           int* status_traj, int* iters_traj, double* cost_traj, float* u_plan, float* x_plan,
+                           float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
+                           int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
+                           int* nearest_traj, int* crash_tick);
 
 #ifdef __cplusplus
 }
