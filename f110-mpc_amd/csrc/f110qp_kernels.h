@@ -435,4 +435,17 @@ hipError_t launch_clearance(const ClearParams& P, const RaceParams& Q, int B, in
                             const double* circles, double* clearance, int* nearest, const ContactMark& M,
                             hipStream_t stream);
 
+// ---- standings (standings_kernels.hip) ------------------------------------------------------------
+// The projection of rows x B poses x [rows][B][3] onto the closed path wp [W][2] with cumulative lengths
+// cum [W+1] (the model of include/f110qp.h): seg [rows][B] or null, s [rows][B], lateral [rows][B] or null.
+// One workgroup per car, at most progress_grid(B) of them striding over the cars; one launch.
+int progress_grid(int B);
+hipError_t launch_progress(int B, int rows, const double* x, const double* wp, const double* cum, int W, int* seg,
+                           double* s, double* lateral, hipStream_t stream);
+// The standings of the B / G races from s [rows][B] on a path of length L: dist [rows][B], lap [rows][B] or
+// null, rank [rows][B]. Two launches on the stream (the accumulation in row order, one thread per car; then
+// the ranks, one thread per row and car), nothing between them but the stream's order.
+hipError_t launch_standings(int G, int B, int rows, const double* s, double L, double* dist, int* lap, int* rank,
+                            hipStream_t stream);
+
 }  // namespace f110qp

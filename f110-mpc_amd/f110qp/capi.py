@@ -135,6 +135,10 @@ EXPORTED = (
     "f110qp_default_contact_config",
     "f110qp_rollout_contact_dev",
     "f110qp_rollout_contact",
+    "f110qp_path_lengths",
+    "f110qp_progress_dev",
+    "f110qp_standings_dev",
+    "f110qp_race_standings",
 )
 CAST_CIRCLE_TILE = 256  # F110QP_CAST_CIRCLE_TILE: circles per LDS tile of the ray-cast kernel
 SCRATCH_NAMES = {0: "none (wave back end)", 1: "LDS fp64", 2: "LDS fp32", 3: "HBM fp64", 4: "HBM fp32"}
@@ -301,6 +305,10 @@ def load(test: bool = False):
     L.f110qp_clearance_dev.argtypes = [wcp, rcp, C.c_int, C.c_int] + [fp] * 5
     L.f110qp_rollout_contact_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, C.c_int] + [fp] * 24
     L.f110qp_rollout_contact.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, C.c_int] + [fp] * 23
+    L.f110qp_path_lengths.argtypes = [fp, C.c_int, fp]
+    L.f110qp_progress_dev.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_int] + [fp] * 4
+    L.f110qp_standings_dev.argtypes = [rcp, C.c_int, C.c_int, fp, C.c_double] + [fp] * 4
+    L.f110qp_race_standings.argtypes = [rcp, C.c_int, C.c_int, fp, fp, C.c_int] + [fp] * 6
     L.f110qp_select_dev.argtypes = [C.c_int, fp, C.c_int, fp, fp, fp, fp, fp]
     L.f110qp_backend_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
     L.f110qp_lane_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -1286,6 +1294,87 @@ def clearance_dev(wc: WorldConfig, race: RaceConfig, x, circles, clearance, near
         stream = torch.cuda.current_stream(x.device)
     _check(load().f110qp_clearance_dev(C.byref(wc), C.byref(race), B, rows, _tp(x), _tp(circles), _tp(clearance),
                                        _tp(nearest), C.c_void_p(stream.cuda_stream)), "f110qp_clearance_dev")
+
+
+def _rows_of(x, last, name):
+    """(rows, B) of a [rows,B(,last)] array or tensor, or of one row [B(,last)]."""
+    shape = tuple(int(v) for v in x.shape)
+    nd = 2 + (last is not None)
+    want = "[rows, B, 3]" if last else "[rows, B]"
+    if len(shape) not in (nd - 1, nd) or (last is not None and shape[-1] != last):
+        raise F110QPError(f"{name} must be {want} or one row of it, got {shape}")
+    rows, B = (1, shape[0]) if len(shape) == nd - 1 else shape[:2]
+    if rows < 1 or B < 1:
+        raise F110QPError(f"{name} must hold at least one row and one car")
+    return rows, B
+
+
+def _path(waypoints):
+    wp = _f64(waypoints, (-1, 2), "waypoints")
+    if wp.shape[0] < 2:
+        raise F110QPError("the path needs at least 2 waypoints")
+    return wp
+
+
+def path_lengths(waypoints):
+    """The closed path's cumulative lengths (f110qp_path_lengths, on the host): waypoints [W,2] f64 -> cum [W+1]
+    f64, cum[0] = 0 and cum[W] the path's length."""
+    wp = _path(waypoints)
+    cum = np.empty(wp.shape[0] + 1, np.float64)
+    _check(load().f110qp_path_lengths(_p(wp), wp.shape[0], _p(cum)), "f110qp_path_lengths")
+    return cum
+
+
+def progress_dev(x, waypoints, cum, s, seg=None, lateral=None, stream=None):
+    """Every pose's place on the closed path (f110qp_progress_dev): x [rows,B,3] f64 (or [B,3]: one row),
+    waypoints [W,2] f64, cum [W+1] f64 (path_lengths' array, on the device) -> s [rows,B] f64 and, optionally,
+    seg [rows,B] i32 and lateral [rows,B] f64."""
+    import torch
+
+    rows, B = _rows_of(x, 3, "x")
+    if waypoints.dim() != 2 or waypoints.shape[1] != 2 or waypoints.shape[0] < 2:
+        raise F110QPError(f"waypoints must be [W, 2] with W >= 2, got {tuple(waypoints.shape)}")
+    W = int(waypoints.shape[0])
+    _devs((x, "f64", 3 * B * rows, "x"), (waypoints, "f64", 2 * W, "waypoints"), (cum, "f64", W + 1, "cum"),
+          (s, "f64", B * rows, "s"), (seg, "i32", B * rows, "seg", True),
+          (lateral, "f64", B * rows, "lateral", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_progress_dev(B, rows, _tp(x), _tp(waypoints), _tp(cum), W, _tp(seg), _tp(s), _tp(lateral),
+                                      C.c_void_p(stream.cuda_stream)), "f110qp_progress_dev")
+
+
+def standings_dev(race: RaceConfig, s, path_length: float, dist, rank, lap=None, stream=None):
+    """Distance driven, laps and positions inside every race (f110qp_standings_dev): s [rows,B] f64 (or [B]: one
+    row) on a path of length path_length -> dist [rows,B] f64, rank [rows,B] i32 and, optionally, lap [rows,B]
+    i32."""
+    import torch
+
+    rows, B = _rows_of(s, None, "s")
+    _check_race(race, B)
+    _devs((s, "f64", B * rows, "s"), (dist, "f64", B * rows, "dist"), (rank, "i32", B * rows, "rank"),
+          (lap, "i32", B * rows, "lap", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(s.device)
+    _check(load().f110qp_standings_dev(C.byref(race), B, rows, _tp(s), float(path_length), _tp(dist), _tp(lap),
+                                       _tp(rank), C.c_void_p(stream.cuda_stream)), "f110qp_standings_dev")
+
+
+def race_standings(race: RaceConfig, x, waypoints, seg=True, lateral=True, lap=True):
+    """Both on host arrays, synchronous (f110qp_race_standings): x [rows,B,3] f64 (or [B,3]), waypoints [W,2] f64
+    -> a dict of seg, s, lateral, dist, lap and rank, each [rows,B]; an optional output that is switched off is
+    None."""
+    x = np.ascontiguousarray(x, np.float64)
+    rows, B = _rows_of(x, 3, "x")
+    wp = _path(waypoints)
+    _check_race(race, B)
+    i32 = lambda on: np.empty((rows, B), np.int32) if on else None  # noqa: E731
+    f64 = lambda on: np.empty((rows, B), np.float64) if on else None  # noqa: E731
+    o = dict(seg=i32(seg), s=f64(True), lateral=f64(lateral), dist=f64(True), lap=i32(lap), rank=i32(True))
+    _check(load().f110qp_race_standings(C.byref(race), B, rows, _p(x), _p(wp), wp.shape[0], _p(o["seg"]), _p(o["s"]),
+                                        _p(o["lateral"]), _p(o["dist"]), _p(o["lap"]), _p(o["rank"])),
+           "f110qp_race_standings")
+    return o
 
 
 def replan_start_dev(rp: ReplanConfig, sc, x, have_path, x_ref, gap, pose, kind, list_, count, hs=None, stream=None):

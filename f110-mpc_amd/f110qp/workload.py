@@ -379,6 +379,101 @@ def clearance(x, circles, group_size: int = 1, car_radius: float = 0.3, center_o
     return (clear[0], near[0]) if one else (clear, near)
 
 
+# ---- race standings (f110qp_path_lengths, f110qp_progress_dev, f110qp_standings_dev) ------------------------
+
+def path_lengths(wp) -> np.ndarray:
+    """cum [W + 1] of the closed path wp [W, 2] (f110qp_path_lengths): cum[0] = 0, cum[j + 1] = cum[j] +
+    sqrt(ex ex + ey ey) with e = wp[(j + 1) % W] - wp[j], summed in index order."""
+    wp = np.asarray(wp, np.float64)
+    e = np.roll(wp, -1, 0) - wp
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.concatenate([[0.0], np.cumsum(np.sqrt(e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]))])
+
+
+def progress(x, wp):
+    """The projection of include/f110qp.h (f110qp_progress_dev) in numpy, the device kernel's expressions in its
+    order: poses x [rows, B, 3] (or [B, 3]) on the closed path wp [W, 2] -> (seg [rows, B] int32, s [rows, B],
+    lateral [rows, B]). Per segment t = clamp((w.e) / (e.e)) (0 when e.e == 0), d2 = |p - (a + t e)|^2; the
+    minimum, the lowest index on equal values, NaN values never chosen, seg -1 and NaN without a candidate;
+    s = cum[j] + t (cum[j + 1] - cum[j]), lateral = sqrt(d2), negated unless ex wy - ey wx >= 0."""
+    x = np.asarray(x, np.float64)
+    one = x.ndim == 2
+    x = x[None] if one else x
+    wp = np.asarray(wp, np.float64)
+    rows, B = x.shape[:2]
+    cum = path_lengths(wp)
+    ax, ay = wp[None, :, 0], wp[None, :, 1]
+    seg = np.full((rows, B), -1, np.int32)
+    s = np.full((rows, B), np.nan)
+    lat = np.full((rows, B), np.nan)
+    car = np.arange(B)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        nx, ny = np.roll(wp[:, 0], -1)[None, :], np.roll(wp[:, 1], -1)[None, :]
+        ex, ey = nx - ax, ny - ay
+        ee = ex * ex + ey * ey
+        for r in range(rows):
+            px, py = x[r, :, 0:1], x[r, :, 1:2]
+            wx, wy = px - ax, py - ay
+            t = (wx * ex + wy * ey) / ee
+            t = np.where(ee == 0, 0.0, np.where(t < 0, 0.0, np.where(t > 1, 1.0, t)))
+            dx, dy = px - (ax + t * ex), py - (ay + t * ey)
+            d2 = dx * dx + dy * dy
+            d2 = np.where(np.isnan(d2), np.inf, d2)
+            j = np.argmin(d2, axis=1)                            # the first of equal values: the lowest index
+            best = d2[car, j]
+            hit = best < np.inf
+            tj = t[car, j]
+            sv = cum[j] + tj * (cum[j + 1] - cum[j])
+            root = np.sqrt(best)
+            left = ex[0, j] * wy[car, j] - ey[0, j] * wx[car, j] >= 0
+            seg[r] = np.where(hit, j, -1)
+            s[r] = np.where(hit, sv, np.nan)
+            lat[r] = np.where(hit, np.where(left, root, -root), np.nan)
+    return (seg[0], s[0], lat[0]) if one else (seg, s, lat)
+
+
+def standings(s, L: float, group_size: int = 1):
+    """The standings of include/f110qp.h (f110qp_standings_dev) in numpy: s [rows, B] (or [B]) on a path of
+    length L, the B cars being B / G races -> (dist [rows, B], lap [rows, B] int32, rank [rows, B] int32). Row 0
+    relative to the race's first car, every later row the row before plus the wrapped step, in row order; lap =
+    floor((dist - dist[0]) / L), INT_MIN where dist is NaN; rank = the race-mates ahead (a larger dist, or an
+    equal one with a lower index; NaN behind every number, the lower index ahead among NaN)."""
+    s = np.asarray(s, np.float64)
+    one = s.ndim == 1
+    s = s[None] if one else s
+    rows, B = s.shape
+    G, L = int(group_size), float(L)
+    if G < 1 or B % G:
+        raise ValueError(f"group_size must be >= 1 and divide B = {B}, got {G}")
+    half = 0.5 * L
+
+    def wrap(v):
+        return np.where(v > half, v - L, np.where(v <= -half, v + L, v))
+
+    dist = np.empty((rows, B))
+    lap = np.empty((rows, B), np.int32)
+    rank = np.empty((rows, B), np.int32)
+    first = np.arange(B) - np.arange(B) % G
+    m = np.arange(G)
+    with np.errstate(invalid="ignore"):
+        for r in range(rows):
+            if r == 0:
+                s0 = s[0, first]
+                dist[0] = s0 + wrap(s[0] - s0)
+            else:
+                dist[r] = dist[r - 1] + wrap(s[r] - s[r - 1])
+            d = dist[r]
+            num = ~np.isnan(d)
+            lp = np.floor((d - dist[0]) / L)
+            lap[r] = np.where(num, np.where(num, lp, 0.0).astype(np.int64), np.iinfo(np.int32).min).astype(np.int32)
+            dr = d.reshape(B // G, G)
+            dm, db = dr[:, None, :], dr[:, :, None]              # [race, car, mate]
+            lower = m[None, None, :] < m[None, :, None]
+            ahead = np.where(np.isnan(db), ~np.isnan(dm) | lower, (dm > db) | ((dm == db) & lower))
+            rank[r] = ahead.sum(axis=2).reshape(B)
+    return (dist[0], lap[0], rank[0]) if one else (dist, lap, rank)
+
+
 def make_race_grid(races: int, group_size: int, seed: int = 0, spacing: float = 1.2, lateral: float = 0.4) -> np.ndarray:
     """Start states [races * group_size, 3] float64 (x, y, yaw) of `races` races on track_waypoints(): a race
     starts at a seeded position on the path; its car i stands i * spacing metres behind car 0 along the path,

@@ -1026,6 +1026,83 @@ int f110qp_rollout_contact(f110qp_ctx* ctx, const f110qp_rollout_config* rc, con
                            int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
                            int* nearest_traj, int* crash_tick);
 
+/* ---- race standings: progress along the track, laps and positions ---------------------------------------
+ * The calls above return poses; the calls below say who is ahead. They run after the fact on x_traj, or on any
+ * [rows][B][3] pose array: nothing inside a closed loop reads a standing, so there is no rollout family of
+ * their own. Additive: F110QP_API_VERSION stays 6, and no call above changes its results.
+ *
+ * The path is waypoints [W][2] double, W >= 2, closed: segment j runs from a = wp[j] to b = wp[(j + 1) % W].
+ * Its cumulative length is cum [W + 1] double: cum[0] = 0, cum[j + 1] = cum[j] + sqrt(ex ex + ey ey) with
+ * e = b - a, summed in index order (the correctly rounded square root, every product and sum rounded);
+ * L = cum[W] is the path's length. The device call takes cum as an argument: the lengths are the caller's bits.
+ *
+ * Projection. The projected point is the pose's (x, y) itself, which is what Trajectory::get_best_global_idx
+ * measures from; ori is not read. All fp64, every product and sum rounded (no fused multiply-add). Per
+ * segment j, with p = (x, y):
+ *   e = b - a, w = p - a, ee = ex ex + ey ey
+ *   t = (wx ex + wy ey) / ee, clamped by t < 0 ? 0 : (t > 1 ? 1 : t); t = 0 when ee == 0
+ *   c = a + t e, d = p - c, d2 = dx dx + dy dy
+ * The winner is the minimum d2, the lowest j on equal values: a candidate replaces the running (best, index)
+ * only when d2 < best, or d2 == best with a lower j, from the start (+inf, -1). Per pose:
+ *   seg     = the winner's j
+ *   s       = cum[j] + t (cum[j + 1] - cum[j])
+ *   lateral = sqrt(d2), negated unless ex wy - ey wx >= 0: positive to the left of the direction of travel.
+ * Consequences: a NaN passes no compare, so a segment with a non-finite end point has a NaN d2 and is never
+ * chosen, and the segments next to it are undisturbed; a pose with a non-finite x or y has a NaN or +inf d2 on
+ * every segment, keeps the start value and gives seg = -1, s = NaN, lateral = NaN. A pose exactly on a vertex
+ * is at d2 = 0 on the segment that starts there (t = 0, c = a) and, where a + (b - a) is b exactly, on the one
+ * that ends there too (t = 1): the lower index wins, and at vertex 0 that is segment 0 over segment W - 1, so
+ * s = 0 there and never L. The minimum is over
+ * per-segment values that do not depend on the other segments: the result is the exact minimum (no cull).
+ * Limit: the nearest point is global. A track whose distinct sections come closer to each other than the cars
+ * stray from the path is outside this model: a car between two such sections is projected onto whichever is
+ * nearer, and its s jumps. The shipped ellipse and a world of walls 1.6 m to either side of it are inside it. */
+
+/* Host, plain C++ (no HIP call, no environment): cum [num_waypoints + 1] of waypoints [num_waypoints][2] as
+ * above. F110QP_ERR_INVALID: a NULL pointer, num_waypoints < 2. */
+int f110qp_path_lengths(const double* waypoints, int num_waypoints, double* cum);
+
+/* The projection of rows x B poses (device pointers, asynchronous on `stream`, one launch, no allocation,
+ * synchronisation or read-back):
+ *   x [rows][B][3] double, waypoints [W][2] double, cum [W + 1] double
+ *   -> seg [rows][B] int (may be NULL), s [rows][B] double, lateral [rows][B] double (may be NULL).
+ * F110QP_ERR_INVALID before any HIP call: a NULL x, waypoints, cum or s; batch < 1, rows < 1,
+ * num_waypoints < 2; rows x batch above 2^30. No cap on num_waypoints. Workgroups stride over the cars, one car
+ * each, at most min(batch, 1024) of them (what the device holds at once). */
+int f110qp_progress_dev(int batch, int rows, const double* x, const double* waypoints, const double* cum,
+                        int num_waypoints, int* seg, double* s, double* lateral, void* stream);
+
+/* Standings. The B cars of every row are B / G races as in f110qp_cast_scans_race_dev (only race->group_size
+ * is read; car_radius and center_offset are checked as there). With L = path_length and
+ *   wrap(v) = v > L/2 ? v - L : (v <= -L/2 ? v + L : v):
+ *   row 0, relative to the race's first car g0 = G (b / G):  dist[0][b] = s[0][g0] + wrap(s[0][b] - s[0][g0])
+ *   row r >= 1:  dist[r][b] = dist[r-1][b] + wrap(s[r][b] - s[r-1][b]), accumulated in row order
+ *   lap[r][b]  = (int)floor((dist[r][b] - dist[0][b]) / L), INT_MIN where dist is NaN
+ *   rank[r][b] = the number of race-mates m with dist[r][m] > dist[r][b], or equal with m < b. A car with a
+ *                NaN dist is behind every car with a number, and among NaN cars the lower index is ahead.
+ * dist is the distance driven along the path, unwrapped: it grows past L on the second lap and falls when a
+ * car reverses. 0 is the leader, and the ranks of a race are a permutation of 0 .. G-1 at every row. A NaN s
+ * makes that row and every later row of the car NaN (by the sums; a NaN s of the race's first car at row 0
+ * does the same to the whole race). A parked car's pose repeats, so its dist stands still: no special case.
+ * The model holds while a car moves less than L/2 along the path between two rows, and while a race's cars
+ * stand within L/2 of its first car at row 0.
+ *   s [rows][B] double -> dist [rows][B] double, lap [rows][B] int (may be NULL), rank [rows][B] int.
+ * Device pointers, asynchronous on `stream`: two launches (the sums in row order, then the ranks) with nothing
+ * but the stream's order between them; no allocation, synchronisation or read-back. No cap on G.
+ * F110QP_ERR_INVALID before any HIP call: every race rule of f110qp_cast_scans_race_dev; batch < 1, rows < 1;
+ * rows x batch above 2^30; a path_length that is not positive and finite; a NULL s, dist or rank. */
+int f110qp_standings_dev(const f110qp_race_config* race, int batch, int rows, const double* s, double path_length,
+                         double* dist, int* lap, int* rank, void* stream);
+
+/* Both on host pointers (synchronous): cum by f110qp_path_lengths, L = cum[W]; x, waypoints and cum staged
+ * through device buffers that the call owns and frees on every exit path (there is no context), the two device
+ * calls, every output that was given copied back, one synchronisation. seg, lateral and lap may be NULL.
+ * Bit-identical to the two device calls. F110QP_ERR_INVALID as theirs, before any HIP call (a path whose
+ * length is not positive and finite included). */
+int f110qp_race_standings(const f110qp_race_config* race, int batch, int rows, const double* x,
+                          const double* waypoints, int num_waypoints, int* seg, double* s, double* lateral,
+                          double* dist, int* lap, int* rank);
+
 #ifdef __cplusplus
 }
 #endif
