@@ -169,10 +169,47 @@ def track_case(B=8, G=4, seed=11):
     return ContactCase("track", workload.make_race_grid(B // G, G, seed), G, wc_.track_world())
 
 
+GRID = 1024      # clearance_grid's cap: a larger batch strides, a workgroup takes car b and then b + GRID
+PASS = 8         # kClearPoses: the rows of a car that one pass takes
+PASS_ROWS = (PASS, PASS + 1, 2 * PASS + 1)  # one whole pass; a second of one row; a third, after two whole ones
+OFFSETS = (0.0, CENTER_OFFSET)
+
+
+def rows_case(rows, off=CENTER_OFFSET, seed=101):
+    """Two races of G = 3 in 40 circles, every row scattered anew within 3.2 m (a centre left over from the
+    pass before is metres off, as is a mate read at row p for row r0 + p), and one circle over car 0 at the
+    last row: at rows = 9 and 17 the nearest of the only pose of a pass cut short."""
+    x = poses(rows, 6, seed + rows) * [8.0, 8.0, 1.0]
+    ci = wc_.random_world(40, seed + rows + 1)
+    # (|off| - 1) - 0.3 <= -1.13: under any mate's -0.6 and any other circle's (0 - 0.6) - 0.3
+    ci[-1] = [x[rows - 1, 0, 0], x[rows - 1, 0, 1], 1.0]
+    return ContactCase(f"rows {rows} G 3 off {off}", x, 3, ci, off)
+
+
+def stride_case(per_car=True, off=CENTER_OFFSET, rows=2, G=5, C=3, seed=111):
+    """B = GRID + 6 = 1030 cars within 3.2 m in races of G: the workgroups of cars 0..5 take cars 1024..1029
+    too, on the same LDS. G = 5: races 204 (cars 1020..1024) and 205 (1025..1029) have their mates in other
+    workgroups' strides. per_car: every car its own C circles, other ones for car b than for car b + GRID."""
+    B = GRID + 6
+    x = poses(rows, B, seed + rows + G) * [8.0, 8.0, 1.0]
+    ci = wc_.random_world(C, seed + 1, B if per_car else None, spread=3.0)
+    if per_car:
+        assert (ci[:B - GRID] != ci[GRID:]).any(axis=(1, 2)).all(), "car b and car b + GRID: different worlds"
+    return ContactCase(f"stride B {B} rows {rows} G {G} C {C} world_rows {B if per_car else 1} off {off}", x, G, ci, off)
+
+
+def stride_rows_case(off=CENTER_OFFSET):
+    """The second pass of the second car of a workgroup: B = 1030 in pairs, rows = 9, one circle per car."""
+    return stride_case(True, off, rows=PASS + 1, G=2, C=1)
+
+
 def oracle_cases():
     out = [random_case(False), random_case(True), random_case(False, 0.0), random_case(True, 0.0), crowd_case(), track_case()]
     out += [edge_case(C, rows) for C in (0, 1, TILE - 1, TILE, TILE + 1, 2 * TILE + 1) for rows in (1, 5)]
     out += [batch_case(B, rows) for B in (1, 63, 65, 257) for rows in (1, 5)]
+    out += [rows_case(rows, off) for rows in PASS_ROWS for off in OFFSETS]
+    out += [stride_case(per_car, off) for per_car in (True, False) for off in OFFSETS]
+    out += [stride_rows_case(off) for off in OFFSETS]
     return out
 
 
@@ -181,14 +218,52 @@ def oracle_cases():
 BLOCK_R, BLOCK_GAP = 1.0, 0.012  # the circle's radius and the clearance of car 0 at row 0
 
 
-def crash_scene(B=8, G=4, seed=41, gap=BLOCK_GAP):
-    """(x0 [B,3], circles [C,3]): make_race_grid in the track world, plus one circle of radius BLOCK_R whose
-    face is `gap` metres ahead of car 0's body (gap < 0: in contact at row 0). Without a path a car applies
-    fail_u (0.5 m/s): 5 mm a tick, so the body reaches the face within three ticks."""
+def block_ahead(x, gap):
+    """The circle of radius BLOCK_R whose face is `gap` metres ahead of the body of the car at pose x."""
+    q = x[:2] + CENTER_OFFSET * np.array([np.cos(x[2]), np.sin(x[2])])
+    c = q + (CAR_RADIUS + BLOCK_R + gap) * np.array([np.cos(x[2]), np.sin(x[2])])
+    return [c[0], c[1], BLOCK_R]
+
+
+WALLS = 1000  # make_world's first rows: the two walls of 500 circles
+
+
+def crash_scene(B=8, G=4, seed=41, gap=BLOCK_GAP, blocked=(0,), gaps=None, per_car=False):
+    """(x0 [B,3], circles [C,3]): make_race_grid in the track world, plus one circle of radius BLOCK_R per car of
+    `blocked`, its face gaps[i] (default: `gap`) metres ahead of that car's body (a gap < 0: in contact at row 0).
+    Without a path a car applies fail_u (0.5 m/s): 5 mm a tick, so the body reaches the face within three ticks.
+    per_car: circles [B,1001,3], every car a world of its own: the track's walls and one more circle, the car's
+    block or, for a car that has none, a circle out of everybody's reach."""
     x0 = workload.make_race_grid(B // G, G, seed)
-    q = x0[0, :2] + CENTER_OFFSET * np.array([np.cos(x0[0, 2]), np.sin(x0[0, 2])])
-    c = q + (CAR_RADIUS + BLOCK_R + gap) * np.array([np.cos(x0[0, 2]), np.sin(x0[0, 2])])
-    return x0, np.ascontiguousarray(np.concatenate([wc_.track_world(), [[c[0], c[1], BLOCK_R]]]))
+    gaps = [gap] * len(blocked) if gaps is None else gaps
+    blocks = [block_ahead(x0[b], g) for b, g in zip(blocked, gaps)]
+    if not per_car:
+        return x0, np.ascontiguousarray(np.concatenate([wc_.track_world(), blocks]))
+    w = np.empty((B, WALLS + 1, 3))
+    w[:, :WALLS] = wc_.track_world()[:WALLS]
+    w[:, WALLS] = [60.0, 60.0, 0.1]
+    w[list(blocked), WALLS] = blocks
+    return x0, w
+
+
+# The second scene: 65 races of four (two workgroups of the plant step, a last wave of four lanes). The races
+# start at seeded places of one 58 m track and overlap there, which harms nothing (a car touches and sees its
+# own race only) but for the blocks: hence crash_scene's per-car worlds. They hold the track's walls only: its
+# obstacles stand 0.9 m off the path, and of 260 cars 0.4 m off it some would start inside one.
+# Nine ticks, one more than the eight that would hold every crash: a free car plans at tick 0, solves at ticks 1 .. 6,
+# holds at tick 7 and plans again at tick 8, and that second plan list is the one the waves ballot for with parked
+# lanes among them.
+WIDE_B, WIDE_G, WIDE_T = 260, 4, 9
+# car -> gap: the first and the last lane of a wave (0 and 63, 64 and 255), both sides of the workgroup edge
+# (255, 256), the batch's last car; one in contact at row 0, the others 5 mm a tick from their block (a car
+# this close to a wall finds no plan), so at ticks 1 .. 5. Race 64 holds two of them, the second crashing
+# behind the first.
+WIDE_BLOCKED = {0: -0.05, 63: 0.003, 64: 0.007, 255: 0.012, 256: 0.017, 259: 0.022}
+
+
+def wide_crash_scene():
+    """(x0 [260,3], circles [260,1001,3])."""
+    return crash_scene(WIDE_B, WIDE_G, 43, blocked=tuple(WIDE_BLOCKED), gaps=list(WIDE_BLOCKED.values()), per_car=True)
 
 
 if __name__ == "__main__":

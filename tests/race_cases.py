@@ -92,6 +92,21 @@ def follower_start(gap=GAP, seed=5):
     return RaceCase(f"follower {gap} m", workload.make_race_grid(1, 2, seed, spacing=gap, lateral=0.0), 2, None)
 
 
+CAST_GRID = 768  # cast_scans_grid's cap: a larger batch strides
+
+
+def stride_race(B=CAST_GRID + 12, G=4, seed=51, beams=64):
+    """B = 780 cars within 1.6 m of the origin in races of 4, every car its own world of three circles, other
+    ones for car b than for car b + CAST_GRID: twelve workgroups of the race instantiation take a second car.
+    Compared with the plain cast (oracle-tested above its cap by world_cases.per_car_case) at center_offset = 0,
+    so it is no oracle case."""
+    x = wc_.poses_near_origin(B, seed)
+    x[:, :2] *= 4.0
+    static = wc_.random_world(3, seed + 1, B, spread=3.0)
+    assert B > CAST_GRID and B % G == 0 and (static[:B - CAST_GRID] != static[CAST_GRID:]).any(axis=(1, 2)).all()
+    return RaceCase(f"stride B {B} G {G}", x, G, static, wc_.geometry(beams), beams, center_offset=0.0)
+
+
 def oracle_cases():
     return [track_race(), pair_in_line(), crowd(250), crowd(0), rollout_race_start(), follower_start()]
 

@@ -1,7 +1,9 @@
 """The clearance kernel on MI355X (f110qp_clearance_dev, include/f110qp.h "contact") against the numpy oracle
 workload.clearance: bit equality at center_offset = 0, contact_cases' derived bound and skip rule with the
-default offset, the tile and tail edges, ties, permutations, non-finite and odd inputs, symmetry. Every case
-is built in contact_cases.py (test_contact_cases.py holds them to the skip cap on the CPU)."""
+default offset, the tile and tail edges, more rows than a pass takes, more cars than workgroups, ties,
+permutations, non-finite and odd inputs, symmetry. Every call writes between two guard rows that must stay as
+they were. Every case is built in contact_cases.py (test_contact_cases.py holds them to the skip cap on the
+CPU)."""
 import contact_cases as cc_
 import numpy as np
 import pytest
@@ -21,11 +23,19 @@ def clearance(capi, cuda, x, circles, G, off=cc_.CENTER_OFFSET, R=cc_.CAR_RADIUS
     Cn = 0 if circles is None else circles.shape[-2]
     wc = capi.default_world_config(num_circles=Cn, world_rows=1 if circles is None or circles.ndim == 2 else B)
     race = capi.default_race_config(group_size=G, car_radius=R, center_offset=off)
-    out = torch.full((rows, B), -7.0, dtype=torch.float64, device=cuda)
-    near = torch.full((rows, B), -7, dtype=torch.int32, device=cuda) if nearest else None
-    capi.clearance_dev(wc, race, dev(cuda, x), None if circles is None else dev(cuda, circles), out, near)
+    # one guard row in front of the call's rows and one behind: the call must leave both as they are
+    out = torch.full((rows + 2, B), -7.0, dtype=torch.float64, device=cuda)
+    near = torch.full((rows + 2, B), -7, dtype=torch.int32, device=cuda) if nearest else None
+    capi.clearance_dev(wc, race, dev(cuda, x), None if circles is None else dev(cuda, circles), out[1:-1],
+                       near[1:-1] if nearest else None)
     torch.cuda.synchronize(cuda)
-    return out.cpu().numpy(), near.cpu().numpy() if nearest else None
+    out = out.cpu().numpy()
+    assert (out[[0, -1]] == -7.0).all(), "clearance: a guard row was written"
+    if not nearest:
+        return np.ascontiguousarray(out[1:-1]), None
+    near = near.cpu().numpy()
+    assert (near[[0, -1]] == -7).all(), "nearest: a guard row was written"
+    return np.ascontiguousarray(out[1:-1]), np.ascontiguousarray(near[1:-1])
 
 
 def run(capi, cuda, c):
@@ -75,6 +85,48 @@ def test_mates_span_two_tiles(capi, cuda):
 @pytest.mark.parametrize("B", [1, 63, 65, 257])
 def test_batch_sizes(capi, cuda, B, rows):
     c = cc_.batch_case(B, rows)
+    c.check(*run(capi, cuda, c))
+
+
+@pytest.mark.parametrize("off", cc_.OFFSETS, ids=["offset_0", "default_offset"])
+@pytest.mark.parametrize("rows", cc_.PASS_ROWS)
+def test_row_passes(capi, cuda, rows, off):
+    """More rows than one pass of eight takes: a whole pass, a second pass of one row, a third behind two whole
+    ones. Every row is scattered anew and G = 3, so a centre kept from the pass before, or an output or a mate's
+    row indexed inside the pass instead of inside the call, is metres off. The circle over car 0 at the last
+    row is the nearest there."""
+    c = cc_.rows_case(rows, off)
+    clear, near = run(capi, cuda, c)
+    c.check(clear, near)
+    wnear = c.oracle()[1]
+    assert wnear[rows - 1, 0] == c.C - 1 and (wnear[:rows - 1, 0] != c.C - 1).any()
+    assert (wnear >= c.C).any() and (wnear < c.C).any(), "mates and circles are both somebody's nearest"
+    if off == 0.0:
+        no_idx, _ = clearance(capi, cuda, c.x, c.circles, c.G, off, nearest=False)  # nearest NULL
+        assert (bits(no_idx) == bits(clear)).all()
+
+
+@pytest.mark.parametrize("off", cc_.OFFSETS, ids=["offset_0", "default_offset"])
+@pytest.mark.parametrize("per_car", [True, False], ids=["world_per_car", "one_world"])
+def test_grid_stride(capi, cuda, per_car, off):
+    """B = GRID + 6: six workgroups take a second car, whose world lies past the cap's offset, and the races
+    around car 1,024 have their mates in other workgroups' strides."""
+    c = cc_.stride_case(per_car, off)
+    assert c.B == cc_.GRID + 6 and c.B % c.G == 0 and (cc_.GRID // c.G) * c.G < cc_.GRID < (cc_.GRID // c.G + 1) * c.G
+    clear, near = run(capi, cuda, c)
+    c.check(clear, near)
+    wnear = c.oracle()[1][:, cc_.GRID - 4:]
+    assert (wnear >= c.C).any() and (wnear < c.C).any(), "past the cap: mates and circles are both somebody's nearest"
+    if per_car and off == 0.0:
+        no_idx, _ = clearance(capi, cuda, c.x, c.circles, c.G, off, nearest=False)  # nearest NULL
+        assert (bits(no_idx) == bits(clear)).all()
+
+
+@pytest.mark.parametrize("off", cc_.OFFSETS, ids=["offset_0", "default_offset"])
+def test_grid_stride_with_a_second_pass(capi, cuda, off):
+    """B = GRID + 6 and rows = 9: the second pass of the second car of a workgroup."""
+    c = cc_.stride_rows_case(off)
+    assert c.B == cc_.GRID + 6 and c.rows == cc_.PASS + 1 and c.world_rows == c.B
     c.check(*run(capi, cuda, c))
 
 

@@ -96,6 +96,19 @@ def test_opponents_across_circle_tiles(capi, cuda, C):
     print(f"crowd C {C}: worst {worst:.3f} of the bound")
 
 
+def test_more_cars_than_workgroups(capi, cuda):
+    """4b. B = 780 in races of 4, above the grid cap of 768, one world of three circles per car, at offset 0:
+    bit-equal to the plain cast on built rows. The plain kernel above its cap meets the oracle in
+    test_gpu_world_scan_edges.py, so this ties the race instantiation's stride and per-car world offset to it."""
+    c = rc_.stride_race()
+    got = race_cast(capi, cuda, c.x, c.static, c.G, c.geom, c.beams, center_offset=0.0)
+    same_bits(got, plain_route(capi, cuda, c.x, c.static, c.G, c.geom, c.beams), c.name)
+    alone = cast(capi, cuda, c.x, c.static, c.geom, c.beams)
+    past = slice(rc_.CAST_GRID - c.G, None)  # the races with a car past the cap
+    assert (got[past] != alone[past]).any(axis=1).sum() >= 8, "the cars past the cap see their race-mates"
+    assert (alone[past] < wc_.MAX_RANGE).any(axis=1).sum() >= 8, "... and their own circles"
+
+
 def test_order_independence(capi, cuda):
     """5. Permuting the cars inside each race permutes the scans, bit for bit (and so does the order of the
     static circles)."""

@@ -29,7 +29,8 @@ def race_case(B, G, seed=41, static="track"):
 
 
 def configs(capi, circles, G):
-    wc = capi.default_world_config(num_circles=0 if circles is None else circles.shape[-2])
+    wc = capi.default_world_config(num_circles=0 if circles is None else circles.shape[-2],
+                                   world_rows=1 if circles is None or circles.ndim == 2 else circles.shape[0])
     return wc, capi.default_race_config(group_size=G)
 
 
