@@ -31,8 +31,13 @@ constexpr size_t seg_lds_per_wave(int N, int S, bool f32 = false) {
 // them, else float ones, possibly in more than one dispatch round: 16,384 x N = 40 runs S = 4 on
 // fp32 scratch in one round, 32,768 x N = 40 in two, round 4). Among those the launch takes the S with the shortest per-pass chain by the
 // instruction model of DESIGN.md 2b': sequential N x ~255 instructions, segmented ceil(N / S) x
-// ~350 + (S - 1) x ~230 (the two segment recursions). A forced QPs-per-wave or scratch placement
-// keeps lane_kernel.h.
+// ~350 + the segment ends: at S = 8 (S - 1) x ~230 (the ring's two recursions), at S <= 4 ~140 +
+// (S / 2 - 1) x ~260 (the two-sided elimination, from the ISA of the S = 2 / S = 4 kernels against
+// their ring versions: operand and result selects ~75, the meet ~65 + 18 DPP moves, a full step ~195
+// and a short one ~45 with their exchanges). The cheaper ends put S = 4 ahead of S = 8 at N = 21 ..
+// 28 by 5 % of the modelled chain, which is inside the model's error and not measured: where the
+// ring's constants chose S = 8, S = 8 stays. A forced QPs-per-wave or scratch placement keeps
+// lane_kernel.h.
 int lane_segments(const KParams& P, int B, const LaneWork& lw) {
   const int N = P.N;
   // dispatch rounds of the segmented grid: waves per CU over the waves the CU's 160 KiB of LDS
@@ -56,19 +61,25 @@ int lane_segments(const KParams& P, int B, const LaneWork& lw) {
   if (lw.seg == 1) return 1;
   if (lw.seg == 2 || lw.seg == 4 || lw.seg == 8) return rounds(lw.seg) > 0 ? lw.seg : 1;
   if (lw.qpw != 0 || (lw.mode != 0 && lw.mode != 1)) return 1;
-  int best = 1;
-  double cbest = 255.0 * N;
+  int best = 1, ring_best = 1;  // (ring_best: the choice under the ring's segment-end cost at every S)
+  double cbest = 255.0 * N, cring = cbest;
   for (int S = 2; S <= 8; S <<= 1) {
     const int r = rounds(S);
     if (r == 0) continue;
     // per-pass chain x dispatch rounds (the sequential kernel keeps its grid resident: HBM scratch)
-    const double c = r * (350.0 * ((N + S - 1) / S) + 230.0 * (S - 1));
+    const double stages = 350.0 * ((N + S - 1) / S);
+    const double ends = S <= 4 ? 140.0 + 260.0 * (S / 2 - 1) : 230.0 * (S - 1);
+    const double c = r * (stages + ends), cr = r * (stages + 230.0 * (S - 1));
     if (c < cbest) {
       best = S;
       cbest = c;
     }
+    if (cr < cring) {
+      ring_best = S;
+      cring = cr;
+    }
   }
-  return best;
+  return ring_best == 8 ? 8 : best;
 }
 
 #ifndef F110QP_LANE_ALL

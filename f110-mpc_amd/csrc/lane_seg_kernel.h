@@ -20,10 +20,14 @@
 //    boundary problem, solved by a Riccati recursion over the segments, lam_{j-1} = M_j x + m_j:
 //      T_j = (I - M_{j+1} Gam_j)^-1 M_{j+1} Phi_j,  t_j = (I - M_{j+1} Gam_j)^-1 (M_{j+1} psi_j + m_{j+1}),
 //      M_j = P_j + Phi_j' T_j,  m_j = a_j + Phi_j' t_j,   then lam_j = T_j x_s^(j) + t_j forward.
-//    (I - M Gam has eigenvalues >= 1: M is positive definite, Gam negative semidefinite.) Every
-//    lane runs every step on its own data with its neighbour's (M, m) / x_e from a lane shuffle;
-//    the top segment's (Phi, psi, Gam) are zeroed so that its lane reproduces (P, a) and hands
-//    x_e = 0 to segment 0 round the ring: S - 1 identical steps each way, no selects.
+//    (I - M Gam has eigenvalues >= 1: M is positive definite, Gam negative semidefinite.)
+//    S <= 4: eliminated from both ends at once. The lower half of the QP's lanes runs the same
+//    step on exchanged operands (x_j = alpha_{j-1} + beta_{j-1} lam_{j-1} from x_s^(0) = 0), the
+//    two sides meet in the middle in one 3 x 3 vector solve and hand (x_s, lam) outwards again:
+//    S / 2 - 1 full steps, the meet and S / 2 - 1 short steps, one instruction stream.
+//    S = 8: every lane runs every step on its own data with its neighbour's (M, m) / x_e from a
+//    lane shuffle; the top segment's (Phi, psi, Gam) are zeroed so that its lane reproduces (P, a)
+//    and hands x_e = 0 to segment 0 round the ring: S - 1 identical steps each way, no selects.
 // 3. refresh, all segments: the lam-part of the feed-forward, p^lam_e = lam_j,
 //    k_i += -S_i^-1 B' p^lam_{i+1},  p^lam_i = A' p^lam_{i+1} + K_i' B' p^lam_{i+1}
 //    (the p-recursion of the Riccati step restricted to its lam-dependent part).
@@ -32,8 +36,8 @@
 // A pass's result equals the sequential pass's up to rounding (tests/diag_segment_riccati_model.py:
 // 1.8e-15 relative on random masks), so the PDAS iterates, the single-flip rule (the first
 // violation over the whole horizon: a min over the QP's lanes) and the stopping test are
-// lane_kernel.h's. Per pass the chain is m stages of ~(200 + 120 + 30) instructions plus
-// 2 (S - 1) segment steps instead of N stages of ~255.
+// lane_kernel.h's. Per pass the chain is m stages of ~(200 + 120 + 30) instructions plus the
+// segment ends (S = 8: 2 (S - 1) steps; S <= 4: S - 2 and the meet) instead of N stages of ~255.
 //
 // Layout (fp64 throughout): lane l = S slot + j works on QP L w + slot, segment j (a QP's segments
 // are adjacent lanes: its segment-end exchanges stay inside a quad at S <= 4). LDS per wave,
@@ -661,35 +665,60 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     }
     SACC(acc_bw, t_bw);
     SSTAMP(t_dual);
-    // ---- 2. the segment ends: Riccati over the segments, then lam_j, x_s^(j) forward ----
-    // the top segment hands (P, a) up the chain and x_e = 0 round the ring to segment 0
-    if (top) {
-      F00 = F01 = F02 = F10 = F11 = F12 = F20 = F21 = F22 = 0.0;
-      s0v = s1v = s2v = 0.0;
-      G00 = G01 = G02 = G11 = G12 = G22 = 0.0;
-    }
+    // ---- 2. the segment ends: the boundary problem over the segments, eliminated from both ends ----
+    // S <= 4: the lower half of a QP's lanes (x_s^(0) = 0 below) and the upper half (the true terminal
+    // cost on top) eliminate towards the middle in lockstep, S / 2 - 1 full steps each, and meet in
+    // one 3 x 3 vector solve; S / 2 - 1 short steps per side then hand (x_s, lam) outwards. The lower
+    // side's recursion x_j = alpha_{j-1} + beta_{j-1} lam_{j-1}, (alpha, beta)_0 = (psi, Gam)_0, is the
+    // upper side's step with the operands exchanged,
+    //   (Mn, mn, Gam, Phi, psi, P, a) <- (beta_{j-1}, alpha_{j-1}, P_j, Phi_j', a_j, Gam_j, psi_j),
+    // so both halves run one instruction stream on operand copies selected once per pass (the
+    // forward sweep still needs the lane's own P, a and Phi). beta stays symmetric negative
+    // semidefinite and M positive semidefinite: I - beta P, I - M Gam and the meet's I - beta M have
+    // eigenvalues >= 1. S = 8 keeps the one-sided ring: the top segment's (Phi, psi, Gam) zeroed so
+    // that its lane hands (P, a) up the chain and x_e = 0 round the ring, S - 1 steps each way.
+    // (tests/diag_seg_ends_model.py: both against a dense solve of the boundary system)
     lm0 = lm1 = lm2 = 0.0;
     xs0 = xs1 = xs2 = 0.0;
     if constexpr (S > 1) {
-      double M00 = P00, M01 = P01, M02 = P02, M11 = P11, M12 = P12, M22 = P22;
-      double m0 = p0, m1 = p1, m2 = p2;
+      constexpr bool TWO = S <= 4;
+      const bool low = TWO && seg < S / 2;
+      if constexpr (!TWO) {
+        if (top) {
+          F00 = F01 = F02 = F10 = F11 = F12 = F20 = F21 = F22 = 0.0;
+          s0v = s1v = s2v = 0.0;
+          G00 = G01 = G02 = G11 = G12 = G22 = 0.0;
+        }
+      }
+      // the step's operands: the lane's own, exchanged on the lower side (Phi' is a renaming)
+      const double gG00 = low ? P00 : G00, gG01 = low ? P01 : G01, gG02 = low ? P02 : G02;
+      const double gG11 = low ? P11 : G11, gG12 = low ? P12 : G12, gG22 = low ? P22 : G22;
+      const double gF00 = F00, gF11 = F11, gF22 = F22;
+      const double gF01 = low ? F10 : F01, gF10 = low ? F01 : F10, gF02 = low ? F20 : F02;
+      const double gF20 = low ? F02 : F20, gF12 = low ? F21 : F12, gF21 = low ? F12 : F21;
+      const double gs0 = low ? p0 : s0v, gs1 = low ? p1 : s1v, gs2 = low ? p2 : s2v;
+      const double gP00 = low ? G00 : P00, gP01 = low ? G01 : P01, gP02 = low ? G02 : P02;
+      const double gP11 = low ? G11 : P11, gP12 = low ? G12 : P12, gP22 = low ? G22 : P22;
+      const double gp0 = low ? s0v : p0, gp1 = low ? s1v : p1, gp2 = low ? s2v : p2;
+      // what the lane hands on: (M, m) upwards, (beta, alpha) on the lower side; before any step
+      // the top segment's (P, a) and segment 0's (Gam, psi)
+      double M00 = gP00, M01 = gP01, M02 = gP02, M11 = gP11, M12 = gP12, M22 = gP22;
+      double m0 = gp0, m1 = gp1, m2 = gp2;
       double T00 = 0, T01 = 0, T02 = 0, T10 = 0, T11 = 0, T12 = 0, T20 = 0, T21 = 0, T22 = 0;
       double t0 = 0, t1 = 0, t2 = 0;
-#pragma unroll 1
-      for (int it = 0; it < S - 1; it++) {
-        const double N00 = seg_up<S>(M00, lane), N01 = seg_up<S>(M01, lane), N02 = seg_up<S>(M02, lane);
-        const double N11 = seg_up<S>(M11, lane), N12 = seg_up<S>(M12, lane), N22 = seg_up<S>(M22, lane);
-        const double n0 = seg_up<S>(m0, lane), n1 = seg_up<S>(m1, lane), n2 = seg_up<S>(m2, lane);
+      // one full elimination step with the neighbour's (Mn, mn): T, t and the lane's new (M, m)
+      auto step = [&](double N00, double N01, double N02, double N11, double N12, double N22, double n0,
+                      double n1, double n2) {
         // Z = I - Mn Gam
-        const double Z00 = 1.0 - (N00 * G00 + N01 * G01 + N02 * G02);
-        const double Z01 = -(N00 * G01 + N01 * G11 + N02 * G12);
-        const double Z02 = -(N00 * G02 + N01 * G12 + N02 * G22);
-        const double Z10 = -(N01 * G00 + N11 * G01 + N12 * G02);
-        const double Z11 = 1.0 - (N01 * G01 + N11 * G11 + N12 * G12);
-        const double Z12 = -(N01 * G02 + N11 * G12 + N12 * G22);
-        const double Z20 = -(N02 * G00 + N12 * G01 + N22 * G02);
-        const double Z21 = -(N02 * G01 + N12 * G11 + N22 * G12);
-        const double Z22 = 1.0 - (N02 * G02 + N12 * G12 + N22 * G22);
+        const double Z00 = 1.0 - (N00 * gG00 + N01 * gG01 + N02 * gG02);
+        const double Z01 = -(N00 * gG01 + N01 * gG11 + N02 * gG12);
+        const double Z02 = -(N00 * gG02 + N01 * gG12 + N02 * gG22);
+        const double Z10 = -(N01 * gG00 + N11 * gG01 + N12 * gG02);
+        const double Z11 = 1.0 - (N01 * gG01 + N11 * gG11 + N12 * gG12);
+        const double Z12 = -(N01 * gG02 + N11 * gG12 + N12 * gG22);
+        const double Z20 = -(N02 * gG00 + N12 * gG01 + N22 * gG02);
+        const double Z21 = -(N02 * gG01 + N12 * gG11 + N22 * gG12);
+        const double Z22 = 1.0 - (N02 * gG02 + N12 * gG12 + N22 * gG22);
         // Z^-1 by the adjugate
         const double A00 = Z11 * Z22 - Z12 * Z21, A01 = Z02 * Z21 - Z01 * Z22, A02 = Z01 * Z12 - Z02 * Z11;
         const double A10 = Z12 * Z20 - Z10 * Z22, A11 = Z00 * Z22 - Z02 * Z20, A12 = Z02 * Z10 - Z00 * Z12;
@@ -707,54 +736,122 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         const double Y11 = iz * (A10 * N01 + A11 * N11 + A12 * N12);
         const double Y12 = iz * (A10 * N02 + A11 * N12 + A12 * N22);
         const double Y22 = iz * (A20 * N02 + A21 * N12 + A22 * N22);
-        T00 = Y00 * F00 + Y01 * F10 + Y02 * F20; T01 = Y00 * F01 + Y01 * F11 + Y02 * F21;
-        T02 = Y00 * F02 + Y01 * F12 + Y02 * F22;
-        T10 = Y01 * F00 + Y11 * F10 + Y12 * F20; T11 = Y01 * F01 + Y11 * F11 + Y12 * F21;
-        T12 = Y01 * F02 + Y11 * F12 + Y12 * F22;
-        T20 = Y02 * F00 + Y12 * F10 + Y22 * F20; T21 = Y02 * F01 + Y12 * F11 + Y22 * F21;
-        T22 = Y02 * F02 + Y12 * F12 + Y22 * F22;
+        T00 = Y00 * gF00 + Y01 * gF10 + Y02 * gF20; T01 = Y00 * gF01 + Y01 * gF11 + Y02 * gF21;
+        T02 = Y00 * gF02 + Y01 * gF12 + Y02 * gF22;
+        T10 = Y01 * gF00 + Y11 * gF10 + Y12 * gF20; T11 = Y01 * gF01 + Y11 * gF11 + Y12 * gF21;
+        T12 = Y01 * gF02 + Y11 * gF12 + Y12 * gF22;
+        T20 = Y02 * gF00 + Y12 * gF10 + Y22 * gF20; T21 = Y02 * gF01 + Y12 * gF11 + Y22 * gF21;
+        T22 = Y02 * gF02 + Y12 * gF12 + Y22 * gF22;
         const double an0 = A00 * n0 + A01 * n1 + A02 * n2, an1 = A10 * n0 + A11 * n1 + A12 * n2;
         const double an2 = A20 * n0 + A21 * n1 + A22 * n2;
-        t0 = Y00 * s0v + Y01 * s1v + Y02 * s2v + iz * an0;
-        t1 = Y01 * s0v + Y11 * s1v + Y12 * s2v + iz * an1;
-        t2 = Y02 * s0v + Y12 * s1v + Y22 * s2v + iz * an2;
-        // (Q > 0: nothing reads (M, m) after the last step: segment 0 has no lower neighbour and
-        // x_s^(0) = 0; a scalar branch instead of ~27 fp64 operations per pass)
-        if constexpr (Q > 0) {
-          if (it == S - 2) break;
-        }
+        t0 = Y00 * gs0 + Y01 * gs1 + Y02 * gs2 + iz * an0;
+        t1 = Y01 * gs0 + Y11 * gs1 + Y12 * gs2 + iz * an1;
+        t2 = Y02 * gs0 + Y12 * gs1 + Y22 * gs2 + iz * an2;
         // M = P + Phi' T, m = a + Phi' t
-        M00 = P00 + F00 * T00 + F10 * T10 + F20 * T20;
-        M01 = P01 + F00 * T01 + F10 * T11 + F20 * T21;
-        M02 = P02 + F00 * T02 + F10 * T12 + F20 * T22;
-        M11 = P11 + F01 * T01 + F11 * T11 + F21 * T21;
-        M12 = P12 + F01 * T02 + F11 * T12 + F21 * T22;
-        M22 = P22 + F02 * T02 + F12 * T12 + F22 * T22;
-        m0 = p0 + F00 * t0 + F10 * t1 + F20 * t2;
-        m1 = p1 + F01 * t0 + F11 * t1 + F21 * t2;
-        m2 = p2 + F02 * t0 + F12 * t1 + F22 * t2;
-      }
+        M00 = gP00 + gF00 * T00 + gF10 * T10 + gF20 * T20;
+        M01 = gP01 + gF00 * T01 + gF10 * T11 + gF20 * T21;
+        M02 = gP02 + gF00 * T02 + gF10 * T12 + gF20 * T22;
+        M11 = gP11 + gF01 * T01 + gF11 * T11 + gF21 * T21;
+        M12 = gP12 + gF01 * T02 + gF11 * T12 + gF21 * T22;
+        M22 = gP22 + gF02 * T02 + gF12 * T12 + gF22 * T22;
+        m0 = gp0 + gF00 * t0 + gF10 * t1 + gF20 * t2;
+        m1 = gp1 + gF01 * t0 + gF11 * t1 + gF21 * t2;
+        m2 = gp2 + gF02 * t0 + gF12 * t1 + gF22 * t2;
+      };
+      // a short step from the lane's unknown y (x_s going up, lam going down): w = T y + t (lam_j
+      // up, x_s down) and what the next lane outwards starts from, e = Phi y + psi + Gam w
+      // (x_s^(j+1) up; lam_{j-1} = Phi' lam + a + P x_s down)
+      auto hand_on = [&](double y0, double y1, double y2, double& w0, double& w1, double& w2, double& e0,
+                         double& e1, double& e2) {
+        w0 = T00 * y0 + T01 * y1 + T02 * y2 + t0;
+        w1 = T10 * y0 + T11 * y1 + T12 * y2 + t1;
+        w2 = T20 * y0 + T21 * y1 + T22 * y2 + t2;
+        e0 = gF00 * y0 + gF01 * y1 + gF02 * y2 + gs0 + gG00 * w0 + gG01 * w1 + gG02 * w2;
+        e1 = gF10 * y0 + gF11 * y1 + gF12 * y2 + gs1 + gG01 * w0 + gG11 * w1 + gG12 * w2;
+        e2 = gF20 * y0 + gF21 * y1 + gF22 * y2 + gs2 + gG02 * w0 + gG12 * w1 + gG22 * w2;
+      };
+      if constexpr (TWO) {
+        // quad_perm [1, 0, 3, 2]: segment 1 reads segment 0 and segment 2 segment 3 in one move (the
+        // outer lanes run the step on what they receive and drop the result)
+        constexpr int kPair = 0xB1;
+        if constexpr (S == 4) {
+          step(dpp_d<kPair>(M00), dpp_d<kPair>(M01), dpp_d<kPair>(M02), dpp_d<kPair>(M11), dpp_d<kPair>(M12),
+               dpp_d<kPair>(M22), dpp_d<kPair>(m0), dpp_d<kPair>(m1), dpp_d<kPair>(m2));
+        }
+        // the meet: with the other side's (R, r) each middle lane solves for its own unknown,
+        //   y = (I - R M)^-1 (r + R m):  x_s^(h) on the upper side (R = beta), lam_{h-1} on the lower
+        // (R = M_h; lam = M x + m and x = alpha + beta lam give (I - M beta) lam = m + M alpha).
+        // A vector solve: one Z, one adjugate, no Y, T or M. quad_perm [0, 2, 1, 3] at S = 4.
+        constexpr int kMeet = S == 2 ? 0xB1 : 0xD8;
+        const double R00 = dpp_d<kMeet>(M00), R01 = dpp_d<kMeet>(M01), R02 = dpp_d<kMeet>(M02);
+        const double R11 = dpp_d<kMeet>(M11), R12 = dpp_d<kMeet>(M12), R22 = dpp_d<kMeet>(M22);
+        const double r0m = dpp_d<kMeet>(m0), r1m = dpp_d<kMeet>(m1), r2m = dpp_d<kMeet>(m2);
+        const double Z00 = 1.0 - (R00 * M00 + R01 * M01 + R02 * M02);
+        const double Z01 = -(R00 * M01 + R01 * M11 + R02 * M12);
+        const double Z02 = -(R00 * M02 + R01 * M12 + R02 * M22);
+        const double Z10 = -(R01 * M00 + R11 * M01 + R12 * M02);
+        const double Z11 = 1.0 - (R01 * M01 + R11 * M11 + R12 * M12);
+        const double Z12 = -(R01 * M02 + R11 * M12 + R12 * M22);
+        const double Z20 = -(R02 * M00 + R12 * M01 + R22 * M02);
+        const double Z21 = -(R02 * M01 + R12 * M11 + R22 * M12);
+        const double Z22 = 1.0 - (R02 * M02 + R12 * M12 + R22 * M22);
+        const double A00 = Z11 * Z22 - Z12 * Z21, A01 = Z02 * Z21 - Z01 * Z22, A02 = Z01 * Z12 - Z02 * Z11;
+        const double A10 = Z12 * Z20 - Z10 * Z22, A11 = Z00 * Z22 - Z02 * Z20, A12 = Z02 * Z10 - Z00 * Z12;
+        const double A20 = Z10 * Z21 - Z11 * Z20, A21 = Z01 * Z20 - Z00 * Z21, A22 = Z00 * Z11 - Z01 * Z10;
+        const double zdet = Z00 * A00 + Z01 * A10 + Z02 * A20;
+        double iz = __builtin_amdgcn_rcp(zdet);
+        iz = fma(iz, fma(-zdet, iz, 1.0), iz);
+        iz = fma(iz, fma(-zdet, iz, 1.0), iz);
+        const double v0 = r0m + R00 * m0 + R01 * m1 + R02 * m2;
+        const double v1 = r1m + R01 * m0 + R11 * m1 + R12 * m2;
+        const double v2 = r2m + R02 * m0 + R12 * m1 + R22 * m2;
+        const double y0 = iz * (A00 * v0 + A01 * v1 + A02 * v2);
+        const double y1 = iz * (A10 * v0 + A11 * v1 + A12 * v2);
+        const double y2 = iz * (A20 * v0 + A21 * v1 + A22 * v2);
+        if constexpr (S == 2) {
+          // segment 0: x_s = 0 and lam_0 = y; the top segment: x_s = y and lam = 0
+          xs0 = low ? 0.0 : y0; xs1 = low ? 0.0 : y1; xs2 = low ? 0.0 : y2;
+          lm0 = low ? y0 : 0.0; lm1 = low ? y1 : 0.0; lm2 = low ? y2 : 0.0;
+        } else {
+          // the middle lanes keep (y, w) as their (x_s, lam) (the lower one as (lam, x_s)) and hand
+          // e outwards: segment 0 takes lam_0 and keeps x_s = 0, the top one x_s and keeps lam = 0
+          double w0, w1, w2, e0, e1, e2;
+          hand_on(y0, y1, y2, w0, w1, w2, e0, e1, e2);
+          const double f0 = dpp_d<kPair>(e0), f1 = dpp_d<kPair>(e1), f2 = dpp_d<kPair>(e2);
+          const bool mid = seg == 1 || seg == 2;
+          xs0 = mid ? (low ? w0 : y0) : (low ? 0.0 : f0);
+          xs1 = mid ? (low ? w1 : y1) : (low ? 0.0 : f1);
+          xs2 = mid ? (low ? w2 : y2) : (low ? 0.0 : f2);
+          lm0 = mid ? (low ? y0 : w0) : (low ? f0 : 0.0);
+          lm1 = mid ? (low ? y1 : w1) : (low ? f1 : 0.0);
+          lm2 = mid ? (low ? y2 : w2) : (low ? f2 : 0.0);
+        }
+      } else {
 #pragma unroll 1
-      for (int it = 0; it < S - 1; it++) {
-        const double l0 = T00 * xs0 + T01 * xs1 + T02 * xs2 + t0;
-        const double l1 = T10 * xs0 + T11 * xs1 + T12 * xs2 + t1;
-        const double l2 = T20 * xs0 + T21 * xs1 + T22 * xs2 + t2;
-        const double e0 = F00 * xs0 + F01 * xs1 + F02 * xs2 + s0v + G00 * l0 + G01 * l1 + G02 * l2;
-        const double e1 = F10 * xs0 + F11 * xs1 + F12 * xs2 + s1v + G01 * l0 + G11 * l1 + G12 * l2;
-        const double e2 = F20 * xs0 + F21 * xs1 + F22 * xs2 + s2v + G02 * l0 + G12 * l1 + G22 * l2;
-        xs0 = seg_dn<S>(e0, lane);
-        xs1 = seg_dn<S>(e1, lane);
-        xs2 = seg_dn<S>(e2, lane);
+        for (int it = 0; it < S - 1; it++) {
+          step(seg_up<S>(M00, lane), seg_up<S>(M01, lane), seg_up<S>(M02, lane), seg_up<S>(M11, lane),
+               seg_up<S>(M12, lane), seg_up<S>(M22, lane), seg_up<S>(m0, lane), seg_up<S>(m1, lane),
+               seg_up<S>(m2, lane));
+        }
+        double l0, l1, l2, e0, e1, e2;
+#pragma unroll 1
+        for (int it = 0; it < S - 1; it++) {
+          hand_on(xs0, xs1, xs2, l0, l1, l2, e0, e1, e2);
+          xs0 = seg_dn<S>(e0, lane);
+          xs1 = seg_dn<S>(e1, lane);
+          xs2 = seg_dn<S>(e2, lane);
+        }
+        lm0 = top ? 0.0 : T00 * xs0 + T01 * xs1 + T02 * xs2 + t0;
+        lm1 = top ? 0.0 : T10 * xs0 + T11 * xs1 + T12 * xs2 + t1;
+        lm2 = top ? 0.0 : T20 * xs0 + T21 * xs1 + T22 * xs2 + t2;
       }
-      lm0 = top ? 0.0 : T00 * xs0 + T01 * xs1 + T02 * xs2 + t0;
-      lm1 = top ? 0.0 : T10 * xs0 + T11 * xs1 + T12 * xs2 + t1;
-      lm2 = top ? 0.0 : T20 * xs0 + T21 * xs1 + T22 * xs2 + t2;
     }
     SACC(acc_dual, t_dual);
     SSTAMP(t_ref);
     // ---- 3. refresh: the lam-part of the feed-forward, backward over the segment ----
     // (FST: nothing to refresh; the forward sweep adds F_i lam_j to k_i and the costate at the
-    // segment start takes p^lam_s = Phi_s' lam_j. Phi's top-lane zeroing is harmless: lam = 0 there.)
+    // segment start takes p^lam_s = Phi_s' lam_j. The top lane's lam is 0, so its Phi, zeroed by the
+    // S = 8 ring and kept at S <= 4, does not matter.)
     double pl0 = lm0, pl1 = lm1, pl2 = lm2;
     if constexpr (FST) {
       pl0 = F00 * lm0 + F10 * lm1 + F20 * lm2;

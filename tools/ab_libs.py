@@ -3,8 +3,9 @@ Run:  python tools/ab_libs.py PARENT_SO BRANCH_SO OUT_JSON [B:N ...]
 Per shape both libraries solve the same batch (make_batch, heading frame) through f110qp_solve_batch_dev;
 the builds alternate in ROUNDS rounds of LAUNCHES back-to-back launches between two events, and the
 figure of a round is its time per launch. Written per shape: median [min, max] over the rounds in us
-for each build, each build's route (segments, fixed segment length, starts), and whether status,
-iters, u and x of the two builds are bit-identical."""
+for each build, each build's route (segments, fixed segment length, starts), whether status,
+iters, u and x of the two builds are bit-identical, the largest absolute difference in u and x over
+the QPs both solved, and the number of QPs whose iters differ."""
 import json
 import os
 import sys
@@ -59,7 +60,14 @@ for B, N in shapes:
             runs[name][3].append(e0.elapsed_time(e1) * 1e3 / LAUNCHES)
     host = {n: {k: v.cpu().numpy() for k, v in runs[n][1].items()} for n in runs}
     same = all(np.array_equal(host["parent"][k], host["branch"][k], equal_nan=True) for k in ("u", "x", "st", "it"))
+    # the largest difference in u and x over the QPs both builds solved, and the QPs whose pass counts differ
+    ok = (host["parent"]["st"] == 1) & (host["branch"]["st"] == 1)
+    du, dx = (float(np.abs(host["parent"][k][ok].astype(np.float64) - host["branch"][k][ok]).max()) if ok.any() else 0.0
+              for k in ("u", "x"))
     row = dict(B=B, N=N, rounds=ROUNDS, launches=LAUNCHES, outputs_bit_identical=bool(same),
+               status_equal=bool(np.array_equal(host["parent"]["st"], host["branch"]["st"])),
+               max_abs_diff_u=du, max_abs_diff_x=dx,
+               iters_differ=int((host["parent"]["it"] != host["branch"]["it"]).sum()),
                iters_max=int(host["branch"]["it"].max()))
     for n in runs:
         t = np.array(runs[n][3])

@@ -27,6 +27,10 @@ int main() {
   run(k<0x101>, "row_shl1");
   run(k<0x134>, "wave_rol1");
   run(k<0x13C>, "wave_ror1");
+  // quad permutes of the segment ends at S <= 4 (control = sel0 | sel1 << 2 | sel2 << 4 | sel3 << 6:
+  // lane 4q + i reads lane 4q + sel_i): the pair exchange and the meet's middle exchange
+  run(k<0xB1>, "quad_perm_1032");
+  run(k<0xD8>, "quad_perm_0213");
   hipFree(d);
   return 0;
 }
