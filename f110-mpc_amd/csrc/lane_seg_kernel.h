@@ -584,7 +584,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         const double Y00 = q0 + P00, Y01 = P01, Y11 = q1 + P11, Y02 = e0, Y12 = e1;
         const double Y22 = ROT ? q2 + e2 + a12 * e1 : q2 + e2 + a02 * e0 + a12 * e1;
         const double hx0 = -q0 * rxi + g0, hx1 = -q1 * ryi + g1;
-        const double hx2 = ROT ? -q2 * rti + g2 + a12 * g1 : -q2 * rti + g2 + a02 * g0 + a12 * g1;
+        const double hx2 = ROT ? g2 - q2 * rti + a12 * g1 : g2 - q2 * rti + a02 * g0 + a12 * g1;
         // the stage's masked 2 x 2 solve from its code's table entry: M = the free block of H with
         // ones on the fixed diagonal, S^-1 rows of the fixed inputs zero (exact: products with 0 / 1)
         {
@@ -604,7 +604,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         const double K10 = -I01 * X00 - I11 * X10, K11 = -I01 * X01 - I11 * X11;
         const double K12 = -I01 * X02 - I11 * X12;
         const double w0 = h0 + H00 * bA0 + H01 * bA1, w1 = h1 + H01 * bA0 + H11 * bA1;
-        const double k0 = bA0 - (I00 * w0 + I01 * w1), k1 = bA1 - (I01 * w0 + I11 * w1);
+        const double k0 = bA0 - I00 * w0 - I01 * w1, k1 = bA1 - I01 * w0 - I11 * w1;
         if constexpr (Q > 0) {
           seg_gput<kQReg, NV>(gr, sc, t, 0, K00); seg_gput<kQReg, NV>(gr, sc, t, 1, K01); seg_gput<kQReg, NV>(gr, sc, t, 2, K02); seg_gput<kQReg, NV>(gr, sc, t, 3, K10); seg_gput<kQReg, NV>(gr, sc, t, 4, K11);
           seg_gput<kQReg, NV>(gr, sc, t, 5, K12); seg_gput<kQReg, NV>(gr, sc, t, 6, k0); seg_gput<kQReg, NV>(gr, sc, t, 7, k1);
@@ -642,24 +642,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
           s[8 * 64] = L00; s[9 * 64] = L01; s[10 * 64] = L02;
           s[11 * 64] = L10; s[12 * 64] = L11; s[13 * 64] = L12;
         }
+        // The accumulations below are written acc + a b + c d (left to right: a chain of FMAs on the
+        // accumulator), where acc += a b + c d compiled to a multiply, an FMA and an add
         // psi += W k + Phi C
-        s0v += W00 * k0 + W01 * k1 + (ROT ? F02 * c2 : F00 * c0 + F01 * c1 + F02 * c2);
-        s1v += W10 * k0 + W11 * k1 + (ROT ? F12 * c2 : F10 * c0 + F11 * c1 + F12 * c2);
-        s2v += W20 * k0 + W21 * k1 + (ROT ? F22 * c2 : F20 * c0 + F21 * c1 + F22 * c2);
+        s0v = ROT ? s0v + W00 * k0 + W01 * k1 + F02 * c2
+                  : s0v + W00 * k0 + W01 * k1 + F00 * c0 + F01 * c1 + F02 * c2;
+        s1v = ROT ? s1v + W10 * k0 + W11 * k1 + F12 * c2
+                  : s1v + W10 * k0 + W11 * k1 + F10 * c0 + F11 * c1 + F12 * c2;
+        s2v = ROT ? s2v + W20 * k0 + W21 * k1 + F22 * c2
+                  : s2v + W20 * k0 + W21 * k1 + F20 * c0 + F21 * c1 + F22 * c2;
         // Gam += W Fl
-        G00 += W00 * L00 + W01 * L10;
-        G01 += W00 * L01 + W01 * L11;
-        G02 += W00 * L02 + W01 * L12;
-        G11 += W10 * L01 + W11 * L11;
-        G12 += W10 * L02 + W11 * L12;
-        G22 += W20 * L02 + W21 * L12;
+        G00 = G00 + W00 * L00 + W01 * L10;
+        G01 = G01 + W00 * L01 + W01 * L11;
+        G02 = G02 + W00 * L02 + W01 * L12;
+        G11 = G11 + W10 * L01 + W11 * L11;
+        G12 = G12 + W10 * L02 + W11 * L12;
+        G22 = G22 + W20 * L02 + W21 * L12;
         // Phi = Phi A + W K  (A = I + E, E = a02 e_0 e_2' + a12 e_1 e_2')
         const double n02 = (ROT ? F02 + a12 * F01 : F02 + a02 * F00 + a12 * F01) + W00 * K02 + W01 * K12;
         const double n12 = (ROT ? F12 + a12 * F11 : F12 + a02 * F10 + a12 * F11) + W10 * K02 + W11 * K12;
         const double n22 = (ROT ? F22 + a12 * F21 : F22 + a02 * F20 + a12 * F21) + W20 * K02 + W21 * K12;
-        F00 += W00 * K00 + W01 * K10; F01 += W00 * K01 + W01 * K11;
-        F10 += W10 * K00 + W11 * K10; F11 += W10 * K01 + W11 * K11;
-        F20 += W20 * K00 + W21 * K10; F21 += W20 * K01 + W21 * K11;
+        F00 = F00 + W00 * K00 + W01 * K10; F01 = F01 + W00 * K01 + W01 * K11;
+        F10 = F10 + W10 * K00 + W11 * K10; F11 = F11 + W10 * K01 + W11 * K11;
+        F20 = F20 + W20 * K00 + W21 * K10; F21 = F21 + W20 * K01 + W21 * K11;
         F02 = n02; F12 = n12; F22 = n22;
       }
     }
@@ -709,16 +714,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
       // one full elimination step with the neighbour's (Mn, mn): T, t and the lane's new (M, m)
       auto step = [&](double N00, double N01, double N02, double N11, double N12, double N22, double n0,
                       double n1, double n2) {
-        // Z = I - Mn Gam
-        const double Z00 = 1.0 - (N00 * gG00 + N01 * gG01 + N02 * gG02);
+        // Z = I - Mn Gam (the diagonal as FMA chains on the 1)
+        const double Z00 = 1.0 - N00 * gG00 - N01 * gG01 - N02 * gG02;
         const double Z01 = -(N00 * gG01 + N01 * gG11 + N02 * gG12);
         const double Z02 = -(N00 * gG02 + N01 * gG12 + N02 * gG22);
         const double Z10 = -(N01 * gG00 + N11 * gG01 + N12 * gG02);
-        const double Z11 = 1.0 - (N01 * gG01 + N11 * gG11 + N12 * gG12);
+        const double Z11 = 1.0 - N01 * gG01 - N11 * gG11 - N12 * gG12;
         const double Z12 = -(N01 * gG02 + N11 * gG12 + N12 * gG22);
         const double Z20 = -(N02 * gG00 + N12 * gG01 + N22 * gG02);
         const double Z21 = -(N02 * gG01 + N12 * gG11 + N22 * gG12);
-        const double Z22 = 1.0 - (N02 * gG02 + N12 * gG12 + N22 * gG22);
+        const double Z22 = 1.0 - N02 * gG02 - N12 * gG12 - N22 * gG22;
         // Z^-1 by the adjugate
         const double A00 = Z11 * Z22 - Z12 * Z21, A01 = Z02 * Z21 - Z01 * Z22, A02 = Z01 * Z12 - Z02 * Z11;
         const double A10 = Z12 * Z20 - Z10 * Z22, A11 = Z00 * Z22 - Z02 * Z20, A12 = Z02 * Z10 - Z00 * Z12;
@@ -763,12 +768,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
       // (x_s^(j+1) up; lam_{j-1} = Phi' lam + a + P x_s down)
       auto hand_on = [&](double y0, double y1, double y2, double& w0, double& w1, double& w2, double& e0,
                          double& e1, double& e2) {
-        w0 = T00 * y0 + T01 * y1 + T02 * y2 + t0;
-        w1 = T10 * y0 + T11 * y1 + T12 * y2 + t1;
-        w2 = T20 * y0 + T21 * y1 + T22 * y2 + t2;
-        e0 = gF00 * y0 + gF01 * y1 + gF02 * y2 + gs0 + gG00 * w0 + gG01 * w1 + gG02 * w2;
-        e1 = gF10 * y0 + gF11 * y1 + gF12 * y2 + gs1 + gG01 * w0 + gG11 * w1 + gG12 * w2;
-        e2 = gF20 * y0 + gF21 * y1 + gF22 * y2 + gs2 + gG02 * w0 + gG12 * w1 + gG22 * w2;
+        w0 = t0 + T00 * y0 + T01 * y1 + T02 * y2;
+        w1 = t1 + T10 * y0 + T11 * y1 + T12 * y2;
+        w2 = t2 + T20 * y0 + T21 * y1 + T22 * y2;
+        e0 = gs0 + gF00 * y0 + gF01 * y1 + gF02 * y2 + gG00 * w0 + gG01 * w1 + gG02 * w2;
+        e1 = gs1 + gF10 * y0 + gF11 * y1 + gF12 * y2 + gG01 * w0 + gG11 * w1 + gG12 * w2;
+        e2 = gs2 + gF20 * y0 + gF21 * y1 + gF22 * y2 + gG02 * w0 + gG12 * w1 + gG22 * w2;
       };
       if constexpr (TWO) {
         // quad_perm [1, 0, 3, 2]: segment 1 reads segment 0 and segment 2 segment 3 in one move (the
@@ -786,15 +791,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         const double R00 = dpp_d<kMeet>(M00), R01 = dpp_d<kMeet>(M01), R02 = dpp_d<kMeet>(M02);
         const double R11 = dpp_d<kMeet>(M11), R12 = dpp_d<kMeet>(M12), R22 = dpp_d<kMeet>(M22);
         const double r0m = dpp_d<kMeet>(m0), r1m = dpp_d<kMeet>(m1), r2m = dpp_d<kMeet>(m2);
-        const double Z00 = 1.0 - (R00 * M00 + R01 * M01 + R02 * M02);
+        const double Z00 = 1.0 - R00 * M00 - R01 * M01 - R02 * M02;
         const double Z01 = -(R00 * M01 + R01 * M11 + R02 * M12);
         const double Z02 = -(R00 * M02 + R01 * M12 + R02 * M22);
         const double Z10 = -(R01 * M00 + R11 * M01 + R12 * M02);
-        const double Z11 = 1.0 - (R01 * M01 + R11 * M11 + R12 * M12);
+        const double Z11 = 1.0 - R01 * M01 - R11 * M11 - R12 * M12;
         const double Z12 = -(R01 * M02 + R11 * M12 + R12 * M22);
         const double Z20 = -(R02 * M00 + R12 * M01 + R22 * M02);
         const double Z21 = -(R02 * M01 + R12 * M11 + R22 * M12);
-        const double Z22 = 1.0 - (R02 * M02 + R12 * M12 + R22 * M22);
+        const double Z22 = 1.0 - R02 * M02 - R12 * M12 - R22 * M22;
         const double A00 = Z11 * Z22 - Z12 * Z21, A01 = Z02 * Z21 - Z01 * Z22, A02 = Z01 * Z12 - Z02 * Z11;
         const double A10 = Z12 * Z20 - Z10 * Z22, A11 = Z00 * Z22 - Z02 * Z20, A12 = Z02 * Z10 - Z00 * Z12;
         const double A20 = Z10 * Z21 - Z11 * Z20, A21 = Z01 * Z20 - Z00 * Z21, A22 = Z00 * Z11 - Z01 * Z10;
@@ -875,8 +880,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         }
         const double bp0 = ROT ? b00 * pl0 + b20 * pl2 : b00 * pl0 + b10 * pl1 + b20 * pl2;  // B' p
         const double bp1 = b21 * pl2;
-        s[6 * 64] = k0 - (I00 * bp0 + I01 * bp1);
-        s[7 * 64] = k1 - (I01 * bp0 + I11 * bp1);
+        s[6 * 64] = k0 - I00 * bp0 - I01 * bp1;
+        s[7 * 64] = k1 - I01 * bp0 - I11 * bp1;
         const double n0 = pl0 + K00 * bp0 + K10 * bp1, n1 = pl1 + K01 * bp0 + K11 * bp1;
         pl2 = (ROT ? pl2 + a12 * pl1 : pl2 + a02 * pl0 + a12 * pl1) + K02 * bp0 + K12 * bp1;
         pl0 = n0; pl1 = n1;
@@ -894,10 +899,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     auto forward = [&](auto mode_tag) {
       constexpr int MODE = decltype(mode_tag)::value;
       double x0 = xs0, x1 = xs1, x2 = xs2;
-      double l0 = P00 * x0 + P01 * x1 + P02 * x2 + p0 + pl0;  // costate at x_s
-      double l1 = P01 * x0 + P11 * x1 + P12 * x2 + p1 + pl1;
-      double l2 = P02 * x0 + P12 * x1 + P22 * x2 + p2 + pl2;
+      double l0 = p0 + pl0 + P00 * x0 + P01 * x1 + P02 * x2;  // costate at x_s
+      double l1 = p1 + pl1 + P01 * x0 + P11 * x1 + P12 * x2;
+      double l2 = p2 + pl2 + P02 * x0 + P12 * x1 + P22 * x2;
       bool flipped = false;
+      // Q > 0, PDAS passes: the re-guessed codes are collected in a word of their own, every test's bit
+      // selected at its place in it (the same integers as before), and `changed` is one compare of
+      // the two words after the sweep instead of a compare and a mask OR per stage
+      constexpr bool kWord = Q > 0 && MODE == 0;
+      unsigned npk = 0u;
       double rx = Q > 0 ? rr[0] : r64[0], ry = Q > 0 ? rr[Q > 0 ? 1 : 0] : r64[64], rt = Q > 0 ? rr[Q > 0 ? 2 : 0] : r64[2 * 64];
       int old_n = Q > 0 ? (int)(apk & 15u) : ap[0];
       constexpr int NG = FST ? 14 : 8;
@@ -932,8 +942,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
           ry = Q > 0 ? rr[3 * tn + 1] : r64[(3 * tn + 1) * 64];
           rt = Q > 0 ? rr[3 * tn + 2] : r64[(3 * tn + 2) * 64];
         }
-        const double u0 = K00 * x0 + K01 * x1 + K02 * x2 + k0;
-        const double u1 = K10 * x0 + K11 * x1 + K12 * x2 + k1;
+        const double u0 = k0 + K00 * x0 + K01 * x1 + K02 * x2;  // (an FMA chain on k)
+        const double u1 = k1 + K10 * x0 + K11 * x1 + K12 * x2;
         const double w0 = l0 - q0 * (x0 - rxi), w1 = l1 - q1 * (x1 - ryi);
         const double w2 = l2 - q2 * (x2 - rti);
         l0 = w0; l1 = w1; l2 = ROT ? w2 - a12 * w1 : w2 - a02 * w0 - a12 * w1;
@@ -960,7 +970,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
             nhi = !nlo & (((ca == 2) & (g < gta)) | ((ca == 0) & (u > ubx)));
           }
           const int nca = (int)nlo | ((int)nhi << 1);
-          if constexpr (MODE == 0) {
+          if constexpr (kWord) {
+            npk |= (nhi ? 2u : (unsigned)nlo) << (4 * t + 2 * a);  // (= nca: the tests exclude each other)
+          } else if constexpr (MODE == 0) {
             st |= nca << (2 * a);
           } else {
             const bool take = (nca != ca) & !flipped;
@@ -968,18 +980,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
             flipped |= take;
           }
         }
-        const bool ch = st != old;
-        if constexpr (MODE == 1) {
-          fi = (ch & (fi == N)) ? s0 + t : fi;
-          fold_st = (ch & (fi == s0 + t)) ? old : fold_st;
+        if constexpr (!kWord) {
+          const bool ch = st != old;
+          if constexpr (MODE == 1) {
+            fi = (ch & (fi == N)) ? s0 + t : fi;
+            fold_st = (ch & (fi == s0 + t)) ? old : fold_st;
+          }
+          changed |= ch;
+          if constexpr (Q > 0) apk = (apk & ~(15u << (4 * t))) | ((unsigned)st << (4 * t));
+          else ap[t * 64] = st;
         }
-        changed |= ch;
-        if constexpr (Q > 0) apk = (apk & ~(15u << (4 * t))) | ((unsigned)st << (4 * t));
-        else ap[t * 64] = st;
         const double nx0 = ROT ? x0 + b00 * u0 : x0 + a02 * x2 + b00 * u0 + c0;
         const double nx1 = ROT ? x1 + a12 * x2 : x1 + a12 * x2 + b10 * u0 + c1;
         const double nx2 = x2 + b20 * u0 + b21 * u1 + c2;
         x0 = nx0; x1 = nx1; x2 = nx2;
+      }
+      if constexpr (kWord) {
+        changed = npk != apk;
+        apk = npk;
       }
     };
     if (single) forward(SegMode<1>{});
@@ -1066,8 +1084,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         constexpr bool OBJ = decltype(obj_tag)::value != 0;
 #pragma unroll
         for (int t = 0; t < Q; t++) {
-          const double u0 = seg_gget<kQReg, NV>(gr, sc, t, 0) * x0 + seg_gget<kQReg, NV>(gr, sc, t, 1) * x1 + seg_gget<kQReg, NV>(gr, sc, t, 2) * x2 + seg_gget<kQReg, NV>(gr, sc, t, 6);
-          const double u1 = seg_gget<kQReg, NV>(gr, sc, t, 3) * x0 + seg_gget<kQReg, NV>(gr, sc, t, 4) * x1 + seg_gget<kQReg, NV>(gr, sc, t, 5) * x2 + seg_gget<kQReg, NV>(gr, sc, t, 7);
+          const double u0 = seg_gget<kQReg, NV>(gr, sc, t, 6) + seg_gget<kQReg, NV>(gr, sc, t, 0) * x0 + seg_gget<kQReg, NV>(gr, sc, t, 1) * x1 + seg_gget<kQReg, NV>(gr, sc, t, 2) * x2;
+          const double u1 = seg_gget<kQReg, NV>(gr, sc, t, 7) + seg_gget<kQReg, NV>(gr, sc, t, 3) * x0 + seg_gget<kQReg, NV>(gr, sc, t, 4) * x1 + seg_gget<kQReg, NV>(gr, sc, t, 5) * x2;
           if constexpr (OBJ) {
             qterm(rr[3 * t], rr[3 * t + 1], rr[3 * t + 2], x0, x1, x2);
             J += 0.5 * (r0 * (u0 - ud0) * (u0 - ud0) + r1 * (u1 - ud1) * (u1 - ud1));
@@ -1106,10 +1124,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
       const double k0 = FST ? s[6 * 64] + s[8 * 64] * lm0 + s[9 * 64] * lm1 + s[10 * 64] * lm2 : s[6 * 64];
       const double k1 = FST ? s[7 * 64] + s[11 * 64] * lm0 + s[12 * 64] * lm1 + s[13 * 64] * lm2 : s[7 * 64];
       // fp32 scratch: clamp a free input that sits outside its box by the single-flip tolerance
-      const double u0 = F32 ? fmin(fmax(K00 * x0 + K01 * x1 + K02 * x2 + k0, lb0), ub0)
-                            : K00 * x0 + K01 * x1 + K02 * x2 + k0;
-      const double u1 = F32 ? fmin(fmax(K10 * x0 + K11 * x1 + K12 * x2 + k1, lb1), ub1)
-                            : K10 * x0 + K11 * x1 + K12 * x2 + k1;
+      const double u0 = F32 ? fmin(fmax(k0 + K00 * x0 + K01 * x1 + K02 * x2, lb0), ub0)
+                            : k0 + K00 * x0 + K01 * x1 + K02 * x2;
+      const double u1 = F32 ? fmin(fmax(k1 + K10 * x0 + K11 * x1 + K12 * x2, lb1), ub1)
+                            : k1 + K10 * x0 + K11 * x1 + K12 * x2;
       if (want_obj) {
         qterm(r64[(3 * t) * 64], r64[(3 * t + 1) * 64], r64[(3 * t + 2) * 64], x0, x1, x2);
         J += 0.5 * (r0 * (u0 - ud0) * (u0 - ud0) + r1 * (u1 - ud1) * (u1 - ud1));
