@@ -9,7 +9,7 @@
 #include <string>
 
 #include "f110qp.h"
-#include "f110qp_kernels.h"
+#include "lane_plan.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -135,8 +135,10 @@ static inline int check_scan_config(const f110qp_scan_config* sc, bool rows, int
   return F110QP_OK;
 }
 
-// Back end of a call and, for the lane back end (or the gap screen), its workspace (f110qp_api.cpp).
-int lane_work(f110qp_ctx* c, int batch, hipStream_t s, int* backend, f110qp::LaneWork* lw, bool grouped = false);
+// Back end of a call and, for the lane back end (or the gap screen), its workspace and its launch plan
+// (f110qp_api.cpp).
+int lane_work(f110qp_ctx* c, int batch, hipStream_t s, int* backend, f110qp::LaneWork* lw, f110qp::LanePlan* plan,
+              bool grouped = false);
 
 // A plan config's limits, with its grid_blocks into *G (api_plan.cpp).
 int validate_plan(const f110qp_plan_config* c, int* G);

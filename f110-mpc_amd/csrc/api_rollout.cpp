@@ -178,6 +178,7 @@ struct LoopWork {
   size_t rstep = 0;
   int backend;
   f110qp::LaneWork lw;
+  f110qp::LanePlan plan;  // of every tick's solve: the same batch and knobs
 };
 
 // rows: the loop computes gap rows from scan_rows x B scans, into hs_traj when the caller gave one.
@@ -205,7 +206,7 @@ static int loop_prologue(f110qp_ctx* c, const RolloutIO& io, bool rows, int scan
       w->rstep = 0;
     }
   }
-  return lane_work(c, io.B, s, &w->backend, &w->lw);
+  return lane_work(c, io.B, s, &w->backend, &w->lw, &w->plan);
 }
 
 // The T ticks of a checked rollout on device pointers (per tick the launches of one _dbl solve call,
@@ -238,9 +239,8 @@ static int rollout_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io,
     float* u_t = io.up(t, w.wup);
     f110qp::ObjOut oo;
     oo.cost = io.cost(t);
-    hipError_t e = f110qp::launch_solve(kp, io.B, (const double*)io.x(t), (const double*)io.ul(t),
-                                        (const double*)io.x_ref, h, u_t, io.xp(t, w.wxp), io.st(t), io.it(t),
-                                        f110qp::WarmState(), w.backend, w.lw, oo, s);
+    const f110qp::SolveIO<double> sio{io.B, io.x(t), io.ul(t), io.x_ref, h, u_t, io.xp(t, w.wxp), io.st(t), io.it(t)};
+    hipError_t e = f110qp::launch_solve(kp, sio, f110qp::WarmState(), w.backend, w.lw, w.plan, oo, s);
     if (e != hipSuccess) return hip_fail(e, "rollout solve launch");
     if (sl && t + 1 < T)
       e = f110qp::launch_advance_scan(cfg.ap, io.B, io.N, io.x(t), u_t, io.st(t), sl->sc->num_ranges,
@@ -383,9 +383,8 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
     float* u_t = io.up(t, w.wup);
     f110qp::ObjOut oo;
     oo.cost = io.cost(t);
-    e = f110qp::launch_solve(c->kp, io.B, (const double*)io.x(t), (const double*)io.ul(t),
-                             (const double*)io.x_ref, h, u_t, io.xp(t, w.wxp), io.st(t), io.it(t),
-                             f110qp::WarmState(), w.backend, w.lw, oo, s);
+    const f110qp::SolveIO<double> sio{io.B, io.x(t), io.ul(t), io.x_ref, h, u_t, io.xp(t, w.wxp), io.st(t), io.it(t)};
+    e = f110qp::launch_solve(c->kp, sio, f110qp::WarmState(), w.backend, w.lw, w.plan, oo, s);
     if (e != hipSuccess) return hip_fail(e, "rollout solve launch");
     const bool last = t + 1 == T;  // no tick T: neither its kind and list nor its rows
     f110qp::ReplanStep S{};

@@ -79,10 +79,10 @@ static void test_hooks(f110qp_ctx* c) {
 // hipStreamSynchronize round trip measured 12.2 us p50 against 6.5 us for the polled word on an
 // empty kernel (tools/microbench/flag_latency.hip). Arms the signal in *oo when the
 // call's kernels raise it; *armed false: the caller synchronises the stream.
-static int arm_signal(f110qp_ctx* c, int batch, int backend, const float* h, const f110qp::LaneWork& lw,
+static int arm_signal(f110qp_ctx* c, int batch, int backend, const float* h, const f110qp::LanePlan& plan,
                       hipStream_t s, f110qp::ObjOut* oo, bool* armed) {
   *armed = false;
-  if (!c->sig_poll || !f110qp::launch_signals(c->kp, batch, backend, h, lw)) return F110QP_OK;
+  if (!c->sig_poll || !f110qp::launch_signals(batch, backend, h, plan)) return F110QP_OK;
   if (!c->hsig.p) {
     hipError_t e = c->hsig.ensure(64);
     if (e != hipSuccess) return hip_fail(e, "hipHostMalloc completion word");
@@ -244,9 +244,22 @@ static f110qp::LaneWork lane_knobs(const f110qp_ctx* c) {
   return lw;
 }
 
-// Back end of a call and, for the lane back end (or the gap screen), its workspace.
-int lane_work(f110qp_ctx* c, int batch, hipStream_t s, int* backend, f110qp::LaneWork* lw, bool grouped) {
+// The introspection calls' view of a call of `batch` QPs: its back end, and the plan of its lane launch
+// by the same resolve_backend, lane_knobs and lane_plan as the call itself (gap rows: the plan of the
+// box screen's lane solve, whose kernels have no fixed-length variant). Not the lane back end: the
+// neutral plan (one segment, one QP per wave, one start, no scratch).
+static f110qp::LanePlan info_plan(f110qp_ctx* c, int batch, bool grouped, int* be) {
+  *be = resolve_backend(c, batch, grouped);
+  if (*be != F110QP_BACKEND_LANE) return f110qp::LanePlan();
+  return f110qp::lane_plan(c->kp, batch, lane_knobs(c), c->cfg.gap_mode == F110QP_GAP_ACTIVE);
+}
+
+// Back end of a call and, for the lane back end (or the gap screen), its workspace and the plan of its
+// lane launch (resolved here, once per call: launch_solve and arm_signal read it).
+int lane_work(f110qp_ctx* c, int batch, hipStream_t s, int* backend, f110qp::LaneWork* lw, f110qp::LanePlan* plan,
+              bool grouped) {
   *lw = lane_knobs(c);
+  *plan = f110qp::LanePlan();
   *backend = resolve_backend(c, batch, grouped) == F110QP_BACKEND_LANE ? f110qp::BACKEND_LANE
                                                                       : f110qp::BACKEND_WAVE;
   hipError_t e;
@@ -268,6 +281,7 @@ int lane_work(f110qp_ctx* c, int batch, hipStream_t s, int* backend, f110qp::Lan
   e = c->lscr.ensure(((size_t)batch + 63) * N * 8 * sizeof(double));
   if (e != hipSuccess) return hip_fail(e, "hipMalloc lane workspace");
   lw->scratch = (double*)c->lscr.p;
+  *plan = f110qp::lane_plan(c->kp, batch, *lw, lw->screen != 0);
   return F110QP_OK;
 }
 
@@ -313,14 +327,16 @@ static int solve_dev(f110qp_ctx* c, int batch, const IN* x0, const IN* ul, const
   if (rc) return rc;
   int backend;
   f110qp::LaneWork lw;
-  rc = lane_work(c, batch, s, &backend, &lw);
+  f110qp::LanePlan plan;
+  rc = lane_work(c, batch, s, &backend, &lw, &plan);
   if (rc) return rc;
   f110qp::ObjOut oo;
   oo.obj = obj;
   oo.cost = cost;
   bool armed = false;
-  if (sync && (rc = arm_signal(c, batch, backend, h, lw, s, &oo, &armed))) return rc;
-  hipError_t e = f110qp::launch_solve(c->kp, batch, x0, ul, xr, h, uo, xo, st, it, ws, backend, lw, oo, s);
+  if (sync && (rc = arm_signal(c, batch, backend, h, plan, s, &oo, &armed))) return rc;
+  const f110qp::SolveIO<IN> io{batch, x0, ul, xr, h, uo, xo, st, it};
+  hipError_t e = f110qp::launch_solve(c->kp, io, ws, backend, lw, plan, oo, s);
   if (e != hipSuccess) return hip_fail(e, "solve kernel launch");
   return sync ? wait_done(c, s, armed) : F110QP_OK;
 }
@@ -338,12 +354,13 @@ static int solve_grouped_dev(f110qp_ctx* c, int batch, const IN* x0, const IN* u
   if ((rc = group_state(c, group, num_groups, &gws, &leader, f110qp::kGroupKeyWords<IN>))) return rc;
   int backend;
   f110qp::LaneWork lw;
-  if ((rc = lane_work(c, batch, (hipStream_t)stream, &backend, &lw, true))) return rc;
+  f110qp::LanePlan plan;
+  if ((rc = lane_work(c, batch, (hipStream_t)stream, &backend, &lw, &plan, true))) return rc;
   f110qp::ObjOut oo;
   oo.obj = obj;
   oo.cost = cost;
-  hipError_t e = f110qp::launch_solve_grouped(c->kp, batch, x0, ul, xr, h, uo, xo, st, it, gws,
-                                              leader, backend, lw, oo, (hipStream_t)stream);
+  const f110qp::SolveIO<IN> io{batch, x0, ul, xr, h, uo, xo, st, it};
+  hipError_t e = f110qp::launch_solve_grouped(c->kp, io, gws, leader, backend, lw, plan, oo, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "grouped solve launch");
   return F110QP_OK;
 }
@@ -396,33 +413,30 @@ static int solve_host(f110qp_ctx* c, int batch, const IN* x0, const IN* ul, cons
   }
   int backend;
   f110qp::LaneWork lw;
+  f110qp::LanePlan plan;
   f110qp::ObjOut oo;
   bool armed = false;
   oo.obj = obj ? (double*)(dq + o_ob) : nullptr;
   oo.cost = cost ? (double*)(dq + o_co) : nullptr;
+  const f110qp::SolveIO<IN> io{batch, (const IN*)di, (const IN*)(di + o_ul), (const IN*)(di + o_xr),
+                               gap ? (const float*)(di + o_hs) : nullptr, (float*)dq, (float*)(dq + o_xo),
+                               (int*)(dq + o_st), (int*)(dq + o_it)};
   if (group) {
     if ((e = c->dgrp.ensure(B * 4)) || (e = hipMemcpyAsync(c->dgrp.p, group, B * 4, hipMemcpyHostToDevice, s)))
       return hip_fail(e, "group ids H2D");
     f110qp::WarmState gws;
     int* leader;
     if ((rc = group_state(c, (const int*)c->dgrp.p, num_groups, &gws, &leader, f110qp::kGroupKeyWords<IN>))) return rc;
-    if ((rc = lane_work(c, batch, s, &backend, &lw, true))) return rc;
-    e = f110qp::launch_solve_grouped(c->kp, batch, (const IN*)di, (const IN*)(di + o_ul),
-                                     (const IN*)(di + o_xr), gap ? (const float*)(di + o_hs) : nullptr,
-                                     (float*)dq, (float*)(dq + o_xo), (int*)(dq + o_st),
-                                     (int*)(dq + o_it), gws, leader, backend, lw, oo, s);
+    if ((rc = lane_work(c, batch, s, &backend, &lw, &plan, true))) return rc;
+    e = f110qp::launch_solve_grouped(c->kp, io, gws, leader, backend, lw, plan, oo, s);
   } else {
     f110qp::WarmState ws;
     if (sizeof(IN) == 4 && (rc = warm_state(c, batch, s, &ws))) return rc;  // (double inputs: cold)
-    if ((rc = lane_work(c, batch, s, &backend, &lw))) return rc;
+    if ((rc = lane_work(c, batch, s, &backend, &lw, &plan))) return rc;
     // zero-copy: the kernel's stores are the outputs the host reads, so its completion word ends
     // the wait (staged batches wait for the D2H copy on the stream)
-    if (zc && (rc = arm_signal(c, batch, backend, gap ? (const float*)(di + o_hs) : nullptr, lw, s, &oo, &armed)))
-      return rc;
-    e = f110qp::launch_solve(c->kp, batch, (const IN*)di, (const IN*)(di + o_ul),
-                             (const IN*)(di + o_xr), gap ? (const float*)(di + o_hs) : nullptr,
-                             (float*)dq, (float*)(dq + o_xo), (int*)(dq + o_st), (int*)(dq + o_it),
-                             ws, backend, lw, oo, s);
+    if (zc && (rc = arm_signal(c, batch, backend, io.hs, plan, s, &oo, &armed))) return rc;
+    e = f110qp::launch_solve(c->kp, io, ws, backend, lw, plan, oo, s);
   }
   if (e != hipSuccess) return hip_fail(e, "solve kernel launch");
   if (!zc && (e = hipMemcpyAsync(c->hout.p, dq, out_bytes, hipMemcpyDeviceToHost, s)))
@@ -662,50 +676,35 @@ int f110qp_backend_info(f110qp_ctx* c, int batch, int grouped, int* backend, int
                         int* scratch) {
   if (!c) return fail(F110QP_ERR_INVALID, "ctx is NULL");
   if (batch < 1) return fail(F110QP_ERR_INVALID, "batch must be >= 1");
-  const f110qp::LaneWork lw = lane_knobs(c);
-  const int be = resolve_backend(c, batch, grouped != 0);
-  const bool lane = be == F110QP_BACKEND_LANE;  // gap rows: the box screen's lane solve
-  const int segs = lane ? f110qp::lane_segments(c->kp, batch, lw) : 1;
+  int be;
+  const f110qp::LanePlan plan = info_plan(c, batch, grouped != 0, &be);
   if (backend) *backend = be;
-  if (qps_per_wave) *qps_per_wave = lane ? (segs > 1 ? 64 / segs : f110qp::lane_qps_per_wave(batch, lw.qpw)) : 1;
-  if (scratch)
-    *scratch = !lane ? 0 : segs > 1 ? f110qp::lane_seg_scratch(c->kp, batch, segs, lw)
-                                    : f110qp::lane_scratch_mode(c->kp, batch, lw);
+  if (qps_per_wave) *qps_per_wave = plan.qpw;
+  if (scratch) *scratch = plan.mode;
   return F110QP_OK;
 }
 
 int f110qp_lane_segments(f110qp_ctx* c, int batch, int* segments) {
   if (!c || !segments) return fail(F110QP_ERR_INVALID, "ctx / segments is NULL");
   if (batch < 1) return fail(F110QP_ERR_INVALID, "batch must be >= 1");
-  int be = 0;
-  const int rc = f110qp_backend_info(c, batch, 0, &be, nullptr, nullptr);
-  if (rc) return rc;
-  const f110qp::LaneWork lw = lane_knobs(c);
-  if (be != F110QP_BACKEND_LANE) *segments = 1;
-  else *segments = f110qp::lane_segments(c->kp, batch, lw);
+  int be;
+  *segments = info_plan(c, batch, false, &be).S;
   return F110QP_OK;
 }
 
 int f110qp_lane_starts(f110qp_ctx* c, int batch, int* starts) {
   if (!c || !starts) return fail(F110QP_ERR_INVALID, "ctx / starts is NULL");
   if (batch < 1) return fail(F110QP_ERR_INVALID, "batch must be >= 1");
-  int segs = 1;
-  const int rc = f110qp_lane_segments(c, batch, &segs);
-  if (rc) return rc;
-  const f110qp::LaneWork lw = lane_knobs(c);
-  *starts = segs > 1 ? f110qp::lane_seg_starts(c->kp, batch, segs, lw) : 1;
+  int be;
+  *starts = info_plan(c, batch, false, &be).starts;
   return F110QP_OK;
 }
 
 int f110qp_lane_fixed_q(f110qp_ctx* c, int batch, int* stages) {
   if (!c || !stages) return fail(F110QP_ERR_INVALID, "ctx / stages is NULL");
   if (batch < 1) return fail(F110QP_ERR_INVALID, "batch must be >= 1");
-  int segs = 1;
-  const int rc = f110qp_lane_segments(c, batch, &segs);
-  if (rc) return rc;
-  const f110qp::LaneWork lw = lane_knobs(c);
-  const bool box = c->cfg.gap_mode != F110QP_GAP_ACTIVE;  // (the gap-row screen's kernels have no fixed-length variant)
-  *stages = (box && segs > 1) ? f110qp::lane_seg_fixedq(c->kp, batch, segs, lw) : 0;
+  int be;
+  *stages = info_plan(c, batch, false, &be).Q;
   return F110QP_OK;
 }
 

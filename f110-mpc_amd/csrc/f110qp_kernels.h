@@ -107,7 +107,7 @@ struct LaneWork {
   double* scratch = nullptr;
   int kmax = 16;  // PDAS passes (all violations flip) before single flips (least index)
   int mode = 0;   // scratch: 0 auto, 1 LDS fp64, 2 LDS fp32, 3 HBM fp64, 4 HBM fp32 (workspace)
-  int qpw = 0;    // QPs per wave: 0 auto (lane_qps_per_wave), else a power of two <= 64
+  int qpw = 0;    // QPs per wave: 0 auto (lane_plan.h), else a power of two <= 64
   int rot = 1;    // 1: heading-frame kernel when q0 == q1 (lane_kernel.h ROT); 0: general frame
   int dref = 1;   // 1: fp64 references in LDS when the resident waves fit (DREF); 0: float
   int seg = 0;    // horizon segments per QP (lane_seg_kernel.h): 0 auto, 1 off, 2 / 4 / 8 forced
@@ -145,10 +145,13 @@ struct ObjOut {
   unsigned sig_seq = 0;
 };
 
+// The launch plan of a lane back end call (lane_plan.h).
+struct LanePlan;
+
 // whether launch_solve's kernels for this call raise ObjOut's completion signal (every ungrouped
 // call: its last kernel is a lane, wave or re-check kernel that signals); the caller synchronises
 // the stream otherwise
-bool launch_signals(const KParams& P, int B, int backend, const float* hs, const LaneWork& lw);
+bool launch_signals(int B, int backend, const float* hs, const LanePlan& plan);
 
 // The completion signal at the very end of a call's last kernel (ObjOut::sig_*): every wave's
 // stores visible at system scope (zero-copy outputs in pinned host memory; device outputs written
@@ -173,64 +176,57 @@ __device__ __forceinline__ void signal_call_done(const ObjOut& oo, bool wrote = 
   }
 }
 
-// waves the lane kernel's grid aims for (one per CU of the MI355X's 256)
-constexpr int kLaneTargetWaves = 256;
-int lane_qps_per_wave(int B, int qpw);
-// scratch placement the lane launch picks for a batch: 1 LDS fp64, 2 LDS fp32, 3 HBM fp64, 4 HBM fp32
-int lane_scratch_mode(const KParams& P, int B, const LaneWork& lw);
-// horizon segments per QP the lane launch picks for a batch (1 = lane_kernel.h, one QP per lane
-// group of 64 / L identical lanes; S > 1 = lane_seg_kernel.h, 64 / S QPs per wave)
-int lane_segments(const KParams& P, int B, const LaneWork& lw);
-// scratch of the segmented kernel at S segments: 1 LDS fp64, 2 LDS fp32 (lane_seg_kernel.h)
-int lane_seg_scratch(const KParams& P, int B, int S, const LaneWork& lw);
-// PDAS starts per QP of the segmented kernel at S segments: 2 with the twin start (lane_seg_kernel.h)
-int lane_seg_starts(const KParams& P, int B, int S, const LaneWork& lw);
-// segment length of the fixed-length segmented kernels a box-only batch runs at S segments (5), 0
-// where it runs the run-time-length ones (lane_seg_kernel.h seg_fixedq)
-int lane_seg_fixedq(const KParams& P, int B, int S, const LaneWork& lw);
+// IN in the launch functions below: the input scalar of x0, u_lin and x_ref, float or double (the
+// *_dbl entry points of include/f110qp.h); both are instantiated in the kernels' objects.
+// The arrays of one solve call of B QPs, from the ABI down to the kernel launch (the kernels take
+// them as loose parameters).
+template <typename IN>
+struct SolveIO {
+  int B;
+  const IN* x0;
+  const IN* u_lin;
+  const IN* x_ref;
+  const float* hs;  // the half-space rows, or null (box rows alone)
+  float* u_out;
+  float* x_out;
+  int* status;
+  int* iters;
+};
 
 // fp64 re-check of the gap-row QPs the wave kernel did not report SOLVED (its certificate
 // failed, or GI ended infeasible / at its cap): the fp64 Goldfarb-Idnani of gi64_kernel.h over
 // the device-side list (count, list: HandLayout c_rc / rc), every listed QP, its outputs rewritten.
 template <typename IN>
-hipError_t launch_gap_recheck(const KParams& P, int B, const IN* x0, const IN* u_lin,
-                              const IN* x_ref, const float* hs, float* u_out, float* x_out,
-                              int* status, int* iters, const int* list, const int* count,
+hipError_t launch_gap_recheck(const KParams& P, const SolveIO<IN>& io, const int* list, const int* count,
                               const ObjOut& oo, hipStream_t stream);
 
 enum Backend { BACKEND_WAVE = 0, BACKEND_LANE = 1 };
 
-// IN in the launch functions below: the input scalar of x0, u_lin and x_ref, float or double (the
-// *_dbl entry points of include/f110qp.h); both are instantiated in the kernels' objects. The
-// per-group key of a grouped call (gws.key) holds kGroupKeyWords<IN> unsigned words per group.
+// The per-group key of a grouped call (gws.key) holds kGroupKeyWords<IN> unsigned words per group.
 template <typename IN>
 constexpr int kGroupKeyWords = sizeof(IN) == 8 ? 8 : 4;
 
 // Solve B QPs. hs == nullptr -> box-only kernels (gap rows inactive). backend LANE: box rows, the
 // lane-per-QP Riccati/PDAS kernel alone (one launch, no hand-over). Gap rows: lw.screen, the box
 // solve on the lane kernel, GI for the QPs whose box optimum violates a gap row; else GI for every
-// QP; then the fp64 re-check of what GI did not certify.
+// QP; then the fp64 re-check of what GI did not certify. plan: lane_plan(P, io.B, lw, lw.screen)
+// where a lane kernel runs (backend LANE on box rows, lw.screen on gap rows; not read otherwise),
+// resolved once by the caller, which arms the completion signal from the same record.
 template <typename IN>
-hipError_t launch_solve(const KParams& P, int B, const IN* x0, const IN* u_lin,
-                        const IN* x_ref, const float* hs, float* u_out, float* x_out,
-                        int* status, int* iters, const WarmState& warm, int backend,
-                        const LaneWork& lw, const ObjOut& oo, hipStream_t stream);
+hipError_t launch_solve(const KParams& P, const SolveIO<IN>& io, const WarmState& warm, int backend,
+                        const LaneWork& lw, const LanePlan& plan, const ObjOut& oo, hipStream_t stream);
 
-// The lane-per-QP kernel alone (box rows).
+// The lane-per-QP kernel alone (box rows): the instance and launch parameters plan names.
 template <typename IN>
-hipError_t launch_lane(const KParams& P, int B, const IN* x0, const IN* u_lin,
-                       const IN* x_ref, float* u_out, float* x_out, int* status, int* iters,
-                       const WarmState& warm, const LaneWork& lw, const ObjOut& oo,
-                       hipStream_t stream);
+hipError_t launch_lane(const KParams& P, const SolveIO<IN>& io, const WarmState& warm, const LaneWork& lw,
+                       const LanePlan& plan, const ObjOut& oo, hipStream_t stream);
 
 // Grouped solve: leader (smallest member) of every group, W = H^-1 per group from its leader,
 // then the solve (wave back end; the lane back end has no factor to share and ignores groups).
 // ws.W/ws.key hold ngroups slots, leader ngroups ints.
 template <typename IN>
-hipError_t launch_solve_grouped(const KParams& P, int B, const IN* x0, const IN* u_lin,
-                                const IN* x_ref, const float* hs, float* u_out, float* x_out,
-                                int* status, int* iters, const WarmState& gws, int* leader,
-                                int backend, const LaneWork& lw, const ObjOut& oo,
+hipError_t launch_solve_grouped(const KParams& P, const SolveIO<IN>& io, const WarmState& gws, int* leader,
+                                int backend, const LaneWork& lw, const LanePlan& plan, const ObjOut& oo,
                                 hipStream_t stream);
 
 // Per-scenario selection (the argmin of src/project.cpp:125-136 taken over the

@@ -5,33 +5,28 @@
 // (N <= 48; BASELINE config C4 is N = 40). GAP selects the kernel with follow-the-gap rows.
 #include <hip/hip_runtime.h>
 
-#include "f110qp_kernels.h"
+#include "lane_plan.h"
 
 namespace f110qp {
 
 // IN below: the input scalar of x0 / u_lin / x_ref, float or double (the *_dbl entry points of
 // include/f110qp.h). The host dispatch is one template over it; the kernels' IN instantiations are
 // objects of their own (Makefile).
+// (list, count: the device-side list of QPs a GI launch behind the screen works through; Hd, gd: the
+// condensed H and g of launch_condense_debug; null otherwise. The grid is io.B waves.)
 template <int NUM, bool GAP, typename IN>
-hipError_t launch_t(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
-                    const float* hs, float* uo, float* xo, int* st, int* its, double* Hd,
-                    double* gd, const WarmState& ws, const int* list, const int* count, int grid,
-                    const ObjOut& oo, hipStream_t s);  // solve_inst.hip
+hipError_t launch_t(const KParams& P, const SolveIO<IN>& io, double* Hd, double* gd, const WarmState& ws,
+                    const int* list, const int* count, const ObjOut& oo, hipStream_t s);  // solve_inst.hip
 template <int NUM, bool GAP, typename IN>
-hipError_t launch_prep_t(const KParams& P, int B, const IN* x0, const IN* ul,
-                         const IN* xr, const float* hs, const WarmState& ws, const int* leader,
+hipError_t launch_prep_t(const KParams& P, const SolveIO<IN>& io, const WarmState& ws, const int* leader,
                          hipStream_t s);  // solve_inst.hip
 
 template <bool GAP, typename IN>
-static hipError_t launch_g(const KParams& P, int B, const IN* x0, const IN* ul,
-                           const IN* xr, const float* hs, float* uo, float* xo, int* st,
-                           int* its, double* Hd, double* gd, const WarmState& ws, const int* list,
-                           const int* count, int grid, const ObjOut& oo, hipStream_t s) {
+static hipError_t launch_g(const KParams& P, const SolveIO<IN>& io, double* Hd, double* gd, const WarmState& ws,
+                           const int* list, const int* count, const ObjOut& oo, hipStream_t s) {
   const int NU = 2 * P.N;
-#define F110QP_CASE(NUM)                                                                    \
-  if (NU <= NUM)                                                                            \
-    return launch_t<NUM, GAP, IN>(P, B, x0, ul, xr, hs, uo, xo, st, its, Hd, gd, ws, list, count, \
-                              grid, oo, s);
+#define F110QP_CASE(NUM) \
+  if (NU <= NUM) return launch_t<NUM, GAP, IN>(P, io, Hd, gd, ws, list, count, oo, s);
   F110QP_CASE(8) F110QP_CASE(16) F110QP_CASE(24) F110QP_CASE(32) F110QP_CASE(40)
   F110QP_CASE(48) F110QP_CASE(56) F110QP_CASE(64) F110QP_CASE(80) F110QP_CASE(96)
 #undef F110QP_CASE
@@ -155,20 +150,13 @@ __global__ __launch_bounds__(256) void list_all_kernel(const int B, int* __restr
 // kernel has at most kSignalMaxGrid workgroups are armed; the others synchronise the stream, whose
 // end-of-kernel release writes each L2 back once.
 constexpr int kSignalMaxGrid = 256;
-bool launch_signals(const KParams& P, int B, int backend, const float* hs, const LaneWork& lw) {
+bool launch_signals(int B, int backend, const float* hs, const LanePlan& plan) {
   if (B <= 0) return false;
-  long grid;
+  int grid;
   if (hs) {
     grid = B < 256 ? B : 256;  // the fp64 re-check's grid (launch_gap_recheck)
   } else if (backend == BACKEND_LANE) {
-    const int S = lane_segments(P, B, lw);
-    if (S > 1) {
-      const long L = 64 / S;
-      grid = (((long)B << (lane_seg_starts(P, B, S, lw) == 2 ? 1 : 0)) + L - 1) / L;
-    } else {
-      const long L = lane_qps_per_wave(B, lw.qpw);
-      grid = (B + L - 1) / L;
-    }
+    grid = plan.grid;
   } else {
     grid = B;  // one wave per QP
   }
@@ -176,13 +164,13 @@ bool launch_signals(const KParams& P, int B, int backend, const float* hs, const
 }
 
 template <typename IN>
-hipError_t launch_solve(const KParams& P, int B, const IN* x0, const IN* ul,
-                        const IN* xr, const float* hs, float* uo, float* xo, int* st,
-                        int* its, const WarmState& ws, int backend, const LaneWork& lw,
-                        const ObjOut& oo_in, hipStream_t s) {
+hipError_t launch_solve(const KParams& P, const SolveIO<IN>& io, const WarmState& ws, int backend,
+                        const LaneWork& lw, const LanePlan& plan, const ObjOut& oo_in, hipStream_t s) {
+  const int B = io.B;
+  const float* hs = io.hs;
   if (B <= 0) return hipSuccess;
   ObjOut oo = oo_in;
-  if (!launch_signals(P, B, backend, hs, lw)) oo.sig_host = nullptr;  // several kernels: no signal
+  if (!launch_signals(B, backend, hs, plan)) oo.sig_host = nullptr;  // several kernels: no signal
   if (hs) {
     // Gap rows. With the screen: the box-only lane solve of every QP (the segmented kernel
     // evaluates the screen in its output sweep, in fp64, and writes each QP's GI priority; the
@@ -197,46 +185,44 @@ hipError_t launch_solve(const KParams& P, int B, const IN* x0, const IN* ul,
     if (lw.recheck_all) {  // test build: the re-check's own answer for every QP (no screen, no fp32 GI)
       hipLaunchKernelGGL(list_all_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, H.c_rc, H.rc);
       if ((e = hipGetLastError()) != hipSuccess) return e;
-      return launch_gap_recheck(P, B, x0, ul, xr, hs, uo, xo, st, its, H.rc, H.c_rc, oo, s);
+      return launch_gap_recheck(P, io, H.rc, H.c_rc, oo, s);
     }
     ObjOut go = base;
     go.rc_count = H.c_rc;
     go.rc_list = H.rc;
     if (lw.screen) {
-      const bool fused = lane_segments(P, B, lw) > 1;
+      const bool fused = plan.S > 1;
       ObjOut so = base;
       if (fused) {
         so.scr_hs = hs;
         so.scr_prio = H.prio;
       }
-      if ((e = launch_lane(P, B, x0, ul, xr, uo, xo, st, its, WarmState(), lw, so, s)) != hipSuccess) return e;
+      if ((e = launch_lane(P, io, WarmState(), lw, plan, so, s)) != hipSuccess) return e;
       if (!fused) {
-        hipLaunchKernelGGL(gap_screen_kernel<IN>, dim3((B + 255) / 256), dim3(256), 0, s, B, P.N, x0, hs, xo, st, H.prio);
+        hipLaunchKernelGGL(gap_screen_kernel<IN>, dim3((B + 255) / 256), dim3(256), 0, s, B, P.N, io.x0, hs,
+                           io.x_out, io.status, H.prio);
         if ((e = hipGetLastError()) != hipSuccess) return e;
       }
       hipLaunchKernelGGL(gap_order_kernel, dim3(1), dim3(1024), 0, s, B, H.prio, H.c_list, H.list, H.c_rc);
       if ((e = hipGetLastError()) != hipSuccess) return e;
-      e = launch_g<true>(P, B, x0, ul, xr, hs, uo, xo, st, its, nullptr, nullptr, WarmState(), H.list, H.c_list, B,
-                         go, s);
+      e = launch_g<true>(P, io, nullptr, nullptr, WarmState(), H.list, H.c_list, go, s);
     } else {
       if ((e = hipMemsetAsync(H.c_rc, 0, sizeof(int), s)) != hipSuccess) return e;
-      e = launch_g<true>(P, B, x0, ul, xr, hs, uo, xo, st, its, nullptr, nullptr, ws, nullptr, nullptr, B, go, s);
+      e = launch_g<true>(P, io, nullptr, nullptr, ws, nullptr, nullptr, go, s);
     }
     if (e != hipSuccess) return e;
-    return launch_gap_recheck(P, B, x0, ul, xr, hs, uo, xo, st, its, H.rc, H.c_rc, oo, s);
+    return launch_gap_recheck(P, io, H.rc, H.c_rc, oo, s);
   }
-  if (backend == BACKEND_LANE) return launch_lane(P, B, x0, ul, xr, uo, xo, st, its, ws, lw, oo, s);
-  return launch_g<false>(P, B, x0, ul, xr, hs, uo, xo, st, its, nullptr, nullptr, ws, nullptr,
-                         nullptr, B, oo, s);
+  if (backend == BACKEND_LANE) return launch_lane(P, io, ws, lw, plan, oo, s);
+  return launch_g<false>(P, io, nullptr, nullptr, ws, nullptr, nullptr, oo, s);
 }
 
 template <bool GAP, typename IN>
-static hipError_t launch_prep_g(const KParams& P, int B, const IN* x0, const IN* ul,
-                                const IN* xr, const float* hs, const WarmState& ws,
-                                const int* leader, hipStream_t s) {
+static hipError_t launch_prep_g(const KParams& P, const SolveIO<IN>& io, const WarmState& ws, const int* leader,
+                                hipStream_t s) {
   const int NU = 2 * P.N;
 #define F110QP_CASE(NUM) \
-  if (NU <= NUM) return launch_prep_t<NUM, GAP, IN>(P, B, x0, ul, xr, hs, ws, leader, s);
+  if (NU <= NUM) return launch_prep_t<NUM, GAP, IN>(P, io, ws, leader, s);
   F110QP_CASE(8) F110QP_CASE(16) F110QP_CASE(24) F110QP_CASE(32) F110QP_CASE(40)
   F110QP_CASE(48) F110QP_CASE(56) F110QP_CASE(64) F110QP_CASE(80) F110QP_CASE(96)
 #undef F110QP_CASE
@@ -254,20 +240,20 @@ __global__ __launch_bounds__(256) void group_mark_kernel(const int B, const int*
 }
 
 template <typename IN>
-hipError_t launch_solve_grouped(const KParams& P, int B, const IN* x0, const IN* ul,
-                                const IN* xr, const float* hs, float* uo, float* xo, int* st,
-                                int* its, const WarmState& gws, int* leader, int backend,
-                                const LaneWork& lw, const ObjOut& oo, hipStream_t s) {
+hipError_t launch_solve_grouped(const KParams& P, const SolveIO<IN>& io, const WarmState& gws, int* leader,
+                                int backend, const LaneWork& lw, const LanePlan& plan, const ObjOut& oo,
+                                hipStream_t s) {
+  const int B = io.B;
+  const float* hs = io.hs;
   if (B <= 0) return hipSuccess;
   if (backend == BACKEND_LANE || (hs && (lw.screen || lw.recheck_all)))  // per-QP Riccati: nothing to share
-    return launch_solve(P, B, x0, ul, xr, hs, uo, xo, st, its, WarmState(), backend, lw, oo, s);
+    return launch_solve(P, io, WarmState(), backend, lw, plan, oo, s);
   hipError_t e = hipMemsetAsync(leader, 0x7f, (size_t)gws.ngroups * sizeof(int), s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(group_mark_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, gws.group,
                      gws.ngroups, leader);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  e = hs ? launch_prep_g<true>(P, B, x0, ul, xr, hs, gws, leader, s)
-         : launch_prep_g<false>(P, B, x0, ul, xr, hs, gws, leader, s);
+  e = hs ? launch_prep_g<true>(P, io, gws, leader, s) : launch_prep_g<false>(P, io, gws, leader, s);
   if (e != hipSuccess) return e;
   if (hs) {
     const HandLayout H(lw.hand, B);
@@ -276,21 +262,19 @@ hipError_t launch_solve_grouped(const KParams& P, int B, const IN* x0, const IN*
     go.rc_count = H.c_rc;
     go.rc_list = H.rc;
     if ((e = hipMemsetAsync(H.c_rc, 0, sizeof(int), s)) != hipSuccess) return e;
-    e = launch_g<true>(P, B, x0, ul, xr, hs, uo, xo, st, its, nullptr, nullptr, gws, nullptr, nullptr, B, go, s);
+    e = launch_g<true>(P, io, nullptr, nullptr, gws, nullptr, nullptr, go, s);
     if (e != hipSuccess) return e;
-    return launch_gap_recheck(P, B, x0, ul, xr, hs, uo, xo, st, its, H.rc, H.c_rc, oo, s);
+    return launch_gap_recheck(P, io, H.rc, H.c_rc, oo, s);
   }
-  return launch_g<false>(P, B, x0, ul, xr, hs, uo, xo, st, its, nullptr, nullptr, gws, nullptr, nullptr, B, oo, s);
+  return launch_g<false>(P, io, nullptr, nullptr, gws, nullptr, nullptr, oo, s);
 }
 
-#define F110QP_SOLVE_LAUNCH_INST(IN)                                                               \
-  template hipError_t launch_solve<IN>(const KParams&, int, const IN*, const IN*, const IN*,       \
-                                       const float*, float*, float*, int*, int*, const WarmState&, \
-                                       int, const LaneWork&, const ObjOut&, hipStream_t);          \
-  template hipError_t launch_solve_grouped<IN>(const KParams&, int, const IN*, const IN*,          \
-                                               const IN*, const float*, float*, float*, int*,      \
-                                               int*, const WarmState&, int*, int, const LaneWork&, \
-                                               const ObjOut&, hipStream_t);
+#define F110QP_SOLVE_LAUNCH_INST(IN)                                                                      \
+  template hipError_t launch_solve<IN>(const KParams&, const SolveIO<IN>&, const WarmState&, int,         \
+                                       const LaneWork&, const LanePlan&, const ObjOut&, hipStream_t);     \
+  template hipError_t launch_solve_grouped<IN>(const KParams&, const SolveIO<IN>&, const WarmState&, int*, \
+                                               int, const LaneWork&, const LanePlan&, const ObjOut&,      \
+                                               hipStream_t);
 F110QP_SOLVE_LAUNCH_INST(float)
 F110QP_SOLVE_LAUNCH_INST(double)
 #undef F110QP_SOLVE_LAUNCH_INST
@@ -298,8 +282,8 @@ F110QP_SOLVE_LAUNCH_INST(double)
 hipError_t launch_condense_debug(const KParams& P, int B, const float* x0, const float* ul,
                                  const float* xr, double* Hd, double* gd, hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  return launch_g<false>(P, B, x0, ul, xr, nullptr, nullptr, nullptr, nullptr, nullptr, Hd, gd,
-                         WarmState(), nullptr, nullptr, B, ObjOut(), s);
+  const SolveIO<float> io{B, x0, ul, xr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  return launch_g<false>(P, io, Hd, gd, WarmState(), nullptr, nullptr, ObjOut(), s);
 }
 
 // ---- per-scenario selection (f110qp_select_dev) --------------------------------------------

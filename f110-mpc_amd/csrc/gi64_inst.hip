@@ -50,29 +50,27 @@ hipError_t launch_gi64_t(const KParams& P, int grid, const IN* x0, const IN* ul,
                          const int* count, const ObjOut& oo, hipStream_t s);  // one object per NUM and IN
 
 template <typename IN>
-hipError_t launch_gap_recheck(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
-                              const float* hs, float* uo, float* xo, int* st, int* its, const int* list,
-                              const int* count, const ObjOut& oo, hipStream_t s) {
-  if (B <= 0) return hipSuccess;
-  const int grid = B < kRecheckGrid ? B : kRecheckGrid;
+hipError_t launch_gap_recheck(const KParams& P, const SolveIO<IN>& io, const int* list, const int* count,
+                              const ObjOut& oo, hipStream_t s) {
+  if (io.B <= 0) return hipSuccess;
+  const int grid = io.B < kRecheckGrid ? io.B : kRecheckGrid;
   ObjOut o = oo;
   o.rc_count = nullptr;
   o.rc_list = nullptr;
   const int NU = 2 * P.N;
 #define F110QP_CASE(NUM) \
-  if (NU <= NUM) return launch_gi64_t<NUM, IN>(P, grid, x0, ul, xr, hs, uo, xo, st, its, list, count, o, s);
+  if (NU <= NUM)         \
+    return launch_gi64_t<NUM, IN>(P, grid, io.x0, io.u_lin, io.x_ref, io.hs, io.u_out, io.x_out, io.status, \
+                                  io.iters, list, count, o, s);
   F110QP_CASE(8) F110QP_CASE(16) F110QP_CASE(24) F110QP_CASE(32) F110QP_CASE(40)
   F110QP_CASE(48) F110QP_CASE(56) F110QP_CASE(64) F110QP_CASE(80) F110QP_CASE(96)
 #undef F110QP_CASE
   return hipErrorInvalidValue;
 }
-#define F110QP_RECHECK_INST(IN)                                                                        \
-  template hipError_t launch_gap_recheck<IN>(const KParams&, int, const IN*, const IN*, const IN*,     \
-                                             const float*, float*, float*, int*, int*, const int*,     \
-                                             const int*, const ObjOut&, hipStream_t);
-F110QP_RECHECK_INST(float)
-F110QP_RECHECK_INST(double)
-#undef F110QP_RECHECK_INST
+template hipError_t launch_gap_recheck<float>(const KParams&, const SolveIO<float>&, const int*, const int*,
+                                              const ObjOut&, hipStream_t);
+template hipError_t launch_gap_recheck<double>(const KParams&, const SolveIO<double>&, const int*, const int*,
+                                               const ObjOut&, hipStream_t);
 #endif
 
 }  // namespace f110qp

@@ -21,8 +21,8 @@ namespace f110qp {
   F110QP_INST_R(ST, SLDS, false, false)
 #define F110QP_INST_R(ST, SLDS, ROT, DREF)                                                     \
   template hipError_t launch_lane_t<ST, SLDS, F110QP_LQ, ROT, DREF, F110QP_IN>(                \
-      const KParams&, int, const F110QP_IN*, const F110QP_IN*, const F110QP_IN*, float*, float*, int*, int*, \
-      const WarmState&, const LaneWork&, const ObjOut&, size_t, hipStream_t);
+      const KParams&, const SolveIO<F110QP_IN>&, const WarmState&, const LaneWork&, const LanePlan&,      \
+      const ObjOut&, hipStream_t);
 F110QP_INST(double, true)
 F110QP_INST(float, true)
 F110QP_INST(float, false)

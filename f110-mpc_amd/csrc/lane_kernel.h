@@ -58,7 +58,7 @@
 
 #include <type_traits>
 
-#include "f110qp_kernels.h"
+#include "lane_plan.h"
 
 namespace f110qp {
 
@@ -779,17 +779,16 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
 }
 
 template <typename ST, bool SLDS, int L, bool ROT, bool DREF, typename IN>
-hipError_t launch_lane_t(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
-                         float* uo, float* xo, int* st, int* its, const WarmState& ws,
-                         const LaneWork& lw, const ObjOut& oo, size_t lds, hipStream_t s) {
-  const int waves = (B + L - 1) / L;
-  if (lds > 64 * 1024) {
+hipError_t launch_lane_t(const KParams& P, const SolveIO<IN>& io, const WarmState& ws, const LaneWork& lw,
+                         const LanePlan& plan, const ObjOut& oo, hipStream_t s) {
+  if (plan.lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lane_kernel<ST, SLDS, L, ROT, DREF, IN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((lane_kernel<ST, SLDS, L, ROT, DREF, IN>), dim3(waves), dim3(64), lds, s, P, B, x0, ul, xr,
-                     uo, xo, st, its, lw.scratch, ws, lw.kmax, oo);
+  hipLaunchKernelGGL((lane_kernel<ST, SLDS, L, ROT, DREF, IN>), dim3(plan.grid), dim3(64), plan.lds, s, P, io.B,
+                     io.x0, io.u_lin, io.x_ref, io.u_out, io.x_out, io.status, io.iters, lw.scratch, ws, lw.kmax,
+                     oo);
   return hipGetLastError();
 }
 

@@ -10,15 +10,13 @@
 #endif
 
 namespace f110qp {
-// F110QP_IN: the input scalar of x0 / u_lin / x_ref (float; double in the *_dbl objects, which
-// define F110QP_SEG_DBL and leave the policy functions below to the float objects)
+// F110QP_IN: the input scalar of x0 / u_lin / x_ref (float; double in the *_dbl objects)
 #ifndef F110QP_IN
 #define F110QP_IN float
 #endif
 #define F110QP_SEG_INST_IN(S, ROT, SCR, IN)                                                          \
-  template hipError_t launch_lane_seg_t<S, ROT, SCR, IN>(const KParams&, int, const IN*, const IN*,  \
-                                                         const IN*, float*, float*, int*, int*,      \
-                                                         const WarmState&, const LaneWork&, const ObjOut&, \
+  template hipError_t launch_lane_seg_t<S, ROT, SCR, IN>(const KParams&, const SolveIO<IN>&, const WarmState&, \
+                                                         const LaneWork&, const LanePlan&, const ObjOut&,       \
                                                          hipStream_t);
 #ifdef F110QP_SEG_ALL
 #define F110QP_SEG_INST(S, ROT, SCR) F110QP_SEG_INST_IN(S, ROT, SCR, float) F110QP_SEG_INST_IN(S, ROT, SCR, double)
@@ -40,14 +38,4 @@ F110QP_SEG_INST_ALL(true)
 #endif
 #undef F110QP_SEG_INST_ALL
 #undef F110QP_SEG_INST
-
-#if defined(F110QP_SEG_ALL) || (F110QP_SEG_SCR == 0 && !defined(F110QP_SEG_DBL))
-int lane_seg_scratch(const KParams& P, int B, int S, const LaneWork& lw) {
-  return seg_scratch_mode(P, seg_twin(P, B, S, lw) ? 2 * B : B, S, lw);
-}
-int lane_seg_starts(const KParams& P, int B, int S, const LaneWork& lw) { return seg_twin(P, B, S, lw) ? 2 : 1; }
-int lane_seg_fixedq(const KParams& P, int B, int S, const LaneWork& lw) {
-  return seg_fixedq(P, B, S, lw.rot && P.q[0] == P.q[1], false, lw);
-}
-#endif
 }  // namespace f110qp

@@ -48,7 +48,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "f110qp_kernels.h"
+#include "lane_plan.h"
 
 namespace f110qp {
 
@@ -63,32 +63,6 @@ __device__ unsigned long long g_sstamps[4096 * kSegStampSlots];
 #define SSTAMP(var)
 #define SACC(acc, since)
 #endif
-
-// LDS bytes per wave of the segmented kernel for horizon N split into S segments (rows for the
-// longest segment, ceil(N / S) stages)
-// FST: the scratch keeps the lam-gains F_i (6) instead of S_i^-1 (3): 14 doubles per stage
-// F32: references and Riccati scratch held as float (the fp64 arithmetic is unchanged): 60 instead
-// of 116 bytes per stage and lane, so 16,384 x N = 40 QPs per GPU fit at S = 4 (DESIGN.md 2b')
-// + the per-wave tables of the active-state codes (kSegTabBytes: the backward sweep's bound values
-// and free masks, the fp64-scratch forward sweep's re-guess thresholds, 16 codes x 8 doubles each)
-constexpr size_t kSegTabBytes = 16 * 8 * 8;
-constexpr size_t seg_lds_bytes(int N, int S, bool fst = false, bool f32 = false) {
-  return (size_t)((N + S - 1) / S) * 64 * (3 * (f32 ? 4 : 8) + 4 + (fst ? 14 : 11) * (f32 ? 4 : 8)) +
-         (f32 ? 1 : 2) * kSegTabBytes;
-}
-
-// The fixed-length kernels (lane_seg_kernel<..., Q > 0>: EVEN, FST, fp64 scratch, Q stages per segment)
-// keep a lane's references, its PDAS state and the first seg_fixedq_reg_gains of a stage's 8 feedback
-// gains (K 6, then k 2) in registers; their LDS holds the lam-gains F (6 per stage), the gains that
-// are not in registers and the two code tables. (The references are not staged: every lane loads
-// its own 3 Q scalars from global memory.)
-#ifndef F110QP_SEG_QREG
-#define F110QP_SEG_QREG 8  // (knob: 0 .. 8)
-#endif
-constexpr int seg_fixedq_reg_gains(int Q) { return Q > 0 ? F110QP_SEG_QREG : 0; }
-constexpr size_t seg_fixedq_lds_bytes(int Q) {
-  return (size_t)Q * 64 * 8 * (14 - seg_fixedq_reg_gains(Q)) + 2 * kSegTabBytes;
-}
 
 // Gain e (K 0 .. 5, k 6 .. 7) of stage t in the fixed-length kernels: its register (gr, the first KQ
 // gains of a stage; constant t and e only) or its scratch row behind the stage's six lam-gain rows;
@@ -258,7 +232,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   // ---- stage the wave's reference paths (IN, [3N][L]) into the scratch region ----
   // (room: (3 N LR + 64) sizeof(IN) bytes, junk row included, at most 24 N 64 / S + 512 for doubles,
   // in a region of mM NV 64 sizeof(ST) >= 44 (N / S) 64 bytes: fits whenever N / S >= 2, which
-  // lane_segments requires of every S it returns)
+  // lane_plan_segments requires of every S it returns)
   // Element e = q 3N + c of the wave's nq rows (row stride 3 xr_stride in HBM) goes to
   // stg[c L + q]. (q, c) advance by 64 elements per step without a division, every load reads a
   // valid address (clamped) and every store lands (past the staged rows for e >= tot), so the
@@ -1228,92 +1202,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   signal_call_done(oo);  // a synchronous call's completion word (f110qp_kernels.h)
 }
 
-// Scratch of the segmented kernel for a batch: 1 fp64 (the lam-gains kept when they fit), 2 fp32
-// (references and scratch as float) when fp64 does not fit the CU's 160 KiB at the grid's waves
-// per CU (the float grid may then take more than one dispatch round), or when forced (lw.seg32:
-// F110QP_LANE_SEG_F32=1); 0 if neither fits.
-inline int seg_scratch_mode(const KParams& P, int B, int S, const LaneWork& lw) {
-  const size_t waves = ((size_t)B * S + 63) / 64;
-  const size_t per_cu = (waves + 255) / 256;
-  const bool f64 = per_cu * seg_lds_bytes(P.N, S, false) <= 160 * 1024;
-  const bool f32 = seg_lds_bytes(P.N, S, false, true) <= 160 * 1024;  // in one or more rounds
-  if (lw.seg32 && f32) return 2;
-  return f64 ? 1 : (f32 ? 2 : 0);
-}
-
-// Twin starts (lane_seg_kernel<..., TWIN = true>): each QP solved from the cold start and from the
-// speed bound u_des sits on held over the first half of the horizon, in adjacent slots of one wave.
-// Taken when u_des is on a speed bound (the shipped params.yaml:42,46: des_vel = umax), the doubled
-// grid is at most two waves per CU and the lam-gain (FST) scratch of those waves fits a CU's LDS:
-// C2 (1,024 QPs, 128 waves) 26.4 -> 23.4 us. C5 (4,096, 512 waves, two per CU) measured 28.8 ->
-// 30.9 while the segment ends went through ds_bpermute, and 28.95 -> 28.55 us (cold 28.84 -> 28.3)
-// with the DPP exchanges (same box; its slowest tick's passes 5 -> 4). lw.twin = 0 (test build,
-// F110QP_LANE_TWIN=0) turns it off.
-#ifndef F110QP_TWIN_MAX_WAVES
-#define F110QP_TWIN_MAX_WAVES 512  // (measurement builds: tools/build_seg_variant.sh -D...)
-#endif
-constexpr long kTwinMaxWaves = F110QP_TWIN_MAX_WAVES;
-inline bool seg_twin(const KParams& P, int B, int S, const LaneWork& lw) {
-  if (!lw.twin || !(P.udes[0] >= (double)P.umax[0] || P.udes[0] <= (double)P.umin[0])) return false;
-  const long waves2 = (2L * B * S + 63) / 64;
-  const long per_cu = (waves2 + 255) / 256;
-  return waves2 <= kTwinMaxWaves && seg_scratch_mode(P, 2 * B, S, lw) == 1 && lw.dref &&
-         per_cu * seg_lds_bytes(P.N, S, true) <= 160 * 1024;  // the FST kernel, all waves resident
-}
-
-// Segment length of the fixed-length kernels a batch runs (lane_seg_kernel<..., Q = 5>), 0 for the
-// run-time-length ones: five-stage segments at S = 4 in the heading frame (C2, C5, the single-QP
-// tick at N = 20), exactly where the EVEN, FST, fp64 kernel would run without the gap-row screen.
-// The policy functions above are unchanged and still count that kernel's LDS; only the launch's
-// request is the smaller one. lw.fixedq = 0 (test build, F110QP_SEG_FIXEDQ=0) keeps the
-// run-time-length kernel.
-inline int seg_fixedq(const KParams& P, int B, int S, bool rot, bool scr, const LaneWork& lw) {
-  if (!lw.fixedq || S != 4 || !rot || scr || P.N != 5 * S) return 0;
-  const int twin = seg_twin(P, B, S, lw) ? 1 : 0;
-  const size_t waves = (((size_t)B << twin) * S + 63) / 64, per_cu = (waves + 255) / 256;
-  const bool fst = seg_scratch_mode(P, B << twin, S, lw) == 1 && lw.dref &&
-                   per_cu * seg_lds_bytes(P.N, S, true) <= 160 * 1024;
-  return (twin || fst) ? 5 : 0;
-}
-
+// The launch of one call: the instance plan names (lane_plan.h: FST, ST, TWIN, EVEN and Q within this
+// S, ROT, SCR), its LDS attribute above 64 KiB, the launch.
 template <int S, bool ROT, bool SCR, typename IN>
-hipError_t launch_lane_seg_t(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
-                             float* uo, float* xo, int* st, int* its, const WarmState& ws,
-                             const LaneWork& lw, const ObjOut& oo, hipStream_t s) {
-  constexpr int L = 64 / S;
-  const int twin = seg_twin(P, B, S, lw) ? 1 : 0;  // (one wave per CU at most: FST fits)
-  const int waves = ((B << twin) + L - 1) / L;
-  const int mode = seg_scratch_mode(P, B << twin, S, lw);
-  // the lam-gains stored (FST, no refresh sweep: measured C5 30.5 -> see DESIGN.md 2b') when the
-  // resident waves' LDS holds 14 doubles per stage, else the refresh sweep (11); lw.dref = 0
-  // forces the refresh (test hook, F110QP_LANE_DREF=0)
-  const size_t per_cu = ((size_t)waves + 255) / 256;
-  const bool fst = mode == 1 && lw.dref && per_cu * seg_lds_bytes(P.N, S, true) <= 160 * 1024;
-  auto go1 = [&](auto kern, size_t lds) -> hipError_t {
-    if (lds > 64 * 1024) {
+hipError_t launch_lane_seg_t(const KParams& P, const SolveIO<IN>& io, const WarmState& ws, const LaneWork& lw,
+                             const LanePlan& plan, const ObjOut& oo, hipStream_t s) {
+  auto go1 = [&](auto kern) -> hipError_t {
+    if (plan.lds > 64 * 1024) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds);
       if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(waves), dim3(64), lds, s, P, B, x0, ul, xr, uo, xo, st, its, ws,
-                       lw.kmax, oo);
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(64), plan.lds, s, P, io.B, io.x0, io.u_lin, io.x_ref, io.u_out,
+                       io.x_out, io.status, io.iters, ws, lw.kmax, oo);
     return hipGetLastError();
   };
-  const bool even = P.N % S == 0;  // equal segments: the EVEN instantiation
+  const bool twin = plan.starts == 2;
   if constexpr (S == 4 && ROT && !SCR) {
-    if (seg_fixedq(P, B, S, ROT, SCR, lw) == 5) {
-      const size_t lds = seg_fixedq_lds_bytes(5);
-      return twin ? go1(&lane_seg_kernel<4, true, true, double, false, true, true, IN, 5>, lds)
-                  : go1(&lane_seg_kernel<4, true, true, double, false, false, true, IN, 5>, lds);
-    }
+    if (plan.Q == 5)
+      return twin ? go1(&lane_seg_kernel<4, true, true, double, false, true, true, IN, 5>)
+                  : go1(&lane_seg_kernel<4, true, true, double, false, false, true, IN, 5>);
   }
-#define F110QP_SEG_GO(FST_, ST_, TWIN_, LDS_)                                              \
-  (even ? go1(&lane_seg_kernel<S, ROT, FST_, ST_, SCR, TWIN_, true, IN>, LDS_)                 \
-        : go1(&lane_seg_kernel<S, ROT, FST_, ST_, SCR, TWIN_, false, IN>, LDS_))
-  if (twin) return F110QP_SEG_GO(true, double, true, seg_lds_bytes(P.N, S, true));
-  if (mode == 2) return F110QP_SEG_GO(false, float, false, seg_lds_bytes(P.N, S, false, true));
-  return fst ? F110QP_SEG_GO(true, double, false, seg_lds_bytes(P.N, S, true))
-             : F110QP_SEG_GO(false, double, false, seg_lds_bytes(P.N, S, false));
+#define F110QP_SEG_GO(FST_, ST_, TWIN_)                                                  \
+  (plan.even ? go1(&lane_seg_kernel<S, ROT, FST_, ST_, SCR, TWIN_, true, IN>)            \
+             : go1(&lane_seg_kernel<S, ROT, FST_, ST_, SCR, TWIN_, false, IN>))
+  if (twin) return F110QP_SEG_GO(true, double, true);
+  if (plan.mode == 2) return F110QP_SEG_GO(false, float, false);
+  return plan.fst ? F110QP_SEG_GO(true, double, false) : F110QP_SEG_GO(false, double, false);
 #undef F110QP_SEG_GO
 }
 

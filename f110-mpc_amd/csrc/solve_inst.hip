@@ -11,12 +11,10 @@
 #define F110QP_IN float
 #endif
 #define F110QP_INSTANTIATE_IN(NUM, GAP, IN)                                                    \
-  template hipError_t f110qp::launch_t<NUM, GAP, IN>(                                          \
-      const KParams&, int, const IN*, const IN*, const IN*, const float*, float*,              \
-      float*, int*, int*, double*, double*, const WarmState&, const int*, const int*, int,       \
-      const ObjOut&, hipStream_t);                                                             \
-  template hipError_t f110qp::launch_prep_t<NUM, GAP, IN>(const KParams&, int, const IN*,      \
-                                                          const IN*, const IN*, const float*,  \
+  template hipError_t f110qp::launch_t<NUM, GAP, IN>(const KParams&, const SolveIO<IN>&, double*, double*, \
+                                                     const WarmState&, const int*, const int*,            \
+                                                     const ObjOut&, hipStream_t);                         \
+  template hipError_t f110qp::launch_prep_t<NUM, GAP, IN>(const KParams&, const SolveIO<IN>&,             \
                                                           const WarmState&, const int*, hipStream_t);
 #ifdef F110QP_ALL_INST
 #define F110QP_INSTANTIATE(NUM, GAP) F110QP_INSTANTIATE_IN(NUM, GAP, float) F110QP_INSTANTIATE_IN(NUM, GAP, double)

@@ -2437,22 +2437,19 @@ __global__ __launch_bounds__(64) void group_prep_kernel(const KParams P, const i
 // launch of one instantiation
 // ------------------------------------------------------------------------------------------
 template <int NUM, bool GAP, typename IN>
-hipError_t launch_t(const KParams& P, int B, const IN* x0, const IN* ul, const IN* xr,
-                    const float* hs, float* uo, float* xo, int* st, int* its, double* Hd,
-                    double* gd, const WarmState& ws, const int* list, const int* count, int grid,
-                    const ObjOut& oo, hipStream_t s) {
-  hipLaunchKernelGGL((solve_kernel<NUM, GAP, IN>), dim3(grid), dim3(64), 0, s, P, B, x0, ul, xr, hs,
-                     uo, xo, st, its, Hd, gd, ws, list, count, oo);
+hipError_t launch_t(const KParams& P, const SolveIO<IN>& io, double* Hd, double* gd, const WarmState& ws,
+                    const int* list, const int* count, const ObjOut& oo, hipStream_t s) {
+  hipLaunchKernelGGL((solve_kernel<NUM, GAP, IN>), dim3(io.B), dim3(64), 0, s, P, io.B, io.x0, io.u_lin, io.x_ref,
+                     io.hs, io.u_out, io.x_out, io.status, io.iters, Hd, gd, ws, list, count, oo);
   return hipGetLastError();
 }
 
 template <int NUM, bool GAP, typename IN>
-hipError_t launch_prep_t(const KParams& P, int B, const IN* x0, const IN* ul,
-                         const IN* xr, const float* hs, const WarmState& ws, const int* leader,
+hipError_t launch_prep_t(const KParams& P, const SolveIO<IN>& io, const WarmState& ws, const int* leader,
                          hipStream_t s) {
   if (ws.ngroups <= 0) return hipSuccess;
   hipLaunchKernelGGL((group_prep_kernel<NUM, GAP, IN>), dim3(ws.ngroups), dim3(64), 0, s, P,
-                     ws.ngroups, x0, ul, xr, hs, ws, leader, B);
+                     ws.ngroups, io.x0, io.u_lin, io.x_ref, io.hs, ws, leader, io.B);
   return hipGetLastError();
 }
 
