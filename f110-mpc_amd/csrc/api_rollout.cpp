@@ -2,7 +2,8 @@
 // rollout (f110qp_advance_dev, f110qp_rollout[_dev]), the rollout with gap rows from the scans
 // (f110qp_rollout_scan[_dev]), with re-planning (f110qp_rollout_replan[_dev]), in a world of circles
 // (f110qp_rollout_world[_dev]), with race-mates (f110qp_rollout_race[_dev]) and with contact
-// (f110qp_clearance_dev, f110qp_rollout_contact[_dev]), and the parts of each.
+// (f110qp_clearance_dev, f110qp_rollout_contact[_dev]) and with rectangular bodies (f110qp_clearance_body_dev,
+// f110qp_cast_scans_body_dev, f110qp_rollout_body[_dev]), and the parts of each.
 // Host-side responsibilities only: argument validation, workspaces, H2D/D2H of the host-pointer calls
 // (the staging table of api_stage.h). No C++ exception crosses this boundary.
 #include <cmath>
@@ -100,6 +101,19 @@ static int contact_params(const f110qp_contact_config* cc) {
   return F110QP_OK;
 }
 
+// The rectangular body of f110qp_clearance_body_dev, f110qp_cast_scans_body_dev and f110qp_rollout_body[_dev],
+// checked, into *H.
+static int body_params(const f110qp_body_config* body, f110qp::BodyParams* H) {
+  if (!body) return fail(F110QP_ERR_INVALID, "body config is NULL");
+  if (!(body->half_length > 0.0) || !std::isfinite(body->half_length))
+    return fail(F110QP_ERR_INVALID, "half_length must be positive and finite");
+  if (!(body->half_width > 0.0) || !std::isfinite(body->half_width))
+    return fail(F110QP_ERR_INVALID, "half_width must be positive and finite");
+  H->hl = body->half_length;
+  H->hw = body->half_width;
+  return F110QP_OK;
+}
+
 // The scan geometry of the re-planning kernels' argument records (ReplanStart, ReplanStep).
 template <typename S>
 static void scan_geometry(S* s, const f110qp_scan_config& sc) {
@@ -112,8 +126,9 @@ static void scan_geometry(S* s, const f110qp_scan_config& sc) {
 
 // The family of a rollout call, in the order each was built on the one before: from kScan a scan
 // config is read, from kReplan the loop re-plans, from kWorld the scans are cast (so neither `ranges`
-// nor sc->scan_rows is read), kRace casts see the race-mates, and kContact records every row's clearance.
-enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact };
+// nor sc->scan_rows is read), kRace casts see the race-mates, kContact records every row's clearance,
+// and kBody is kContact with rectangular bodies in every cast and clearance.
+enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact, kBody };
 
 // The configs of a rollout call as the caller gave them and, once check_args has passed, the
 // kernels' parameters.
@@ -262,6 +277,8 @@ struct WorldLoop {
   float* ranges_traj;     // [T][B][num_ranges] or null: one row set in the context, listed cars only
   bool race;
   f110qp::RaceParams Q;
+  bool body;  // f110qp_rollout_body[_dev]: the mates are rectangles, in the casts and in the clearances
+  f110qp::BodyParams H;
 };
 
 // f110qp_rollout_contact[_dev]: the race rollout with one clearance launch per row of x_traj, which also
@@ -274,6 +291,7 @@ struct ContactLoop {
 
 static hipError_t world_cast(const WorldLoop& wl, int batch, const int* list, const int* count, const double* x,
                              float* ranges, hipStream_t s) {
+  if (wl.body) return f110qp::launch_cast_scans_body(wl.P, wl.Q, wl.H, batch, list, count, x, wl.circles, ranges, s);
   return wl.race ? f110qp::launch_cast_scans_race(wl.P, wl.Q, batch, list, count, x, wl.circles, ranges, s)
                  : f110qp::launch_cast_scans(wl.P, batch, list, count, x, wl.circles, ranges, s);
 }
@@ -362,8 +380,11 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
   auto clearance_row = [&](size_t t) {
     const f110qp::ClearParams cp{wl->P.C, wl->P.world_rows};
     const f110qp::ContactMark mk{cl->io.crash_tick, (int)t, t == 0, cl->margin};
-    return f110qp::launch_clearance(cp, wl->Q, io.B, 1, io.x(t), wl->circles, cl->io.clear_traj + t * B,
-                                    cl->io.nearest_traj ? cl->io.nearest_traj + t * B : nullptr, mk, s);
+    int* near = cl->io.nearest_traj ? cl->io.nearest_traj + t * B : nullptr;
+    return wl->body ? f110qp::launch_clearance_body(cp, wl->Q, wl->H, io.B, 1, io.x(t), wl->circles,
+                                                    cl->io.clear_traj + t * B, near, mk, s)
+                    : f110qp::launch_clearance(cp, wl->Q, io.B, 1, io.x(t), wl->circles, cl->io.clear_traj + t * B,
+                                               near, mk, s);
   };
   if (cl && (e = clearance_row(0)) != hipSuccess) return hip_fail(e, "clearance launch");
   for (size_t t = 0; t < T; t++) {
@@ -527,18 +548,21 @@ static int replan_call(f110qp_ctx* c, LoopCfg cfg, RolloutIO io, const ReplanIO&
 }
 
 // f110qp_rollout_world[_dev] (kWorld; race not read), f110qp_rollout_race[_dev] (kRace) and
-// f110qp_rollout_contact[_dev] (kContact: cc and the records k).
+// f110qp_rollout_contact[_dev] (kContact: cc and the records k) and f110qp_rollout_body[_dev] (kBody: body too).
 static int world_call(f110qp_ctx* c, LoopCfg cfg, const f110qp_world_config* wc, const f110qp_race_config* race,
                       RolloutIO io, const ReplanIO& r, const double* circles, float* rgt, Where w,
-                      const f110qp_contact_config* cc = nullptr, const ContactIO* k = nullptr) {
+                      const f110qp_contact_config* cc = nullptr, const ContactIO* k = nullptr,
+                      const f110qp_body_config* body = nullptr) {
   WorldLoop wl{};
   int rv = check_args(c, &cfg, &io, nullptr, nullptr, &r);
   if (rv) return rv;
   if ((rv = world_params(cfg.sc, wc, io.B, circles, &wl.P))) return rv;
   wl.race = cfg.fam >= kRace;
   if (wl.race && (rv = race_params(race, io.B, wc->num_circles, &wl.Q))) return rv;
-  const bool contact = cfg.fam == kContact;
+  const bool contact = cfg.fam >= kContact;
   if (contact && (rv = contact_params(cc))) return rv;
+  wl.body = cfg.fam == kBody;
+  if (wl.body && (rv = body_params(body, &wl.H))) return rv;
   if (io.B == 0) return F110QP_OK;
   if (contact && (!k->clear_traj || !k->crash_tick))
     return fail(F110QP_ERR_INVALID, "clear_traj/crash_tick must be non-NULL");
@@ -965,6 +989,88 @@ int f110qp_rollout_contact(f110qp_ctx* c, const f110qp_rollout_config* rc, const
   const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
   const ContactIO k{clt, nrt, crash};
   return world_call(c, LoopCfg{kContact, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k);
+}
+
+// ---- rectangular car bodies (f110qp_clearance_body_dev, f110qp_cast_scans_body_dev, -----------------------
+// ---- f110qp_rollout_body[_dev]) ------------------------------------------------------------------------
+
+void f110qp_default_body_config(f110qp_body_config* body) {
+  if (!body) return;
+  std::memset(body, 0, sizeof(*body));
+  body->half_length = 0.29;  // a 0.58 x 0.31 m car
+  body->half_width = 0.155;
+}
+
+int f110qp_clearance_body_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
+                              const f110qp_body_config* body, int batch, int rows, const double* x,
+                              const double* circles, double* clearance, int* nearest, void* stream) {
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  f110qp::CastParams P;
+  f110qp::RaceParams Q;
+  f110qp::BodyParams H;
+  int rv = world_params(nullptr, wc, batch, circles, &P);
+  if (rv) return rv;
+  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
+  if ((rv = body_params(body, &H))) return rv;
+  if (rows < 1) return fail(F110QP_ERR_INVALID, "rows must be >= 1");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !clearance) return fail(F110QP_ERR_INVALID, "x/clearance must be non-NULL");
+  if ((long long)rows * batch > (1ll << 30)) return fail(F110QP_ERR_INVALID, "rows x batch too large");
+  const hipError_t e = f110qp::launch_clearance_body(f110qp::ClearParams{P.C, P.world_rows}, Q, H, batch, rows, x,
+                                                     circles, clearance, nearest,
+                                                     f110qp::ContactMark{nullptr, 0, 0, 0.0}, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "body clearance launch");
+  return F110QP_OK;
+}
+
+int f110qp_cast_scans_body_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
+                               const f110qp_race_config* race, const f110qp_body_config* body, int batch,
+                               const int* list, const int* count, const double* x, const double* circles,
+                               float* ranges, void* stream) {
+  int rv = check_scan_config(sc, false, 0);
+  if (rv) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  f110qp::CastParams P;
+  f110qp::RaceParams Q;
+  f110qp::BodyParams H;
+  if ((rv = world_params(sc, wc, batch, circles, &P))) return rv;
+  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
+  if ((rv = body_params(body, &H))) return rv;
+  if ((list != nullptr) != (count != nullptr))
+    return fail(F110QP_ERR_INVALID, "list and count must be given together");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !ranges) return fail(F110QP_ERR_INVALID, "x/ranges must be non-NULL");
+  const hipError_t e =
+      f110qp::launch_cast_scans_body(P, Q, H, batch, list, count, x, circles, ranges, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "body scan cast launch");
+  return F110QP_OK;
+}
+
+int f110qp_rollout_body_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                            const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                            const f110qp_race_config* race, const f110qp_contact_config* cc,
+                            const f110qp_body_config* body, int batch, const double* table, const double* wp,
+                            double* xr, int* have, const double* circles, double* xt, double* ult, float* ua,
+                            int* stt, int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst,
+                            int* btt, int* bgt, double* poset, float* rgt, double* clt, int* nrt, int* crash,
+                            void* stream) {
+  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
+  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
+  const ContactIO k{clt, nrt, crash};
+  return world_call(c, LoopCfg{kBody, rc, sc, rp}, wc, race, io, r, circles, rgt, on_stream(stream), cc, &k, body);
+}
+
+int f110qp_rollout_body(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                        const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                        const f110qp_race_config* race, const f110qp_contact_config* cc,
+                        const f110qp_body_config* body, int batch, const double* table, const double* wp, double* xr,
+                        int* have, const double* circles, double* xt, double* ult, float* ua, int* stt, int* itt,
+                        double* cot, float* up, float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt,
+                        double* poset, float* rgt, double* clt, int* nrt, int* crash) {
+  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
+  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
+  const ContactIO k{clt, nrt, crash};
+  return world_call(c, LoopCfg{kBody, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k, body);
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@
 // to stand on), and the result is the exact minimum by construction. No cap on C or G.
 #include <hip/hip_runtime.h>
 
+#include "body_geom.h"
 #include "f110qp_kernels.h"
 
 namespace f110qp {
@@ -165,6 +166,129 @@ hipError_t launch_clearance(const ClearParams& P, const RaceParams& Q, int B, in
   const int nwg = clearance_grid(B);
   hipLaunchKernelGGL(clearance_kernel, dim3(nwg), dim3(kClearThreads), 0, s, P, Q, B, rows, nwg, x, circles, clearance,
                      nearest, M);
+  return hipGetLastError();
+}
+
+// ---- rectangular bodies (f110qp_clearance_body_dev, f110qp_rollout_body[_dev]) ---------------------------
+// The body is the rectangle of body_geom.h: centre q as above, axes (cos, sin) of the heading, half extents H;
+// Q.car_radius is not read. A static circle gives v = body_sd(c; body) - |r|, a mate v = body_pair(own, mate),
+// the same bits from either side. Index, update rule, start value and the NaN rule are the circle kernel's,
+// and so are the mapping, the passes, the reduction and the crash record: LDS holds (cos, sin) per pose next
+// to q, and a mate's frame is built by the thread that takes it, one sincos per pose. The mate loop is not
+// unrolled (one body_pair in the code instead of eight, its value folded into the pose's registers by an
+// unrolled select), which is what keeps the kernel's registers down.
+__global__ __launch_bounds__(kClearThreads) void clearance_body_kernel(
+    const ClearParams P, const RaceParams Q, const BodyParams H, const int B, const int rows, const int nwg,
+    const double* __restrict__ x, const double* __restrict__ circles, double* __restrict__ clearance,
+    int* __restrict__ nearest, const ContactMark M) {
+#pragma clang fp contract(off)
+  __shared__ double s_qx[kClearPoses], s_qy[kClearPoses], s_c[kClearPoses], s_s[kClearPoses];
+  __shared__ double s_best[kClearWaves][kClearPoses];
+  __shared__ int s_idx[kClearWaves][kClearPoses];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double inf = __longlong_as_double(0x7ff0000000000000ll);
+  const int nc = P.C + Q.G - 1;  // the circles and the G - 1 mates behind them
+  for (int b = blockIdx.x; b < B; b += nwg) {
+    const double* cw = circles + (P.world_rows == 1 ? (size_t)0 : (size_t)b * (size_t)P.C * 3);
+    const int own = b % Q.G, first = b - own;
+    int crash = -1;  // thread 0: the first row at or under the margin
+    if (M.crash_tick && !M.init && tid == 0) crash = M.crash_tick[b];
+    for (int r0 = 0; r0 < rows; r0 += kClearPoses) {
+      const int np = min(kClearPoses, rows - r0);
+      if (tid < np) {  // the body frame of pose tid of the pass
+        const double* xp = x + ((size_t)(r0 + tid) * (size_t)B + (size_t)b) * 3;
+        double so, co;
+        sincos(xp[2], &so, &co);
+        s_qx[tid] = xp[0] + Q.center_offset * co;
+        s_qy[tid] = xp[1] + Q.center_offset * so;
+        s_c[tid] = co;
+        s_s[tid] = so;
+      }
+      __syncthreads();
+      double best[kClearPoses];
+      int idx[kClearPoses];
+#pragma unroll
+      for (int p = 0; p < kClearPoses; p++) {
+        best[p] = inf;
+        idx[p] = -1;
+      }
+      for (int c0 = 0; c0 < nc; c0 += kCastCircleTile) {
+        const int j = c0 + tid;
+        if (j < P.C) {
+          const double cx = cw[(size_t)j * 3 + 0], cy = cw[(size_t)j * 3 + 1];
+          const double ra = fabs(cw[(size_t)j * 3 + 2]);
+#pragma unroll
+          for (int p = 0; p < kClearPoses; p++)
+            if (p < np) take_min(best[p], idx[p], body_sd(cx, cy, s_qx[p], s_qy[p], s_c[p], s_s[p], H) - ra, j);
+        } else if (j < nc) {  // mate k of the race, stepped over the own slot: index i inside the race
+          const int k = j - P.C, i = k + (k >= own ? 1 : 0);
+#pragma unroll 1
+          for (int p = 0; p < np; p++) {
+            const double* xm = x + ((size_t)(r0 + p) * (size_t)B + (size_t)(first + i)) * 3;
+            double sm, cm;
+            sincos(xm[2], &sm, &cm);
+            const double mx = xm[0] + Q.center_offset * cm, my = xm[1] + Q.center_offset * sm;
+            const double v = body_pair(s_qx[p], s_qy[p], s_c[p], s_s[p], mx, my, cm, sm, H);
+#pragma unroll
+            for (int q = 0; q < kClearPoses; q++)
+              if (q == p) take_min(best[q], idx[q], v, P.C + i);
+          }
+        }
+      }
+      // the wave's (value, index) minimum per pose, then the four waves' through LDS
+#pragma unroll
+      for (int p = 0; p < kClearPoses; p++) {
+        if (p < np) {  // uniform
+#pragma unroll
+          for (int m = 32; m >= 1; m >>= 1) {
+            const double ov = __shfl_xor(best[p], m, 64);
+            const int oi = __shfl_xor(idx[p], m, 64);
+            take_min(best[p], idx[p], ov, oi);
+          }
+          if (lane == 0) {
+            s_best[wave][p] = best[p];
+            s_idx[wave][p] = idx[p];
+          }
+        }
+      }
+      __syncthreads();
+      if (tid < np) {
+        double v = s_best[0][tid];
+        int i = s_idx[0][tid];
+#pragma unroll
+        for (int w = 1; w < kClearWaves; w++) take_min(v, i, s_best[w][tid], s_idx[w][tid]);
+        const size_t o = (size_t)(r0 + tid) * (size_t)B + (size_t)b;
+        clearance[o] = v;
+        if (nearest) nearest[o] = i;
+        s_best[0][tid] = v;  // for the mark below (read by thread 0 behind the barrier)
+      }
+      if (M.crash_tick) {  // uniform
+        __syncthreads();
+        if (tid == 0)
+          for (int p = 0; p < np; p++)
+            if (crash < 0 && s_best[0][p] <= M.margin) crash = M.row0 + r0 + p;
+      }
+      __syncthreads();  // the next pass (or car) rewrites the frames and the waves' results
+    }
+    if (M.crash_tick && tid == 0) M.crash_tick[b] = crash;
+  }
+}
+
+// Grid: one workgroup per car up to 512. The kernel holds 185 VGPRs (the code-object metadata, DESIGN.md 2i;
+// no scratch), allocated in granules of eight as 192, so a SIMD keeps floor(512 / 192) = 2 of its waves; a
+// workgroup is one wave on each of a CU's four SIMDs and 640 B of LDS, so a CU holds two workgroups and the
+// MI355X's 256 CUs hold 512 at once: derived as clearance_grid's 1,024 was, from the occupancy and not from a
+// sweep of caps (none was measured).
+constexpr int kClearBodyMaxGrid = 512;
+int clearance_body_grid(int B) { return B < kClearBodyMaxGrid ? B : kClearBodyMaxGrid; }
+
+hipError_t launch_clearance_body(const ClearParams& P, const RaceParams& Q, const BodyParams& H, int B, int rows,
+                                 const double* x, const double* circles, double* clearance, int* nearest,
+                                 const ContactMark& M, hipStream_t s) {
+  if (B <= 0 || rows <= 0) return hipSuccess;
+  const int nwg = clearance_body_grid(B);
+  hipLaunchKernelGGL(clearance_body_kernel, dim3(nwg), dim3(kClearThreads), 0, s, P, Q, H, B, rows, nwg, x, circles,
+                     clearance, nearest, M);
   return hipGetLastError();
 }
 

@@ -406,6 +406,16 @@ struct RaceParams {
 };
 hipError_t launch_cast_scans_race(const CastParams& P, const RaceParams& Q, int B, const int* list, const int* count,
                                   const double* x, const double* circles, float* ranges, hipStream_t stream);
+// Rectangular bodies (body_geom.h): a car is the rectangle with centre (x + center_offset cos(ori), y +
+// center_offset sin(ori)), axes along and across the heading and half extents (hl, hw); Q.car_radius is not read.
+struct BodyParams {
+  double hl, hw;  // half length, half width
+};
+// launch_cast_scans_race with every mate a rectangle (the slab test) in place of the race circle.
+int cast_scans_body_grid(int B);
+hipError_t launch_cast_scans_body(const CastParams& P, const RaceParams& Q, const BodyParams& H, int B, const int* list,
+                                  const int* count, const double* x, const double* circles, float* ranges,
+                                  hipStream_t stream);
 
 // ---- contact (contact_kernels.hip) ----------------------------------------------------------------
 // The clearance of rows x B poses x [rows][B][3] to everything each car can touch: the C circles of its
@@ -430,6 +440,11 @@ int clearance_grid(int B);
 hipError_t launch_clearance(const ClearParams& P, const RaceParams& Q, int B, int rows, const double* x,
                             const double* circles, double* clearance, int* nearest, const ContactMark& M,
                             hipStream_t stream);
+// The same with the own car and its mates rectangles: body_sd(c; body) - |r| per circle, body_pair per mate.
+int clearance_body_grid(int B);
+hipError_t launch_clearance_body(const ClearParams& P, const RaceParams& Q, const BodyParams& H, int B, int rows,
+                                 const double* x, const double* circles, double* clearance, int* nearest,
+                                 const ContactMark& M, hipStream_t stream);
 
 // ---- standings (standings_kernels.hip) ------------------------------------------------------------
 // The projection of rows x B poses x [rows][B][3] onto the closed path wp [W][2] with cumulative lengths

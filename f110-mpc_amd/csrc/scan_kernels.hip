@@ -41,6 +41,7 @@
 // instantiation; every race statement is behind `if constexpr`.
 #include <hip/hip_runtime.h>
 
+#include "body_geom.h"
 #include "f110qp_kernels.h"
 
 namespace f110qp {
@@ -66,6 +67,21 @@ constexpr double kCastMinInc = 1e-9;
 struct CastSlot {
   double px, py, r2, flo, nd;
 };
+// The body instantiation's slot: a mate is culled and given its beam interval through its circumscribed
+// circle (the fields above), and phase B runs the slab test on the rectangle with axes (c, s).
+struct CastBodySlot {
+  double px, py, r2, flo, nd;
+  double c, s;
+  int mate;  // 0: a static circle (cast_beams), 1: a race-mate's rectangle (cast_beams_body)
+};
+template <bool BODY>
+struct SlotOf {
+  using type = CastSlot;
+};
+template <>
+struct SlotOf<true> {
+  using type = CastBodySlot;
+};
 
 // The exact hit test of circle (px, py, pp, r2) on beams lo .. hi of the scan (clipped to the beam tile
 // [cb, cb + nb)), lanes striding by kCastLanes.
@@ -86,12 +102,31 @@ __device__ __forceinline__ void cast_beams(const double px, const double py, con
   }
 }
 
+// The slab test of body_geom.h on beams lo .. hi of the scan for the mate whose centre is (px, py) from the
+// LiDAR and whose axes are (c, s): the beams and the fold are cast_beams'.
 #pragma clang fp contract(off)
-template <bool RACE>
-__device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& Q, const int b,
+__device__ __forceinline__ void cast_beams_body(const double px, const double py, const double c, const double s,
+                                                const BodyParams& H, int lo, int hi, const int cb, const int nb,
+                                                const int sub, const double* s_dx, const double* s_dy,
+                                                unsigned long long* s_min) {
+  lo = max(lo, cb) - cb;
+  hi = min(hi, cb + nb - 1) - cb;
+  const double of = -(px * c + py * s), ol = -(py * c - px * s);
+  for (int i = lo + sub; i <= hi; i += kCastLanes) {
+    double th;
+    if (body_slab(of, ol, c, s, s_dx[i], s_dy[i], H, th))
+      atomicMin(&s_min[i], (unsigned long long)__double_as_longlong(th));
+  }
+}
+
+#pragma clang fp contract(off)
+template <bool RACE, bool BODY>
+__device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& Q, const BodyParams& H, const int b,
                                          const double* __restrict__ x, const double* __restrict__ circles,
                                          float* __restrict__ ranges, double* s_dx, double* s_dy,
-                                         unsigned long long* s_min, CastSlot* s_slot) {
+                                         unsigned long long* s_min, typename SlotOf<BODY>::type* s_slot) {
+  static_assert(RACE || !BODY, "bodies are the race-mates'");
+  using Slot = typename SlotOf<BODY>::type;
   const int tid = threadIdx.x;
   const double ori = x[(size_t)b * 3 + 2];
   double so, co;
@@ -122,7 +157,7 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
     __syncthreads();
     for (int c0 = 0; c0 < nc; c0 += kCastCircleTile) {
       {  // A: circle c0 + tid -> slot tid
-        CastSlot sl{0.0, 0.0, 0.0, 0.0, 0.0};
+        Slot sl{};
         const int j = c0 + tid;
         if (j < nc) {
           double cx, cy, r;
@@ -135,7 +170,14 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
             sincos(xm[2], &sm, &cm);
             cx = xm[0] + Q.center_offset * cm;
             cy = xm[1] + Q.center_offset * sm;
-            r = Q.car_radius;
+            if constexpr (BODY) {  // the circumscribed circle, for the culls and the interval only
+              r = __dsqrt_rn(H.hl * H.hl + H.hw * H.hw) * kCastRel;
+              sl.c = cm;
+              sl.s = sm;
+              sl.mate = 1;
+            } else {
+              r = Q.car_radius;
+            }
           } else {
             r = cw[(size_t)j * 3 + 2];
             cx = cw[(size_t)j * 3 + 0];
@@ -165,11 +207,21 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
       {  // B: kCastLanes lanes per kept circle
         const int nt = min(kCastCircleTile, nc - c0), sub = tid % kCastLanes;
         for (int j = tid / kCastLanes; j < nt; j += kCastGroups) {
-          const CastSlot sl = s_slot[j];
+          const Slot sl = s_slot[j];
           if (sl.nd == 0.0) continue;
           const double pp = sl.px * sl.px + sl.py * sl.py;
+          // the exact test of the slot on beams lo .. hi: the slab test on a mate's rectangle
+          auto test = [&](const int lo, const int hi) {
+            if constexpr (BODY) {
+              if (sl.mate) {
+                cast_beams_body(sl.px, sl.py, sl.c, sl.s, H, lo, hi, cb, nb, sub, s_dx, s_dy, s_min);
+                return;
+              }
+            }
+            cast_beams(sl.px, sl.py, pp, sl.r2, lo, hi, cb, nb, sub, s_dx, s_dy, s_min);
+          };
           if (sl.nd < 0.0) {
-            cast_beams(sl.px, sl.py, pp, sl.r2, 0, nr - 1, cb, nb, sub, s_dx, s_dy, s_min);
+            test(0, nr - 1);
             continue;
           }
           // the interval and its copies a turn apart; the first starts below beam 0 (flo < per)
@@ -177,7 +229,7 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
             const double s = floor(sl.flo + k * per) - 1.0;
             if (!(s <= last)) break;
             const double lo = fmax(s, 0.0), hi = fmin(s + sl.nd, last);
-            if (lo <= hi) cast_beams(sl.px, sl.py, pp, sl.r2, (int)lo, (int)hi, cb, nb, sub, s_dx, s_dy, s_min);
+            if (lo <= hi) test((int)lo, (int)hi);
           }
         }
       }
@@ -191,20 +243,20 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
 
 // Workgroup w takes cars w, w + nwg, ... below B, or with a list the cars list[w], list[w + nwg], ...
 // below min(*count, B) (plan_listed_kernel's rule: one past the count leaves at that load).
-template <bool RACE>
-__device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams& Q, const int B, const int nwg,
-                                           const int* __restrict__ list, const int* __restrict__ count,
-                                           const double* __restrict__ x, const double* __restrict__ circles,
-                                           float* __restrict__ ranges) {
+template <bool RACE, bool BODY = false>
+__device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams& Q, const BodyParams& H, const int B,
+                                           const int nwg, const int* __restrict__ list,
+                                           const int* __restrict__ count, const double* __restrict__ x,
+                                           const double* __restrict__ circles, float* __restrict__ ranges) {
   __shared__ double s_dx[kCastBeamTile];
   __shared__ double s_dy[kCastBeamTile];
   __shared__ unsigned long long s_min[kCastBeamTile];
-  __shared__ CastSlot s_slot[kCastCircleTile];
+  __shared__ typename SlotOf<BODY>::type s_slot[kCastCircleTile];
   const int n = list ? min(*count, B) : B;
   for (int k = blockIdx.x; k < n; k += nwg) {
     const int b = list ? list[k] : k;
     if (b >= 0 && b < B)  // uniform over the workgroup
-      cast_one<RACE>(P, Q, b, x, circles, ranges, s_dx, s_dy, s_min, s_slot);
+      cast_one<RACE, BODY>(P, Q, H, b, x, circles, ranges, s_dx, s_dy, s_min, s_slot);
   }
 }
 
@@ -216,7 +268,7 @@ __global__ __launch_bounds__(kCastThreads) void cast_scans_kernel(const CastPara
                                                                   const double* __restrict__ x,
                                                                   const double* __restrict__ circles,
                                                                   float* __restrict__ ranges) {
-  cast_scans<false>(P, RaceParams{}, B, nwg, list, count, x, circles, ranges);
+  cast_scans<false>(P, RaceParams{}, BodyParams{}, B, nwg, list, count, x, circles, ranges);
 }
 
 // The same with the race-mates of every car behind its circles (x is also the opponents' poses).
@@ -224,7 +276,16 @@ __global__ __launch_bounds__(kCastThreads) void cast_scans_race_kernel(
     const CastParams P, const RaceParams Q, const int B, const int nwg, const int* __restrict__ list,
     const int* __restrict__ count, const double* __restrict__ x, const double* __restrict__ circles,
     float* __restrict__ ranges) {
-  cast_scans<true>(P, Q, B, nwg, list, count, x, circles, ranges);
+  cast_scans<true>(P, Q, BodyParams{}, B, nwg, list, count, x, circles, ranges);
+}
+
+// The race cast with every mate the rectangle of body_geom.h in place of the race circle (BODY; Q.car_radius
+// is not read): phase A's slot is the mate's circumscribed circle, phase B's test the slab test.
+__global__ __launch_bounds__(kCastThreads) void cast_scans_body_kernel(
+    const CastParams P, const RaceParams Q, const BodyParams H, const int B, const int nwg,
+    const int* __restrict__ list, const int* __restrict__ count, const double* __restrict__ x,
+    const double* __restrict__ circles, float* __restrict__ ranges) {
+  cast_scans<true, true>(P, Q, H, B, nwg, list, count, x, circles, ranges);
 }
 
 // Grid: one workgroup per car up to 768. The kernel holds 155 VGPRs (the code-object metadata,
@@ -250,6 +311,23 @@ hipError_t launch_cast_scans_race(const CastParams& P, const RaceParams& Q, int 
   if (B <= 0) return hipSuccess;
   const int nwg = cast_scans_grid(B);
   hipLaunchKernelGGL(cast_scans_race_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, Q, B, nwg, list, count, x,
+                     circles, ranges);
+  return hipGetLastError();
+}
+
+// Grid: one workgroup per car up to 512. The body instantiation holds 183 VGPRs (the code-object metadata,
+// DESIGN.md 2i; no scratch), allocated in granules of eight as 184, so a SIMD keeps floor(512 / 184) = 2 of
+// its waves and a CU two of its four-wave workgroups (44,032 B of LDS each would allow three): 512 on the
+// MI355X's 256 CUs, derived as cast_scans_grid's 768 is and not from a sweep of caps.
+constexpr int kCastBodyMaxGrid = 512;
+int cast_scans_body_grid(int B) { return B < kCastBodyMaxGrid ? B : kCastBodyMaxGrid; }
+
+hipError_t launch_cast_scans_body(const CastParams& P, const RaceParams& Q, const BodyParams& H, int B, const int* list,
+                                  const int* count, const double* x, const double* circles, float* ranges,
+                                  hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  const int nwg = cast_scans_body_grid(B);
+  hipLaunchKernelGGL(cast_scans_body_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, Q, H, B, nwg, list, count, x,
                      circles, ranges);
   return hipGetLastError();
 }

@@ -135,6 +135,11 @@ EXPORTED = (
     "f110qp_default_contact_config",
     "f110qp_rollout_contact_dev",
     "f110qp_rollout_contact",
+    "f110qp_default_body_config",
+    "f110qp_clearance_body_dev",
+    "f110qp_cast_scans_body_dev",
+    "f110qp_rollout_body_dev",
+    "f110qp_rollout_body",
     "f110qp_path_lengths",
     "f110qp_progress_dev",
     "f110qp_standings_dev",
@@ -231,6 +236,13 @@ class ContactConfig(C.Structure):
     ]
 
 
+class BodyConfig(C.Structure):
+    _fields_ = [
+        ("half_length", C.c_double),
+        ("half_width", C.c_double),
+    ]
+
+
 # f110qp_gap_record (16 bytes) as a numpy record
 GAP_RECORD_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("r_lo", np.float32), ("r_hi", np.float32)])
 
@@ -305,6 +317,12 @@ def load(test: bool = False):
     L.f110qp_clearance_dev.argtypes = [wcp, rcp, C.c_int, C.c_int] + [fp] * 5
     L.f110qp_rollout_contact_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, C.c_int] + [fp] * 24
     L.f110qp_rollout_contact.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, C.c_int] + [fp] * 23
+    bcp = C.POINTER(BodyConfig)
+    L.f110qp_default_body_config.argtypes = [bcp]
+    L.f110qp_clearance_body_dev.argtypes = [wcp, rcp, bcp, C.c_int, C.c_int] + [fp] * 5
+    L.f110qp_cast_scans_body_dev.argtypes = [sp, wcp, rcp, bcp, C.c_int] + [fp] * 6
+    L.f110qp_rollout_body_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, C.c_int] + [fp] * 24
+    L.f110qp_rollout_body.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, C.c_int] + [fp] * 23
     L.f110qp_path_lengths.argtypes = [fp, C.c_int, fp]
     L.f110qp_progress_dev.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_int] + [fp] * 4
     L.f110qp_standings_dev.argtypes = [rcp, C.c_int, C.c_int, fp, C.c_double] + [fp] * 4
@@ -424,6 +442,15 @@ def default_contact_config(**over) -> ContactConfig:
     """f110qp_default_contact_config: stop_on_contact 0, margin 0.0."""
     c = ContactConfig()
     load().f110qp_default_contact_config(C.byref(c))
+    for k, v in over.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_body_config(**over) -> BodyConfig:
+    """f110qp_default_body_config: half_length 0.29, half_width 0.155."""
+    c = BodyConfig()
+    load().f110qp_default_body_config(C.byref(c))
     for k, v in over.items():
         setattr(c, k, v)
     return c
@@ -907,7 +934,7 @@ class Solver:
                           waypoints, x_ref, have_path, circles, x_traj, u_lin_traj, u_applied, status_traj,
                           iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
                           plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
-                          ranges_traj=None, stream=None, _race=None, _contact=None):
+                          ranges_traj=None, stream=None, _race=None, _contact=None, _body=None):
         """rollout_replan_dev with every tick's scan cast at that tick's pose (f110qp_rollout_world_dev): wc
         and circles [world_rows,C,3] f64 replace ranges, sc.scan_rows is not read, and the optional
         ranges_traj [T,B,num_ranges] f32 records every car's scan of every tick."""
@@ -928,6 +955,8 @@ class Solver:
                     (crash_tick, "i32", B, "crash_tick")]
             name, cfgs, tail = "f110qp_rollout_contact_dev", cfgs + [C.byref(cc)], [_tp(clear_traj), _tp(nearest_traj),
                                                                                    _tp(crash_tick)]
+            if _body is not None:  # the body config behind cc
+                name, cfgs = "f110qp_rollout_body_dev", cfgs + [C.byref(_body)]
         _devs(*self._plan_specs(rp, B, *plan), (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
               *self._traj_specs(T, B, *traj), *self._record_specs(T, B, *rec),
               (ranges_traj, "f32", T * B * int(sc.num_ranges), "ranges_traj", True), *more)
@@ -966,9 +995,23 @@ class Solver:
                                plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
                                _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick))
 
+    def rollout_body_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
+                         cc: ContactConfig, body: BodyConfig, table, waypoints, x_ref, have_path, circles, x_traj,
+                         u_lin_traj, u_applied, status_traj, clear_traj, crash_tick, nearest_traj=None, iters_traj=None,
+                         cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None, plan_status_traj=None,
+                         best_traj_traj=None, best_global_traj=None, pose_traj=None, ranges_traj=None, stream=None):
+        """rollout_contact_dev with rectangular car bodies in every cast and every clearance
+        (f110qp_rollout_body_dev): body follows cc, everything else as there."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig):
+            raise F110QPError("race must be a RaceConfig, cc a ContactConfig and body a BodyConfig")
+        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
+                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
+                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
+                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body)
+
     def rollout_world(self, x0, u_lin, circles, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
                       wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
-                      scans=False, rc=None, _race=None, _contact=None):
+                      scans=False, rc=None, _race=None, _contact=None, _body=None):
         """rollout_replan() in a world of circles (f110qp_rollout_world, synchronous): circles [C,3] (one world
         for all cars) or [B,C,3] float64 replace ranges; wc defaults to f110qp_default_world_config with
         num_circles and world_rows taken from the array. scans=True adds ranges_traj [T,B,num_ranges]."""
@@ -996,6 +1039,8 @@ class Solver:
             out["crash_tick"] = np.empty(B, np.int32)
             name, cfgs = "f110qp_rollout_contact", cfgs + [C.byref(_contact[0])]
             tail = [_p(out["clear_traj"]), _p(out.get("nearest_traj")), _p(out["crash_tick"])]
+            if _body is not None:  # the body config behind cc
+                name, cfgs = "f110qp_rollout_body", cfgs + [C.byref(_body)]
         self._chk(getattr(self.lib, name)(
             self._h, C.byref(self._ticks_config(rc, T)), C.byref(sc), C.byref(rp), C.byref(w),
             *cfgs, B, _p(tab), _p(wp) if wp.shape[0] else None, _p(xr), _p(hv),
@@ -1021,6 +1066,15 @@ class Solver:
             raise F110QPError("race must be a RaceConfig and cc a ContactConfig")
         return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
                                   objective, rows, scans, rc, _race=race, _contact=(cc, nearest))
+
+    def rollout_body(self, x0, u_lin, circles, race: RaceConfig, cc: ContactConfig, body: BodyConfig, sc: ScanConfig,
+                     rp: ReplanConfig, table, waypoints, ticks, wc: WorldConfig = None, x_ref=None, have_path=None,
+                     plans=False, objective=False, rows=True, scans=False, nearest=True, rc=None):
+        """rollout_contact() with rectangular car bodies (f110qp_rollout_body, synchronous)."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig):
+            raise F110QPError("race must be a RaceConfig, cc a ContactConfig and body a BodyConfig")
+        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
+                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body)
 
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
@@ -1294,6 +1348,48 @@ def clearance_dev(wc: WorldConfig, race: RaceConfig, x, circles, clearance, near
         stream = torch.cuda.current_stream(x.device)
     _check(load().f110qp_clearance_dev(C.byref(wc), C.byref(race), B, rows, _tp(x), _tp(circles), _tp(clearance),
                                        _tp(nearest), C.c_void_p(stream.cuda_stream)), "f110qp_clearance_dev")
+
+
+def cast_scans_body_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, x, circles, ranges,
+                        list_=None, count=None, stream=None):
+    """cast_scans_race_dev with every race-mate a rectangle (f110qp_cast_scans_body_dev)."""
+    import torch
+
+    if not isinstance(body, BodyConfig):
+        raise F110QPError("body must be a BodyConfig")
+    B, Cn, WR = int(x.shape[0]), int(wc.num_circles), int(wc.world_rows)
+    _check_race(race, B)
+    _devs((x, "f64", 3 * B, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
+          (ranges, "f32", B * int(sc.num_ranges), "ranges"), (list_, "i32", B, "list", True),
+          (count, "i32", 1, "count", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_cast_scans_body_dev(C.byref(sc), C.byref(wc), C.byref(race), C.byref(body), B, _tp(list_),
+                                             _tp(count), _tp(x), _tp(circles), _tp(ranges),
+                                             C.c_void_p(stream.cuda_stream)), "f110qp_cast_scans_body_dev")
+
+
+def clearance_body_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, x, circles, clearance, nearest=None,
+                       stream=None):
+    """clearance_dev with the car and its race-mates rectangles (f110qp_clearance_body_dev)."""
+    import torch
+
+    if not isinstance(body, BodyConfig):
+        raise F110QPError("body must be a BodyConfig")
+    if x.dim() not in (2, 3) or x.shape[-1] != 3:
+        raise F110QPError(f"x must be [rows, B, 3] or [B, 3], got {tuple(x.shape)}")
+    rows, B = (1, int(x.shape[0])) if x.dim() == 2 else (int(x.shape[0]), int(x.shape[1]))
+    if rows < 1:
+        raise F110QPError("x must hold at least one row")
+    Cn, WR = int(wc.num_circles), int(wc.world_rows)
+    _check_race(race, B)
+    _devs((x, "f64", 3 * B * rows, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
+          (clearance, "f64", B * rows, "clearance"), (nearest, "i32", B * rows, "nearest", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_clearance_body_dev(C.byref(wc), C.byref(race), C.byref(body), B, rows, _tp(x), _tp(circles),
+                                            _tp(clearance), _tp(nearest), C.c_void_p(stream.cuda_stream)),
+           "f110qp_clearance_body_dev")
 
 
 def _rows_of(x, last, name):

@@ -379,6 +379,148 @@ def clearance(x, circles, group_size: int = 1, car_radius: float = 0.3, center_o
     return (clear[0], near[0]) if one else (clear, near)
 
 
+# ---- rectangular car bodies (f110qp_clearance_body_dev, f110qp_cast_scans_body_dev) ------------------------
+# The model of include/f110qp.h "rectangular car bodies" in numpy, in csrc/body_geom.h's expressions and order.
+# np.fmin / np.fmax are the kernels' fmin / fmax (of a NaN and a number: the number).
+
+HALF_LENGTH, HALF_WIDTH = 0.29, 0.155  # f110qp_default_body_config
+
+
+def body_sd(px, py, qx, qy, c, s, hl, hw):
+    """Signed distance of the points (px, py) to the rectangles (centre (qx, qy), axes (c, s), half extents
+    (hl, hw)): rule 1, negative inside, a NaN in gives a NaN out."""
+    dx, dy = px - qx, py - qy
+    u = dx * c + dy * s
+    w = dy * c - dx * s
+    au, aw = np.abs(u) - hl, np.abs(w) - hw
+    ex, ey = np.where(au < 0.0, 0.0, au), np.where(aw < 0.0, 0.0, aw)
+    return np.where((au <= 0.0) & (aw <= 0.0), np.fmax(au, aw), np.sqrt(ex * ex + ey * ey))
+
+
+def _body_corner_min(ax, ay, ac, as_, bx, by, bc, bs, hl, hw):
+    fx, fy = hl * ac, hl * as_
+    lx, ly = hw * as_, hw * ac
+    v0 = body_sd((ax + fx) - lx, (ay + fy) + ly, bx, by, bc, bs, hl, hw)
+    v1 = body_sd((ax + fx) + lx, (ay + fy) - ly, bx, by, bc, bs, hl, hw)
+    v2 = body_sd((ax - fx) - lx, (ay - fy) + ly, bx, by, bc, bs, hl, hw)
+    v3 = body_sd((ax - fx) + lx, (ay - fy) - ly, bx, by, bc, bs, hl, hw)
+    return np.fmin(np.fmin(v0, v1), np.fmin(v2, v3))
+
+
+def body_pair(bx, by, bc, bs, mx, my, mc, ms, hl, hw):
+    """Rectangle b against rectangle m (rule 3): the largest separating-axis gap when it is <= 0, otherwise the
+    least of the eight corner distances. The same bits with b and m swapped."""
+    dx, dy = mx - bx, my - by
+    cc = np.abs(bc * mc + bs * ms)
+    cr = np.abs(mc * bs - ms * bc)
+    el = hl * cc + hw * cr
+    ew = hl * cr + hw * cc
+    gfb = (np.abs(dx * bc + dy * bs) - hl) - el
+    glb = (np.abs(dy * bc - dx * bs) - hw) - ew
+    gfm = (np.abs(dx * mc + dy * ms) - hl) - el
+    glm = (np.abs(dy * mc - dx * ms) - hw) - ew
+    g = np.fmax(np.fmax(gfb, gfm), np.fmax(glb, glm))
+    far = np.fmin(_body_corner_min(mx, my, mc, ms, bx, by, bc, bs, hl, hw),
+                  _body_corner_min(bx, by, bc, bs, mx, my, mc, ms, hl, hw))
+    return np.where(g <= 0.0, g, far)
+
+
+def _mates(B, G):
+    """[B, G - 1]: the cars of b's race in the order of the car index, the own car left out."""
+    own = np.arange(B) % G
+    k = np.arange(G - 1)[None, :]
+    return (np.arange(B) - own)[:, None] + k + (k >= own[:, None])
+
+
+def clearance_body(x, circles, group_size: int = 1, center_offset: float = 0.1651, half_length: float = HALF_LENGTH,
+                   half_width: float = HALF_WIDTH):
+    """f110qp_clearance_body_dev in numpy, the device kernel's expressions in its order: clearance() with the car
+    and its race-mates rectangles. Poses x [rows, B, 3] (or [B, 3]) in circles [C, 3], [B, C, 3] or None ->
+    (clearance [rows, B] float64, nearest [rows, B] int32)."""
+    x = np.asarray(x, np.float64)
+    one = x.ndim == 2
+    x = x[None] if one else x
+    rows, B = x.shape[:2]
+    G, hl, hw = int(group_size), float(half_length), float(half_width)
+    if G < 1 or B % G:
+        raise ValueError(f"group_size must be >= 1 and divide B = {B}, got {G}")
+    ci = np.zeros((0, 3)) if circles is None else np.asarray(circles, np.float64)
+    Cn = ci.shape[-2]
+    own = np.arange(B) % G
+    k = np.arange(G - 1)[None, :]
+    mate_idx = Cn + k + (k >= own[:, None])
+    mate = _mates(B, G)
+    clear = np.full((rows, B), np.inf)
+    near = np.full((rows, B), -1, np.int32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r in range(rows):
+            c, s = np.cos(x[r, :, 2]), np.sin(x[r, :, 2])
+            qx, qy = x[r, :, 0] + center_offset * c, x[r, :, 1] + center_offset * s
+            cw = np.broadcast_to(ci, (B, Cn, 3)) if ci.ndim == 2 else ci
+            v = body_sd(cw[:, :, 0], cw[:, :, 1], qx[:, None], qy[:, None], c[:, None], s[:, None], hl, hw) \
+                - np.abs(cw[:, :, 2])
+            idx = np.broadcast_to(np.arange(Cn)[None, :], (B, Cn))
+            if G > 1:
+                vm = body_pair(qx[:, None], qy[:, None], c[:, None], s[:, None], qx[mate], qy[mate], c[mate], s[mate],
+                               hl, hw)
+                v = np.concatenate([v, vm], 1)
+                idx = np.concatenate([idx, mate_idx], 1)
+            if v.shape[1] == 0:
+                continue
+            v = np.where(np.isnan(v), np.inf, v)
+            a = np.argmin(v, axis=1)                             # the first of equal values: the lowest index
+            best = v[np.arange(B), a]
+            hit = best < np.inf
+            clear[r] = np.where(hit, best, np.inf)
+            near[r] = np.where(hit, idx[np.arange(B), a], -1)
+    return (clear[0], near[0]) if one else (clear, near)
+
+
+def body_slab(of, ol, c, s, dx, dy, hl, hw):
+    """The slab test of rule 5 on broadcastable arrays: (th, hit)."""
+    def axis(o, d, h):
+        zero = d == 0.0
+        dd = np.where(zero, 1.0, d)                              # no 0 / 0: the d == 0 lanes are replaced below
+        t1, t2 = (-h - o) / dd, (h - o) / dd
+        inside = np.abs(o) <= h
+        lo = np.where(zero, np.where(inside, -np.inf, np.inf), np.fmin(t1, t2))
+        hi = np.where(zero, np.where(inside, np.inf, -np.inf), np.fmax(t1, t2))
+        return lo, hi
+    lo_f, hi_f = axis(of, dx * c + dy * s, hl)
+    lo_l, hi_l = axis(ol, dy * c - dx * s, hw)
+    th = np.fmax(lo_f, lo_l)
+    return th, (th <= np.fmin(hi_f, hi_l)) & (th > 0.0)
+
+
+def ray_bodies(x, geom, beams, group_size, center_offset: float = 0.1651, half_length: float = HALF_LENGTH,
+               half_width: float = HALF_WIDTH, lidar_offset: float = 0.275, max_range: float = 10.0):
+    """The opponents' part of f110qp_cast_scans_body_dev in numpy: ranges [B, beams] float64 of every car's beams
+    against the rectangles of its race-mates at the poses x [B, 3] (geom = (angle_min, angle_increment, ...) as
+    float32), max_range where nothing is hit. The scan is np.minimum of this and the static circles' ranges
+    (_ray_circles) before the cast to float32. An opponent with a non-finite pose hits nothing."""
+    x = np.asarray(x, np.float64)
+    B, G, hl, hw = x.shape[0], int(group_size), float(half_length), float(half_width)
+    if G < 1 or B % G:
+        raise ValueError(f"group_size must be >= 1 and divide B = {B}, got {G}")
+    out = np.full((B, beams), float(max_range))
+    if G == 1:
+        return out
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        c, s = np.cos(x[:, 2]), np.sin(x[:, 2])
+        ox, oy = x[:, 0] + lidar_offset * c, x[:, 1] + lidar_offset * s
+        qx, qy = x[:, 0] + center_offset * c, x[:, 1] + center_offset * s
+        ang = x[:, 2:3] + (np.float64(geom[0]) + np.float64(geom[1]) * np.arange(beams, dtype=np.float64))[None, :]
+        dx, dy = np.cos(ang)[:, :, None], np.sin(ang)[:, :, None]          # [B, R, 1]
+        mate = _mates(B, G)
+        px, py = qx[mate] - ox[:, None], qy[mate] - oy[:, None]           # [B, G - 1]
+        cm, sm = c[mate], s[mate]
+        of, ol = -(px * cm + py * sm), -(py * cm - px * sm)
+        ok = np.isfinite(x[mate]).all(axis=2) & np.isfinite(x).all(axis=1)[:, None]
+        th, hit = body_slab(of[:, None, :], ol[:, None, :], cm[:, None, :], sm[:, None, :], dx, dy, hl, hw)
+        th = np.where(hit & ok[:, None, :], th, np.inf)
+        return np.minimum(th.min(axis=2), out)
+
+
 # ---- race standings (f110qp_path_lengths, f110qp_progress_dev, f110qp_standings_dev) ------------------------
 
 def path_lengths(wp) -> np.ndarray:

@@ -1026,6 +1026,99 @@ int f110qp_rollout_contact(f110qp_ctx* ctx, const f110qp_rollout_config* rc, con
                            int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
                            int* nearest_traj, int* crash_tick);
 
+/* ---- rectangular car bodies: clearance, opponents in the LiDAR, rollout ---------------------------------
+ * The race and contact calls above model a car as a circle of radius 0.3 m: twice as wide as the 0.58 x 0.31 m
+ * car. The calls below take the car as an oriented rectangle, as the f1tenth simulator the reference runs in
+ * does; they sit next to the circle calls, which keep their bits. Additive: F110QP_API_VERSION stays 6.
+ *
+ * The rectangle of the car at pose (x, y, ori): centre q = (x + off cos(ori), y + off sin(ori)) with off =
+ * race->center_offset (the LiDAR origin's and the race circle's expressions, one sincos(double)), axes
+ * f = (cos, sin) and l = (-sin, cos), half extents hl = half_length along f and hw = half_width along l.
+ * race->car_radius is checked as before and not read.
+ * Arithmetic: all fp64, every product and sum rounded (no fused multiply-add), the correctly rounded square
+ * root, in the expression order written here. min and max of a NaN and a number give the number (fmin, fmax).
+ *
+ * 1. Point against rectangle, sd(p; q, f, hl, hw): d = p - q, u = d.x f.x + d.y f.y, w = d.y f.x - d.x f.y,
+ *    au = |u| - hl, aw = |w| - hw. If au <= 0 and aw <= 0: sd = max(au, aw) (negative inside). Otherwise
+ *    ex = (au < 0 ? 0 : au), ey = (aw < 0 ? 0 : aw), sd = sqrt(ex ex + ey ey): a NaN au or aw stays a NaN.
+ * 2. Body against a static circle (cx, cy, r): v = sd(c; body) - |r|.
+ * 3. Body b against race-mate m at the same row, with d = q_m - q_b, cc = |f_b.x f_m.x + f_b.y f_m.y| and
+ *    cr = |f_m.x f_b.y - f_m.y f_b.x|, el = hl cc + hw cr and ew = hl cr + hw cc (the other car's extent on an
+ *    f axis and on an l axis): the separating-axis gaps
+ *      g_fb = (|d.f_b| - hl) - el, g_lb = (|d.l_b| - hw) - ew, g_fm = (|d.f_m| - hl) - el,
+ *      g_lm = (|d.l_m| - hw) - ew     (d.f and d.l as u and w above),
+ *    g = max(max(g_fb, g_fm), max(g_lb, g_lm)). If g <= 0 the rectangles touch or overlap and v = g (-g is
+ *    the penetration depth). Otherwise v = min(cm(m, b), cm(b, m)), cm(A, B) = the least sd against B of the
+ *    four corners of A, ((q.x + hl f.x) - hw f.y, (q.y + hl f.y) + hw f.x), ((q.x + hl f.x) + hw f.y,
+ *    (q.y + hl f.y) - hw f.x), ((q.x - hl f.x) - hw f.y, (q.y - hl f.y) + hw f.x), ((q.x - hl f.x) + hw f.y,
+ *    (q.y - hl f.y) - hw f.x), folded min(min(v0, v1), min(v2, v3)): the distance of two disjoint convex
+ *    polygons is attained at a vertex of one of them, so this is the exact distance.
+ *    Swapping b and m negates d and the cross term exactly and leaves cc's products as they are; the eight
+ *    corner terms are the same function with the roles swapped: v is bit-identical in both directions.
+ * 4. Clearance and nearest follow f110qp_clearance_dev rule for rule: index j for a circle, C + i for the mate
+ *    with index i inside the race; a candidate replaces the running minimum only on v < best, or v == best with
+ *    a lower index, from (+inf, -1); a NaN v is never chosen; a car with a non-finite pose keeps (+inf, -1); a
+ *    negative radius acts as |r|; bit-identical for every order of the circles and of the race's cars.
+ * 5. LiDAR, a beam along (dx, dy) from the origin o against the rectangle of mate m (a slab test in the
+ *    mate's frame): p = q_m - o, o' = (-(p.f_m), -(p.l_m)), d' = (d.f_m, d.l_m). Per axis a with half extent h:
+ *    when d'_a != 0, t1 = (-h - o'_a) / d'_a, t2 = (h - o'_a) / d'_a and the axis contributes
+ *    [min(t1, t2), max(t1, t2)]; when d'_a == 0 it contributes (-inf, +inf) if |o'_a| <= h and a miss
+ *    otherwise. th = the larger of the two lower ends; a hit when th <= the smaller of the two upper ends and
+ *    th > 0, so a LiDAR inside an opponent's rectangle sees through it, as with a circle. An opponent with a
+ *    non-finite pose hits nothing. range = (float)min(min over the static circles of th (the test of
+ *    f110qp_cast_scans_dev, unchanged), min over the mates of th, max_range): per (beam, obstacle) pair the
+ *    value depends on nothing else, so the result is bit-identical for every order of circles and cars. */
+typedef struct {
+  double half_length;  /* 0.29  (0.58 m car), finite, > 0 */
+  double half_width;   /* 0.155 (0.31 m car), finite, > 0 */
+} f110qp_body_config;
+
+/* Zeroes *body, then half_length 0.29, half_width 0.155. */
+void f110qp_default_body_config(f110qp_body_config* body);
+
+/* f110qp_clearance_dev for rectangular bodies (rules 1 to 4; one launch): arguments and rules of that call.
+ * F110QP_ERR_INVALID before any HIP call: every rule of f110qp_clearance_dev, a NULL body, a non-finite or
+ * non-positive half_length or half_width. Workgroups stride over the cars, at most min(batch, 512) of them. */
+int f110qp_clearance_body_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
+                              const f110qp_body_config* body, int batch, int rows, const double* x,
+                              const double* circles, double* clearance, int* nearest, void* stream);
+
+/* f110qp_cast_scans_race_dev with every race-mate the rectangle of rule 5 in place of the race circle (one
+ * launch): arguments, list / count rules and errors of that call, plus the body rules above. The static circles
+ * keep f110qp_cast_scans_dev's test; group_size 1 gives that call's bits. At most min(batch, 512) workgroups. */
+int f110qp_cast_scans_body_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
+                               const f110qp_race_config* race, const f110qp_body_config* body, int batch,
+                               const int* list, const int* count, const double* x, const double* circles,
+                               float* ranges, void* stream);
+
+/* f110qp_rollout_contact_dev with every cast f110qp_cast_scans_body_dev's and every clearance launch
+ * f110qp_clearance_body_dev's: clear_traj row t is f110qp_clearance_body_dev at x_traj row t. Everything else
+ * is that call's: arguments (body follows cc), launch count, stream order, no host synchronisation, read-back
+ * or allocation inside the loop, parking at stop_on_contact = 1, and every argument checked before the first
+ * launch (that call's checks and the body rules). With group_size 1 every array but clear_traj, nearest_traj
+ * and crash_tick is bit-identical to f110qp_rollout_contact_dev's at stop_on_contact = 0. */
+int f110qp_rollout_body_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                            const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                            const f110qp_race_config* race, const f110qp_contact_config* cc,
+                            const f110qp_body_config* body, int batch, const double* table,
+                            const double* waypoints, double* x_ref, int* have_path, const double* circles,
+                            double* x_traj, double* u_lin_traj, float* u_applied, int* status_traj,
+                            int* iters_traj, double* cost_traj, float* u_plan, float* x_plan, float* hs_traj,
+                            int* kind_traj, int* plan_status_traj, int* best_traj_traj, int* best_global_traj,
+                            double* pose_traj, float* ranges_traj, double* clear_traj, int* nearest_traj,
+                            int* crash_tick, void* stream);
+
+/* Same on host pointers (synchronous), staged as f110qp_rollout_contact. */
+int f110qp_rollout_body(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                        const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                        const f110qp_race_config* race, const f110qp_contact_config* cc,
+                        const f110qp_body_config* body, int batch, const double* table, const double* waypoints,
+                        double* x_ref, int* have_path, const double* circles, double* x_traj,
+                        double* u_lin_traj, float* u_applied, int* status_traj, int* iters_traj,
+                        double* cost_traj, float* u_plan, float* x_plan, float* hs_traj, int* kind_traj,
+                        int* plan_status_traj, int* best_traj_traj, int* best_global_traj, double* pose_traj,
+                        float* ranges_traj, double* clear_traj, int* nearest_traj, int* crash_tick);
+
 /* ---- race standings: progress along the track, laps and positions ---------------------------------------
  * The calls above return poses; the calls below say who is ahead. They run after the fact on x_traj, or on any
  * [rows][B][3] pose array: nothing inside a closed loop reads a standing, so there is no rollout family of
