@@ -3,7 +3,8 @@
 // (f110qp_rollout_scan[_dev]), with re-planning (f110qp_rollout_replan[_dev]), in a world of circles
 // (f110qp_rollout_world[_dev]), with race-mates (f110qp_rollout_race[_dev]) and with contact
 // (f110qp_clearance_dev, f110qp_rollout_contact[_dev]) and with rectangular bodies (f110qp_clearance_body_dev,
-// f110qp_cast_scans_body_dev, f110qp_rollout_body[_dev]), and the parts of each.
+// f110qp_cast_scans_body_dev, f110qp_rollout_body[_dev]) and with straight walls (f110qp_cast_scans_walls_dev,
+// f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]), and the parts of each.
 // Host-side responsibilities only: argument validation, workspaces, H2D/D2H of the host-pointer calls
 // (the staging table of api_stage.h). No C++ exception crosses this boundary.
 #include <cmath>
@@ -114,6 +115,22 @@ static int body_params(const f110qp_body_config* body, f110qp::BodyParams* H) {
   return F110QP_OK;
 }
 
+// The straight walls of f110qp_cast_scans_walls_dev, f110qp_clearance_walls_dev and f110qp_rollout_walls[_dev],
+// checked, into *Wl. obstacles: num_circles + group_size - 1, which race_params has checked to fit an int.
+static int wall_params(const f110qp_walls_config* walls, int batch, long long obstacles, const void* segments,
+                       f110qp::WallParams* Wl) {
+  if (!walls) return fail(F110QP_ERR_INVALID, "walls config is NULL");
+  if (walls->num_segments < 0) return fail(F110QP_ERR_INVALID, "num_segments < 0");
+  if (walls->wall_rows != 1 && walls->wall_rows != batch)
+    return fail(F110QP_ERR_INVALID, "wall_rows must be 1 or batch");
+  if (walls->num_segments > 0 && !segments) return fail(F110QP_ERR_INVALID, "num_segments > 0 needs the segments");
+  if (obstacles + 1 + walls->num_segments > 0x7fffffffll)
+    return fail(F110QP_ERR_INVALID, "num_circles + group_size + num_segments does not fit an int");
+  Wl->S = walls->num_segments;
+  Wl->wall_rows = walls->wall_rows;
+  return F110QP_OK;
+}
+
 // The scan geometry of the re-planning kernels' argument records (ReplanStart, ReplanStep).
 template <typename S>
 static void scan_geometry(S* s, const f110qp_scan_config& sc) {
@@ -127,8 +144,9 @@ static void scan_geometry(S* s, const f110qp_scan_config& sc) {
 // The family of a rollout call, in the order each was built on the one before: from kScan a scan
 // config is read, from kReplan the loop re-plans, from kWorld the scans are cast (so neither `ranges`
 // nor sc->scan_rows is read), kRace casts see the race-mates, kContact records every row's clearance,
-// and kBody is kContact with rectangular bodies in every cast and clearance.
-enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact, kBody };
+// kBody is kContact with rectangular bodies in every cast and clearance, and kWalls is kBody with straight wall
+// segments next to the circles.
+enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact, kBody, kWalls };
 
 // The configs of a rollout call as the caller gave them and, once check_args has passed, the
 // kernels' parameters.
@@ -279,6 +297,9 @@ struct WorldLoop {
   f110qp::RaceParams Q;
   bool body;  // f110qp_rollout_body[_dev]: the mates are rectangles, in the casts and in the clearances
   f110qp::BodyParams H;
+  bool walls;  // f110qp_rollout_walls[_dev]: the body family with the segments in the casts and the clearances
+  f110qp::WallParams Wl;
+  const double* segments;  // [wall_rows][S][4] or null
 };
 
 // f110qp_rollout_contact[_dev]: the race rollout with one clearance launch per row of x_traj, which also
@@ -291,6 +312,9 @@ struct ContactLoop {
 
 static hipError_t world_cast(const WorldLoop& wl, int batch, const int* list, const int* count, const double* x,
                              float* ranges, hipStream_t s) {
+  if (wl.walls)
+    return f110qp::launch_cast_scans_walls(wl.P, wl.Q, wl.H, wl.Wl, batch, list, count, x, wl.circles, wl.segments,
+                                           ranges, s);
   if (wl.body) return f110qp::launch_cast_scans_body(wl.P, wl.Q, wl.H, batch, list, count, x, wl.circles, ranges, s);
   return wl.race ? f110qp::launch_cast_scans_race(wl.P, wl.Q, batch, list, count, x, wl.circles, ranges, s)
                  : f110qp::launch_cast_scans(wl.P, batch, list, count, x, wl.circles, ranges, s);
@@ -381,6 +405,9 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
     const f110qp::ClearParams cp{wl->P.C, wl->P.world_rows};
     const f110qp::ContactMark mk{cl->io.crash_tick, (int)t, t == 0, cl->margin};
     int* near = cl->io.nearest_traj ? cl->io.nearest_traj + t * B : nullptr;
+    if (wl->walls)
+      return f110qp::launch_clearance_walls(cp, wl->Q, wl->H, wl->Wl, io.B, 1, io.x(t), wl->circles, wl->segments,
+                                            cl->io.clear_traj + t * B, near, mk, s);
     return wl->body ? f110qp::launch_clearance_body(cp, wl->Q, wl->H, io.B, 1, io.x(t), wl->circles,
                                                     cl->io.clear_traj + t * B, near, mk, s)
                     : f110qp::launch_clearance(cp, wl->Q, io.B, 1, io.x(t), wl->circles, cl->io.clear_traj + t * B,
@@ -512,7 +539,9 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
   ReplanIO dr;
   WorldIO hw{}, dw{};
   ContactLoop dcl{};
-  if (wl) hw = WorldIO{wl->circles, (size_t)wl->P.world_rows * (size_t)wl->P.C * 3 * 8, wl->ranges_traj};
+  if (wl)
+    hw = WorldIO{wl->circles, (size_t)wl->P.world_rows * (size_t)wl->P.C * 3 * 8, wl->ranges_traj, wl->segments,
+                 wl->walls ? (size_t)wl->Wl.wall_rows * (size_t)wl->Wl.S * 4 * 8 : 0};
   if (cl) dcl = *cl;
   stage::replan_fields(L, io, &d, r, &dr, *cfg.sc, (size_t)cfg.K.T, (size_t)cfg.K.P, (size_t)cfg.rp->num_waypoints,
                        wl ? &hw : nullptr, &dw, cl ? &cl->io : nullptr, &dcl.io);
@@ -522,6 +551,7 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
     dwl = *wl;
     dwl.circles = dw.circles;
     dwl.ranges_traj = dw.ranges_traj;
+    dwl.segments = dw.segments;
   }
   if ((rv = replan_ticks(c, cfg, d, dr, s, wl ? &dwl : nullptr, cl ? &dcl : nullptr))) return rv;
   return stage_out(c, L, s);
@@ -548,11 +578,13 @@ static int replan_call(f110qp_ctx* c, LoopCfg cfg, RolloutIO io, const ReplanIO&
 }
 
 // f110qp_rollout_world[_dev] (kWorld; race not read), f110qp_rollout_race[_dev] (kRace) and
-// f110qp_rollout_contact[_dev] (kContact: cc and the records k) and f110qp_rollout_body[_dev] (kBody: body too).
+// f110qp_rollout_contact[_dev] (kContact: cc and the records k), f110qp_rollout_body[_dev] (kBody: body too) and
+// f110qp_rollout_walls[_dev] (kWalls: walls and segments too).
 static int world_call(f110qp_ctx* c, LoopCfg cfg, const f110qp_world_config* wc, const f110qp_race_config* race,
                       RolloutIO io, const ReplanIO& r, const double* circles, float* rgt, Where w,
                       const f110qp_contact_config* cc = nullptr, const ContactIO* k = nullptr,
-                      const f110qp_body_config* body = nullptr) {
+                      const f110qp_body_config* body = nullptr, const f110qp_walls_config* walls = nullptr,
+                      const double* segments = nullptr) {
   WorldLoop wl{};
   int rv = check_args(c, &cfg, &io, nullptr, nullptr, &r);
   if (rv) return rv;
@@ -561,8 +593,12 @@ static int world_call(f110qp_ctx* c, LoopCfg cfg, const f110qp_world_config* wc,
   if (wl.race && (rv = race_params(race, io.B, wc->num_circles, &wl.Q))) return rv;
   const bool contact = cfg.fam >= kContact;
   if (contact && (rv = contact_params(cc))) return rv;
-  wl.body = cfg.fam == kBody;
+  wl.body = cfg.fam >= kBody;
   if (wl.body && (rv = body_params(body, &wl.H))) return rv;
+  wl.walls = cfg.fam == kWalls;
+  if (wl.walls && (rv = wall_params(walls, io.B, (long long)wc->num_circles + race->group_size - 1, segments, &wl.Wl)))
+    return rv;
+  wl.segments = wl.walls ? segments : nullptr;
   if (io.B == 0) return F110QP_OK;
   if (contact && (!k->clear_traj || !k->crash_tick))
     return fail(F110QP_ERR_INVALID, "clear_traj/crash_tick must be non-NULL");
@@ -1071,6 +1107,95 @@ int f110qp_rollout_body(f110qp_ctx* c, const f110qp_rollout_config* rc, const f1
   const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
   const ContactIO k{clt, nrt, crash};
   return world_call(c, LoopCfg{kBody, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k, body);
+}
+
+// ---- straight walls (f110qp_cast_scans_walls_dev, f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]) ------
+
+void f110qp_default_walls_config(f110qp_walls_config* walls) {
+  if (!walls) return;
+  std::memset(walls, 0, sizeof(*walls));
+  walls->wall_rows = 1;
+}
+
+int f110qp_cast_scans_walls_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
+                                const f110qp_race_config* race, const f110qp_body_config* body,
+                                const f110qp_walls_config* walls, int batch, const int* list, const int* count,
+                                const double* x, const double* circles, const double* segments, float* ranges,
+                                void* stream) {
+  int rv = check_scan_config(sc, false, 0);
+  if (rv) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  f110qp::CastParams P;
+  f110qp::RaceParams Q;
+  f110qp::BodyParams H;
+  f110qp::WallParams Wl;
+  if ((rv = world_params(sc, wc, batch, circles, &P))) return rv;
+  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
+  if ((rv = body_params(body, &H))) return rv;
+  if ((rv = wall_params(walls, batch, (long long)wc->num_circles + race->group_size - 1, segments, &Wl))) return rv;
+  if ((list != nullptr) != (count != nullptr))
+    return fail(F110QP_ERR_INVALID, "list and count must be given together");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !ranges) return fail(F110QP_ERR_INVALID, "x/ranges must be non-NULL");
+  const hipError_t e = f110qp::launch_cast_scans_walls(P, Q, H, Wl, batch, list, count, x, circles, segments, ranges,
+                                                       (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "walls scan cast launch");
+  return F110QP_OK;
+}
+
+int f110qp_clearance_walls_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
+                               const f110qp_body_config* body, const f110qp_walls_config* walls, int batch, int rows,
+                               const double* x, const double* circles, const double* segments, double* clearance,
+                               int* nearest, void* stream) {
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  f110qp::CastParams P;
+  f110qp::RaceParams Q;
+  f110qp::BodyParams H;
+  f110qp::WallParams Wl;
+  int rv = world_params(nullptr, wc, batch, circles, &P);
+  if (rv) return rv;
+  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
+  if ((rv = body_params(body, &H))) return rv;
+  if ((rv = wall_params(walls, batch, (long long)wc->num_circles + race->group_size - 1, segments, &Wl))) return rv;
+  if (rows < 1) return fail(F110QP_ERR_INVALID, "rows must be >= 1");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !clearance) return fail(F110QP_ERR_INVALID, "x/clearance must be non-NULL");
+  if ((long long)rows * batch > (1ll << 30)) return fail(F110QP_ERR_INVALID, "rows x batch too large");
+  const hipError_t e = f110qp::launch_clearance_walls(f110qp::ClearParams{P.C, P.world_rows}, Q, H, Wl, batch, rows, x,
+                                                      circles, segments, clearance, nearest,
+                                                      f110qp::ContactMark{nullptr, 0, 0, 0.0}, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "walls clearance launch");
+  return F110QP_OK;
+}
+
+int f110qp_rollout_walls_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                             const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                             const f110qp_race_config* race, const f110qp_contact_config* cc,
+                             const f110qp_body_config* body, const f110qp_walls_config* walls, int batch,
+                             const double* table, const double* wp, double* xr, int* have, const double* circles,
+                             const double* segments, double* xt, double* ult, float* ua, int* stt, int* itt,
+                             double* cot, float* up, float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt,
+                             double* poset, float* rgt, double* clt, int* nrt, int* crash, void* stream) {
+  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
+  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
+  const ContactIO k{clt, nrt, crash};
+  return world_call(c, LoopCfg{kWalls, rc, sc, rp}, wc, race, io, r, circles, rgt, on_stream(stream), cc, &k, body,
+                    walls, segments);
+}
+
+int f110qp_rollout_walls(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                         const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                         const f110qp_race_config* race, const f110qp_contact_config* cc,
+                         const f110qp_body_config* body, const f110qp_walls_config* walls, int batch,
+                         const double* table, const double* wp, double* xr, int* have, const double* circles,
+                         const double* segments, double* xt, double* ult, float* ua, int* stt, int* itt, double* cot,
+                         float* up, float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset,
+                         float* rgt, double* clt, int* nrt, int* crash) {
+  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
+  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
+  const ContactIO k{clt, nrt, crash};
+  return world_call(c, LoopCfg{kWalls, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k, body, walls,
+                    segments);
 }
 
 }  // extern "C"

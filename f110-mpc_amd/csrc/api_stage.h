@@ -67,6 +67,9 @@ struct WorldIO {
   const double* circles;  // [world_rows][C][3] or null
   size_t circle_bytes;    // 0: no circles
   float* ranges_traj;     // [T][B][num_ranges] or null
+  // the walls family's, trailing so that three initialisers still make a WorldIO
+  const double* segments;  // [wall_rows][S][4] or null
+  size_t segment_bytes;    // 0: no segments
 };
 
 // What the contact rollout records on top of the race rollout's arrays.
@@ -95,7 +98,7 @@ struct Field {
 };
 
 struct Layout {
-  static constexpr int kMaxFields = 24;
+  static constexpr int kMaxFields = 32;  // the walls family declares 25
   Field f[kMaxFields];
   int n = 0;
   size_t total = 0;  // bytes of the staging buffer: the end of the last field
@@ -151,7 +154,8 @@ inline void rollout_fields(Layout& L, const RolloutIO& h, RolloutIO* d, size_t x
 
 // f110qp_rollout_replan (w null: r.ranges read) and f110qp_rollout_world / _race (w: its circles staged
 // in, its ranges_traj, when given, copied back) and f110qp_rollout_contact (w and k: its three records,
-// every row of them the device's). table_rows = steer_discrete + 1.
+// every row of them the device's); the walls family's segments (w->segment_bytes > 0) are staged in behind the
+// circles. table_rows = steer_discrete + 1.
 inline void replan_fields(Layout& L, const RolloutIO& h, RolloutIO* d, const ReplanIO& r, ReplanIO* dr,
                           const f110qp_scan_config& sc, size_t table_rows, size_t xr_points, size_t num_waypoints,
                           const WorldIO* w, WorldIO* dw, const ContactIO* k = nullptr, ContactIO* dk = nullptr) {
@@ -171,6 +175,7 @@ inline void replan_fields(Layout& L, const RolloutIO& h, RolloutIO* d, const Rep
   if (!w) return;
   *dw = *w;
   L.add(w->circles, &dw->circles, w->circle_bytes, true, kIn);
+  L.add(w->segments, &dw->segments, w->segment_bytes, true, kIn);
   L.add(w->ranges_traj, &dw->ranges_traj, TB * nr * 4, w->ranges_traj, kOut);
   if (!k) return;
   *dk = *k;

@@ -28,6 +28,7 @@
 
 #include "body_geom.h"
 #include "f110qp_kernels.h"
+#include "wall_geom.h"
 
 namespace f110qp {
 
@@ -289,6 +290,140 @@ hipError_t launch_clearance_body(const ClearParams& P, const RaceParams& Q, cons
   const int nwg = clearance_body_grid(B);
   hipLaunchKernelGGL(clearance_body_kernel, dim3(nwg), dim3(kClearThreads), 0, s, P, Q, H, B, rows, nwg, x, circles,
                      clearance, nearest, M);
+  return hipGetLastError();
+}
+
+// ---- straight walls (f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]) -----------------------------
+// clearance_body_kernel with the S segments of wall_geom.h as a third stretch of the obstacle list: index j in
+// [C + G - 1, C + G - 1 + S) is segment k = j - (C + G - 1), index C + G + k in nearest. The thread reads its
+// segment once per pass (32 contiguous bytes) and tests it against every pose of the pass with wall_body (rule
+// W2); like the mate loop, the pose loop is not unrolled, so there is one wall_body in the code. The mapping,
+// the passes, the (value, index) reduction and the crash record are clearance_body_kernel's.
+__global__ __launch_bounds__(kClearThreads) void clearance_walls_kernel(
+    const ClearParams P, const RaceParams Q, const BodyParams H, const WallParams Wl, const int B, const int rows,
+    const int nwg, const double* __restrict__ x, const double* __restrict__ circles,
+    const double* __restrict__ segments, double* __restrict__ clearance, int* __restrict__ nearest,
+    const ContactMark M) {
+#pragma clang fp contract(off)
+  __shared__ double s_qx[kClearPoses], s_qy[kClearPoses], s_c[kClearPoses], s_s[kClearPoses];
+  __shared__ double s_best[kClearWaves][kClearPoses];
+  __shared__ int s_idx[kClearWaves][kClearPoses];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double inf = __longlong_as_double(0x7ff0000000000000ll);
+  const int ns = P.C + Q.G - 1;  // the circles and the G - 1 mates behind them, then the segments
+  const int nc = ns + Wl.S;
+  for (int b = blockIdx.x; b < B; b += nwg) {
+    const double* cw = circles + (P.world_rows == 1 ? (size_t)0 : (size_t)b * (size_t)P.C * 3);
+    const double* sw = segments + (Wl.wall_rows == 1 ? (size_t)0 : (size_t)b * (size_t)Wl.S * 4);
+    const int own = b % Q.G, first = b - own;
+    int crash = -1;  // thread 0: the first row at or under the margin
+    if (M.crash_tick && !M.init && tid == 0) crash = M.crash_tick[b];
+    for (int r0 = 0; r0 < rows; r0 += kClearPoses) {
+      const int np = min(kClearPoses, rows - r0);
+      if (tid < np) {  // the body frame of pose tid of the pass
+        const double* xp = x + ((size_t)(r0 + tid) * (size_t)B + (size_t)b) * 3;
+        double so, co;
+        sincos(xp[2], &so, &co);
+        s_qx[tid] = xp[0] + Q.center_offset * co;
+        s_qy[tid] = xp[1] + Q.center_offset * so;
+        s_c[tid] = co;
+        s_s[tid] = so;
+      }
+      __syncthreads();
+      double best[kClearPoses];
+      int idx[kClearPoses];
+#pragma unroll
+      for (int p = 0; p < kClearPoses; p++) {
+        best[p] = inf;
+        idx[p] = -1;
+      }
+      for (int c0 = 0; c0 < nc; c0 += kCastCircleTile) {
+        const int j = c0 + tid;
+        if (j < P.C) {
+          const double cx = cw[(size_t)j * 3 + 0], cy = cw[(size_t)j * 3 + 1];
+          const double ra = fabs(cw[(size_t)j * 3 + 2]);
+#pragma unroll
+          for (int p = 0; p < kClearPoses; p++)
+            if (p < np) take_min(best[p], idx[p], body_sd(cx, cy, s_qx[p], s_qy[p], s_c[p], s_s[p], H) - ra, j);
+        } else if (j < ns) {  // mate k of the race, stepped over the own slot: index i inside the race
+          const int k = j - P.C, i = k + (k >= own ? 1 : 0);
+#pragma unroll 1
+          for (int p = 0; p < np; p++) {
+            const double* xm = x + ((size_t)(r0 + p) * (size_t)B + (size_t)(first + i)) * 3;
+            double sm, cm;
+            sincos(xm[2], &sm, &cm);
+            const double mx = xm[0] + Q.center_offset * cm, my = xm[1] + Q.center_offset * sm;
+            const double v = body_pair(s_qx[p], s_qy[p], s_c[p], s_s[p], mx, my, cm, sm, H);
+#pragma unroll
+            for (int q = 0; q < kClearPoses; q++)
+              if (q == p) take_min(best[q], idx[q], v, P.C + i);
+          }
+        } else if (j < nc) {  // segment j - ns
+          const double* sg = sw + (size_t)(j - ns) * 4;
+          const double ax = sg[0], ay = sg[1], bx = sg[2], by = sg[3];
+          const int i = P.C + Q.G + (j - ns);
+#pragma unroll 1
+          for (int p = 0; p < np; p++) {
+            const double v = wall_body(ax, ay, bx, by, s_qx[p], s_qy[p], s_c[p], s_s[p], H);
+#pragma unroll
+            for (int q = 0; q < kClearPoses; q++)
+              if (q == p) take_min(best[q], idx[q], v, i);
+          }
+        }
+      }
+      // the wave's (value, index) minimum per pose, then the four waves' through LDS
+#pragma unroll
+      for (int p = 0; p < kClearPoses; p++) {
+        if (p < np) {  // uniform
+#pragma unroll
+          for (int m = 32; m >= 1; m >>= 1) {
+            const double ov = __shfl_xor(best[p], m, 64);
+            const int oi = __shfl_xor(idx[p], m, 64);
+            take_min(best[p], idx[p], ov, oi);
+          }
+          if (lane == 0) {
+            s_best[wave][p] = best[p];
+            s_idx[wave][p] = idx[p];
+          }
+        }
+      }
+      __syncthreads();
+      if (tid < np) {
+        double v = s_best[0][tid];
+        int i = s_idx[0][tid];
+#pragma unroll
+        for (int w = 1; w < kClearWaves; w++) take_min(v, i, s_best[w][tid], s_idx[w][tid]);
+        const size_t o = (size_t)(r0 + tid) * (size_t)B + (size_t)b;
+        clearance[o] = v;
+        if (nearest) nearest[o] = i;
+        s_best[0][tid] = v;  // for the mark below (read by thread 0 behind the barrier)
+      }
+      if (M.crash_tick) {  // uniform
+        __syncthreads();
+        if (tid == 0)
+          for (int p = 0; p < np; p++)
+            if (crash < 0 && s_best[0][p] <= M.margin) crash = M.row0 + r0 + p;
+      }
+      __syncthreads();  // the next pass (or car) rewrites the frames and the waves' results
+    }
+    if (M.crash_tick && tid == 0) M.crash_tick[b] = crash;
+  }
+}
+
+// Grid: one workgroup per car up to 512. The kernel holds 185 VGPRs (the code-object metadata; no
+// VGPR spill, no scratch), allocated as 192, so a SIMD keeps two of its waves; a workgroup is one wave on each
+// of a CU's four SIMDs and 640 B of LDS, so a CU holds two workgroups and the MI355X's 256 CUs hold 512 at once:
+// derived as clearance_body_grid's cap is.
+constexpr int kClearWallsMaxGrid = 512;
+int clearance_walls_grid(int B) { return B < kClearWallsMaxGrid ? B : kClearWallsMaxGrid; }
+
+hipError_t launch_clearance_walls(const ClearParams& P, const RaceParams& Q, const BodyParams& H, const WallParams& Wl,
+                                  int B, int rows, const double* x, const double* circles, const double* segments,
+                                  double* clearance, int* nearest, const ContactMark& M, hipStream_t s) {
+  if (B <= 0 || rows <= 0) return hipSuccess;
+  const int nwg = clearance_walls_grid(B);
+  hipLaunchKernelGGL(clearance_walls_kernel, dim3(nwg), dim3(kClearThreads), 0, s, P, Q, H, Wl, B, rows, nwg, x,
+                     circles, segments, clearance, nearest, M);
   return hipGetLastError();
 }
 

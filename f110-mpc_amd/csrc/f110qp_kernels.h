@@ -416,6 +416,17 @@ int cast_scans_body_grid(int B);
 hipError_t launch_cast_scans_body(const CastParams& P, const RaceParams& Q, const BodyParams& H, int B, const int* list,
                                   const int* count, const double* x, const double* circles, float* ranges,
                                   hipStream_t stream);
+// Straight walls (wall_geom.h): S segments (ax, ay, bx, by) behind the circles and the mates, segments
+// [wall_rows][S][4] (null when S = 0); car b reads row 0 (wall_rows 1) or row b (wall_rows B).
+struct WallParams {
+  int S;
+  int wall_rows;  // 1 or B
+};
+// launch_cast_scans_body with the segments in every scan (rule W1).
+int cast_scans_walls_grid(int B);
+hipError_t launch_cast_scans_walls(const CastParams& P, const RaceParams& Q, const BodyParams& H, const WallParams& Wl,
+                                   int B, const int* list, const int* count, const double* x, const double* circles,
+                                   const double* segments, float* ranges, hipStream_t stream);
 
 // ---- contact (contact_kernels.hip) ----------------------------------------------------------------
 // The clearance of rows x B poses x [rows][B][3] to everything each car can touch: the C circles of its
@@ -445,6 +456,12 @@ int clearance_body_grid(int B);
 hipError_t launch_clearance_body(const ClearParams& P, const RaceParams& Q, const BodyParams& H, int B, int rows,
                                  const double* x, const double* circles, double* clearance, int* nearest,
                                  const ContactMark& M, hipStream_t stream);
+// launch_clearance_body with the segments as a third stretch of the obstacle list (rule W2): segment k has
+// index C + G + k in nearest.
+int clearance_walls_grid(int B);
+hipError_t launch_clearance_walls(const ClearParams& P, const RaceParams& Q, const BodyParams& H, const WallParams& Wl,
+                                  int B, int rows, const double* x, const double* circles, const double* segments,
+                                  double* clearance, int* nearest, const ContactMark& M, hipStream_t stream);
 
 // ---- standings (standings_kernels.hip) ------------------------------------------------------------
 // The projection of rows x B poses x [rows][B][3] onto the closed path wp [W][2] with cumulative lengths

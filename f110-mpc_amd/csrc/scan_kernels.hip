@@ -39,10 +39,19 @@
 // pose fails the range compare and hits nothing, and the minimum is the same for every order of the
 // race's cars. The tile loop runs to C + G - 1: no cap on G. The plain kernel is the RACE = false
 // instantiation; every race statement is behind `if constexpr`.
+//
+// Walls (WALLS, cast_scans_walls_kernel): the body cast with S straight segments (wall_geom.h, rule W1)
+// as a third stretch of the list, index j in [C + G - 1, C + G - 1 + S). Phase A culls a segment by its
+// distance from the LiDAR and gives it the beams of the arc between atan2(A) and atan2(B) the short way, with
+// the circle path's margin and wrap rule; an arc that is not safely below pi (the LiDAR on or next to the
+// segment), or an increment below the margin threshold: every beam. A beam outside the arc cannot meet the
+// segment at th > 0, so here too the interval changes the work and not the result. Every wall statement is
+// behind `if constexpr`.
 #include <hip/hip_runtime.h>
 
 #include "body_geom.h"
 #include "f110qp_kernels.h"
+#include "wall_geom.h"
 
 namespace f110qp {
 
@@ -61,6 +70,8 @@ constexpr double kCastRel = 1.000001;
 constexpr double kCastArcSlack = 1e-9;
 // below this increment the one-beam margin is not safely above the rounding of the arc: every beam
 constexpr double kCastMinInc = 1e-9;
+// a segment's arc at or above this is too close to pi for "the short way" to be trusted: every beam
+constexpr double kCastWallArc = 3.1415;
 
 // A circle of the current tile as phase B reads it. nd: beams per interval less one (0: culled, < 0:
 // every beam of the scan).
@@ -72,7 +83,8 @@ struct CastSlot {
 struct CastBodySlot {
   double px, py, r2, flo, nd;
   double c, s;
-  int mate;  // 0: a static circle (cast_beams), 1: a race-mate's rectangle (cast_beams_body)
+  int mate;  // 0: a static circle (cast_beams), 1: a race-mate's rectangle (cast_beams_body), 2 (WALLS): a
+             // segment with A = (px, py) and B = (c, s) from the LiDAR (cast_beams_wall)
 };
 template <bool BODY>
 struct SlotOf {
@@ -119,13 +131,62 @@ __device__ __forceinline__ void cast_beams_body(const double px, const double py
   }
 }
 
+// Rule W1 (wall_geom.h) on beams lo .. hi of the scan for the segment whose ends are (ax, ay) and (bx, by) from
+// the LiDAR: the beams and the fold are cast_beams'.
 #pragma clang fp contract(off)
-template <bool RACE, bool BODY>
-__device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& Q, const BodyParams& H, const int b,
-                                         const double* __restrict__ x, const double* __restrict__ circles,
+__device__ __forceinline__ void cast_beams_wall(const double ax, const double ay, const double bx, const double by,
+                                                int lo, int hi, const int cb, const int nb, const int sub,
+                                                const double* s_dx, const double* s_dy, unsigned long long* s_min) {
+  lo = max(lo, cb) - cb;
+  hi = min(hi, cb + nb - 1) - cb;
+  for (int i = lo + sub; i <= hi; i += kCastLanes) {
+    double th;
+    if (wall_hit(ax, ay, bx, by, s_dx[i], s_dy[i], th))
+      atomicMin(&s_min[i], (unsigned long long)__double_as_longlong(th));
+  }
+}
+
+// Phase A of a segment (WALLS): sg = (ax, ay, bx, by) into the slot with A = (px, py) and B = (c, s) from the
+// LiDAR (ox, oy). Culled when the segment's nearest point is past max_range (a NaN field fails the compare: it
+// hits nothing anyway); otherwise the beams of the arc from atan2(A) to atan2(B) the short way.
+#pragma clang fp contract(off)
+__device__ __forceinline__ void wall_slot(const double* __restrict__ sg, const double ox, const double oy,
+                                          const double ori, const double amin, const double ainc,
+                                          const double max_range, CastBodySlot& sl) {
+  const double ax = sg[0] - ox, ay = sg[1] - oy, bx = sg[2] - ox, by = sg[3] - oy;
+  const double ex = bx - ax, ey = by - ay, ee = ex * ex + ey * ey;
+  double t = -(ax * ex + ay * ey) / ee;  // the nearest point of the segment: A + t e, t in [0, 1]
+  t = ee > 0.0 ? fmin(fmax(t, 0.0), 1.0) : 0.0;
+  const double nx = ax + t * ex, ny = ay + t * ey;
+  if (!(__dsqrt_rn(nx * nx + ny * ny) <= max_range * kCastRel)) return;
+  sl.px = ax;
+  sl.py = ay;
+  sl.c = bx;
+  sl.s = by;
+  sl.mate = 2;
+  const double aa = atan2(ay, ax);
+  double da = atan2(by, bx) - aa;  // to B the short way: in [-pi, pi]
+  da -= kTwoPi * rint(da / kTwoPi);
+  const double w = fabs(da) + 2.0 * kCastArcSlack;
+  if (w < kCastWallArc && w + 4.0 * ainc < kTwoPi && ainc >= kCastMinInc) {
+    double rel = (aa + fmin(da, 0.0)) - ori - amin - kCastArcSlack;  // the arc's low edge from beam 0
+    rel -= kTwoPi * floor(rel / kTwoPi);
+    sl.flo = rel / ainc;
+    sl.nd = ceil(w / ainc) + 3.0;
+  } else {
+    sl.nd = -1.0;
+  }
+}
+
+#pragma clang fp contract(off)
+template <bool RACE, bool BODY, bool WALLS>
+__device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& Q, const BodyParams& H,
+                                         const WallParams& Wl, const int b, const double* __restrict__ x,
+                                         const double* __restrict__ circles, const double* __restrict__ segments,
                                          float* __restrict__ ranges, double* s_dx, double* s_dy,
                                          unsigned long long* s_min, typename SlotOf<BODY>::type* s_slot) {
   static_assert(RACE || !BODY, "bodies are the race-mates'");
+  static_assert(BODY || !WALLS, "walls come with the body cast");
   using Slot = typename SlotOf<BODY>::type;
   const int tid = threadIdx.x;
   const double ori = x[(size_t)b * 3 + 2];
@@ -145,6 +206,12 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
     own = b % Q.G;
     first = b - own;
   }
+  const int ns = nc;  // the first segment's index
+  const double* sw = nullptr;
+  if constexpr (WALLS) {
+    nc += Wl.S;
+    sw = segments + (Wl.wall_rows == 1 ? (size_t)0 : (size_t)b * (size_t)Wl.S * 4);
+  }
   for (int cb = 0; cb < nr; cb += kCastBeamTile) {
     const int nb = min(kCastBeamTile, nr - cb);
     for (int i = tid; i < nb; i += kCastThreads) {
@@ -159,7 +226,12 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
       {  // A: circle c0 + tid -> slot tid
         Slot sl{};
         const int j = c0 + tid;
-        if (j < nc) {
+        bool wall = false;
+        if constexpr (WALLS) wall = j >= ns && j < nc;
+        if constexpr (WALLS) {
+          if (wall) wall_slot(sw + (size_t)(j - ns) * 4, ox, oy, ori, amin, ainc, P.max_range, sl);
+        }
+        if (!wall && j < nc) {
           double cx, cy, r;
           bool mate = false;
           if constexpr (RACE) mate = j >= P.C;
@@ -212,6 +284,12 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
           const double pp = sl.px * sl.px + sl.py * sl.py;
           // the exact test of the slot on beams lo .. hi: the slab test on a mate's rectangle
           auto test = [&](const int lo, const int hi) {
+            if constexpr (WALLS) {
+              if (sl.mate == 2) {
+                cast_beams_wall(sl.px, sl.py, sl.c, sl.s, lo, hi, cb, nb, sub, s_dx, s_dy, s_min);
+                return;
+              }
+            }
             if constexpr (BODY) {
               if (sl.mate) {
                 cast_beams_body(sl.px, sl.py, sl.c, sl.s, H, lo, hi, cb, nb, sub, s_dx, s_dy, s_min);
@@ -243,11 +321,13 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
 
 // Workgroup w takes cars w, w + nwg, ... below B, or with a list the cars list[w], list[w + nwg], ...
 // below min(*count, B) (plan_listed_kernel's rule: one past the count leaves at that load).
-template <bool RACE, bool BODY = false>
+template <bool RACE, bool BODY = false, bool WALLS = false>
 __device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams& Q, const BodyParams& H, const int B,
                                            const int nwg, const int* __restrict__ list,
                                            const int* __restrict__ count, const double* __restrict__ x,
-                                           const double* __restrict__ circles, float* __restrict__ ranges) {
+                                           const double* __restrict__ circles, float* __restrict__ ranges,
+                                           const WallParams& Wl = WallParams{},
+                                           const double* __restrict__ segments = nullptr) {
   __shared__ double s_dx[kCastBeamTile];
   __shared__ double s_dy[kCastBeamTile];
   __shared__ unsigned long long s_min[kCastBeamTile];
@@ -256,7 +336,7 @@ __device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams
   for (int k = blockIdx.x; k < n; k += nwg) {
     const int b = list ? list[k] : k;
     if (b >= 0 && b < B)  // uniform over the workgroup
-      cast_one<RACE, BODY>(P, Q, H, b, x, circles, ranges, s_dx, s_dy, s_min, s_slot);
+      cast_one<RACE, BODY, WALLS>(P, Q, H, Wl, b, x, circles, segments, ranges, s_dx, s_dy, s_min, s_slot);
   }
 }
 
@@ -286,6 +366,14 @@ __global__ __launch_bounds__(kCastThreads) void cast_scans_body_kernel(
     const int* __restrict__ list, const int* __restrict__ count, const double* __restrict__ x,
     const double* __restrict__ circles, float* __restrict__ ranges) {
   cast_scans<true, true>(P, Q, H, B, nwg, list, count, x, circles, ranges);
+}
+
+// The body cast with the straight walls of wall_geom.h behind the circles and the mates (WALLS).
+__global__ __launch_bounds__(kCastThreads) void cast_scans_walls_kernel(
+    const CastParams P, const RaceParams Q, const BodyParams H, const WallParams Wl, const int B, const int nwg,
+    const int* __restrict__ list, const int* __restrict__ count, const double* __restrict__ x,
+    const double* __restrict__ circles, const double* __restrict__ segments, float* __restrict__ ranges) {
+  cast_scans<true, true, true>(P, Q, H, B, nwg, list, count, x, circles, ranges, Wl, segments);
 }
 
 // Grid: one workgroup per car up to 768. The kernel holds 155 VGPRs (the code-object metadata,
@@ -329,6 +417,23 @@ hipError_t launch_cast_scans_body(const CastParams& P, const RaceParams& Q, cons
   const int nwg = cast_scans_body_grid(B);
   hipLaunchKernelGGL(cast_scans_body_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, Q, H, B, nwg, list, count, x,
                      circles, ranges);
+  return hipGetLastError();
+}
+
+// Grid: one workgroup per car up to 512. The walls instantiation holds 185 VGPRs (the code-object metadata,
+// DESIGN.md 2i; no VGPR spill, no scratch), allocated in granules of eight as 192, so a SIMD keeps
+// floor(512 / 192) = 2 of its waves and a CU two of its four-wave workgroups (44,032 B of LDS each would allow
+// three): 512 on the MI355X's 256 CUs, derived as cast_scans_body_grid's cap is.
+constexpr int kCastWallsMaxGrid = 512;
+int cast_scans_walls_grid(int B) { return B < kCastWallsMaxGrid ? B : kCastWallsMaxGrid; }
+
+hipError_t launch_cast_scans_walls(const CastParams& P, const RaceParams& Q, const BodyParams& H, const WallParams& Wl,
+                                   int B, const int* list, const int* count, const double* x, const double* circles,
+                                   const double* segments, float* ranges, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  const int nwg = cast_scans_walls_grid(B);
+  hipLaunchKernelGGL(cast_scans_walls_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, Q, H, Wl, B, nwg, list, count, x,
+                     circles, segments, ranges);
   return hipGetLastError();
 }
 

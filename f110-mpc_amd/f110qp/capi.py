@@ -140,6 +140,11 @@ EXPORTED = (
     "f110qp_cast_scans_body_dev",
     "f110qp_rollout_body_dev",
     "f110qp_rollout_body",
+    "f110qp_default_walls_config",
+    "f110qp_cast_scans_walls_dev",
+    "f110qp_clearance_walls_dev",
+    "f110qp_rollout_walls_dev",
+    "f110qp_rollout_walls",
     "f110qp_path_lengths",
     "f110qp_progress_dev",
     "f110qp_standings_dev",
@@ -243,6 +248,13 @@ class BodyConfig(C.Structure):
     ]
 
 
+class WallsConfig(C.Structure):
+    _fields_ = [
+        ("num_segments", C.c_int),
+        ("wall_rows", C.c_int),
+    ]
+
+
 # f110qp_gap_record (16 bytes) as a numpy record
 GAP_RECORD_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("r_lo", np.float32), ("r_hi", np.float32)])
 
@@ -323,6 +335,12 @@ def load(test: bool = False):
     L.f110qp_cast_scans_body_dev.argtypes = [sp, wcp, rcp, bcp, C.c_int] + [fp] * 6
     L.f110qp_rollout_body_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, C.c_int] + [fp] * 24
     L.f110qp_rollout_body.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, C.c_int] + [fp] * 23
+    wlp = C.POINTER(WallsConfig)
+    L.f110qp_default_walls_config.argtypes = [wlp]
+    L.f110qp_cast_scans_walls_dev.argtypes = [sp, wcp, rcp, bcp, wlp, C.c_int] + [fp] * 7
+    L.f110qp_clearance_walls_dev.argtypes = [wcp, rcp, bcp, wlp, C.c_int, C.c_int] + [fp] * 6
+    L.f110qp_rollout_walls_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, C.c_int] + [fp] * 25
+    L.f110qp_rollout_walls.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, C.c_int] + [fp] * 24
     L.f110qp_path_lengths.argtypes = [fp, C.c_int, fp]
     L.f110qp_progress_dev.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_int] + [fp] * 4
     L.f110qp_standings_dev.argtypes = [rcp, C.c_int, C.c_int, fp, C.c_double] + [fp] * 4
@@ -451,6 +469,15 @@ def default_body_config(**over) -> BodyConfig:
     """f110qp_default_body_config: half_length 0.29, half_width 0.155."""
     c = BodyConfig()
     load().f110qp_default_body_config(C.byref(c))
+    for k, v in over.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_walls_config(**over) -> WallsConfig:
+    """f110qp_default_walls_config: num_segments 0 (the caller's), wall_rows 1."""
+    c = WallsConfig()
+    load().f110qp_default_walls_config(C.byref(c))
     for k, v in over.items():
         setattr(c, k, v)
     return c
@@ -934,7 +961,7 @@ class Solver:
                           waypoints, x_ref, have_path, circles, x_traj, u_lin_traj, u_applied, status_traj,
                           iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
                           plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
-                          ranges_traj=None, stream=None, _race=None, _contact=None, _body=None):
+                          ranges_traj=None, stream=None, _race=None, _contact=None, _body=None, _walls=None):
         """rollout_replan_dev with every tick's scan cast at that tick's pose (f110qp_rollout_world_dev): wc
         and circles [world_rows,C,3] f64 replace ranges, sc.scan_rows is not read, and the optional
         ranges_traj [T,B,num_ranges] f32 records every car's scan of every tick."""
@@ -957,12 +984,18 @@ class Solver:
                                                                                    _tp(crash_tick)]
             if _body is not None:  # the body config behind cc
                 name, cfgs = "f110qp_rollout_body_dev", cfgs + [C.byref(_body)]
+        world = [_tp(circles)]
+        if _walls is not None:  # (walls, segments): the config behind body, the segments behind circles
+            walls, segments = _walls
+            Sn = int(walls.num_segments)
+            more = more + [(segments, "f64", 4 * max(Sn, 0) * max(int(walls.wall_rows), 0), "segments", Sn <= 0)]
+            name, cfgs, world = "f110qp_rollout_walls_dev", cfgs + [C.byref(walls)], world + [_tp(segments)]
         _devs(*self._plan_specs(rp, B, *plan), (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
               *self._traj_specs(T, B, *traj), *self._record_specs(T, B, *rec),
               (ranges_traj, "f32", T * B * int(sc.num_ranges), "ranges_traj", True), *more)
         self._chk(getattr(self.lib, name)(
             self._h, C.byref(rc), C.byref(sc), C.byref(rp), C.byref(wc), *cfgs,
-            B, *map(_tp, plan), _tp(circles), *map(_tp, traj), *map(_tp, rec), _tp(ranges_traj), *tail,
+            B, *map(_tp, plan), *world, *map(_tp, traj), *map(_tp, rec), _tp(ranges_traj), *tail,
             self._stream(stream, x_traj)), name)
 
     def rollout_race_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
@@ -1009,9 +1042,27 @@ class Solver:
                                plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
                                _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body)
 
+    def rollout_walls_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
+                          cc: ContactConfig, body: BodyConfig, walls: WallsConfig, table, waypoints, x_ref, have_path,
+                          circles, segments, x_traj, u_lin_traj, u_applied, status_traj, clear_traj, crash_tick,
+                          nearest_traj=None, iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None,
+                          kind_traj=None, plan_status_traj=None, best_traj_traj=None, best_global_traj=None,
+                          pose_traj=None, ranges_traj=None, stream=None):
+        """rollout_body_dev with straight wall segments next to the circles in every cast and every clearance
+        (f110qp_rollout_walls_dev): walls follows body, segments [wall_rows,S,4] f64 (None for S = 0) follows
+        circles, everything else as there."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
+                or not isinstance(walls, WallsConfig):
+            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig and walls a WallsConfig")
+        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
+                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
+                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
+                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
+                               _walls=(walls, segments))
+
     def rollout_world(self, x0, u_lin, circles, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
                       wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
-                      scans=False, rc=None, _race=None, _contact=None, _body=None):
+                      scans=False, rc=None, _race=None, _contact=None, _body=None, _segments=None):
         """rollout_replan() in a world of circles (f110qp_rollout_world, synchronous): circles [C,3] (one world
         for all cars) or [B,C,3] float64 replace ranges; wc defaults to f110qp_default_world_config with
         num_circles and world_rows taken from the array. scans=True adds ranges_traj [T,B,num_ranges]."""
@@ -1041,10 +1092,20 @@ class Solver:
             tail = [_p(out["clear_traj"]), _p(out.get("nearest_traj")), _p(out["crash_tick"])]
             if _body is not None:  # the body config behind cc
                 name, cfgs = "f110qp_rollout_body", cfgs + [C.byref(_body)]
+        world = [_p(ci) if ci.size else None]
+        if _segments is not None:  # the walls config behind body, the segments behind circles
+            if not isinstance(_segments, np.ndarray) or _segments.dtype != np.float64 or _segments.ndim not in (2, 3) \
+                    or _segments.shape[-1] != 4:
+                raise F110QPError("segments must be a float64 numpy array [S, 4] or [B, S, 4]")
+            sg = np.ascontiguousarray(_segments)
+            wl = default_walls_config(num_segments=sg.shape[-2], wall_rows=1 if sg.ndim == 2 else sg.shape[0])
+            if wl.wall_rows not in (1, B):
+                raise F110QPError(f"segments must hold one set or B = {B} sets, got {wl.wall_rows}")
+            name, cfgs, world = "f110qp_rollout_walls", cfgs + [C.byref(wl)], world + [_p(sg) if sg.size else None]
         self._chk(getattr(self.lib, name)(
             self._h, C.byref(self._ticks_config(rc, T)), C.byref(sc), C.byref(rp), C.byref(w),
             *cfgs, B, _p(tab), _p(wp) if wp.shape[0] else None, _p(xr), _p(hv),
-            _p(ci) if ci.size else None, *self._out_args(out), _p(out.get("ranges_traj")), *tail), name)
+            *world, *self._out_args(out), _p(out.get("ranges_traj")), *tail), name)
         return out
 
     def rollout_race(self, x0, u_lin, circles, race: RaceConfig, sc: ScanConfig, rp: ReplanConfig, table, waypoints,
@@ -1075,6 +1136,17 @@ class Solver:
             raise F110QPError("race must be a RaceConfig, cc a ContactConfig and body a BodyConfig")
         return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
                                   objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body)
+
+    def rollout_walls(self, x0, u_lin, circles, segments, race: RaceConfig, cc: ContactConfig, body: BodyConfig,
+                      sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks, wc: WorldConfig = None, x_ref=None,
+                      have_path=None, plans=False, objective=False, rows=True, scans=False, nearest=True, rc=None):
+        """rollout_body() with straight wall segments [S,4] or [B,S,4] float64 next to the circles
+        (f110qp_rollout_walls, synchronous); circles may be an empty [0,3] array."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig):
+            raise F110QPError("race must be a RaceConfig, cc a ContactConfig and body a BodyConfig")
+        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
+                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
+                                  _segments=segments)
 
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
@@ -1390,6 +1462,58 @@ def clearance_body_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, x, c
     _check(load().f110qp_clearance_body_dev(C.byref(wc), C.byref(race), C.byref(body), B, rows, _tp(x), _tp(circles),
                                             _tp(clearance), _tp(nearest), C.c_void_p(stream.cuda_stream)),
            "f110qp_clearance_body_dev")
+
+
+def _wall_spec(walls, segments):
+    if not isinstance(walls, WallsConfig):
+        raise F110QPError("walls must be a WallsConfig")
+    Sn = int(walls.num_segments)
+    return (segments, "f64", 4 * max(Sn, 0) * max(int(walls.wall_rows), 0), "segments", Sn <= 0)
+
+
+def cast_scans_walls_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, x,
+                         circles, segments, ranges, list_=None, count=None, stream=None):
+    """cast_scans_body_dev with straight wall segments in every scan (f110qp_cast_scans_walls_dev): segments
+    [wall_rows,S,4] f64 = (ax, ay, bx, by), None for S = 0."""
+    import torch
+
+    if not isinstance(body, BodyConfig):
+        raise F110QPError("body must be a BodyConfig")
+    B, Cn, WR = int(x.shape[0]), int(wc.num_circles), int(wc.world_rows)
+    _check_race(race, B)
+    _devs((x, "f64", 3 * B, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
+          _wall_spec(walls, segments), (ranges, "f32", B * int(sc.num_ranges), "ranges"),
+          (list_, "i32", B, "list", True), (count, "i32", 1, "count", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_cast_scans_walls_dev(C.byref(sc), C.byref(wc), C.byref(race), C.byref(body), C.byref(walls), B,
+                                              _tp(list_), _tp(count), _tp(x), _tp(circles), _tp(segments), _tp(ranges),
+                                              C.c_void_p(stream.cuda_stream)), "f110qp_cast_scans_walls_dev")
+
+
+def clearance_walls_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, x, circles, segments,
+                        clearance, nearest=None, stream=None):
+    """clearance_body_dev with straight wall segments behind the circles and the mates
+    (f110qp_clearance_walls_dev): segment k has index C + G + k in nearest."""
+    import torch
+
+    if not isinstance(body, BodyConfig):
+        raise F110QPError("body must be a BodyConfig")
+    if x.dim() not in (2, 3) or x.shape[-1] != 3:
+        raise F110QPError(f"x must be [rows, B, 3] or [B, 3], got {tuple(x.shape)}")
+    rows, B = (1, int(x.shape[0])) if x.dim() == 2 else (int(x.shape[0]), int(x.shape[1]))
+    if rows < 1:
+        raise F110QPError("x must hold at least one row")
+    Cn, WR = int(wc.num_circles), int(wc.world_rows)
+    _check_race(race, B)
+    _devs((x, "f64", 3 * B * rows, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
+          _wall_spec(walls, segments), (clearance, "f64", B * rows, "clearance"),
+          (nearest, "i32", B * rows, "nearest", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_clearance_walls_dev(C.byref(wc), C.byref(race), C.byref(body), C.byref(walls), B, rows, _tp(x),
+                                             _tp(circles), _tp(segments), _tp(clearance), _tp(nearest),
+                                             C.c_void_p(stream.cuda_stream)), "f110qp_clearance_walls_dev")
 
 
 def _rows_of(x, last, name):

@@ -521,6 +521,129 @@ def ray_bodies(x, geom, beams, group_size, center_offset: float = 0.1651, half_l
         return np.minimum(th.min(axis=2), out)
 
 
+# ---- straight walls (f110qp_cast_scans_walls_dev, f110qp_clearance_walls_dev) -------------------------------
+# The model of include/f110qp.h "straight walls" in numpy, in csrc/wall_geom.h's expressions and order.
+
+def ray_segments(ox, oy, dx, dy, segments, max_range: float = 10.0):
+    """Rule W1: ranges (float64, the shape of dx) of beams from the origins (ox, oy) along (dx, dy) against the
+    segments [S, 4] or [..., S, 4] = (ax, ay, bx, by), max_range where nothing is hit. ox, oy, dx, dy broadcast
+    against each other; a leading world axis of segments broadcasts against them too."""
+    sg = np.asarray(segments, np.float64)
+    ox, oy, dx, dy = (np.asarray(v, np.float64)[..., None] for v in np.broadcast_arrays(ox, oy, dx, dy))
+    if sg.shape[-2] == 0:
+        return np.full(dx.shape[:-1], float(max_range))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        ax, ay, bx, by = sg[..., 0] - ox, sg[..., 1] - oy, sg[..., 2] - ox, sg[..., 3] - oy
+        ca = dx * ay - dy * ax
+        cb = dx * by - dy * bx
+        ta = ax * dx + ay * dy
+        tb = bx * dx + by * dy
+        den = ca - cb
+        straddle = ((ca <= 0.0) & (cb >= 0.0)) | ((ca >= 0.0) & (cb <= 0.0))
+        th = ta + (tb - ta) * (ca / np.where(den != 0.0, den, 1.0))
+        th = np.where(straddle & (den != 0.0) & (th > 0.0), th, np.inf)
+        return np.minimum(th.min(axis=-1), float(max_range))
+
+
+def ray_walls(x, geom, beams, segments, lidar_offset: float = 0.275, max_range: float = 10.0):
+    """The segments' part of f110qp_cast_scans_walls_dev in numpy: ranges [B, beams] float64 of every car's beams
+    at the poses x [B, 3] against segments [S, 4] or [B, S, 4] (geom = (angle_min, angle_increment, ...) as
+    float32). The scan is np.minimum of this, the static circles' and the opponents' ranges before the cast to
+    float32."""
+    x = np.asarray(x, np.float64)
+    sg = np.asarray(segments, np.float64)
+    with np.errstate(invalid="ignore"):
+        ox, oy = x[:, 0] + lidar_offset * np.cos(x[:, 2]), x[:, 1] + lidar_offset * np.sin(x[:, 2])
+        ang = x[:, 2:3] + (np.float64(geom[0]) + np.float64(geom[1]) * np.arange(beams, dtype=np.float64))[None, :]
+        return ray_segments(ox[:, None], oy[:, None], np.cos(ang), np.sin(ang), sg if sg.ndim == 2 else sg[:, None],
+                            max_range)
+
+
+def _wall_sd(u, w, hl, hw):
+    au, aw = np.abs(u) - hl, np.abs(w) - hw
+    ex, ey = np.where(au < 0.0, 0.0, au), np.where(aw < 0.0, 0.0, aw)
+    return np.where((au <= 0.0) & (aw <= 0.0), np.fmax(au, aw), np.sqrt(ex * ex + ey * ey))
+
+
+def _slab_axis(o, d, h):
+    zero = d == 0.0
+    dd = np.where(zero, 1.0, d)
+    t1, t2 = (-h - o) / dd, (h - o) / dd
+    inside = np.abs(o) <= h
+    return (np.where(zero, np.where(inside, -np.inf, np.inf), np.fmin(t1, t2)),
+            np.where(zero, np.where(inside, np.inf, -np.inf), np.fmax(t1, t2)))
+
+
+def segment_body(ax, ay, bx, by, qx, qy, c, s, hl: float = HALF_LENGTH, hw: float = HALF_WIDTH):
+    """Rule W2 on broadcastable arrays: the body (centre (qx, qy), axes (c, s), half extents (hl, hw)) against the
+    segment from (ax, ay) to (bx, by): <= 0 when the segment crosses or touches the rectangle, otherwise the exact
+    distance; +inf for a NaN or infinite field or pose."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        dax, day, dbx, dby = ax - qx, ay - qy, bx - qx, by - qy
+        ua, wa = dax * c + day * s, day * c - dax * s
+        ub, wb = dbx * c + dby * s, dby * c - dbx * s
+        ex, ey = ub - ua, wb - wa
+        ee = ex * ex + ey * ey
+        lo_f, hi_f = _slab_axis(ua, ex, hl)
+        lo_l, hi_l = _slab_axis(wa, ey, hw)
+        m = np.fmin(_wall_sd(ua, wa, hl, hw), _wall_sd(ub, wb, hl, hw))
+        cross = np.fmax(np.fmax(lo_f, lo_l), 0.0) <= np.fmin(np.fmin(hi_f, hi_l), 1.0)
+
+        def corner(cx, cy):
+            gx, gy = cx - ua, cy - wa
+            t = (gx * ex + gy * ey) / np.where(ee == 0.0, 1.0, ee)
+            t = np.where(t < 0.0, 0.0, np.where(t > 1.0, 1.0, t))
+            t = np.where(ee == 0.0, 0.0, t)
+            rx, ry = gx - t * ex, gy - t * ey
+            return np.sqrt(rx * rx + ry * ry)
+        k = np.fmin(np.fmin(corner(hl, hw), corner(hl, -hw)), np.fmin(corner(-hl, hw), corner(-hl, -hw)))
+        v = np.where(cross, np.fmin(m, 0.0), np.fmin(m, k))
+        return np.where(ee < np.inf, v, np.inf)
+
+
+def clearance_walls(x, circles, segments, group_size: int = 1, center_offset: float = 0.1651,
+                    half_length: float = HALF_LENGTH, half_width: float = HALF_WIDTH):
+    """f110qp_clearance_walls_dev in numpy: clearance_body() with the segments [S, 4], [B, S, 4] or None as a third
+    stretch of the obstacle list, segment k at index C + G + k. -> (clearance [rows, B], nearest [rows, B])."""
+    x = np.asarray(x, np.float64)
+    one = x.ndim == 2
+    x = x[None] if one else x
+    rows, B = x.shape[:2]
+    G, hl, hw = int(group_size), float(half_length), float(half_width)
+    clear, near = clearance_body(x, circles, G, center_offset, hl, hw)
+    sg = np.zeros((0, 4)) if segments is None else np.asarray(segments, np.float64)
+    S = sg.shape[-2]
+    Cn = 0 if circles is None else np.asarray(circles).shape[-2]
+    if S:
+        sw = np.broadcast_to(sg, (B, S, 4)) if sg.ndim == 2 else sg
+        with np.errstate(invalid="ignore"):
+            c, s = np.cos(x[..., 2]), np.sin(x[..., 2])
+            qx, qy = x[..., 0] + center_offset * c, x[..., 1] + center_offset * s
+        v = segment_body(sw[None, :, :, 0], sw[None, :, :, 1], sw[None, :, :, 2], sw[None, :, :, 3], qx[..., None],
+                         qy[..., None], c[..., None], s[..., None], hl, hw)          # [rows, B, S]
+        v = np.where(np.isnan(v), np.inf, v)
+        a = np.argmin(v, axis=2)                                                     # the lowest index on equal values
+        best = np.take_along_axis(v, a[..., None], 2)[..., 0]
+        take = best < clear                                                          # equal: the lower index stays
+        clear = np.where(take, best, clear)
+        near = np.where(take, Cn + G + a, near).astype(np.int32)
+    return (clear[0], near[0]) if one else (clear, near)
+
+
+def make_wall_world(seed: int = 0, obstacles: int = 40, every: int = 4):
+    """make_world(seed, obstacles) with straight walls: (segments [S, 4], circles [obstacles, 3]) float64. The two
+    walls of make_world as two closed polylines through every `every`-th wall point (consecutive segments share the
+    vertex's bits, the last closes on the first), left wall first; the obstacle circles are make_world's own,
+    drawn from the same generator in the same order."""
+    w = make_world(seed, obstacles)
+    W = (w.shape[0] - obstacles) // 2
+    segs = []
+    for wall in (w[:W, :2], w[W:2 * W, :2]):
+        v = wall[::every]
+        segs.append(np.concatenate([v, np.roll(v, -1, 0)], 1))
+    return np.ascontiguousarray(np.concatenate(segs)), np.ascontiguousarray(w[2 * W:])
+
+
 # ---- race standings (f110qp_path_lengths, f110qp_progress_dev, f110qp_standings_dev) ------------------------
 
 def path_lengths(wp) -> np.ndarray:

@@ -1119,6 +1119,111 @@ int f110qp_rollout_body(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const 
                         int* plan_status_traj, int* best_traj_traj, int* best_global_traj, double* pose_traj,
                         float* ranges_traj, double* clear_traj, int* nearest_traj, int* crash_tick);
 
+/* ---- straight walls: segments in the LiDAR, the clearance and the rollout -------------------------------
+ * The worlds above are made of circles only, so a track wall is a chain of discs and every scan carries their
+ * ripple. The calls below take a world that holds straight wall segments next to its circles, as the map of the
+ * f1tenth simulator the reference runs in does; the body is the rectangle of the section above. They sit next
+ * to the body calls, which keep their bits. Additive: F110QP_API_VERSION stays 6. The disc-body families get no
+ * walls.
+ *
+ * segments is [wall_rows][S][4] double, each row (ax, ay, bx, by): the wall from a to b. A wall has no thickness
+ * and is seen from both sides. wall_rows is independent of wc->world_rows. Arithmetic as everywhere in this
+ * family: all fp64, every product and sum rounded (no fused multiply-add), sincos(double), the correctly rounded
+ * square root and division; min and max of a NaN and a number give the number (fmin, fmax).
+ *
+ * W1. A beam against a segment. With the LiDAR origin o and the beam direction d = (cos, sin), both exactly as
+ *     f110qp_cast_scans_dev builds them, A = a - o and B = b - o:
+ *       ca = d.x A.y - d.y A.x,  cb = d.x B.y - d.y B.x,  ta = A.x d.x + A.y d.y,  tb = B.x d.x + B.y d.y,
+ *       den = ca - cb.
+ *     The beam meets the segment when the ends straddle it, (ca <= 0 && cb >= 0) || (ca >= 0 && cb <= 0), and
+ *     den != 0, and th = ta + (tb - ta) * (ca / den) is > 0.
+ *     range = (float)min(circles' th, mates' th (rule 5), segments' th, max_range).
+ *     Consequences. A polyline whose consecutive segments share a vertex's bits cannot leak: ca of a shared
+ *     vertex is the same number in both neighbours, so if the outer ends lie on opposite sides of the beam's
+ *     line, one of the two straddles. (The usual form, which solves for the segment's own parameter and accepts
+ *     it in [0, 1], computes that parameter separately for the two neighbours, and a beam through the joint can
+ *     miss both; a leaked beam reads max_range, which the gap finder takes for a gap in the wall.) A segment seen
+ *     exactly edge-on hits nothing (den == 0), and so does a zero-length segment. A LiDAR on a wall does not see
+ *     that wall (th is not > 0). A segment with a NaN field fails every compare and disturbs nobody; one with an
+ *     infinite field gives a NaN th by the arithmetic and hits nothing either. The value of a (beam, segment)
+ *     pair depends on nothing else: the scan is bit-identical for every order of the segment list. Bits under
+ *     swapping a and b are not promised.
+ * W2. The rectangle against a segment. The body's frame is that of rules 1 to 3. Both ends into it: with
+ *     d = a - q, a' = (ua, wa) = (d.x f.x + d.y f.y, d.y f.x - d.x f.y) (rule 1's u and w), b' = (ub, wb)
+ *     likewise; e = b' - a', ee = e.x e.x + e.y e.y. When ee is NaN or +inf (a NaN or infinite field or pose)
+ *     v = +inf, which no compare takes. Otherwise, with sd'(u, w) rule 1's value from au on (the point in the
+ *     body's own frame: au = |u| - hl, aw = |w| - hw, ...), m = min(sd'(a'), sd'(b')).
+ *     The crossing test is the slab test of rule 5 with o' = a', d' = e and the window [0, 1] in place of
+ *     th > 0: the segment crosses or touches the rectangle when
+ *       max(max(lower end on f, lower end on l), 0) <= min(min(upper end on f, upper end on l), 1).
+ *     Crossing: v = min(m, 0): negative when an end lies inside, zero for a wall that passes through.
+ *     Not crossing: v = min(m, k), k the least distance from the four corners to the segment. For a corner c
+ *     of (hl, hw), (hl, -hw), (-hl, hw), (-hl, -hw) (rule 3's order): g = c - a', s = (g.x e.x + g.y e.y) / ee
+ *     clamped by s < 0 ? 0 : (s > 1 ? 1 : s), s = 0 when ee == 0; r = g - s e (each product rounded), distance
+ *     sqrt(r.x r.x + r.y r.y); folded min(min(k0, k1), min(k2, k3)). The distance of two disjoint convex sets is
+ *     attained at a vertex of one of them, so this is the exact distance.
+ *     In clearance and nearest, segment k has index C + G + k; circles keep j and mates C + i. The update rule,
+ *     the start value (+inf, -1), the NaN rule and the order independence are rule 4's.
+ *     Contact stays clearance <= margin: against a wall the value is <= 0 on contact (zero for a wall that
+ *     touches or passes through with both ends outside), not strictly negative on overlap.
+ * There is no swept test, as before: a tick moves a car 0.045 m against a half width of 0.155 m, so a car cannot
+ * step over a wall between two rows. */
+typedef struct {
+  int num_segments;  /* S >= 0 segments per world                                        */
+  int wall_rows;     /* 1: one set for all cars; B: segments [B][S][4], car b reads row b */
+} f110qp_walls_config;
+
+/* Zeroes *walls, then wall_rows 1. */
+void f110qp_default_walls_config(f110qp_walls_config* walls);
+
+/* f110qp_cast_scans_body_dev, word for word, with the segments in every scan (rule W1; one launch): walls
+ * follows body, segments follows circles. F110QP_ERR_INVALID before any HIP call, on top of that call's rules:
+ * a NULL walls, num_segments < 0, wall_rows other than 1 or batch, segments == NULL with num_segments > 0 (and
+ * num_circles + group_size + num_segments above INT_MAX). num_segments == 0 with segments == NULL is valid and
+ * gives f110qp_cast_scans_body_dev's bits; num_circles == 0 is valid. No cap on S. At most min(batch, 512)
+ * workgroups. */
+int f110qp_cast_scans_walls_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
+                                const f110qp_race_config* race, const f110qp_body_config* body,
+                                const f110qp_walls_config* walls, int batch, const int* list, const int* count,
+                                const double* x, const double* circles, const double* segments, float* ranges,
+                                void* stream);
+
+/* f110qp_clearance_body_dev, word for word, with the segments as a third stretch of the obstacle list (rule W2;
+ * one launch). Errors as f110qp_cast_scans_walls_dev's wall rules on top of that call's; num_segments == 0 gives
+ * f110qp_clearance_body_dev's bits. At most min(batch, 512) workgroups. */
+int f110qp_clearance_walls_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
+                               const f110qp_body_config* body, const f110qp_walls_config* walls, int batch,
+                               int rows, const double* x, const double* circles, const double* segments,
+                               double* clearance, int* nearest, void* stream);
+
+/* f110qp_rollout_body_dev, word for word, with every cast f110qp_cast_scans_walls_dev's and every clearance
+ * launch f110qp_clearance_walls_dev's (walls follows body, segments follows circles): that call's launch count,
+ * stream order, parking, and absence of host synchronisation, read-back and allocation inside the loop; every
+ * argument is checked before the first launch (that call's checks and the wall rules). num_segments == 0 gives
+ * f110qp_rollout_body_dev's bits in every array. */
+int f110qp_rollout_walls_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                             const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                             const f110qp_race_config* race, const f110qp_contact_config* cc,
+                             const f110qp_body_config* body, const f110qp_walls_config* walls, int batch,
+                             const double* table, const double* waypoints, double* x_ref, int* have_path,
+                             const double* circles, const double* segments, double* x_traj, double* u_lin_traj,
+                             float* u_applied, int* status_traj, int* iters_traj, double* cost_traj, float* u_plan,
+                             float* x_plan, float* hs_traj, int* kind_traj, int* plan_status_traj,
+                             int* best_traj_traj, int* best_global_traj, double* pose_traj, float* ranges_traj,
+                             double* clear_traj, int* nearest_traj, int* crash_tick, void* stream);
+
+/* Same on host pointers (synchronous), staged as f110qp_rollout_body; the segments are staged in. */
+int f110qp_rollout_walls(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                         const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                         const f110qp_race_config* race, const f110qp_contact_config* cc,
+                         const f110qp_body_config* body, const f110qp_walls_config* walls, int batch,
+                         const double* table, const double* waypoints, double* x_ref, int* have_path,
+                         const double* circles, const double* segments, double* x_traj, double* u_lin_traj,
+                         float* u_applied, int* status_traj, int* iters_traj, double* cost_traj, float* u_plan,
+                         float* x_plan, float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
+                         int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
+                         int* nearest_traj, int* crash_tick);
+
 /* ---- race standings: progress along the track, laps and positions ---------------------------------------
  * The calls above return poses; the calls below say who is ahead. They run after the fact on x_traj, or on any
  * [rows][B][3] pose array: nothing inside a closed loop reads a standing, so there is no rollout family of
