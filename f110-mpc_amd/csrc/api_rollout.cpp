@@ -4,7 +4,8 @@
 // (f110qp_rollout_world[_dev]), with race-mates (f110qp_rollout_race[_dev]) and with contact
 // (f110qp_clearance_dev, f110qp_rollout_contact[_dev]) and with rectangular bodies (f110qp_clearance_body_dev,
 // f110qp_cast_scans_body_dev, f110qp_rollout_body[_dev]) and with straight walls (f110qp_cast_scans_walls_dev,
-// f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]), and the parts of each.
+// f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]) and with a refreshed MPC scan (f110qp_gap_refresh_dev,
+// f110qp_rollout_refresh[_dev]), and the parts of each.
 // Host-side responsibilities only: argument validation, workspaces, H2D/D2H of the host-pointer calls
 // (the staging table of api_stage.h). No C++ exception crosses this boundary.
 #include <cmath>
@@ -131,6 +132,14 @@ static int wall_params(const f110qp_walls_config* walls, int batch, long long ob
   return F110QP_OK;
 }
 
+// The refresh config of f110qp_rollout_refresh[_dev], checked, its period into *every.
+static int refresh_params(const f110qp_refresh_config* rf, int* every) {
+  if (!rf) return fail(F110QP_ERR_INVALID, "refresh config is NULL");
+  if (rf->every < 0) return fail(F110QP_ERR_INVALID, "every must be >= 0");
+  *every = rf->every;
+  return F110QP_OK;
+}
+
 // The scan geometry of the re-planning kernels' argument records (ReplanStart, ReplanStep).
 template <typename S>
 static void scan_geometry(S* s, const f110qp_scan_config& sc) {
@@ -144,9 +153,9 @@ static void scan_geometry(S* s, const f110qp_scan_config& sc) {
 // The family of a rollout call, in the order each was built on the one before: from kScan a scan
 // config is read, from kReplan the loop re-plans, from kWorld the scans are cast (so neither `ranges`
 // nor sc->scan_rows is read), kRace casts see the race-mates, kContact records every row's clearance,
-// kBody is kContact with rectangular bodies in every cast and clearance, and kWalls is kBody with straight wall
-// segments next to the circles.
-enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact, kBody, kWalls };
+// kBody is kContact with rectangular bodies in every cast and clearance, kWalls is kBody with straight wall
+// segments next to the circles, and kRefresh is kWalls with a refresh period for the scan MPC holds.
+enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact, kBody, kWalls, kRefresh };
 
 // The configs of a rollout call as the caller gave them and, once check_args has passed, the
 // kernels' parameters.
@@ -300,6 +309,7 @@ struct WorldLoop {
   bool walls;  // f110qp_rollout_walls[_dev]: the body family with the segments in the casts and the clearances
   f110qp::WallParams Wl;
   const double* segments;  // [wall_rows][S][4] or null
+  int every;  // f110qp_rollout_refresh[_dev]: the refresh period of MPC's scan, 0 (every other family): never
 };
 
 // f110qp_rollout_contact[_dev]: the race rollout with one clearance launch per row of x_traj, which also
@@ -325,7 +335,9 @@ static hipError_t world_cast(const WorldLoop& wl, int batch, const int* list, co
 // state machine with the plant step.
 // wl (the world rollout; r.ranges is not read): per tick the cast in front of the listed plan, on that
 // plan's list or, with ranges_traj, for all cars into row t. The gap records are those of one all-cars
-// cast at row 0 in front of the loop, held as at scan_rows = 1.
+// cast at row 0 in front of the loop, held as at scan_rows = 1. With wl->every = K >= 1 and rows computed, a
+// tick t >= 1 with t % K == 0 casts for all cars and one refresh launch behind the cast replaces the held
+// records and tick t's rows by those of row t's scans at row t's poses.
 // cl (the contact rollout, with wl): one clearance launch on row 0 behind the start kernel and one on row
 // t + 1 behind tick t's plant step, each marking crash_tick; with cl->stop the plant step parks.
 static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, const ReplanIO& r, hipStream_t s,
@@ -418,9 +430,16 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
     int* ps_t = tr.plan_status ? tr.plan_status + t * B : wi + i_ps;
     const float* scan_t = wl ? scan_row(t) : ranges + (scan_rows == 1 ? 0 : t * B * nr);
     if (wl) {
-      const bool all = wl->ranges_traj != nullptr;
+      const bool refresh = rows_on && wl->every > 0 && t > 0 && t % (size_t)wl->every == 0;
+      const bool all = wl->ranges_traj != nullptr || refresh;
       e = world_cast(*wl, io.B, all ? nullptr : list, all ? nullptr : count + t, io.x(t), scan_row(t), s);
       if (e != hipSuccess) return hip_fail(e, "scan cast launch");
+      if (refresh) {  // MPC's scan becomes tick t's: new records, and the rows this tick's solve reads
+        e = f110qp::launch_gap_refresh(io.B, scan_row(t), sc.num_ranges, sc.angle_min, sc.angle_increment,
+                                       sc.angle_max, sc.ftg_thresh, sc.divider, sc.buffer, io.x(t), w.rec,
+                                       w.rows + t * w.rstep, s);
+        if (e != hipSuccess) return hip_fail(e, "gap refresh launch");
+      }
     }
     e = f110qp::launch_plan_listed(cfg.K, io.B, list, count + t, pose_row(t), scan_t, sc.num_ranges, sc.angle_min,
                                    sc.angle_increment, sc.angle_max, r.table, r.waypoints, rp.num_waypoints,
@@ -579,12 +598,12 @@ static int replan_call(f110qp_ctx* c, LoopCfg cfg, RolloutIO io, const ReplanIO&
 
 // f110qp_rollout_world[_dev] (kWorld; race not read), f110qp_rollout_race[_dev] (kRace) and
 // f110qp_rollout_contact[_dev] (kContact: cc and the records k), f110qp_rollout_body[_dev] (kBody: body too) and
-// f110qp_rollout_walls[_dev] (kWalls: walls and segments too).
+// f110qp_rollout_walls[_dev] (kWalls: walls and segments too), f110qp_rollout_refresh[_dev] (kRefresh: rf too).
 static int world_call(f110qp_ctx* c, LoopCfg cfg, const f110qp_world_config* wc, const f110qp_race_config* race,
                       RolloutIO io, const ReplanIO& r, const double* circles, float* rgt, Where w,
                       const f110qp_contact_config* cc = nullptr, const ContactIO* k = nullptr,
                       const f110qp_body_config* body = nullptr, const f110qp_walls_config* walls = nullptr,
-                      const double* segments = nullptr) {
+                      const double* segments = nullptr, const f110qp_refresh_config* rf = nullptr) {
   WorldLoop wl{};
   int rv = check_args(c, &cfg, &io, nullptr, nullptr, &r);
   if (rv) return rv;
@@ -595,10 +614,11 @@ static int world_call(f110qp_ctx* c, LoopCfg cfg, const f110qp_world_config* wc,
   if (contact && (rv = contact_params(cc))) return rv;
   wl.body = cfg.fam >= kBody;
   if (wl.body && (rv = body_params(body, &wl.H))) return rv;
-  wl.walls = cfg.fam == kWalls;
+  wl.walls = cfg.fam >= kWalls;
   if (wl.walls && (rv = wall_params(walls, io.B, (long long)wc->num_circles + race->group_size - 1, segments, &wl.Wl)))
     return rv;
   wl.segments = wl.walls ? segments : nullptr;
+  if (cfg.fam == kRefresh && (rv = refresh_params(rf, &wl.every))) return rv;
   if (io.B == 0) return F110QP_OK;
   if (contact && (!k->clear_traj || !k->crash_tick))
     return fail(F110QP_ERR_INVALID, "clear_traj/crash_tick must be non-NULL");
@@ -1196,6 +1216,59 @@ int f110qp_rollout_walls(f110qp_ctx* c, const f110qp_rollout_config* rc, const f
   const ContactIO k{clt, nrt, crash};
   return world_call(c, LoopCfg{kWalls, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k, body, walls,
                     segments);
+}
+
+// ---- a refreshed MPC scan (f110qp_gap_refresh_dev, f110qp_rollout_refresh[_dev]) -------------------------------
+
+void f110qp_default_refresh_config(f110qp_refresh_config* rf) {
+  if (!rf) return;
+  std::memset(rf, 0, sizeof(*rf));
+}
+
+int f110qp_gap_refresh_dev(const f110qp_scan_config* sc, int batch, const float* ranges, const double* states,
+                           f110qp_gap_record* gap, float* hs, void* stream) {
+  const int rv = check_scan_config(sc, false, 0);
+  if (rv) return rv;
+  if (batch < 1) return fail(F110QP_ERR_INVALID, "batch < 1");
+  if (!ranges || !states || !gap || !hs)
+    return fail(F110QP_ERR_INVALID, "ranges/states/gap_out/hs_out must be non-NULL");
+  const hipError_t e = f110qp::launch_gap_refresh(batch, ranges, sc->num_ranges, sc->angle_min, sc->angle_increment,
+                                                  sc->angle_max, sc->ftg_thresh, sc->divider, sc->buffer, states,
+                                                  (f110qp::GapRecord*)gap, hs, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "gap refresh launch");
+  return F110QP_OK;
+}
+
+int f110qp_rollout_refresh_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                               const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                               const f110qp_race_config* race, const f110qp_contact_config* cc,
+                               const f110qp_body_config* body, const f110qp_walls_config* walls,
+                               const f110qp_refresh_config* rf, int batch, const double* table, const double* wp,
+                               double* xr, int* have, const double* circles, const double* segments, double* xt,
+                               double* ult, float* ua, int* stt, int* itt, double* cot, float* up, float* xp,
+                               float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset, float* rgt,
+                               double* clt, int* nrt, int* crash, void* stream) {
+  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
+  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
+  const ContactIO k{clt, nrt, crash};
+  return world_call(c, LoopCfg{kRefresh, rc, sc, rp}, wc, race, io, r, circles, rgt, on_stream(stream), cc, &k, body,
+                    walls, segments, rf);
+}
+
+int f110qp_rollout_refresh(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                           const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                           const f110qp_race_config* race, const f110qp_contact_config* cc,
+                           const f110qp_body_config* body, const f110qp_walls_config* walls,
+                           const f110qp_refresh_config* rf, int batch, const double* table, const double* wp,
+                           double* xr, int* have, const double* circles, const double* segments, double* xt,
+                           double* ult, float* ua, int* stt, int* itt, double* cot, float* up, float* xp, float* hst,
+                           int* kt, int* pst, int* btt, int* bgt, double* poset, float* rgt, double* clt, int* nrt,
+                           int* crash) {
+  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
+  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
+  const ContactIO k{clt, nrt, crash};
+  return world_call(c, LoopCfg{kRefresh, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k, body, walls,
+                    segments, rf);
 }
 
 }  // extern "C"

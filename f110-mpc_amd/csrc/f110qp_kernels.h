@@ -296,6 +296,12 @@ hipError_t launch_gap_search(int count, const float* ranges, int num_ranges, flo
 hipError_t launch_half_space_rows(int B, int num_ranges, float angle_min, float angle_inc,
                                   const GapRecord* gap, const double* states, float* hs,
                                   hipStream_t stream);
+// Both in one launch, one wave per car (f110qp_gap_refresh_dev): ranges [B][num_ranges] and states
+// [B][3] double -> rec [B] and hs [B][2][3], bit-identical to launch_gap_search followed by
+// launch_half_space_rows on the same arrays.
+hipError_t launch_gap_refresh(int B, const float* ranges, int num_ranges, float angle_min, float angle_inc,
+                              float angle_max, float thresh, float divider, float buffer, const double* states,
+                              GapRecord* rec, float* hs, hipStream_t stream);
 
 // launch_advance plus that geometry at x_next, written to hs_next [B][2][3] (null: no rows, the plant
 // step alone): one launch. Every other output is bit-identical to launch_advance's.

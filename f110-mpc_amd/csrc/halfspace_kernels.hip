@@ -43,12 +43,33 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
   return v;
 }
 
+// The end of half_space_kernel's REFRESH mode: a scan's record and its rows at the pose, computed by
+// every lane with the same values (half_space_rows on a whole wave costs what it costs on one lane, and
+// a partially masked tail is the slow one); lane 0 stores both.
+__device__ __forceinline__ void refresh_store(const GapRecord g, const int nr, const double poseX,
+                                              const double poseY, const double ori, const float angle_min,
+                                              const float angle_inc, const int lane,
+                                              GapRecord* __restrict__ rec, float* __restrict__ o) {
+  float h[6];
+  half_space_rows(g, nr, poseX, poseY, ori, angle_min, angle_inc, h);
+  if (lane == 0) {
+    *rec = g;
+#pragma unroll
+    for (int j = 0; j < 6; j++) o[j] = h[j];
+  }
+}
+
 // ST: the scalar of states, float or double (f110qp_find_half_spaces_dev_dbl: x and y unrounded, ori
 // narrowed to float where the reference narrows it, float current_angle = state.ori()).
 // SEARCH: the gap search alone (f110qp_gap_search_dev): no pose is read and the geometry tail is
 // left out; lane 0 writes the scan's GapRecord (halfspace_geom.h) to rec[b] instead of hs / gap_lo /
 // gap_hi. The search reads only the scan, so it runs once per scan where the pose changes per tick.
-template <typename ST, bool SEARCH>
+// REFRESH (f110qp_gap_refresh_dev; ST double, SEARCH false): the search, then the record AND the rows
+// of half_space_rows (halfspace_geom.h) at the pose, which is what launch_gap_search followed by
+// launch_half_space_rows leave: this kernel's own tail (the even / odd lane sincos) is left out. The
+// mode is a defaulted third parameter and every branch on it is `if constexpr`, so the three older
+// instantiations compile to the code they had (DESIGN.md 2i lists their metadata).
+template <typename ST, bool SEARCH, bool REFRESH = false>
 __global__ __launch_bounds__(256) void half_space_kernel(int B, const ST* __restrict__ states,
                                                          const float* __restrict__ ranges,
                                                          int nr, float angle_min, float angle_inc,
@@ -129,14 +150,17 @@ __global__ __launch_bounds__(256) void half_space_kernel(int B, const ST* __rest
     best_hi = (int)((float)best_hi - buffer);
     best_lo = (int)((float)best_lo + buffer);
   }
-  if constexpr (!SEARCH) {
+  if constexpr (!SEARCH && !REFRESH) {
     if (lane == 0 && gap_lo) gap_lo[b] = best_lo;
     if (lane == 0 && gap_hi) gap_hi[b] = best_hi;
   }
   float* o = hs + (size_t)b * 6;
   if (best_lo < 0 || best_hi < 0 || best_lo >= nr || best_hi >= nr) {  // wave-uniform
     const float nanv = __int_as_float(0x7fc00000);
-    if constexpr (SEARCH) {
+    if constexpr (REFRESH) {
+      refresh_store(GapRecord{best_lo, best_hi, nanv, nanv}, nr, st0, st1, st2, angle_min, angle_inc, lane,
+                    rec + b, o);
+    } else if constexpr (SEARCH) {
       if (lane == 0) rec[b] = GapRecord{best_lo, best_hi, nanv, nanv};
     } else {
       if (lane == 0)
@@ -150,7 +174,7 @@ __global__ __launch_bounds__(256) void half_space_kernel(int B, const ST* __rest
   const float ang2 = angle_min + (float)best_hi * angle_inc + cur;
   // even lanes evaluate the first end point's cos/sin, odd lanes the second (::cos/::sin(double))
   double s1 = 0., c1d = 0., s2 = 0., c2d = 0.;
-  if constexpr (!SEARCH) {
+  if constexpr (!SEARCH && !REFRESH) {
     double sl, cl;
     sincos((double)((lane & 1) ? ang2 : ang1), &sl, &cl);
     s1 = __shfl(sl, 0), c1d = __shfl(cl, 0);
@@ -176,6 +200,10 @@ __global__ __launch_bounds__(256) void half_space_kernel(int B, const ST* __rest
   }
   if constexpr (SEARCH) {
     if (lane == 0) rec[b] = GapRecord{best_lo, best_hi, rlo, rhi};
+    return;
+  }
+  if constexpr (REFRESH) {
+    refresh_store(GapRecord{best_lo, best_hi, rlo, rhi}, nr, st0, st1, st2, angle_min, angle_inc, lane, rec + b, o);
     return;
   }
   const float p1x = (float)((double)rlo * c1d + poseX);  // :181-185
@@ -222,6 +250,16 @@ hipError_t launch_gap_search(int count, const float* ranges, int nr, float angle
   hipLaunchKernelGGL((half_space_kernel<float, true>), dim3((count + kHsWaves - 1) / kHsWaves),
                      dim3(64 * kHsWaves), 0, s, count, (const float*)nullptr, ranges, nr, angle_min, angle_inc,
                      angle_max, thresh, divider, buffer, (float*)nullptr, (int*)nullptr, (int*)nullptr, rec);
+  return hipGetLastError();
+}
+
+hipError_t launch_gap_refresh(int B, const float* ranges, int nr, float angle_min, float angle_inc,
+                              float angle_max, float thresh, float divider, float buffer, const double* states,
+                              GapRecord* rec, float* hs, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL((half_space_kernel<double, false, true>), dim3((B + kHsWaves - 1) / kHsWaves),
+                     dim3(64 * kHsWaves), 0, s, B, states, ranges, nr, angle_min, angle_inc, angle_max, thresh,
+                     divider, buffer, hs, (int*)nullptr, (int*)nullptr, rec);
   return hipGetLastError();
 }
 

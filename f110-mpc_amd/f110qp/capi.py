@@ -145,6 +145,10 @@ EXPORTED = (
     "f110qp_clearance_walls_dev",
     "f110qp_rollout_walls_dev",
     "f110qp_rollout_walls",
+    "f110qp_default_refresh_config",
+    "f110qp_gap_refresh_dev",
+    "f110qp_rollout_refresh_dev",
+    "f110qp_rollout_refresh",
     "f110qp_path_lengths",
     "f110qp_progress_dev",
     "f110qp_standings_dev",
@@ -255,6 +259,12 @@ class WallsConfig(C.Structure):
     ]
 
 
+class RefreshConfig(C.Structure):
+    _fields_ = [
+        ("every", C.c_int),
+    ]
+
+
 # f110qp_gap_record (16 bytes) as a numpy record
 GAP_RECORD_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("r_lo", np.float32), ("r_hi", np.float32)])
 
@@ -341,6 +351,11 @@ def load(test: bool = False):
     L.f110qp_clearance_walls_dev.argtypes = [wcp, rcp, bcp, wlp, C.c_int, C.c_int] + [fp] * 6
     L.f110qp_rollout_walls_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, C.c_int] + [fp] * 25
     L.f110qp_rollout_walls.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, C.c_int] + [fp] * 24
+    rfp = C.POINTER(RefreshConfig)
+    L.f110qp_default_refresh_config.argtypes = [rfp]
+    L.f110qp_gap_refresh_dev.argtypes = [sp, C.c_int] + [fp] * 5
+    L.f110qp_rollout_refresh_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, C.c_int] + [fp] * 25
+    L.f110qp_rollout_refresh.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, C.c_int] + [fp] * 24
     L.f110qp_path_lengths.argtypes = [fp, C.c_int, fp]
     L.f110qp_progress_dev.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_int] + [fp] * 4
     L.f110qp_standings_dev.argtypes = [rcp, C.c_int, C.c_int, fp, C.c_double] + [fp] * 4
@@ -478,6 +493,15 @@ def default_walls_config(**over) -> WallsConfig:
     """f110qp_default_walls_config: num_segments 0 (the caller's), wall_rows 1."""
     c = WallsConfig()
     load().f110qp_default_walls_config(C.byref(c))
+    for k, v in over.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_refresh_config(**over) -> RefreshConfig:
+    """f110qp_default_refresh_config: every 0 (MPC keeps its first scan, the reference)."""
+    c = RefreshConfig()
+    load().f110qp_default_refresh_config(C.byref(c))
     for k, v in over.items():
         setattr(c, k, v)
     return c
@@ -961,7 +985,8 @@ class Solver:
                           waypoints, x_ref, have_path, circles, x_traj, u_lin_traj, u_applied, status_traj,
                           iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
                           plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
-                          ranges_traj=None, stream=None, _race=None, _contact=None, _body=None, _walls=None):
+                          ranges_traj=None, stream=None, _race=None, _contact=None, _body=None, _walls=None,
+                          _refresh=None):
         """rollout_replan_dev with every tick's scan cast at that tick's pose (f110qp_rollout_world_dev): wc
         and circles [world_rows,C,3] f64 replace ranges, sc.scan_rows is not read, and the optional
         ranges_traj [T,B,num_ranges] f32 records every car's scan of every tick."""
@@ -990,6 +1015,8 @@ class Solver:
             Sn = int(walls.num_segments)
             more = more + [(segments, "f64", 4 * max(Sn, 0) * max(int(walls.wall_rows), 0), "segments", Sn <= 0)]
             name, cfgs, world = "f110qp_rollout_walls_dev", cfgs + [C.byref(walls)], world + [_tp(segments)]
+            if _refresh is not None:  # the refresh config behind walls
+                name, cfgs = "f110qp_rollout_refresh_dev", cfgs + [C.byref(_refresh)]
         _devs(*self._plan_specs(rp, B, *plan), (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
               *self._traj_specs(T, B, *traj), *self._record_specs(T, B, *rec),
               (ranges_traj, "f32", T * B * int(sc.num_ranges), "ranges_traj", True), *more)
@@ -1060,9 +1087,28 @@ class Solver:
                                _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
                                _walls=(walls, segments))
 
+    def rollout_refresh_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
+                            cc: ContactConfig, body: BodyConfig, walls: WallsConfig, rf: RefreshConfig, table, waypoints,
+                            x_ref, have_path, circles, segments, x_traj, u_lin_traj, u_applied, status_traj, clear_traj,
+                            crash_tick, nearest_traj=None, iters_traj=None, cost_traj=None, u_plan=None, x_plan=None,
+                            hs_traj=None, kind_traj=None, plan_status_traj=None, best_traj_traj=None,
+                            best_global_traj=None, pose_traj=None, ranges_traj=None, stream=None):
+        """rollout_walls_dev with the scan MPC holds replaced every rf.every ticks by the scan cast at that tick's
+        pose (f110qp_rollout_refresh_dev): rf follows walls, everything else as there; rf.every = 0 is
+        rollout_walls_dev."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
+                or not isinstance(walls, WallsConfig) or not isinstance(rf, RefreshConfig):
+            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig, walls a WallsConfig "
+                              "and rf a RefreshConfig")
+        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
+                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
+                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
+                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
+                               _walls=(walls, segments), _refresh=rf)
+
     def rollout_world(self, x0, u_lin, circles, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
                       wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
-                      scans=False, rc=None, _race=None, _contact=None, _body=None, _segments=None):
+                      scans=False, rc=None, _race=None, _contact=None, _body=None, _segments=None, _refresh=None):
         """rollout_replan() in a world of circles (f110qp_rollout_world, synchronous): circles [C,3] (one world
         for all cars) or [B,C,3] float64 replace ranges; wc defaults to f110qp_default_world_config with
         num_circles and world_rows taken from the array. scans=True adds ranges_traj [T,B,num_ranges]."""
@@ -1102,6 +1148,8 @@ class Solver:
             if wl.wall_rows not in (1, B):
                 raise F110QPError(f"segments must hold one set or B = {B} sets, got {wl.wall_rows}")
             name, cfgs, world = "f110qp_rollout_walls", cfgs + [C.byref(wl)], world + [_p(sg) if sg.size else None]
+            if _refresh is not None:  # the refresh config behind walls
+                name, cfgs = "f110qp_rollout_refresh", cfgs + [C.byref(_refresh)]
         self._chk(getattr(self.lib, name)(
             self._h, C.byref(self._ticks_config(rc, T)), C.byref(sc), C.byref(rp), C.byref(w),
             *cfgs, B, _p(tab), _p(wp) if wp.shape[0] else None, _p(xr), _p(hv),
@@ -1147,6 +1195,19 @@ class Solver:
         return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
                                   objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
                                   _segments=segments)
+
+    def rollout_refresh(self, x0, u_lin, circles, segments, race: RaceConfig, cc: ContactConfig, body: BodyConfig,
+                        rf: RefreshConfig, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
+                        wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
+                        scans=False, nearest=True, rc=None):
+        """rollout_walls() with the scan MPC holds replaced every rf.every ticks (f110qp_rollout_refresh,
+        synchronous): rf follows body, everything else as there."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
+                or not isinstance(rf, RefreshConfig):
+            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig and rf a RefreshConfig")
+        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
+                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
+                                  _segments=segments, _refresh=rf)
 
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
@@ -1734,6 +1795,23 @@ def half_space_rows_dev(sc: ScanConfig, gap, states, hs_out, stream=None):
         stream = torch.cuda.current_stream(states.device)
     _check(load().f110qp_half_space_rows_dev(C.byref(sc), B, _tp(gap), _tp(states), _tp(hs_out),
                                              C.c_void_p(stream.cuda_stream)), "f110qp_half_space_rows_dev")
+
+
+def gap_refresh_dev(sc: ScanConfig, ranges, states, gap_out, hs_out, stream=None):
+    """gap_search_dev and half_space_rows_dev of B cars in one launch (f110qp_gap_refresh_dev): ranges
+    [B, sc.num_ranges] f32, states [B,3] f64 -> gap_out (an int32 tensor of 4 words per car) and hs_out
+    [B,2,3] f32, both bit-identical to those two calls."""
+    import torch
+
+    B, R = int(states.shape[0]), int(sc.num_ranges)
+    if ranges.dim() != 2 or tuple(ranges.shape) != (B, R):
+        raise F110QPError(f"ranges must be [B = {B}, num_ranges = {R}], got {tuple(ranges.shape)}")
+    _devs((ranges, "f32", B * R, "ranges"), (states, "f64", 3 * B, "states"), (gap_out, "i32", 4 * B, "gap_out"),
+          (hs_out, "f32", 6 * B, "hs_out"))
+    if stream is None:
+        stream = torch.cuda.current_stream(states.device)
+    _check(load().f110qp_gap_refresh_dev(C.byref(sc), B, _tp(ranges), _tp(states), _tp(gap_out), _tp(hs_out),
+                                         C.c_void_p(stream.cuda_stream)), "f110qp_gap_refresh_dev")
 
 
 # ---- planning stage (plan_kernels.hip) ---------------------------------------------------------

@@ -1224,6 +1224,76 @@ int f110qp_rollout_walls(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const
                          int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
                          int* nearest_traj, int* crash_tick);
 
+/* ---- closed loop with a refreshed MPC scan: the gap rows follow the world --------------------------------
+ * In every world family above the gap records come from one all-cars cast at row 0 and are held for the whole
+ * call, as the reference holds its first scan (src/project.cpp:45-49): only the end-point geometry follows the
+ * car, and the rows of tick 40 describe where the walls and the opponents stood at tick 0. The family below is
+ * f110qp_rollout_walls[_dev] with a refresh period for the scan MPC holds. The refresh period is a modelling
+ * choice of this library, not the reference's; every = 0 is the reference. Additive: F110QP_API_VERSION stays 6,
+ * and no call above changes its results. The disc-body families get no refresh. */
+typedef struct {
+  int every;   /* K >= 0. 0: never (the reference: MPC keeps its first scan). K >= 1: MPC's scan is replaced */
+               /* at every tick t with 1 <= t <= T - 1 and t % K == 0 by the scan cast at x_traj row t       */
+} f110qp_refresh_config;
+
+/* Zeroes *rf: every = 0. */
+void f110qp_default_refresh_config(f110qp_refresh_config* rf);
+
+/* The gap search of `batch` scans and the end-point geometry at the given poses in ONE launch (device pointers,
+ * asynchronous, one wavefront per car): ranges [B][num_ranges] float32, states [B][3] double -> gap_out [B] and
+ * hs_out [B][2][3] float32. gap_out is bit-identical to f110qp_gap_search_dev on the same scans, and hs_out to
+ * f110qp_half_space_rows_dev on those records and states (and so to f110qp_find_half_spaces_dev_dbl). A scan
+ * without a gap gives the record with NaN r_lo / r_hi and NaN rows, as those calls do. sc->scan_rows is not read.
+ * F110QP_ERR_INVALID before any HIP call: a NULL sc, ranges, states, gap_out or hs_out, batch < 1, and every sc
+ * rule that f110qp_gap_search_dev checks. */
+int f110qp_gap_refresh_dev(const f110qp_scan_config* sc, int batch, const float* ranges, const double* states,
+                           f110qp_gap_record* gap_out, float* hs_out, void* stream);
+
+/* f110qp_rollout_walls_dev, word for word, with rf following walls.
+ *   Argument check. F110QP_ERR_INVALID before the first launch for a NULL rf or every < 0, on top of every check
+ *     of the walls call.
+ *   every == 0. The call makes the launches of f110qp_rollout_walls_dev, and every array is bit-identical to
+ *     that call's. So is a call whose every exceeds T - 1.
+ *   No rows computed (gap_mode INACTIVE and hs_traj NULL): rf is checked and otherwise not read; no extra launch.
+ *   Refresh tick. At a tick t with 1 <= t <= T - 1 and t % every == 0, tick t's cast runs for all B cars (parked
+ *     cars included) at x_traj row t: with ranges_traj into row t, where it already goes; without it into the
+ *     context's buffer of B rows, in place of the listed cast. The listed plan reads the rows it would have read
+ *     (a car's scan does not depend on the list).
+ *   Refresh launch. One f110qp_gap_refresh_dev launch follows on that scan row and x_traj row t. It replaces all
+ *     B held records and overwrites the rows that tick t's solve reads (those that tick t - 1's plant step had
+ *     computed from the old record). It runs before the listed plan and the solve of tick t.
+ *   Later ticks. From tick t on the fused plant step builds the next rows from the new records, as it does from
+ *     the first ones.
+ *   Non-refresh tick. Exactly the walls call's launches.
+ *   Added work. A refresh tick adds one launch (and, with ranges_traj NULL, casts all cars instead of the listed
+ *     ones). No memset, host synchronisation, read-back or allocation is added inside the loop.
+ *   Inherited. Parking, clearances, crash_tick, NaN rows (a refreshed scan without a gap), fail_u and every
+ *     stream-order statement are the walls call's. */
+int f110qp_rollout_refresh_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                               const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                               const f110qp_race_config* race, const f110qp_contact_config* cc,
+                               const f110qp_body_config* body, const f110qp_walls_config* walls,
+                               const f110qp_refresh_config* rf, int batch, const double* table,
+                               const double* waypoints, double* x_ref, int* have_path, const double* circles,
+                               const double* segments, double* x_traj, double* u_lin_traj, float* u_applied,
+                               int* status_traj, int* iters_traj, double* cost_traj, float* u_plan, float* x_plan,
+                               float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
+                               int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
+                               int* nearest_traj, int* crash_tick, void* stream);
+
+/* Same on host pointers (synchronous), staged as f110qp_rollout_walls: the call adds no array. */
+int f110qp_rollout_refresh(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                           const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                           const f110qp_race_config* race, const f110qp_contact_config* cc,
+                           const f110qp_body_config* body, const f110qp_walls_config* walls,
+                           const f110qp_refresh_config* rf, int batch, const double* table,
+                           const double* waypoints, double* x_ref, int* have_path, const double* circles,
+                           const double* segments, double* x_traj, double* u_lin_traj, float* u_applied,
+                           int* status_traj, int* iters_traj, double* cost_traj, float* u_plan, float* x_plan,
+                           float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
+                           int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
+                           int* nearest_traj, int* crash_tick);
+
 /* ---- race standings: progress along the track, laps and positions ---------------------------------------
  * The calls above return poses; the calls below say who is ahead. They run after the fact on x_traj, or on any
  * [rows][B][3] pose array: nothing inside a closed loop reads a standing, so there is no rollout family of
