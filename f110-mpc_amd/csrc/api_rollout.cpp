@@ -296,19 +296,12 @@ static int rollout_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io,
   return F110QP_OK;
 }
 
-// f110qp_rollout_world[_dev]: tick t's scans are cast at tick t's pose instead of read from `ranges`.
-// race (f110qp_rollout_race[_dev]): every cast also sees the race-mates at the poses it casts from.
+// f110qp_rollout_world[_dev] and the families on top of it: tick t's scans are cast at tick t's pose in the
+// world w instead of read from `ranges`; from WORLD_RACE every cast also sees the race-mates at the poses it
+// casts from, and the clearances are those of the same world.
 struct WorldLoop {
-  f110qp::CastParams P;
-  const double* circles;  // [world_rows][C][3]
-  float* ranges_traj;     // [T][B][num_ranges] or null: one row set in the context, listed cars only
-  bool race;
-  f110qp::RaceParams Q;
-  bool body;  // f110qp_rollout_body[_dev]: the mates are rectangles, in the casts and in the clearances
-  f110qp::BodyParams H;
-  bool walls;  // f110qp_rollout_walls[_dev]: the body family with the segments in the casts and the clearances
-  f110qp::WallParams Wl;
-  const double* segments;  // [wall_rows][S][4] or null
+  f110qp::World w;     // checked (world_of); its circles and segments device pointers in the tick loop
+  float* ranges_traj;  // [T][B][num_ranges] or null: one row set in the context, listed cars only
   int every;  // f110qp_rollout_refresh[_dev]: the refresh period of MPC's scan, 0 (every other family): never
 };
 
@@ -319,16 +312,6 @@ struct ContactLoop {
   double margin;
   ContactIO io;
 };
-
-static hipError_t world_cast(const WorldLoop& wl, int batch, const int* list, const int* count, const double* x,
-                             float* ranges, hipStream_t s) {
-  if (wl.walls)
-    return f110qp::launch_cast_scans_walls(wl.P, wl.Q, wl.H, wl.Wl, batch, list, count, x, wl.circles, wl.segments,
-                                           ranges, s);
-  if (wl.body) return f110qp::launch_cast_scans_body(wl.P, wl.Q, wl.H, batch, list, count, x, wl.circles, ranges, s);
-  return wl.race ? f110qp::launch_cast_scans_race(wl.P, wl.Q, batch, list, count, x, wl.circles, ranges, s)
-                 : f110qp::launch_cast_scans(wl.P, batch, list, count, x, wl.circles, ranges, s);
-}
 
 // The T ticks of a checked re-planning rollout on device pointers. Every workspace is sized in front
 // of the loop; the loop only launches: the listed plan, the launches of one _dbl solve call, the
@@ -387,7 +370,7 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
   if (rows_on) {
     if (wl) {  // MPC's scan is the first one (src/project.cpp:45-49): every car's, at row 0
       ranges = scan_row(0);
-      e = world_cast(*wl, io.B, nullptr, nullptr, io.x(0), scan_row(0), s);
+      e = f110qp::launch_cast_scans(wl->w, io.B, nullptr, nullptr, io.x(0), scan_row(0), s);
       if (e != hipSuccess) return hip_fail(e, "scan cast launch");
     }
     e = f110qp::launch_gap_search(scan_rows * io.B, ranges, sc.num_ranges, sc.angle_min, sc.angle_increment,
@@ -414,16 +397,9 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
   }
   // row t's clearances into clear_traj / nearest_traj, crash_tick started (row 0) or kept up
   auto clearance_row = [&](size_t t) {
-    const f110qp::ClearParams cp{wl->P.C, wl->P.world_rows};
     const f110qp::ContactMark mk{cl->io.crash_tick, (int)t, t == 0, cl->margin};
-    int* near = cl->io.nearest_traj ? cl->io.nearest_traj + t * B : nullptr;
-    if (wl->walls)
-      return f110qp::launch_clearance_walls(cp, wl->Q, wl->H, wl->Wl, io.B, 1, io.x(t), wl->circles, wl->segments,
-                                            cl->io.clear_traj + t * B, near, mk, s);
-    return wl->body ? f110qp::launch_clearance_body(cp, wl->Q, wl->H, io.B, 1, io.x(t), wl->circles,
-                                                    cl->io.clear_traj + t * B, near, mk, s)
-                    : f110qp::launch_clearance(cp, wl->Q, io.B, 1, io.x(t), wl->circles, cl->io.clear_traj + t * B,
-                                               near, mk, s);
+    return f110qp::launch_clearance(wl->w, io.B, 1, io.x(t), cl->io.clear_traj + t * B,
+                                    cl->io.nearest_traj ? cl->io.nearest_traj + t * B : nullptr, mk, s);
   };
   if (cl && (e = clearance_row(0)) != hipSuccess) return hip_fail(e, "clearance launch");
   for (size_t t = 0; t < T; t++) {
@@ -432,7 +408,8 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
     if (wl) {
       const bool refresh = rows_on && wl->every > 0 && t > 0 && t % (size_t)wl->every == 0;
       const bool all = wl->ranges_traj != nullptr || refresh;
-      e = world_cast(*wl, io.B, all ? nullptr : list, all ? nullptr : count + t, io.x(t), scan_row(t), s);
+      e = f110qp::launch_cast_scans(wl->w, io.B, all ? nullptr : list, all ? nullptr : count + t, io.x(t), scan_row(t),
+                                    s);
       if (e != hipSuccess) return hip_fail(e, "scan cast launch");
       if (refresh) {  // MPC's scan becomes tick t's: new records, and the rows this tick's solve reads
         e = f110qp::launch_gap_refresh(io.B, scan_row(t), sc.num_ranges, sc.angle_min, sc.angle_increment,
@@ -559,8 +536,8 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
   WorldIO hw{}, dw{};
   ContactLoop dcl{};
   if (wl)
-    hw = WorldIO{wl->circles, (size_t)wl->P.world_rows * (size_t)wl->P.C * 3 * 8, wl->ranges_traj, wl->segments,
-                 wl->walls ? (size_t)wl->Wl.wall_rows * (size_t)wl->Wl.S * 4 * 8 : 0};
+    hw = WorldIO{wl->w.circles, (size_t)wl->w.P.world_rows * (size_t)wl->w.P.C * 3 * 8, wl->ranges_traj, wl->w.segments,
+                 wl->w.family == f110qp::WORLD_WALLS ? (size_t)wl->w.Wl.wall_rows * (size_t)wl->w.Wl.S * 4 * 8 : 0};
   if (cl) dcl = *cl;
   stage::replan_fields(L, io, &d, r, &dr, *cfg.sc, (size_t)cfg.K.T, (size_t)cfg.K.P, (size_t)cfg.rp->num_waypoints,
                        wl ? &hw : nullptr, &dw, cl ? &cl->io : nullptr, &dcl.io);
@@ -568,9 +545,9 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
   WorldLoop dwl{};
   if (wl) {
     dwl = *wl;
-    dwl.circles = dw.circles;
+    dwl.w.circles = dw.circles;
     dwl.ranges_traj = dw.ranges_traj;
-    dwl.segments = dw.segments;
+    dwl.w.segments = dw.segments;
   }
   if ((rv = replan_ticks(c, cfg, d, dr, s, wl ? &dwl : nullptr, cl ? &dcl : nullptr))) return rv;
   return stage_out(c, L, s);
@@ -596,38 +573,109 @@ static int replan_call(f110qp_ctx* c, LoopCfg cfg, RolloutIO io, const ReplanIO&
   return w.host ? replan_host(c, cfg, io, r, nullptr) : replan_ticks(c, cfg, io, r, w.stream, nullptr);
 }
 
-// f110qp_rollout_world[_dev] (kWorld; race not read), f110qp_rollout_race[_dev] (kRace) and
-// f110qp_rollout_contact[_dev] (kContact: cc and the records k), f110qp_rollout_body[_dev] (kBody: body too) and
-// f110qp_rollout_walls[_dev] (kWalls: walls and segments too), f110qp_rollout_refresh[_dev] (kRefresh: rf too).
-static int world_call(f110qp_ctx* c, LoopCfg cfg, const f110qp_world_config* wc, const f110qp_race_config* race,
-                      RolloutIO io, const ReplanIO& r, const double* circles, float* rgt, Where w,
-                      const f110qp_contact_config* cc = nullptr, const ContactIO* k = nullptr,
-                      const f110qp_body_config* body = nullptr, const f110qp_walls_config* walls = nullptr,
-                      const double* segments = nullptr, const f110qp_refresh_config* rf = nullptr) {
-  WorldLoop wl{};
-  int rv = check_args(c, &cfg, &io, nullptr, nullptr, &r);
+// The configs of a world-family call as the caller gave them; a family reads those up to its own (wc: all,
+// race: from kRace and every clearance, cc: from kContact, body: from kBody, walls: from kWalls, rf: kRefresh).
+struct WorldCfgs {
+  const f110qp_world_config* wc;
+  const f110qp_race_config* race;
+  const f110qp_contact_config* cc;
+  const f110qp_body_config* body;
+  const f110qp_walls_config* walls;
+  const f110qp_refresh_config* rf;
+};
+
+// The world of a cast, a clearance or a world rollout, checked in the one order all of them share, into *w;
+// contact: the call also reads k.cc, whose turn is behind the race's. sc null: no scan geometry (clearances).
+static int world_of(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const WorldCfgs& k, bool contact, int batch,
+                    const double* circles, const double* segments, f110qp::World* w) {
+  int rv = world_params(sc, k.wc, batch, circles, &w->P);
   if (rv) return rv;
-  if ((rv = world_params(cfg.sc, wc, io.B, circles, &wl.P))) return rv;
-  wl.race = cfg.fam >= kRace;
-  if (wl.race && (rv = race_params(race, io.B, wc->num_circles, &wl.Q))) return rv;
-  const bool contact = cfg.fam >= kContact;
-  if (contact && (rv = contact_params(cc))) return rv;
-  wl.body = cfg.fam >= kBody;
-  if (wl.body && (rv = body_params(body, &wl.H))) return rv;
-  wl.walls = cfg.fam >= kWalls;
-  if (wl.walls && (rv = wall_params(walls, io.B, (long long)wc->num_circles + race->group_size - 1, segments, &wl.Wl)))
+  if (fam >= f110qp::WORLD_RACE && (rv = race_params(k.race, batch, k.wc->num_circles, &w->Q))) return rv;
+  if (contact && (rv = contact_params(k.cc))) return rv;
+  if (fam >= f110qp::WORLD_BODY && (rv = body_params(k.body, &w->H))) return rv;
+  const bool walls = fam == f110qp::WORLD_WALLS;
+  if (walls && (rv = wall_params(k.walls, batch, (long long)k.wc->num_circles + k.race->group_size - 1, segments,
+                                 &w->Wl)))
     return rv;
-  wl.segments = wl.walls ? segments : nullptr;
-  if (cfg.fam == kRefresh && (rv = refresh_params(rf, &wl.every))) return rv;
-  if (io.B == 0) return F110QP_OK;
-  if (contact && (!k->clear_traj || !k->crash_tick))
+  w->family = fam;
+  w->circles = circles;
+  w->segments = walls ? segments : nullptr;
+  return F110QP_OK;
+}
+
+// The arrays of a world-family rollout call (a.k: from kContact).
+struct WorldArrays {
+  RolloutIO io;
+  ReplanIO r;
+  ContactIO k;
+};
+static WorldArrays world_arrays(int batch, const double* table, const double* wp, double* xr, int* have, double* xt,
+                                double* ult, float* ua, int* stt, int* itt, double* cot, float* up, float* xp,
+                                float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset, double* clt = nullptr,
+                                int* nrt = nullptr, int* crash = nullptr) {
+  return WorldArrays{RolloutIO{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp},
+                     ReplanIO{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}}, ContactIO{clt, nrt, crash}};
+}
+
+// f110qp_rollout_world[_dev] (kWorld), _race (kRace), _contact (kContact), _body (kBody), _walls (kWalls) and
+// _refresh (kRefresh) on the configs k their family reads.
+static int world_call(f110qp_ctx* c, LoopCfg cfg, const WorldCfgs& k, WorldArrays a, const double* circles,
+                      const double* segments, float* rgt, Where w) {
+  static const f110qp::WorldFamily kOf[] = {f110qp::WORLD_CIRCLES, f110qp::WORLD_RACE, f110qp::WORLD_RACE,
+                                            f110qp::WORLD_BODY,    f110qp::WORLD_WALLS, f110qp::WORLD_WALLS};
+  WorldLoop wl{};
+  int rv = check_args(c, &cfg, &a.io, nullptr, nullptr, &a.r);
+  if (rv) return rv;
+  const bool contact = cfg.fam >= kContact;
+  if ((rv = world_of(kOf[cfg.fam - kWorld], cfg.sc, k, contact, a.io.B, circles, segments, &wl.w))) return rv;
+  if (cfg.fam == kRefresh && (rv = refresh_params(k.rf, &wl.every))) return rv;
+  if (a.io.B == 0) return F110QP_OK;
+  if (contact && (!a.k.clear_traj || !a.k.crash_tick))
     return fail(F110QP_ERR_INVALID, "clear_traj/crash_tick must be non-NULL");
-  wl.circles = circles;
   wl.ranges_traj = rgt;
   ContactLoop cl{};
-  if (contact) cl = ContactLoop{cc->stop_on_contact == 1, cc->margin, *k};
+  if (contact) cl = ContactLoop{k.cc->stop_on_contact == 1, k.cc->margin, a.k};
   const ContactLoop* clp = contact ? &cl : nullptr;
-  return w.host ? replan_host(c, cfg, io, r, &wl, clp) : replan_ticks(c, cfg, io, r, w.stream, &wl, clp);
+  return w.host ? replan_host(c, cfg, a.io, a.r, &wl, clp) : replan_ticks(c, cfg, a.io, a.r, w.stream, &wl, clp);
+}
+
+// f110qp_cast_scans[_race|_body|_walls]_dev on the configs k their family reads.
+static int cast_call(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const WorldCfgs& k, int batch,
+                     const int* list, const int* count, const double* x, const double* circles,
+                     const double* segments, float* ranges, void* stream) {
+  static const char* const kLaunch[] = {"scan cast launch", "race scan cast launch", "body scan cast launch",
+                                        "walls scan cast launch"};
+  int rv = check_scan_config(sc, false, 0);
+  if (rv) return rv;
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  f110qp::World w{};
+  if ((rv = world_of(fam, sc, k, false, batch, circles, segments, &w))) return rv;
+  if ((list != nullptr) != (count != nullptr))
+    return fail(F110QP_ERR_INVALID, "list and count must be given together");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !ranges) return fail(F110QP_ERR_INVALID, "x/ranges must be non-NULL");
+  const hipError_t e = f110qp::launch_cast_scans(w, batch, list, count, x, ranges, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, kLaunch[fam]);
+  return F110QP_OK;
+}
+
+// f110qp_clearance[_body|_walls]_dev on the configs k their family reads (fam >= WORLD_RACE).
+static int clearance_call(f110qp::WorldFamily fam, const WorldCfgs& k, int batch, int rows, const double* x,
+                          const double* circles, const double* segments, double* clearance, int* nearest,
+                          void* stream) {
+  static const char* const kLaunch[] = {nullptr, "clearance launch", "body clearance launch", "walls clearance launch"};
+  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
+  f110qp::World w{};
+  const int rv = world_of(fam, nullptr, k, false, batch, circles, segments, &w);
+  if (rv) return rv;
+  if (rows < 1) return fail(F110QP_ERR_INVALID, "rows must be >= 1");
+  if (batch == 0) return F110QP_OK;
+  if (!x || !clearance) return fail(F110QP_ERR_INVALID, "x/clearance must be non-NULL");
+  if ((long long)rows * batch > (1ll << 30)) return fail(F110QP_ERR_INVALID, "rows x batch too large");
+  const hipError_t e = f110qp::launch_clearance(w, batch, rows, x, clearance, nearest,
+                                                f110qp::ContactMark{nullptr, 0, 0, 0.0}, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, kLaunch[fam]);
+  return F110QP_OK;
 }
 
 extern "C" {
@@ -906,18 +954,7 @@ void f110qp_default_world_config(f110qp_world_config* wc) {
 int f110qp_cast_scans_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc, int batch, const int* list,
                           const int* count, const double* x, const double* circles, float* ranges,
                           void* stream) {
-  int rv = check_scan_config(sc, false, 0);
-  if (rv) return rv;
-  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
-  f110qp::CastParams P;
-  if ((rv = world_params(sc, wc, batch, circles, &P))) return rv;
-  if ((list != nullptr) != (count != nullptr))
-    return fail(F110QP_ERR_INVALID, "list and count must be given together");
-  if (batch == 0) return F110QP_OK;
-  if (!x || !ranges) return fail(F110QP_ERR_INVALID, "x/ranges must be non-NULL");
-  const hipError_t e = f110qp::launch_cast_scans(P, batch, list, count, x, circles, ranges, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "scan cast launch");
-  return F110QP_OK;
+  return cast_call(f110qp::WORLD_CIRCLES, sc, WorldCfgs{wc}, batch, list, count, x, circles, nullptr, ranges, stream);
 }
 
 int f110qp_rollout_world_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -926,9 +963,9 @@ int f110qp_rollout_world_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, con
                              double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up,
                              float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset,
                              float* rgt, void* stream) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  return world_call(c, LoopCfg{kWorld, rc, sc, rp}, wc, nullptr, io, r, circles, rgt, on_stream(stream));
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset);
+  return world_call(c, LoopCfg{kWorld, rc, sc, rp}, WorldCfgs{wc}, a, circles, nullptr, rgt, on_stream(stream));
 }
 
 int f110qp_rollout_world(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -937,9 +974,9 @@ int f110qp_rollout_world(f110qp_ctx* c, const f110qp_rollout_config* rc, const f
                          double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up,
                          float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset,
                          float* rgt) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  return world_call(c, LoopCfg{kWorld, rc, sc, rp}, wc, nullptr, io, r, circles, rgt, on_host());
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset);
+  return world_call(c, LoopCfg{kWorld, rc, sc, rp}, WorldCfgs{wc}, a, circles, nullptr, rgt, on_host());
 }
 
 void f110qp_default_race_config(f110qp_race_config* race) {
@@ -953,21 +990,8 @@ void f110qp_default_race_config(f110qp_race_config* race) {
 int f110qp_cast_scans_race_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
                                const f110qp_race_config* race, int batch, const int* list, const int* count,
                                const double* x, const double* circles, float* ranges, void* stream) {
-  int rv = check_scan_config(sc, false, 0);
-  if (rv) return rv;
-  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
-  f110qp::CastParams P;
-  f110qp::RaceParams Q;
-  if ((rv = world_params(sc, wc, batch, circles, &P))) return rv;
-  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
-  if ((list != nullptr) != (count != nullptr))
-    return fail(F110QP_ERR_INVALID, "list and count must be given together");
-  if (batch == 0) return F110QP_OK;
-  if (!x || !ranges) return fail(F110QP_ERR_INVALID, "x/ranges must be non-NULL");
-  const hipError_t e =
-      f110qp::launch_cast_scans_race(P, Q, batch, list, count, x, circles, ranges, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "race scan cast launch");
-  return F110QP_OK;
+  return cast_call(f110qp::WORLD_RACE, sc, WorldCfgs{wc, race}, batch, list, count, x, circles, nullptr, ranges,
+                   stream);
 }
 
 int f110qp_rollout_race_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -976,9 +1000,9 @@ int f110qp_rollout_race_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, cons
                             double* xr, int* have, const double* circles, double* xt, double* ult, float* ua,
                             int* stt, int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst,
                             int* btt, int* bgt, double* poset, float* rgt, void* stream) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  return world_call(c, LoopCfg{kRace, rc, sc, rp}, wc, race, io, r, circles, rgt, on_stream(stream));
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset);
+  return world_call(c, LoopCfg{kRace, rc, sc, rp}, WorldCfgs{wc, race}, a, circles, nullptr, rgt, on_stream(stream));
 }
 
 int f110qp_rollout_race(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -987,9 +1011,9 @@ int f110qp_rollout_race(f110qp_ctx* c, const f110qp_rollout_config* rc, const f1
                         double* xr, int* have, const double* circles, double* xt, double* ult, float* ua, int* stt,
                         int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst, int* btt,
                         int* bgt, double* poset, float* rgt) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  return world_call(c, LoopCfg{kRace, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host());
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset);
+  return world_call(c, LoopCfg{kRace, rc, sc, rp}, WorldCfgs{wc, race}, a, circles, nullptr, rgt, on_host());
 }
 
 // ---- contact: clearance to walls and race-mates, crashed cars park (f110qp_clearance_dev, ----------------
@@ -1004,21 +1028,8 @@ void f110qp_default_contact_config(f110qp_contact_config* cc) {
 
 int f110qp_clearance_dev(const f110qp_world_config* wc, const f110qp_race_config* race, int batch, int rows,
                          const double* x, const double* circles, double* clearance, int* nearest, void* stream) {
-  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
-  f110qp::CastParams P;
-  f110qp::RaceParams Q;
-  int rv = world_params(nullptr, wc, batch, circles, &P);
-  if (rv) return rv;
-  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
-  if (rows < 1) return fail(F110QP_ERR_INVALID, "rows must be >= 1");
-  if (batch == 0) return F110QP_OK;
-  if (!x || !clearance) return fail(F110QP_ERR_INVALID, "x/clearance must be non-NULL");
-  if ((long long)rows * batch > (1ll << 30)) return fail(F110QP_ERR_INVALID, "rows x batch too large");
-  const hipError_t e = f110qp::launch_clearance(f110qp::ClearParams{P.C, P.world_rows}, Q, batch, rows, x, circles,
-                                                clearance, nearest, f110qp::ContactMark{nullptr, 0, 0, 0.0},
-                                                (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "clearance launch");
-  return F110QP_OK;
+  return clearance_call(f110qp::WORLD_RACE, WorldCfgs{wc, race}, batch, rows, x, circles, nullptr, clearance, nearest,
+                        stream);
 }
 
 int f110qp_rollout_contact_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1028,10 +1039,10 @@ int f110qp_rollout_contact_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, c
                                double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up,
                                float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset,
                                float* rgt, double* clt, int* nrt, int* crash, void* stream) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  const ContactIO k{clt, nrt, crash};
-  return world_call(c, LoopCfg{kContact, rc, sc, rp}, wc, race, io, r, circles, rgt, on_stream(stream), cc, &k);
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kContact, rc, sc, rp}, WorldCfgs{wc, race, cc}, a, circles, nullptr, rgt,
+                    on_stream(stream));
 }
 
 int f110qp_rollout_contact(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1041,10 +1052,9 @@ int f110qp_rollout_contact(f110qp_ctx* c, const f110qp_rollout_config* rc, const
                            double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up, float* xp,
                            float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset, float* rgt, double* clt,
                            int* nrt, int* crash) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  const ContactIO k{clt, nrt, crash};
-  return world_call(c, LoopCfg{kContact, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k);
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kContact, rc, sc, rp}, WorldCfgs{wc, race, cc}, a, circles, nullptr, rgt, on_host());
 }
 
 // ---- rectangular car bodies (f110qp_clearance_body_dev, f110qp_cast_scans_body_dev, -----------------------
@@ -1060,46 +1070,16 @@ void f110qp_default_body_config(f110qp_body_config* body) {
 int f110qp_clearance_body_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
                               const f110qp_body_config* body, int batch, int rows, const double* x,
                               const double* circles, double* clearance, int* nearest, void* stream) {
-  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
-  f110qp::CastParams P;
-  f110qp::RaceParams Q;
-  f110qp::BodyParams H;
-  int rv = world_params(nullptr, wc, batch, circles, &P);
-  if (rv) return rv;
-  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
-  if ((rv = body_params(body, &H))) return rv;
-  if (rows < 1) return fail(F110QP_ERR_INVALID, "rows must be >= 1");
-  if (batch == 0) return F110QP_OK;
-  if (!x || !clearance) return fail(F110QP_ERR_INVALID, "x/clearance must be non-NULL");
-  if ((long long)rows * batch > (1ll << 30)) return fail(F110QP_ERR_INVALID, "rows x batch too large");
-  const hipError_t e = f110qp::launch_clearance_body(f110qp::ClearParams{P.C, P.world_rows}, Q, H, batch, rows, x,
-                                                     circles, clearance, nearest,
-                                                     f110qp::ContactMark{nullptr, 0, 0, 0.0}, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "body clearance launch");
-  return F110QP_OK;
+  return clearance_call(f110qp::WORLD_BODY, WorldCfgs{wc, race, nullptr, body}, batch, rows, x, circles, nullptr,
+                        clearance, nearest, stream);
 }
 
 int f110qp_cast_scans_body_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
                                const f110qp_race_config* race, const f110qp_body_config* body, int batch,
                                const int* list, const int* count, const double* x, const double* circles,
                                float* ranges, void* stream) {
-  int rv = check_scan_config(sc, false, 0);
-  if (rv) return rv;
-  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
-  f110qp::CastParams P;
-  f110qp::RaceParams Q;
-  f110qp::BodyParams H;
-  if ((rv = world_params(sc, wc, batch, circles, &P))) return rv;
-  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
-  if ((rv = body_params(body, &H))) return rv;
-  if ((list != nullptr) != (count != nullptr))
-    return fail(F110QP_ERR_INVALID, "list and count must be given together");
-  if (batch == 0) return F110QP_OK;
-  if (!x || !ranges) return fail(F110QP_ERR_INVALID, "x/ranges must be non-NULL");
-  const hipError_t e =
-      f110qp::launch_cast_scans_body(P, Q, H, batch, list, count, x, circles, ranges, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "body scan cast launch");
-  return F110QP_OK;
+  return cast_call(f110qp::WORLD_BODY, sc, WorldCfgs{wc, race, nullptr, body}, batch, list, count, x, circles, nullptr,
+                   ranges, stream);
 }
 
 int f110qp_rollout_body_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1110,10 +1090,10 @@ int f110qp_rollout_body_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, cons
                             int* stt, int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst,
                             int* btt, int* bgt, double* poset, float* rgt, double* clt, int* nrt, int* crash,
                             void* stream) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  const ContactIO k{clt, nrt, crash};
-  return world_call(c, LoopCfg{kBody, rc, sc, rp}, wc, race, io, r, circles, rgt, on_stream(stream), cc, &k, body);
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kBody, rc, sc, rp}, WorldCfgs{wc, race, cc, body}, a, circles, nullptr, rgt,
+                    on_stream(stream));
 }
 
 int f110qp_rollout_body(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1123,10 +1103,9 @@ int f110qp_rollout_body(f110qp_ctx* c, const f110qp_rollout_config* rc, const f1
                         int* have, const double* circles, double* xt, double* ult, float* ua, int* stt, int* itt,
                         double* cot, float* up, float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt,
                         double* poset, float* rgt, double* clt, int* nrt, int* crash) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  const ContactIO k{clt, nrt, crash};
-  return world_call(c, LoopCfg{kBody, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k, body);
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kBody, rc, sc, rp}, WorldCfgs{wc, race, cc, body}, a, circles, nullptr, rgt, on_host());
 }
 
 // ---- straight walls (f110qp_cast_scans_walls_dev, f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]) ------
@@ -1142,50 +1121,16 @@ int f110qp_cast_scans_walls_dev(const f110qp_scan_config* sc, const f110qp_world
                                 const f110qp_walls_config* walls, int batch, const int* list, const int* count,
                                 const double* x, const double* circles, const double* segments, float* ranges,
                                 void* stream) {
-  int rv = check_scan_config(sc, false, 0);
-  if (rv) return rv;
-  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
-  f110qp::CastParams P;
-  f110qp::RaceParams Q;
-  f110qp::BodyParams H;
-  f110qp::WallParams Wl;
-  if ((rv = world_params(sc, wc, batch, circles, &P))) return rv;
-  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
-  if ((rv = body_params(body, &H))) return rv;
-  if ((rv = wall_params(walls, batch, (long long)wc->num_circles + race->group_size - 1, segments, &Wl))) return rv;
-  if ((list != nullptr) != (count != nullptr))
-    return fail(F110QP_ERR_INVALID, "list and count must be given together");
-  if (batch == 0) return F110QP_OK;
-  if (!x || !ranges) return fail(F110QP_ERR_INVALID, "x/ranges must be non-NULL");
-  const hipError_t e = f110qp::launch_cast_scans_walls(P, Q, H, Wl, batch, list, count, x, circles, segments, ranges,
-                                                       (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "walls scan cast launch");
-  return F110QP_OK;
+  return cast_call(f110qp::WORLD_WALLS, sc, WorldCfgs{wc, race, nullptr, body, walls}, batch, list, count, x, circles,
+                   segments, ranges, stream);
 }
 
 int f110qp_clearance_walls_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
                                const f110qp_body_config* body, const f110qp_walls_config* walls, int batch, int rows,
                                const double* x, const double* circles, const double* segments, double* clearance,
                                int* nearest, void* stream) {
-  if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
-  f110qp::CastParams P;
-  f110qp::RaceParams Q;
-  f110qp::BodyParams H;
-  f110qp::WallParams Wl;
-  int rv = world_params(nullptr, wc, batch, circles, &P);
-  if (rv) return rv;
-  if ((rv = race_params(race, batch, wc->num_circles, &Q))) return rv;
-  if ((rv = body_params(body, &H))) return rv;
-  if ((rv = wall_params(walls, batch, (long long)wc->num_circles + race->group_size - 1, segments, &Wl))) return rv;
-  if (rows < 1) return fail(F110QP_ERR_INVALID, "rows must be >= 1");
-  if (batch == 0) return F110QP_OK;
-  if (!x || !clearance) return fail(F110QP_ERR_INVALID, "x/clearance must be non-NULL");
-  if ((long long)rows * batch > (1ll << 30)) return fail(F110QP_ERR_INVALID, "rows x batch too large");
-  const hipError_t e = f110qp::launch_clearance_walls(f110qp::ClearParams{P.C, P.world_rows}, Q, H, Wl, batch, rows, x,
-                                                      circles, segments, clearance, nearest,
-                                                      f110qp::ContactMark{nullptr, 0, 0, 0.0}, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "walls clearance launch");
-  return F110QP_OK;
+  return clearance_call(f110qp::WORLD_WALLS, WorldCfgs{wc, race, nullptr, body, walls}, batch, rows, x, circles,
+                        segments, clearance, nearest, stream);
 }
 
 int f110qp_rollout_walls_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1196,11 +1141,10 @@ int f110qp_rollout_walls_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, con
                              const double* segments, double* xt, double* ult, float* ua, int* stt, int* itt,
                              double* cot, float* up, float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt,
                              double* poset, float* rgt, double* clt, int* nrt, int* crash, void* stream) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  const ContactIO k{clt, nrt, crash};
-  return world_call(c, LoopCfg{kWalls, rc, sc, rp}, wc, race, io, r, circles, rgt, on_stream(stream), cc, &k, body,
-                    walls, segments);
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kWalls, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls}, a, circles, segments, rgt,
+                    on_stream(stream));
 }
 
 int f110qp_rollout_walls(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1211,11 +1155,10 @@ int f110qp_rollout_walls(f110qp_ctx* c, const f110qp_rollout_config* rc, const f
                          const double* segments, double* xt, double* ult, float* ua, int* stt, int* itt, double* cot,
                          float* up, float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset,
                          float* rgt, double* clt, int* nrt, int* crash) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  const ContactIO k{clt, nrt, crash};
-  return world_call(c, LoopCfg{kWalls, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k, body, walls,
-                    segments);
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kWalls, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls}, a, circles, segments, rgt,
+                    on_host());
 }
 
 // ---- a refreshed MPC scan (f110qp_gap_refresh_dev, f110qp_rollout_refresh[_dev]) -------------------------------
@@ -1248,11 +1191,10 @@ int f110qp_rollout_refresh_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, c
                                double* ult, float* ua, int* stt, int* itt, double* cot, float* up, float* xp,
                                float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset, float* rgt,
                                double* clt, int* nrt, int* crash, void* stream) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  const ContactIO k{clt, nrt, crash};
-  return world_call(c, LoopCfg{kRefresh, rc, sc, rp}, wc, race, io, r, circles, rgt, on_stream(stream), cc, &k, body,
-                    walls, segments, rf);
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kRefresh, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf}, a, circles, segments,
+                    rgt, on_stream(stream));
 }
 
 int f110qp_rollout_refresh(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1264,11 +1206,10 @@ int f110qp_rollout_refresh(f110qp_ctx* c, const f110qp_rollout_config* rc, const
                            double* ult, float* ua, int* stt, int* itt, double* cot, float* up, float* xp, float* hst,
                            int* kt, int* pst, int* btt, int* bgt, double* poset, float* rgt, double* clt, int* nrt,
                            int* crash) {
-  const RolloutIO io{batch, 0, 0, xr, xt, ult, ua, stt, itt, cot, up, xp};
-  const ReplanIO r{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}};
-  const ContactIO k{clt, nrt, crash};
-  return world_call(c, LoopCfg{kRefresh, rc, sc, rp}, wc, race, io, r, circles, rgt, on_host(), cc, &k, body, walls,
-                    segments, rf);
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kRefresh, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf}, a, circles, segments,
+                    rgt, on_host());
 }
 
 }  // extern "C"

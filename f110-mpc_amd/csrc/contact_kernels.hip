@@ -24,6 +24,22 @@
 // loop bound is uniform over the workgroup, so whole waves reach every shuffle and barrier. No atomic. No cull:
 // every pair takes its square root (clearances are negative on contact, so a cheaper sign test has nothing
 // to stand on), and the result is the exact minimum by construction. No cap on C or G.
+//
+// That is the WORLD_RACE instantiation of the one kernel below. What the other two families change, each
+// behind `if constexpr` as in cast_one; index, update rule, start value, NaN rule, mapping, passes, reduction
+// and crash record are the same text for all three:
+//   WORLD_BODY (f110qp_clearance_body_dev, f110qp_rollout_body[_dev]): the body is the rectangle of
+//     body_geom.h, centre q as above, axes (cos, sin) of the heading, half extents H; Q.car_radius is not
+//     read. A static circle gives v = body_sd(c; body) - |r|, a mate v = body_pair(own, mate), the same bits
+//     from either side. LDS holds (cos, sin) per pose next to q, and a mate's frame is built by the thread that
+//     takes it, one sincos per pose. The mate loop is not unrolled (one body_pair in the code instead of
+//     eight, its value folded into the pose's registers by an unrolled select), which is what keeps the
+//     instantiation's registers down.
+//   WORLD_WALLS (f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]): WORLD_BODY with the S segments of
+//     wall_geom.h as a third stretch of the obstacle list: index j in [C + G - 1, C + G - 1 + S) is segment
+//     k = j - (C + G - 1), index C + G + k in nearest. The thread reads its segment once per pass (32
+//     contiguous bytes) and tests it against every pose of the pass with wall_body (rule W2); like the mate
+//     loop, the pose loop is not unrolled, so there is one wall_body in the code.
 #include <hip/hip_runtime.h>
 
 #include "body_geom.h"
@@ -49,32 +65,67 @@ __device__ __forceinline__ void take_min(double& best, int& idx, const double v,
 
 }  // namespace
 
-__global__ __launch_bounds__(kClearThreads) void clearance_kernel(const ClearParams P, const RaceParams Q, const int B,
-                                                                  const int rows, const int nwg,
-                                                                  const double* __restrict__ x,
-                                                                  const double* __restrict__ circles,
-                                                                  double* __restrict__ clearance,
-                                                                  int* __restrict__ nearest, const ContactMark M) {
+// The configs a family's instantiation reads, its first kernel argument. Each instantiation keeps the
+// argument list its family's own kernel had, and with it that kernel's instruction stream: an
+// argument that a family does not read still moves the kernarg loads and, through them, the SGPR spills. So
+// the record grows with the family, and the segments pointer is a parameter pack that only WORLD_WALLS fills.
+template <WorldFamily FAM>
+struct ClearCfg {
+  ClearParams P;
+  RaceParams Q;
+};
+template <>
+struct ClearCfg<WORLD_BODY> {
+  ClearParams P;
+  RaceParams Q;
+  BodyParams H;
+};
+template <>
+struct ClearCfg<WORLD_WALLS> {
+  ClearParams P;
+  RaceParams Q;
+  BodyParams H;
+  WallParams Wl;
+};
+
 #pragma clang fp contract(off)
+template <WorldFamily FAM, typename... Seg>  // Seg: `const double` for WORLD_WALLS, empty otherwise
+__global__ __launch_bounds__(kClearThreads) void clearance_kernel(
+    const ClearCfg<FAM> W, const int B, const int rows, const int nwg, const double* __restrict__ x,
+    const double* __restrict__ circles, Seg* __restrict__... segments, double* __restrict__ clearance,
+    int* __restrict__ nearest, const ContactMark M) {
+  static_assert(FAM >= WORLD_RACE && sizeof...(Seg) == (FAM == WORLD_WALLS ? 1 : 0), "segments come with the walls");
+  constexpr bool BODY = FAM >= WORLD_BODY, WALLS = FAM == WORLD_WALLS;
+  const ClearParams& P = W.P;
+  const RaceParams& Q = W.Q;
   __shared__ double s_qx[kClearPoses], s_qy[kClearPoses];
+  __shared__ double s_c[kClearPoses], s_s[kClearPoses];  // BODY: the frame's axes (not allocated otherwise)
   __shared__ double s_best[kClearWaves][kClearPoses];
   __shared__ int s_idx[kClearWaves][kClearPoses];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const double inf = __longlong_as_double(0x7ff0000000000000ll);
-  const int nc = P.C + Q.G - 1;  // the circles and the G - 1 mates behind them
+  const int ns = P.C + Q.G - 1;  // the circles and the G - 1 mates behind them, then (WALLS) the segments
+  int nc = ns;
+  if constexpr (WALLS) nc += W.Wl.S;
   for (int b = blockIdx.x; b < B; b += nwg) {
     const double* cw = circles + (P.world_rows == 1 ? (size_t)0 : (size_t)b * (size_t)P.C * 3);
+    const double* sw = nullptr;
+    if constexpr (WALLS) sw = (segments, ...) + (W.Wl.wall_rows == 1 ? (size_t)0 : (size_t)b * (size_t)W.Wl.S * 4);
     const int own = b % Q.G, first = b - own;
     int crash = -1;  // thread 0: the first row at or under the margin
     if (M.crash_tick && !M.init && tid == 0) crash = M.crash_tick[b];
     for (int r0 = 0; r0 < rows; r0 += kClearPoses) {
       const int np = min(kClearPoses, rows - r0);
-      if (tid < np) {  // the body centre of pose tid of the pass
+      if (tid < np) {  // the body centre (BODY: frame) of pose tid of the pass
         const double* xp = x + ((size_t)(r0 + tid) * (size_t)B + (size_t)b) * 3;
         double so, co;
         sincos(xp[2], &so, &co);
         s_qx[tid] = xp[0] + Q.center_offset * co;
         s_qy[tid] = xp[1] + Q.center_offset * so;
+        if constexpr (BODY) {
+          s_c[tid] = co;
+          s_s[tid] = so;
+        }
       }
       __syncthreads();
       double best[kClearPoses];
@@ -92,23 +143,54 @@ __global__ __launch_bounds__(kClearThreads) void clearance_kernel(const ClearPar
 #pragma unroll
           for (int p = 0; p < kClearPoses; p++) {
             if (p < np) {
-              const double dx = cx - s_qx[p], dy = cy - s_qy[p];
-              const double d = __dsqrt_rn(dx * dx + dy * dy);
-              take_min(best[p], idx[p], (d - ra) - Q.car_radius, j);
+              if constexpr (BODY) {
+                take_min(best[p], idx[p], body_sd(cx, cy, s_qx[p], s_qy[p], s_c[p], s_s[p], W.H) - ra, j);
+              } else {
+                const double dx = cx - s_qx[p], dy = cy - s_qy[p];
+                const double d = __dsqrt_rn(dx * dx + dy * dy);
+                take_min(best[p], idx[p], (d - ra) - Q.car_radius, j);
+              }
             }
           }
-        } else if (j < nc) {  // mate k of the race, stepped over the own slot: index i inside the race
+        } else if (j < ns) {  // mate k of the race, stepped over the own slot: index i inside the race
           const int k = j - P.C, i = k + (k >= own ? 1 : 0);
-#pragma unroll
-          for (int p = 0; p < kClearPoses; p++) {
-            if (p < np) {
+          if constexpr (BODY) {
+#pragma unroll 1
+            for (int p = 0; p < np; p++) {
               const double* xm = x + ((size_t)(r0 + p) * (size_t)B + (size_t)(first + i)) * 3;
               double sm, cm;
               sincos(xm[2], &sm, &cm);
               const double mx = xm[0] + Q.center_offset * cm, my = xm[1] + Q.center_offset * sm;
-              const double dx = mx - s_qx[p], dy = my - s_qy[p];
-              const double d = __dsqrt_rn(dx * dx + dy * dy);
-              take_min(best[p], idx[p], (d - Q.car_radius) - Q.car_radius, P.C + i);
+              const double v = body_pair(s_qx[p], s_qy[p], s_c[p], s_s[p], mx, my, cm, sm, W.H);
+#pragma unroll
+              for (int q = 0; q < kClearPoses; q++)
+                if (q == p) take_min(best[q], idx[q], v, P.C + i);
+            }
+          } else {
+#pragma unroll
+            for (int p = 0; p < kClearPoses; p++) {
+              if (p < np) {
+                const double* xm = x + ((size_t)(r0 + p) * (size_t)B + (size_t)(first + i)) * 3;
+                double sm, cm;
+                sincos(xm[2], &sm, &cm);
+                const double mx = xm[0] + Q.center_offset * cm, my = xm[1] + Q.center_offset * sm;
+                const double dx = mx - s_qx[p], dy = my - s_qy[p];
+                const double d = __dsqrt_rn(dx * dx + dy * dy);
+                take_min(best[p], idx[p], (d - Q.car_radius) - Q.car_radius, P.C + i);
+              }
+            }
+          }
+        } else if (WALLS && j < nc) {  // segment j - ns
+          if constexpr (WALLS) {
+            const double* sg = sw + (size_t)(j - ns) * 4;
+            const double ax = sg[0], ay = sg[1], bx = sg[2], by = sg[3];
+            const int i = P.C + Q.G + (j - ns);
+#pragma unroll 1
+            for (int p = 0; p < np; p++) {
+              const double v = wall_body(ax, ay, bx, by, s_qx[p], s_qy[p], s_c[p], s_s[p], W.H);
+#pragma unroll
+              for (int q = 0; q < kClearPoses; q++)
+                if (q == p) take_min(best[q], idx[q], v, i);
             }
           }
         }
@@ -152,278 +234,28 @@ __global__ __launch_bounds__(kClearThreads) void clearance_kernel(const ClearPar
   }
 }
 
-// Grid: one workgroup per car up to 1,024. The kernel holds 127 VGPRs (the code-object metadata, DESIGN.md
-// 2i; the fp64 sincos and the eight poses' running minima set that figure), so a SIMD keeps four of its
-// waves; a workgroup is one wave on each of a CU's four SIMDs and 512 B of LDS, so a CU holds four
-// workgroups and the MI355X's 256 CUs hold 1,024 at once: derived from the occupancy, as cast_scans_grid's
-// 768 is, and not from a sweep of caps (none was measured).
-constexpr int kClearMaxGrid = 1024;
-int clearance_grid(int B) { return B < kClearMaxGrid ? B : kClearMaxGrid; }
+int clearance_grid(WorldFamily family, int B) {
+  const int cap = kWorldGrids[family].clearance;
+  return B < cap ? B : cap;
+}
 
-hipError_t launch_clearance(const ClearParams& P, const RaceParams& Q, int B, int rows, const double* x,
-                            const double* circles, double* clearance, int* nearest, const ContactMark& M,
-                            hipStream_t s) {
+hipError_t launch_clearance(const World& w, int B, int rows, const double* x, double* clearance, int* nearest,
+                            const ContactMark& M, hipStream_t s) {
+  if (w.family < WORLD_RACE) return hipErrorInvalidValue;  // contact is between the cars of a race
   if (B <= 0 || rows <= 0) return hipSuccess;
-  const int nwg = clearance_grid(B);
-  hipLaunchKernelGGL(clearance_kernel, dim3(nwg), dim3(kClearThreads), 0, s, P, Q, B, rows, nwg, x, circles, clearance,
-                     nearest, M);
-  return hipGetLastError();
-}
-
-// ---- rectangular bodies (f110qp_clearance_body_dev, f110qp_rollout_body[_dev]) ---------------------------
-// The body is the rectangle of body_geom.h: centre q as above, axes (cos, sin) of the heading, half extents H;
-// Q.car_radius is not read. A static circle gives v = body_sd(c; body) - |r|, a mate v = body_pair(own, mate),
-// the same bits from either side. Index, update rule, start value and the NaN rule are the circle kernel's,
-// and so are the mapping, the passes, the reduction and the crash record: LDS holds (cos, sin) per pose next
-// to q, and a mate's frame is built by the thread that takes it, one sincos per pose. The mate loop is not
-// unrolled (one body_pair in the code instead of eight, its value folded into the pose's registers by an
-// unrolled select), which is what keeps the kernel's registers down.
-__global__ __launch_bounds__(kClearThreads) void clearance_body_kernel(
-    const ClearParams P, const RaceParams Q, const BodyParams H, const int B, const int rows, const int nwg,
-    const double* __restrict__ x, const double* __restrict__ circles, double* __restrict__ clearance,
-    int* __restrict__ nearest, const ContactMark M) {
-#pragma clang fp contract(off)
-  __shared__ double s_qx[kClearPoses], s_qy[kClearPoses], s_c[kClearPoses], s_s[kClearPoses];
-  __shared__ double s_best[kClearWaves][kClearPoses];
-  __shared__ int s_idx[kClearWaves][kClearPoses];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const double inf = __longlong_as_double(0x7ff0000000000000ll);
-  const int nc = P.C + Q.G - 1;  // the circles and the G - 1 mates behind them
-  for (int b = blockIdx.x; b < B; b += nwg) {
-    const double* cw = circles + (P.world_rows == 1 ? (size_t)0 : (size_t)b * (size_t)P.C * 3);
-    const int own = b % Q.G, first = b - own;
-    int crash = -1;  // thread 0: the first row at or under the margin
-    if (M.crash_tick && !M.init && tid == 0) crash = M.crash_tick[b];
-    for (int r0 = 0; r0 < rows; r0 += kClearPoses) {
-      const int np = min(kClearPoses, rows - r0);
-      if (tid < np) {  // the body frame of pose tid of the pass
-        const double* xp = x + ((size_t)(r0 + tid) * (size_t)B + (size_t)b) * 3;
-        double so, co;
-        sincos(xp[2], &so, &co);
-        s_qx[tid] = xp[0] + Q.center_offset * co;
-        s_qy[tid] = xp[1] + Q.center_offset * so;
-        s_c[tid] = co;
-        s_s[tid] = so;
-      }
-      __syncthreads();
-      double best[kClearPoses];
-      int idx[kClearPoses];
-#pragma unroll
-      for (int p = 0; p < kClearPoses; p++) {
-        best[p] = inf;
-        idx[p] = -1;
-      }
-      for (int c0 = 0; c0 < nc; c0 += kCastCircleTile) {
-        const int j = c0 + tid;
-        if (j < P.C) {
-          const double cx = cw[(size_t)j * 3 + 0], cy = cw[(size_t)j * 3 + 1];
-          const double ra = fabs(cw[(size_t)j * 3 + 2]);
-#pragma unroll
-          for (int p = 0; p < kClearPoses; p++)
-            if (p < np) take_min(best[p], idx[p], body_sd(cx, cy, s_qx[p], s_qy[p], s_c[p], s_s[p], H) - ra, j);
-        } else if (j < nc) {  // mate k of the race, stepped over the own slot: index i inside the race
-          const int k = j - P.C, i = k + (k >= own ? 1 : 0);
-#pragma unroll 1
-          for (int p = 0; p < np; p++) {
-            const double* xm = x + ((size_t)(r0 + p) * (size_t)B + (size_t)(first + i)) * 3;
-            double sm, cm;
-            sincos(xm[2], &sm, &cm);
-            const double mx = xm[0] + Q.center_offset * cm, my = xm[1] + Q.center_offset * sm;
-            const double v = body_pair(s_qx[p], s_qy[p], s_c[p], s_s[p], mx, my, cm, sm, H);
-#pragma unroll
-            for (int q = 0; q < kClearPoses; q++)
-              if (q == p) take_min(best[q], idx[q], v, P.C + i);
-          }
-        }
-      }
-      // the wave's (value, index) minimum per pose, then the four waves' through LDS
-#pragma unroll
-      for (int p = 0; p < kClearPoses; p++) {
-        if (p < np) {  // uniform
-#pragma unroll
-          for (int m = 32; m >= 1; m >>= 1) {
-            const double ov = __shfl_xor(best[p], m, 64);
-            const int oi = __shfl_xor(idx[p], m, 64);
-            take_min(best[p], idx[p], ov, oi);
-          }
-          if (lane == 0) {
-            s_best[wave][p] = best[p];
-            s_idx[wave][p] = idx[p];
-          }
-        }
-      }
-      __syncthreads();
-      if (tid < np) {
-        double v = s_best[0][tid];
-        int i = s_idx[0][tid];
-#pragma unroll
-        for (int w = 1; w < kClearWaves; w++) take_min(v, i, s_best[w][tid], s_idx[w][tid]);
-        const size_t o = (size_t)(r0 + tid) * (size_t)B + (size_t)b;
-        clearance[o] = v;
-        if (nearest) nearest[o] = i;
-        s_best[0][tid] = v;  // for the mark below (read by thread 0 behind the barrier)
-      }
-      if (M.crash_tick) {  // uniform
-        __syncthreads();
-        if (tid == 0)
-          for (int p = 0; p < np; p++)
-            if (crash < 0 && s_best[0][p] <= M.margin) crash = M.row0 + r0 + p;
-      }
-      __syncthreads();  // the next pass (or car) rewrites the frames and the waves' results
-    }
-    if (M.crash_tick && tid == 0) M.crash_tick[b] = crash;
-  }
-}
-
-// Grid: one workgroup per car up to 512. The kernel holds 185 VGPRs (the code-object metadata, DESIGN.md 2i;
-// no scratch), allocated in granules of eight as 192, so a SIMD keeps floor(512 / 192) = 2 of its waves; a
-// workgroup is one wave on each of a CU's four SIMDs and 640 B of LDS, so a CU holds two workgroups and the
-// MI355X's 256 CUs hold 512 at once: derived as clearance_grid's 1,024 was, from the occupancy and not from a
-// sweep of caps (none was measured).
-constexpr int kClearBodyMaxGrid = 512;
-int clearance_body_grid(int B) { return B < kClearBodyMaxGrid ? B : kClearBodyMaxGrid; }
-
-hipError_t launch_clearance_body(const ClearParams& P, const RaceParams& Q, const BodyParams& H, int B, int rows,
-                                 const double* x, const double* circles, double* clearance, int* nearest,
-                                 const ContactMark& M, hipStream_t s) {
-  if (B <= 0 || rows <= 0) return hipSuccess;
-  const int nwg = clearance_body_grid(B);
-  hipLaunchKernelGGL(clearance_body_kernel, dim3(nwg), dim3(kClearThreads), 0, s, P, Q, H, B, rows, nwg, x, circles,
-                     clearance, nearest, M);
-  return hipGetLastError();
-}
-
-// ---- straight walls (f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]) -----------------------------
-// clearance_body_kernel with the S segments of wall_geom.h as a third stretch of the obstacle list: index j in
-// [C + G - 1, C + G - 1 + S) is segment k = j - (C + G - 1), index C + G + k in nearest. The thread reads its
-// segment once per pass (32 contiguous bytes) and tests it against every pose of the pass with wall_body (rule
-// W2); like the mate loop, the pose loop is not unrolled, so there is one wall_body in the code. The mapping,
-// the passes, the (value, index) reduction and the crash record are clearance_body_kernel's.
-__global__ __launch_bounds__(kClearThreads) void clearance_walls_kernel(
-    const ClearParams P, const RaceParams Q, const BodyParams H, const WallParams Wl, const int B, const int rows,
-    const int nwg, const double* __restrict__ x, const double* __restrict__ circles,
-    const double* __restrict__ segments, double* __restrict__ clearance, int* __restrict__ nearest,
-    const ContactMark M) {
-#pragma clang fp contract(off)
-  __shared__ double s_qx[kClearPoses], s_qy[kClearPoses], s_c[kClearPoses], s_s[kClearPoses];
-  __shared__ double s_best[kClearWaves][kClearPoses];
-  __shared__ int s_idx[kClearWaves][kClearPoses];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const double inf = __longlong_as_double(0x7ff0000000000000ll);
-  const int ns = P.C + Q.G - 1;  // the circles and the G - 1 mates behind them, then the segments
-  const int nc = ns + Wl.S;
-  for (int b = blockIdx.x; b < B; b += nwg) {
-    const double* cw = circles + (P.world_rows == 1 ? (size_t)0 : (size_t)b * (size_t)P.C * 3);
-    const double* sw = segments + (Wl.wall_rows == 1 ? (size_t)0 : (size_t)b * (size_t)Wl.S * 4);
-    const int own = b % Q.G, first = b - own;
-    int crash = -1;  // thread 0: the first row at or under the margin
-    if (M.crash_tick && !M.init && tid == 0) crash = M.crash_tick[b];
-    for (int r0 = 0; r0 < rows; r0 += kClearPoses) {
-      const int np = min(kClearPoses, rows - r0);
-      if (tid < np) {  // the body frame of pose tid of the pass
-        const double* xp = x + ((size_t)(r0 + tid) * (size_t)B + (size_t)b) * 3;
-        double so, co;
-        sincos(xp[2], &so, &co);
-        s_qx[tid] = xp[0] + Q.center_offset * co;
-        s_qy[tid] = xp[1] + Q.center_offset * so;
-        s_c[tid] = co;
-        s_s[tid] = so;
-      }
-      __syncthreads();
-      double best[kClearPoses];
-      int idx[kClearPoses];
-#pragma unroll
-      for (int p = 0; p < kClearPoses; p++) {
-        best[p] = inf;
-        idx[p] = -1;
-      }
-      for (int c0 = 0; c0 < nc; c0 += kCastCircleTile) {
-        const int j = c0 + tid;
-        if (j < P.C) {
-          const double cx = cw[(size_t)j * 3 + 0], cy = cw[(size_t)j * 3 + 1];
-          const double ra = fabs(cw[(size_t)j * 3 + 2]);
-#pragma unroll
-          for (int p = 0; p < kClearPoses; p++)
-            if (p < np) take_min(best[p], idx[p], body_sd(cx, cy, s_qx[p], s_qy[p], s_c[p], s_s[p], H) - ra, j);
-        } else if (j < ns) {  // mate k of the race, stepped over the own slot: index i inside the race
-          const int k = j - P.C, i = k + (k >= own ? 1 : 0);
-#pragma unroll 1
-          for (int p = 0; p < np; p++) {
-            const double* xm = x + ((size_t)(r0 + p) * (size_t)B + (size_t)(first + i)) * 3;
-            double sm, cm;
-            sincos(xm[2], &sm, &cm);
-            const double mx = xm[0] + Q.center_offset * cm, my = xm[1] + Q.center_offset * sm;
-            const double v = body_pair(s_qx[p], s_qy[p], s_c[p], s_s[p], mx, my, cm, sm, H);
-#pragma unroll
-            for (int q = 0; q < kClearPoses; q++)
-              if (q == p) take_min(best[q], idx[q], v, P.C + i);
-          }
-        } else if (j < nc) {  // segment j - ns
-          const double* sg = sw + (size_t)(j - ns) * 4;
-          const double ax = sg[0], ay = sg[1], bx = sg[2], by = sg[3];
-          const int i = P.C + Q.G + (j - ns);
-#pragma unroll 1
-          for (int p = 0; p < np; p++) {
-            const double v = wall_body(ax, ay, bx, by, s_qx[p], s_qy[p], s_c[p], s_s[p], H);
-#pragma unroll
-            for (int q = 0; q < kClearPoses; q++)
-              if (q == p) take_min(best[q], idx[q], v, i);
-          }
-        }
-      }
-      // the wave's (value, index) minimum per pose, then the four waves' through LDS
-#pragma unroll
-      for (int p = 0; p < kClearPoses; p++) {
-        if (p < np) {  // uniform
-#pragma unroll
-          for (int m = 32; m >= 1; m >>= 1) {
-            const double ov = __shfl_xor(best[p], m, 64);
-            const int oi = __shfl_xor(idx[p], m, 64);
-            take_min(best[p], idx[p], ov, oi);
-          }
-          if (lane == 0) {
-            s_best[wave][p] = best[p];
-            s_idx[wave][p] = idx[p];
-          }
-        }
-      }
-      __syncthreads();
-      if (tid < np) {
-        double v = s_best[0][tid];
-        int i = s_idx[0][tid];
-#pragma unroll
-        for (int w = 1; w < kClearWaves; w++) take_min(v, i, s_best[w][tid], s_idx[w][tid]);
-        const size_t o = (size_t)(r0 + tid) * (size_t)B + (size_t)b;
-        clearance[o] = v;
-        if (nearest) nearest[o] = i;
-        s_best[0][tid] = v;  // for the mark below (read by thread 0 behind the barrier)
-      }
-      if (M.crash_tick) {  // uniform
-        __syncthreads();
-        if (tid == 0)
-          for (int p = 0; p < np; p++)
-            if (crash < 0 && s_best[0][p] <= M.margin) crash = M.row0 + r0 + p;
-      }
-      __syncthreads();  // the next pass (or car) rewrites the frames and the waves' results
-    }
-    if (M.crash_tick && tid == 0) M.crash_tick[b] = crash;
-  }
-}
-
-// Grid: one workgroup per car up to 512. The kernel holds 185 VGPRs (the code-object metadata; no
-// VGPR spill, no scratch), allocated as 192, so a SIMD keeps two of its waves; a workgroup is one wave on each
-// of a CU's four SIMDs and 640 B of LDS, so a CU holds two workgroups and the MI355X's 256 CUs hold 512 at once:
-// derived as clearance_body_grid's cap is.
-constexpr int kClearWallsMaxGrid = 512;
-int clearance_walls_grid(int B) { return B < kClearWallsMaxGrid ? B : kClearWallsMaxGrid; }
-
-hipError_t launch_clearance_walls(const ClearParams& P, const RaceParams& Q, const BodyParams& H, const WallParams& Wl,
-                                  int B, int rows, const double* x, const double* circles, const double* segments,
-                                  double* clearance, int* nearest, const ContactMark& M, hipStream_t s) {
-  if (B <= 0 || rows <= 0) return hipSuccess;
-  const int nwg = clearance_walls_grid(B);
-  hipLaunchKernelGGL(clearance_walls_kernel, dim3(nwg), dim3(kClearThreads), 0, s, P, Q, H, Wl, B, rows, nwg, x,
-                     circles, segments, clearance, nearest, M);
+  const int nwg = clearance_grid(w.family, B);
+  const dim3 grid(nwg), block(kClearThreads);
+  const ClearParams P{w.P.C, w.P.world_rows};
+  if (w.family == WORLD_WALLS)
+    hipLaunchKernelGGL((clearance_kernel<WORLD_WALLS, const double>), grid, block, 0, s,
+                       ClearCfg<WORLD_WALLS>{P, w.Q, w.H, w.Wl}, B, rows, nwg, x, w.circles, w.segments, clearance,
+                       nearest, M);
+  else if (w.family == WORLD_BODY)
+    hipLaunchKernelGGL(clearance_kernel<WORLD_BODY>, grid, block, 0, s, ClearCfg<WORLD_BODY>{P, w.Q, w.H}, B, rows,
+                       nwg, x, w.circles, clearance, nearest, M);
+  else
+    hipLaunchKernelGGL(clearance_kernel<WORLD_RACE>, grid, block, 0, s, ClearCfg<WORLD_RACE>{P, w.Q}, B, rows, nwg, x,
+                       w.circles, clearance, nearest, M);
   return hipGetLastError();
 }
 

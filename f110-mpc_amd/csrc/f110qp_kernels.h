@@ -386,12 +386,9 @@ struct ReplanStart {
 };
 hipError_t launch_replan_start(int B, const ReplanStart& S, hipStream_t stream);
 
-// ---- simulated LiDAR (scan_kernels.hip) -----------------------------------------------------------
-// Ray casting against circles, workload._ray_circles on the device: per car the scan of nr beams at
-// pose x [B][3] from the LiDAR lidar_offset ahead, circles [world_rows][C][3] = (cx, cy, r), ranges
-// [B][nr] float32. One workgroup per car, at most cast_scans_grid(B) of them striding over all B cars
-// (list and count null) or over list[0 .. min(*count, B)) as launch_plan_listed; unlisted cars are
-// not touched. Circles are processed kCastCircleTile at a time (== F110QP_CAST_CIRCLE_TILE).
+// ---- the world of a car: what it sees (scan_kernels.hip) and what it touches (contact_kernels.hip) ---
+// Circles [world_rows][C][3] = (cx, cy, r) (null when C = 0); car b reads row 0 (world_rows 1) or row b.
+// Obstacles are processed kCastCircleTile at a time (== F110QP_CAST_CIRCLE_TILE).
 constexpr int kCastCircleTile = 256;
 struct CastParams {
   int nr;
@@ -400,74 +397,82 @@ struct CastParams {
   int world_rows;  // 1 or B
   double lidar_offset, max_range;
 };
-int cast_scans_grid(int B);
-hipError_t launch_cast_scans(const CastParams& P, int B, const int* list, const int* count, const double* x,
-                             const double* circles, float* ranges, hipStream_t stream);
-// Races: the B cars are B / G races of G consecutive cars (B % G == 0), and every car also sees each of
+// Races: the B cars are B / G races of G consecutive cars (B % G == 0), and every car also meets each of
 // its G - 1 race-mates as the circle (x_m + center_offset cos(ori_m), y_m + center_offset sin(ori_m),
-// car_radius) at the mate's pose in x. Same grid, same list rule; circles may be null when C = 0.
+// car_radius) at the mate's pose in x.
 struct RaceParams {
   int G;
   double car_radius, center_offset;
 };
-hipError_t launch_cast_scans_race(const CastParams& P, const RaceParams& Q, int B, const int* list, const int* count,
-                                  const double* x, const double* circles, float* ranges, hipStream_t stream);
 // Rectangular bodies (body_geom.h): a car is the rectangle with centre (x + center_offset cos(ori), y +
 // center_offset sin(ori)), axes along and across the heading and half extents (hl, hw); Q.car_radius is not read.
 struct BodyParams {
   double hl, hw;  // half length, half width
 };
-// launch_cast_scans_race with every mate a rectangle (the slab test) in place of the race circle.
-int cast_scans_body_grid(int B);
-hipError_t launch_cast_scans_body(const CastParams& P, const RaceParams& Q, const BodyParams& H, int B, const int* list,
-                                  const int* count, const double* x, const double* circles, float* ranges,
-                                  hipStream_t stream);
 // Straight walls (wall_geom.h): S segments (ax, ay, bx, by) behind the circles and the mates, segments
 // [wall_rows][S][4] (null when S = 0); car b reads row 0 (wall_rows 1) or row b (wall_rows B).
 struct WallParams {
   int S;
   int wall_rows;  // 1 or B
 };
-// launch_cast_scans_body with the segments in every scan (rule W1).
-int cast_scans_walls_grid(int B);
-hipError_t launch_cast_scans_walls(const CastParams& P, const RaceParams& Q, const BodyParams& H, const WallParams& Wl,
-                                   int B, const int* list, const int* count, const double* x, const double* circles,
-                                   const double* segments, float* ranges, hipStream_t stream);
+// The families, each the one before plus one thing: circles alone (casts only), the race-mates as circles,
+// the cars as rectangles (the slab test in the cast, body_sd / body_pair in the clearance), the segments
+// (rules W1 and W2).
+enum WorldFamily { WORLD_CIRCLES = 0, WORLD_RACE = 1, WORLD_BODY = 2, WORLD_WALLS = 3 };
+// One description of the world for both jobs. A family reads the records up to its own.
+struct World {
+  WorldFamily family;
+  CastParams P;  // the clearance reads C and world_rows alone
+  RaceParams Q;
+  BodyParams H;
+  WallParams Wl;
+  const double* circles;
+  const double* segments;
+};
 
-// ---- contact (contact_kernels.hip) ----------------------------------------------------------------
+// Grid caps: one 256-thread workgroup per car, one wave on each of a CU's four SIMDs, up to what the MI355X's
+// 256 CUs hold at once; a larger batch strides. From the code-object metadata, not from a sweep
+// of caps (none was measured): a SIMD's 512 VGPRs are allocated in granules of eight, so a kernel with v
+// VGPRs keeps floor(512 / roundup8(v)) waves per SIMD, a CU as many workgroups, and LDS allows more in
+// every row (37,888 B a cast workgroup, 44,032 B with bodies; 512 B and 640 B a clearance workgroup):
+//   cast       circles, race 155 -> 3 -> 768 (forcing four waves spills 17 VGPRs to scratch)
+//              body 183 (184 allocated), walls 185 (192) -> 2 -> 512
+//   clearance  race 127 (the fp64 sincos and the eight poses' running minima) -> 4 -> 1,024
+//              body, walls 185 (192) -> 2 -> 512
+// Nothing spills a VGPR and no kernel has scratch.
+constexpr struct {
+  int cast, clearance;
+} kWorldGrids[4] = {{768, 0}, {768, 1024}, {512, 512}, {512, 512}};  // by WorldFamily
+
+// Ray casting, workload._ray_circles on the device: per car the scan of nr beams at pose x [B][3] from the
+// LiDAR lidar_offset ahead, ranges [B][nr] float32. At most cast_scans_grid(family, B) workgroups striding over
+// all B cars (list and count null) or over list[0 .. min(*count, B)) as launch_plan_listed; unlisted cars
+// are not touched.
+int cast_scans_grid(WorldFamily family, int B);
+hipError_t launch_cast_scans(const World& w, int B, const int* list, const int* count, const double* x, float* ranges,
+                             hipStream_t stream);
+
 // The clearance of rows x B poses x [rows][B][3] to everything each car can touch: the C circles of its
-// world (circles [world_rows][C][3], null when C = 0) and the G - 1 mates of its race at the same row of x,
-// the car's body being the race model's circle. clearance [rows][B], nearest [rows][B] or null (the index
-// of the minimum: j, C + i for mate i of the race, -1 for none). One workgroup per car, at most
-// clearance_grid(B) of them striding over the cars; one launch.
+// world, the G - 1 mates of its race at the same row of x and (WORLD_WALLS) the S segments, the car's body
+// being the race model's circle (WORLD_RACE) or the rectangle. clearance [rows][B], nearest [rows][B] or null
+// (the index of the minimum: j, C + i for mate i of the race, C + G + k for segment k, -1 for none). At most
+// clearance_grid(family, B) workgroups striding over the cars; one launch. No WORLD_CIRCLES clearance.
+// The rollout's crash record, updated by the same launch (crash_tick null: no record): crash_tick[b] is the
+// first row whose clearance is <= margin, counted from row0, or -1. init: the launch starts every car
+// from -1; otherwise from what crash_tick holds (a car that has crashed keeps its row).
 struct ClearParams {
   int C;
   int world_rows;  // 1 or B
 };
-// The rollout's crash record, updated by the same launch (crash_tick null: no record): crash_tick[b] is the
-// first row whose clearance is <= margin, counted from row0, or -1. init: the launch starts every car
-// from -1; otherwise from what crash_tick holds (a car that has crashed keeps its row).
 struct ContactMark {
   int* crash_tick;  // [B] or null
   int row0;         // the row of x_traj that row 0 of this launch is
   int init;
   double margin;
 };
-int clearance_grid(int B);
-hipError_t launch_clearance(const ClearParams& P, const RaceParams& Q, int B, int rows, const double* x,
-                            const double* circles, double* clearance, int* nearest, const ContactMark& M,
-                            hipStream_t stream);
-// The same with the own car and its mates rectangles: body_sd(c; body) - |r| per circle, body_pair per mate.
-int clearance_body_grid(int B);
-hipError_t launch_clearance_body(const ClearParams& P, const RaceParams& Q, const BodyParams& H, int B, int rows,
-                                 const double* x, const double* circles, double* clearance, int* nearest,
-                                 const ContactMark& M, hipStream_t stream);
-// launch_clearance_body with the segments as a third stretch of the obstacle list (rule W2): segment k has
-// index C + G + k in nearest.
-int clearance_walls_grid(int B);
-hipError_t launch_clearance_walls(const ClearParams& P, const RaceParams& Q, const BodyParams& H, const WallParams& Wl,
-                                  int B, int rows, const double* x, const double* circles, const double* segments,
-                                  double* clearance, int* nearest, const ContactMark& M, hipStream_t stream);
+int clearance_grid(WorldFamily family, int B);
+hipError_t launch_clearance(const World& w, int B, int rows, const double* x, double* clearance, int* nearest,
+                            const ContactMark& M, hipStream_t stream);
 
 // ---- standings (standings_kernels.hip) ------------------------------------------------------------
 // The projection of rows x B poses x [rows][B][3] onto the closed path wp [W][2] with cumulative lengths

@@ -376,64 +376,26 @@ __global__ __launch_bounds__(kCastThreads) void cast_scans_walls_kernel(
   cast_scans<true, true, true>(P, Q, H, B, nwg, list, count, x, circles, ranges, Wl, segments);
 }
 
-// Grid: one workgroup per car up to 768. The kernel holds 155 VGPRs (the code-object metadata,
-// DESIGN.md 2i; the fp64 sincos, asin and atan2 set that figure), so a SIMD keeps three of its waves
-// and a CU three of its four-wave workgroups (37,888 B of LDS each would allow four): 768 is what the
-// MI355X's 256 CUs hold at once, the same figure as plan_listed_grid's and derived the same way, from
-// the occupancy and not from a sweep of caps. Forcing four waves per SIMD spills 17 VGPRs to scratch.
-// The race instantiation holds 155 VGPRs too (no scratch): the same cap.
-constexpr int kCastMaxGrid = 768;
-int cast_scans_grid(int B) { return B < kCastMaxGrid ? B : kCastMaxGrid; }
-
-hipError_t launch_cast_scans(const CastParams& P, int B, const int* list, const int* count, const double* x,
-                             const double* circles, float* ranges, hipStream_t s) {
-  if (B <= 0) return hipSuccess;
-  const int nwg = cast_scans_grid(B);
-  hipLaunchKernelGGL(cast_scans_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, B, nwg, list, count, x, circles,
-                     ranges);
-  return hipGetLastError();
+int cast_scans_grid(WorldFamily family, int B) {
+  const int cap = kWorldGrids[family].cast;
+  return B < cap ? B : cap;
 }
 
-hipError_t launch_cast_scans_race(const CastParams& P, const RaceParams& Q, int B, const int* list, const int* count,
-                                  const double* x, const double* circles, float* ranges, hipStream_t s) {
+hipError_t launch_cast_scans(const World& w, int B, const int* list, const int* count, const double* x, float* ranges,
+                             hipStream_t s) {
   if (B <= 0) return hipSuccess;
-  const int nwg = cast_scans_grid(B);
-  hipLaunchKernelGGL(cast_scans_race_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, Q, B, nwg, list, count, x,
-                     circles, ranges);
-  return hipGetLastError();
-}
-
-// Grid: one workgroup per car up to 512. The body instantiation holds 183 VGPRs (the code-object metadata,
-// DESIGN.md 2i; no scratch), allocated in granules of eight as 184, so a SIMD keeps floor(512 / 184) = 2 of
-// its waves and a CU two of its four-wave workgroups (44,032 B of LDS each would allow three): 512 on the
-// MI355X's 256 CUs, derived as cast_scans_grid's 768 is and not from a sweep of caps.
-constexpr int kCastBodyMaxGrid = 512;
-int cast_scans_body_grid(int B) { return B < kCastBodyMaxGrid ? B : kCastBodyMaxGrid; }
-
-hipError_t launch_cast_scans_body(const CastParams& P, const RaceParams& Q, const BodyParams& H, int B, const int* list,
-                                  const int* count, const double* x, const double* circles, float* ranges,
-                                  hipStream_t s) {
-  if (B <= 0) return hipSuccess;
-  const int nwg = cast_scans_body_grid(B);
-  hipLaunchKernelGGL(cast_scans_body_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, Q, H, B, nwg, list, count, x,
-                     circles, ranges);
-  return hipGetLastError();
-}
-
-// Grid: one workgroup per car up to 512. The walls instantiation holds 185 VGPRs (the code-object metadata,
-// DESIGN.md 2i; no VGPR spill, no scratch), allocated in granules of eight as 192, so a SIMD keeps
-// floor(512 / 192) = 2 of its waves and a CU two of its four-wave workgroups (44,032 B of LDS each would allow
-// three): 512 on the MI355X's 256 CUs, derived as cast_scans_body_grid's cap is.
-constexpr int kCastWallsMaxGrid = 512;
-int cast_scans_walls_grid(int B) { return B < kCastWallsMaxGrid ? B : kCastWallsMaxGrid; }
-
-hipError_t launch_cast_scans_walls(const CastParams& P, const RaceParams& Q, const BodyParams& H, const WallParams& Wl,
-                                   int B, const int* list, const int* count, const double* x, const double* circles,
-                                   const double* segments, float* ranges, hipStream_t s) {
-  if (B <= 0) return hipSuccess;
-  const int nwg = cast_scans_walls_grid(B);
-  hipLaunchKernelGGL(cast_scans_walls_kernel, dim3(nwg), dim3(kCastThreads), 0, s, P, Q, H, Wl, B, nwg, list, count, x,
-                     circles, segments, ranges);
+  const int nwg = cast_scans_grid(w.family, B);
+  const dim3 grid(nwg), block(kCastThreads);
+  if (w.family == WORLD_WALLS)
+    hipLaunchKernelGGL(cast_scans_walls_kernel, grid, block, 0, s, w.P, w.Q, w.H, w.Wl, B, nwg, list, count, x,
+                       w.circles, w.segments, ranges);
+  else if (w.family == WORLD_BODY)
+    hipLaunchKernelGGL(cast_scans_body_kernel, grid, block, 0, s, w.P, w.Q, w.H, B, nwg, list, count, x, w.circles,
+                       ranges);
+  else if (w.family == WORLD_RACE)
+    hipLaunchKernelGGL(cast_scans_race_kernel, grid, block, 0, s, w.P, w.Q, B, nwg, list, count, x, w.circles, ranges);
+  else
+    hipLaunchKernelGGL(cast_scans_kernel, grid, block, 0, s, w.P, B, nwg, list, count, x, w.circles, ranges);
   return hipGetLastError();
 }
 

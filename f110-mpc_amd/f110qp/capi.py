@@ -1428,101 +1428,7 @@ def plan_listed_dev(rp: ReplanConfig, sc: ScanConfig, list_, count, pose, ranges
                                          _tp(best_global), C.c_void_p(stream.cuda_stream)), "f110qp_plan_listed_dev")
 
 
-def cast_scans_dev(sc: ScanConfig, wc: WorldConfig, x, circles, ranges, list_=None, count=None, stream=None):
-    """The simulated LiDAR (f110qp_cast_scans_dev): x [B,3] f64, circles [world_rows,C,3] f64 (None for
-    C = 0) -> ranges [B,num_ranges] f32, for all B cars or, with list_ [B] i32 and count [1] i32 on the
-    device, for the listed ones."""
-    import torch
-
-    B, Cn, WR = int(x.shape[0]), int(wc.num_circles), int(wc.world_rows)
-    _devs((x, "f64", 3 * B, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
-          (ranges, "f32", B * int(sc.num_ranges), "ranges"), (list_, "i32", B, "list", True),
-          (count, "i32", 1, "count", True))
-    if stream is None:
-        stream = torch.cuda.current_stream(x.device)
-    _check(load().f110qp_cast_scans_dev(C.byref(sc), C.byref(wc), B, _tp(list_), _tp(count), _tp(x), _tp(circles),
-                                        _tp(ranges), C.c_void_p(stream.cuda_stream)), "f110qp_cast_scans_dev")
-
-
-def cast_scans_race_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, x, circles, ranges, list_=None, count=None,
-                        stream=None):
-    """cast_scans_dev with the race-mates in every scan (f110qp_cast_scans_race_dev): the B cars are
-    B / race.group_size races of consecutive cars, x [B,3] f64 is both the casting poses and the opponents'."""
-    import torch
-
-    B, Cn, WR = int(x.shape[0]), int(wc.num_circles), int(wc.world_rows)
-    _check_race(race, B)
-    _devs((x, "f64", 3 * B, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
-          (ranges, "f32", B * int(sc.num_ranges), "ranges"), (list_, "i32", B, "list", True),
-          (count, "i32", 1, "count", True))
-    if stream is None:
-        stream = torch.cuda.current_stream(x.device)
-    _check(load().f110qp_cast_scans_race_dev(C.byref(sc), C.byref(wc), C.byref(race), B, _tp(list_), _tp(count), _tp(x),
-                                             _tp(circles), _tp(ranges), C.c_void_p(stream.cuda_stream)),
-           "f110qp_cast_scans_race_dev")
-
-
-def clearance_dev(wc: WorldConfig, race: RaceConfig, x, circles, clearance, nearest=None, stream=None):
-    """Every car's clearance to its world's circles and its race-mates (f110qp_clearance_dev): x [rows,B,3] f64
-    (or [B,3]: one row), circles [world_rows,C,3] f64 (None for C = 0) -> clearance [rows,B] f64 and, optionally,
-    nearest [rows,B] i32."""
-    import torch
-
-    if x.dim() not in (2, 3) or x.shape[-1] != 3:
-        raise F110QPError(f"x must be [rows, B, 3] or [B, 3], got {tuple(x.shape)}")
-    rows, B = (1, int(x.shape[0])) if x.dim() == 2 else (int(x.shape[0]), int(x.shape[1]))
-    if rows < 1:
-        raise F110QPError("x must hold at least one row")
-    Cn, WR = int(wc.num_circles), int(wc.world_rows)
-    _check_race(race, B)
-    _devs((x, "f64", 3 * B * rows, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
-          (clearance, "f64", B * rows, "clearance"), (nearest, "i32", B * rows, "nearest", True))
-    if stream is None:
-        stream = torch.cuda.current_stream(x.device)
-    _check(load().f110qp_clearance_dev(C.byref(wc), C.byref(race), B, rows, _tp(x), _tp(circles), _tp(clearance),
-                                       _tp(nearest), C.c_void_p(stream.cuda_stream)), "f110qp_clearance_dev")
-
-
-def cast_scans_body_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, x, circles, ranges,
-                        list_=None, count=None, stream=None):
-    """cast_scans_race_dev with every race-mate a rectangle (f110qp_cast_scans_body_dev)."""
-    import torch
-
-    if not isinstance(body, BodyConfig):
-        raise F110QPError("body must be a BodyConfig")
-    B, Cn, WR = int(x.shape[0]), int(wc.num_circles), int(wc.world_rows)
-    _check_race(race, B)
-    _devs((x, "f64", 3 * B, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
-          (ranges, "f32", B * int(sc.num_ranges), "ranges"), (list_, "i32", B, "list", True),
-          (count, "i32", 1, "count", True))
-    if stream is None:
-        stream = torch.cuda.current_stream(x.device)
-    _check(load().f110qp_cast_scans_body_dev(C.byref(sc), C.byref(wc), C.byref(race), C.byref(body), B, _tp(list_),
-                                             _tp(count), _tp(x), _tp(circles), _tp(ranges),
-                                             C.c_void_p(stream.cuda_stream)), "f110qp_cast_scans_body_dev")
-
-
-def clearance_body_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, x, circles, clearance, nearest=None,
-                       stream=None):
-    """clearance_dev with the car and its race-mates rectangles (f110qp_clearance_body_dev)."""
-    import torch
-
-    if not isinstance(body, BodyConfig):
-        raise F110QPError("body must be a BodyConfig")
-    if x.dim() not in (2, 3) or x.shape[-1] != 3:
-        raise F110QPError(f"x must be [rows, B, 3] or [B, 3], got {tuple(x.shape)}")
-    rows, B = (1, int(x.shape[0])) if x.dim() == 2 else (int(x.shape[0]), int(x.shape[1]))
-    if rows < 1:
-        raise F110QPError("x must hold at least one row")
-    Cn, WR = int(wc.num_circles), int(wc.world_rows)
-    _check_race(race, B)
-    _devs((x, "f64", 3 * B * rows, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
-          (clearance, "f64", B * rows, "clearance"), (nearest, "i32", B * rows, "nearest", True))
-    if stream is None:
-        stream = torch.cuda.current_stream(x.device)
-    _check(load().f110qp_clearance_body_dev(C.byref(wc), C.byref(race), C.byref(body), B, rows, _tp(x), _tp(circles),
-                                            _tp(clearance), _tp(nearest), C.c_void_p(stream.cuda_stream)),
-           "f110qp_clearance_body_dev")
+_NO = object()  # in place of a config that the family of a cast or a clearance does not take
 
 
 def _wall_spec(walls, segments):
@@ -1532,33 +1438,34 @@ def _wall_spec(walls, segments):
     return (segments, "f64", 4 * max(Sn, 0) * max(int(walls.wall_rows), 0), "segments", Sn <= 0)
 
 
-def cast_scans_walls_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, x,
-                         circles, segments, ranges, list_=None, count=None, stream=None):
-    """cast_scans_body_dev with straight wall segments in every scan (f110qp_cast_scans_walls_dev): segments
-    [wall_rows,S,4] f64 = (ax, ay, bx, by), None for S = 0."""
+def _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race=_NO, body=_NO, walls=_NO, segments=None):
+    """The body of the four cast_scans*_dev."""
     import torch
 
-    if not isinstance(body, BodyConfig):
+    if body is not _NO and not isinstance(body, BodyConfig):
         raise F110QPError("body must be a BodyConfig")
     B, Cn, WR = int(x.shape[0]), int(wc.num_circles), int(wc.world_rows)
-    _check_race(race, B)
+    if race is not _NO:
+        _check_race(race, B)
     _devs((x, "f64", 3 * B, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
-          _wall_spec(walls, segments), (ranges, "f32", B * int(sc.num_ranges), "ranges"),
-          (list_, "i32", B, "list", True), (count, "i32", 1, "count", True))
+          *([_wall_spec(walls, segments)] if walls is not _NO else []),
+          (ranges, "f32", B * int(sc.num_ranges), "ranges"), (list_, "i32", B, "list", True),
+          (count, "i32", 1, "count", True))
     if stream is None:
         stream = torch.cuda.current_stream(x.device)
-    _check(load().f110qp_cast_scans_walls_dev(C.byref(sc), C.byref(wc), C.byref(race), C.byref(body), C.byref(walls), B,
-                                              _tp(list_), _tp(count), _tp(x), _tp(circles), _tp(segments), _tp(ranges),
-                                              C.c_void_p(stream.cuda_stream)), "f110qp_cast_scans_walls_dev")
+    family = "_walls" if walls is not _NO else "_body" if body is not _NO else "_race" if race is not _NO else ""
+    name = f"f110qp_cast_scans{family}_dev"
+    cfgs = [C.byref(k) for k in (sc, wc, race, body, walls) if k is not _NO]
+    segs = [_tp(segments)] if walls is not _NO else []
+    _check(getattr(load(), name)(*cfgs, B, _tp(list_), _tp(count), _tp(x), _tp(circles), *segs, _tp(ranges),
+                                 C.c_void_p(stream.cuda_stream)), name)
 
 
-def clearance_walls_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, x, circles, segments,
-                        clearance, nearest=None, stream=None):
-    """clearance_body_dev with straight wall segments behind the circles and the mates
-    (f110qp_clearance_walls_dev): segment k has index C + G + k in nearest."""
+def _clearance(wc, race, x, circles, clearance, nearest, stream, body=_NO, walls=_NO, segments=None):
+    """The body of the three clearance*_dev."""
     import torch
 
-    if not isinstance(body, BodyConfig):
+    if body is not _NO and not isinstance(body, BodyConfig):
         raise F110QPError("body must be a BodyConfig")
     if x.dim() not in (2, 3) or x.shape[-1] != 3:
         raise F110QPError(f"x must be [rows, B, 3] or [B, 3], got {tuple(x.shape)}")
@@ -1568,13 +1475,62 @@ def clearance_walls_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, wal
     Cn, WR = int(wc.num_circles), int(wc.world_rows)
     _check_race(race, B)
     _devs((x, "f64", 3 * B * rows, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
-          _wall_spec(walls, segments), (clearance, "f64", B * rows, "clearance"),
-          (nearest, "i32", B * rows, "nearest", True))
+          *([_wall_spec(walls, segments)] if walls is not _NO else []),
+          (clearance, "f64", B * rows, "clearance"), (nearest, "i32", B * rows, "nearest", True))
     if stream is None:
         stream = torch.cuda.current_stream(x.device)
-    _check(load().f110qp_clearance_walls_dev(C.byref(wc), C.byref(race), C.byref(body), C.byref(walls), B, rows, _tp(x),
-                                             _tp(circles), _tp(segments), _tp(clearance), _tp(nearest),
-                                             C.c_void_p(stream.cuda_stream)), "f110qp_clearance_walls_dev")
+    name = f"f110qp_clearance{'_walls' if walls is not _NO else '_body' if body is not _NO else ''}_dev"
+    cfgs = [C.byref(k) for k in (wc, race, body, walls) if k is not _NO]
+    segs = [_tp(segments)] if walls is not _NO else []
+    _check(getattr(load(), name)(*cfgs, B, rows, _tp(x), _tp(circles), *segs, _tp(clearance), _tp(nearest),
+                                 C.c_void_p(stream.cuda_stream)), name)
+
+
+def cast_scans_dev(sc: ScanConfig, wc: WorldConfig, x, circles, ranges, list_=None, count=None, stream=None):
+    """The simulated LiDAR (f110qp_cast_scans_dev): x [B,3] f64, circles [world_rows,C,3] f64 (None for
+    C = 0) -> ranges [B,num_ranges] f32, for all B cars or, with list_ [B] i32 and count [1] i32 on the
+    device, for the listed ones."""
+    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream)
+
+
+def cast_scans_race_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, x, circles, ranges, list_=None, count=None,
+                        stream=None):
+    """cast_scans_dev with the race-mates in every scan (f110qp_cast_scans_race_dev): the B cars are
+    B / race.group_size races of consecutive cars, x [B,3] f64 is both the casting poses and the opponents'."""
+    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race)
+
+
+def clearance_dev(wc: WorldConfig, race: RaceConfig, x, circles, clearance, nearest=None, stream=None):
+    """Every car's clearance to its world's circles and its race-mates (f110qp_clearance_dev): x [rows,B,3] f64
+    (or [B,3]: one row), circles [world_rows,C,3] f64 (None for C = 0) -> clearance [rows,B] f64 and, optionally,
+    nearest [rows,B] i32."""
+    _clearance(wc, race, x, circles, clearance, nearest, stream)
+
+
+def cast_scans_body_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, x, circles, ranges,
+                        list_=None, count=None, stream=None):
+    """cast_scans_race_dev with every race-mate a rectangle (f110qp_cast_scans_body_dev)."""
+    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race, body)
+
+
+def clearance_body_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, x, circles, clearance, nearest=None,
+                       stream=None):
+    """clearance_dev with the car and its race-mates rectangles (f110qp_clearance_body_dev)."""
+    _clearance(wc, race, x, circles, clearance, nearest, stream, body)
+
+
+def cast_scans_walls_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, x,
+                         circles, segments, ranges, list_=None, count=None, stream=None):
+    """cast_scans_body_dev with straight wall segments in every scan (f110qp_cast_scans_walls_dev): segments
+    [wall_rows,S,4] f64 = (ax, ay, bx, by), None for S = 0."""
+    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race, body, walls, segments)
+
+
+def clearance_walls_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, x, circles, segments,
+                        clearance, nearest=None, stream=None):
+    """clearance_body_dev with straight wall segments behind the circles and the mates
+    (f110qp_clearance_walls_dev): segment k has index C + G + k in nearest."""
+    _clearance(wc, race, x, circles, clearance, nearest, stream, body, walls, segments)
 
 
 def _rows_of(x, last, name):

@@ -47,8 +47,8 @@ HL, HW = workload.HALF_LENGTH, workload.HALF_WIDTH
 RC = float(np.hypot(HL, HW))  # the circumscribed circle
 EPS = 2.0 ** -52
 GRAZE_D, GRAZE_T = 1e-4, 1e-8
-CLEAR_GRID = 512  # clearance_body_grid's cap
-CAST_GRID = 512   # cast_scans_body_grid's cap
+CLEAR_GRID = 512  # clearance_grid's cap for the body family
+CAST_GRID = 512   # cast_scans_grid's cap for the body family
 PASS = cc_.PASS
 
 

@@ -40,8 +40,8 @@ from f110qp import workload
 EPS = 2.0 ** -52
 GRAZE_SIN, GRAZE_V = 1e-4, 1e-8
 CENTER_OFFSET, HL, HW = bc_.CENTER_OFFSET, bc_.HL, bc_.HW
-CLEAR_GRID = 512  # clearance_walls_grid's cap
-CAST_GRID = 512   # cast_scans_walls_grid's cap
+CLEAR_GRID = 512  # clearance_grid's cap for the walls family
+CAST_GRID = 512   # cast_scans_grid's cap for the walls family
 TILE = wc_.TILE
 
 
