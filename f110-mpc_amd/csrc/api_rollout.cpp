@@ -5,7 +5,8 @@
 // (f110qp_clearance_dev, f110qp_rollout_contact[_dev]) and with rectangular bodies (f110qp_clearance_body_dev,
 // f110qp_cast_scans_body_dev, f110qp_rollout_body[_dev]) and with straight walls (f110qp_cast_scans_walls_dev,
 // f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]) and with a refreshed MPC scan (f110qp_gap_refresh_dev,
-// f110qp_rollout_refresh[_dev]), and the parts of each.
+// f110qp_rollout_refresh[_dev]) and with a noisy LiDAR (f110qp_cast_scans_noisy_dev, f110qp_rollout_noisy[_dev]),
+// and the parts of each.
 // Host-side responsibilities only: argument validation, workspaces, H2D/D2H of the host-pointer calls
 // (the staging table of api_stage.h). No C++ exception crosses this boundary.
 #include <cmath>
@@ -140,6 +141,26 @@ static int refresh_params(const f110qp_refresh_config* rf, int* every) {
   return F110QP_OK;
 }
 
+// The noise config of f110qp_cast_scans_noisy_dev and f110qp_rollout_noisy[_dev], checked, into *Z (rule Z2's
+// drop24 taken here, once per call; Z->tick is the caller's).
+static int noise_params(const f110qp_noise_config* noise, int batch, f110qp::NoiseParams* Z) {
+  if (!noise) return fail(F110QP_ERR_INVALID, "noise config is NULL");
+  if (!(noise->sigma_abs >= 0.0) || !std::isfinite(noise->sigma_abs) || !(noise->sigma_rel >= 0.0) ||
+      !std::isfinite(noise->sigma_rel))
+    return fail(F110QP_ERR_INVALID, "sigma_abs and sigma_rel must be >= 0 and finite");
+  if (!(noise->dropout >= 0.0 && noise->dropout <= 1.0)) return fail(F110QP_ERR_INVALID, "dropout must be in [0, 1]");
+  if (noise->car_base < 0) return fail(F110QP_ERR_INVALID, "car_base < 0");
+  if (batch > 0 && noise->car_base > 0x7fffffffffffffffll - batch)
+    return fail(F110QP_ERR_INVALID, "car_base + batch does not fit a long long");
+  Z->seed = noise->seed;
+  Z->car_base = (unsigned long long)noise->car_base;
+  Z->sigma_abs = noise->sigma_abs;
+  Z->sigma_rel = noise->sigma_rel;
+  Z->drop24 = (unsigned)std::floor(noise->dropout * 16777216.0);
+  Z->tick = 0;
+  return F110QP_OK;
+}
+
 // The scan geometry of the re-planning kernels' argument records (ReplanStart, ReplanStep).
 template <typename S>
 static void scan_geometry(S* s, const f110qp_scan_config& sc) {
@@ -154,8 +175,9 @@ static void scan_geometry(S* s, const f110qp_scan_config& sc) {
 // config is read, from kReplan the loop re-plans, from kWorld the scans are cast (so neither `ranges`
 // nor sc->scan_rows is read), kRace casts see the race-mates, kContact records every row's clearance,
 // kBody is kContact with rectangular bodies in every cast and clearance, kWalls is kBody with straight wall
-// segments next to the circles, and kRefresh is kWalls with a refresh period for the scan MPC holds.
-enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact, kBody, kWalls, kRefresh };
+// segments next to the circles, kRefresh is kWalls with a refresh period for the scan MPC holds, and kNoisy is
+// kRefresh with rules Z1 to Z3 on every scan it casts.
+enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact, kBody, kWalls, kRefresh, kNoisy };
 
 // The configs of a rollout call as the caller gave them and, once check_args has passed, the
 // kernels' parameters.
@@ -300,7 +322,8 @@ static int rollout_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io,
 // world w instead of read from `ranges`; from WORLD_RACE every cast also sees the race-mates at the poses it
 // casts from, and the clearances are those of the same world.
 struct WorldLoop {
-  f110qp::World w;     // checked (world_of); its circles and segments device pointers in the tick loop
+  f110qp::World w;     // checked (world_of); its circles and segments device pointers in the tick loop; the
+                       // loop gives every cast its tick (rule Z3, read by WORLD_NOISY alone)
   float* ranges_traj;  // [T][B][num_ranges] or null: one row set in the context, listed cars only
   int every;  // f110qp_rollout_refresh[_dev]: the refresh period of MPC's scan, 0 (every other family): never
 };
@@ -342,6 +365,12 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
     wscan = (float*)c->rscan.p;
   }
   auto scan_row = [&](size_t t) { return wscan ? wscan : wl->ranges_traj + t * B * nr; };
+  // tick t's cast at row t's poses, for all cars (list and count null) or the listed ones
+  auto cast_row = [&](size_t t, const int* cars, const int* n) {
+    f110qp::World ww = wl->w;
+    ww.Z.tick = (int)t;
+    return f110qp::launch_cast_scans(ww, io.B, cars, n, io.x(t), scan_row(t), s);
+  };
   // ReplanWork, the state of the loop in c->rstate: [pose B x 4 doubles unless pose_traj] [u_held B x N
   // float2] then ints: [held_len B | held_idx B | plan_count T + 1] (zeroed by the one memset), [list B],
   // [kind 2 B unless kind_traj], [plan_status B], [best_traj B], [best_global B] unless given
@@ -370,8 +399,7 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
   if (rows_on) {
     if (wl) {  // MPC's scan is the first one (src/project.cpp:45-49): every car's, at row 0
       ranges = scan_row(0);
-      e = f110qp::launch_cast_scans(wl->w, io.B, nullptr, nullptr, io.x(0), scan_row(0), s);
-      if (e != hipSuccess) return hip_fail(e, "scan cast launch");
+      if ((e = cast_row(0, nullptr, nullptr)) != hipSuccess) return hip_fail(e, "scan cast launch");
     }
     e = f110qp::launch_gap_search(scan_rows * io.B, ranges, sc.num_ranges, sc.angle_min, sc.angle_increment,
                                   sc.angle_max, sc.ftg_thresh, sc.divider, sc.buffer, w.rec, s);
@@ -408,8 +436,7 @@ static int replan_ticks(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, 
     if (wl) {
       const bool refresh = rows_on && wl->every > 0 && t > 0 && t % (size_t)wl->every == 0;
       const bool all = wl->ranges_traj != nullptr || refresh;
-      e = f110qp::launch_cast_scans(wl->w, io.B, all ? nullptr : list, all ? nullptr : count + t, io.x(t), scan_row(t),
-                                    s);
+      e = cast_row(t, all ? nullptr : list, all ? nullptr : count + t);
       if (e != hipSuccess) return hip_fail(e, "scan cast launch");
       if (refresh) {  // MPC's scan becomes tick t's: new records, and the rows this tick's solve reads
         e = f110qp::launch_gap_refresh(io.B, scan_row(t), sc.num_ranges, sc.angle_min, sc.angle_increment,
@@ -537,7 +564,7 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
   ContactLoop dcl{};
   if (wl)
     hw = WorldIO{wl->w.circles, (size_t)wl->w.P.world_rows * (size_t)wl->w.P.C * 3 * 8, wl->ranges_traj, wl->w.segments,
-                 wl->w.family == f110qp::WORLD_WALLS ? (size_t)wl->w.Wl.wall_rows * (size_t)wl->w.Wl.S * 4 * 8 : 0};
+                 wl->w.family >= f110qp::WORLD_WALLS ? (size_t)wl->w.Wl.wall_rows * (size_t)wl->w.Wl.S * 4 * 8 : 0};
   if (cl) dcl = *cl;
   stage::replan_fields(L, io, &d, r, &dr, *cfg.sc, (size_t)cfg.K.T, (size_t)cfg.K.P, (size_t)cfg.rp->num_waypoints,
                        wl ? &hw : nullptr, &dw, cl ? &cl->io : nullptr, &dcl.io);
@@ -574,7 +601,8 @@ static int replan_call(f110qp_ctx* c, LoopCfg cfg, RolloutIO io, const ReplanIO&
 }
 
 // The configs of a world-family call as the caller gave them; a family reads those up to its own (wc: all,
-// race: from kRace and every clearance, cc: from kContact, body: from kBody, walls: from kWalls, rf: kRefresh).
+// race: from kRace and every clearance, cc: from kContact, body: from kBody, walls: from kWalls, rf: from kRefresh,
+// noise: kNoisy and the noisy cast).
 struct WorldCfgs {
   const f110qp_world_config* wc;
   const f110qp_race_config* race;
@@ -582,6 +610,7 @@ struct WorldCfgs {
   const f110qp_body_config* body;
   const f110qp_walls_config* walls;
   const f110qp_refresh_config* rf;
+  const f110qp_noise_config* noise;
 };
 
 // The world of a cast, a clearance or a world rollout, checked in the one order all of them share, into *w;
@@ -593,10 +622,11 @@ static int world_of(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const
   if (fam >= f110qp::WORLD_RACE && (rv = race_params(k.race, batch, k.wc->num_circles, &w->Q))) return rv;
   if (contact && (rv = contact_params(k.cc))) return rv;
   if (fam >= f110qp::WORLD_BODY && (rv = body_params(k.body, &w->H))) return rv;
-  const bool walls = fam == f110qp::WORLD_WALLS;
+  const bool walls = fam >= f110qp::WORLD_WALLS;
   if (walls && (rv = wall_params(k.walls, batch, (long long)k.wc->num_circles + k.race->group_size - 1, segments,
                                  &w->Wl)))
     return rv;
+  if (fam == f110qp::WORLD_NOISY && (rv = noise_params(k.noise, batch, &w->Z))) return rv;
   w->family = fam;
   w->circles = circles;
   w->segments = walls ? segments : nullptr;
@@ -617,18 +647,19 @@ static WorldArrays world_arrays(int batch, const double* table, const double* wp
                      ReplanIO{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}}, ContactIO{clt, nrt, crash}};
 }
 
-// f110qp_rollout_world[_dev] (kWorld), _race (kRace), _contact (kContact), _body (kBody), _walls (kWalls) and
-// _refresh (kRefresh) on the configs k their family reads.
+// f110qp_rollout_world[_dev] (kWorld), _race (kRace), _contact (kContact), _body (kBody), _walls (kWalls),
+// _refresh (kRefresh) and _noisy (kNoisy) on the configs k their family reads.
 static int world_call(f110qp_ctx* c, LoopCfg cfg, const WorldCfgs& k, WorldArrays a, const double* circles,
                       const double* segments, float* rgt, Where w) {
   static const f110qp::WorldFamily kOf[] = {f110qp::WORLD_CIRCLES, f110qp::WORLD_RACE, f110qp::WORLD_RACE,
-                                            f110qp::WORLD_BODY,    f110qp::WORLD_WALLS, f110qp::WORLD_WALLS};
+                                            f110qp::WORLD_BODY,    f110qp::WORLD_WALLS, f110qp::WORLD_WALLS,
+                                            f110qp::WORLD_NOISY};
   WorldLoop wl{};
   int rv = check_args(c, &cfg, &a.io, nullptr, nullptr, &a.r);
   if (rv) return rv;
   const bool contact = cfg.fam >= kContact;
   if ((rv = world_of(kOf[cfg.fam - kWorld], cfg.sc, k, contact, a.io.B, circles, segments, &wl.w))) return rv;
-  if (cfg.fam == kRefresh && (rv = refresh_params(k.rf, &wl.every))) return rv;
+  if (cfg.fam >= kRefresh && (rv = refresh_params(k.rf, &wl.every))) return rv;
   if (a.io.B == 0) return F110QP_OK;
   if (contact && (!a.k.clear_traj || !a.k.crash_tick))
     return fail(F110QP_ERR_INVALID, "clear_traj/crash_tick must be non-NULL");
@@ -639,17 +670,20 @@ static int world_call(f110qp_ctx* c, LoopCfg cfg, const WorldCfgs& k, WorldArray
   return w.host ? replan_host(c, cfg, a.io, a.r, &wl, clp) : replan_ticks(c, cfg, a.io, a.r, w.stream, &wl, clp);
 }
 
-// f110qp_cast_scans[_race|_body|_walls]_dev on the configs k their family reads.
+// f110qp_cast_scans[_race|_body|_walls|_noisy]_dev on the configs k their family reads; tick: rule Z3's t of the
+// noisy cast (0 elsewhere).
 static int cast_call(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const WorldCfgs& k, int batch,
                      const int* list, const int* count, const double* x, const double* circles,
-                     const double* segments, float* ranges, void* stream) {
+                     const double* segments, float* ranges, void* stream, int tick = 0) {
   static const char* const kLaunch[] = {"scan cast launch", "race scan cast launch", "body scan cast launch",
-                                        "walls scan cast launch"};
+                                        "walls scan cast launch", "noisy scan cast launch"};
   int rv = check_scan_config(sc, false, 0);
   if (rv) return rv;
   if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
   f110qp::World w{};
   if ((rv = world_of(fam, sc, k, false, batch, circles, segments, &w))) return rv;
+  if (tick < 0) return fail(F110QP_ERR_INVALID, "tick < 0");
+  w.Z.tick = tick;
   if ((list != nullptr) != (count != nullptr))
     return fail(F110QP_ERR_INVALID, "list and count must be given together");
   if (batch == 0) return F110QP_OK;
@@ -1210,6 +1244,52 @@ int f110qp_rollout_refresh(f110qp_ctx* c, const f110qp_rollout_config* rc, const
                                      bgt, poset, clt, nrt, crash);
   return world_call(c, LoopCfg{kRefresh, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf}, a, circles, segments,
                     rgt, on_host());
+}
+
+// ---- a noisy LiDAR (f110qp_cast_scans_noisy_dev, f110qp_rollout_noisy[_dev]) ------------------------------------
+
+void f110qp_default_noise_config(f110qp_noise_config* noise) {
+  if (!noise) return;
+  std::memset(noise, 0, sizeof(*noise));
+}
+
+int f110qp_cast_scans_noisy_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
+                                const f110qp_race_config* race, const f110qp_body_config* body,
+                                const f110qp_walls_config* walls, const f110qp_noise_config* noise, int batch,
+                                int tick, const int* list, const int* count, const double* x, const double* circles,
+                                const double* segments, float* ranges, void* stream) {
+  return cast_call(f110qp::WORLD_NOISY, sc, WorldCfgs{wc, race, nullptr, body, walls, nullptr, noise}, batch, list,
+                   count, x, circles, segments, ranges, stream, tick);
+}
+
+int f110qp_rollout_noisy_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                             const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                             const f110qp_race_config* race, const f110qp_contact_config* cc,
+                             const f110qp_body_config* body, const f110qp_walls_config* walls,
+                             const f110qp_refresh_config* rf, const f110qp_noise_config* noise, int batch,
+                             const double* table, const double* wp, double* xr, int* have, const double* circles,
+                             const double* segments, double* xt, double* ult, float* ua, int* stt, int* itt,
+                             double* cot, float* up, float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt,
+                             double* poset, float* rgt, double* clt, int* nrt, int* crash, void* stream) {
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kNoisy, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf, noise}, a, circles,
+                    segments, rgt, on_stream(stream));
+}
+
+int f110qp_rollout_noisy(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                         const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                         const f110qp_race_config* race, const f110qp_contact_config* cc,
+                         const f110qp_body_config* body, const f110qp_walls_config* walls,
+                         const f110qp_refresh_config* rf, const f110qp_noise_config* noise, int batch,
+                         const double* table, const double* wp, double* xr, int* have, const double* circles,
+                         const double* segments, double* xt, double* ult, float* ua, int* stt, int* itt, double* cot,
+                         float* up, float* xp, float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset,
+                         float* rgt, double* clt, int* nrt, int* crash) {
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kNoisy, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf, noise}, a, circles,
+                    segments, rgt, on_host());
 }
 
 }  // extern "C"

@@ -246,7 +246,7 @@ hipError_t launch_clearance(const World& w, int B, int rows, const double* x, do
   const int nwg = clearance_grid(w.family, B);
   const dim3 grid(nwg), block(kClearThreads);
   const ClearParams P{w.P.C, w.P.world_rows};
-  if (w.family == WORLD_WALLS)
+  if (w.family >= WORLD_WALLS)  // WORLD_NOISY: the clearance never reads the noise
     hipLaunchKernelGGL((clearance_kernel<WORLD_WALLS, const double>), grid, block, 0, s,
                        ClearCfg<WORLD_WALLS>{P, w.Q, w.H, w.Wl}, B, rows, nwg, x, w.circles, w.segments, clearance,
                        nearest, M);

@@ -415,10 +415,19 @@ struct WallParams {
   int S;
   int wall_rows;  // 1 or B
 };
+// A noisy LiDAR (rules Z1 to Z3 of include/f110qp.h): the walls cast with seeded range noise and dropout on
+// every beam it stores. drop24 = floor(dropout * 2^24), taken on the host; tick is rule Z3's t of this launch.
+struct NoiseParams {
+  unsigned long long seed;
+  unsigned long long car_base;  // >= 0: car b draws from stream car_base + b
+  double sigma_abs, sigma_rel;
+  unsigned drop24;
+  int tick;
+};
 // The families, each the one before plus one thing: circles alone (casts only), the race-mates as circles,
 // the cars as rectangles (the slab test in the cast, body_sd / body_pair in the clearance), the segments
-// (rules W1 and W2).
-enum WorldFamily { WORLD_CIRCLES = 0, WORLD_RACE = 1, WORLD_BODY = 2, WORLD_WALLS = 3 };
+// (rules W1 and W2), the noise on the scans (the clearance never reads it: it is the walls').
+enum WorldFamily { WORLD_CIRCLES = 0, WORLD_RACE = 1, WORLD_BODY = 2, WORLD_WALLS = 3, WORLD_NOISY = 4 };
 // One description of the world for both jobs. A family reads the records up to its own.
 struct World {
   WorldFamily family;
@@ -426,6 +435,7 @@ struct World {
   RaceParams Q;
   BodyParams H;
   WallParams Wl;
+  NoiseParams Z;  // the cast of WORLD_NOISY alone
   const double* circles;
   const double* segments;
 };
@@ -439,10 +449,11 @@ struct World {
 //              body 183 (184 allocated), walls 185 (192) -> 2 -> 512
 //   clearance  race 127 (the fp64 sincos and the eight poses' running minima) -> 4 -> 1,024
 //              body, walls 185 (192) -> 2 -> 512
+//              noisy 191 (192) -> 2 -> 512: the walls' caps, and its clearance is the walls instantiation
 // Nothing spills a VGPR and no kernel has scratch.
 constexpr struct {
   int cast, clearance;
-} kWorldGrids[4] = {{768, 0}, {768, 1024}, {512, 512}, {512, 512}};  // by WorldFamily
+} kWorldGrids[5] = {{768, 0}, {768, 1024}, {512, 512}, {512, 512}, {512, 512}};  // by WorldFamily
 
 // Ray casting, workload._ray_circles on the device: per car the scan of nr beams at pose x [B][3] from the
 // LiDAR lidar_offset ahead, ranges [B][nr] float32. At most cast_scans_grid(family, B) workgroups striding over

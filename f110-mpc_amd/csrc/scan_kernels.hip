@@ -47,6 +47,12 @@
 // segment), or an increment below the margin threshold: every beam. A beam outside the arc cannot meet the
 // segment at th > 0, so here too the interval changes the work and not the result. Every wall statement is
 // behind `if constexpr`.
+//
+// Noise (NOISE, cast_scans_noisy_kernel): the walls cast with rules Z1 and Z2 of include/f110qp.h in the loop
+// that converts a tile's minima to float and stores them: a counter-based hash of (seed, car, tick, beam), a
+// dropout draw and a bounded bell curve from four 16-bit fields, integers up to the one fp64 expression of
+// Z2. The car's and the tick's keys are folded once per car (uniform over the workgroup); a beam costs two
+// mixes. No LDS, no launch and no pass over HBM is added. Every noise statement is behind `if constexpr`.
 #include <hip/hip_runtime.h>
 
 #include "body_geom.h"
@@ -178,15 +184,45 @@ __device__ __forceinline__ void wall_slot(const double* __restrict__ sg, const d
   }
 }
 
+// Rule Z1's mix and rule Z2 on one beam: r the noise-free float32 range, kt the (car, tick) key, i the beam's
+// index in the whole scan.
+constexpr unsigned long long kNoiseK = 0x9E3779B97F4A7C15ull;
+constexpr double kNoiseU = 0x1.bb67ae86627e8p-16;  // the double nearest to sqrt(3 / (2^32 - 1))
+__device__ __forceinline__ unsigned long long noise_mix(unsigned long long z) {
+  z ^= z >> 30;
+  z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27;
+  z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
 #pragma clang fp contract(off)
-template <bool RACE, bool BODY, bool WALLS>
+__device__ __forceinline__ float noise_beam(const float r, const unsigned long long kt, const int i,
+                                            const NoiseParams& Z, const double max_range) {
+  const float mr = (float)max_range;
+  if (r == mr) return r;  // no return: untouched
+  const unsigned long long h = noise_mix(kt + kNoiseK * (unsigned long long)(i + 1));
+  const unsigned long long h2 = noise_mix(h + kNoiseK);
+  if ((unsigned)(h2 >> 40) < Z.drop24) return mr;
+  const int g = (int)(h & 0xffffull) + (int)((h >> 16) & 0xffffull) + (int)((h >> 32) & 0xffffull) +
+                (int)(h >> 48) - 131070;
+  const double q = (double)r;
+  const double sigma = Z.sigma_abs + Z.sigma_rel * q;
+  const double e = (sigma * (double)g) * kNoiseU;
+  return (float)fmin(fmax(q + e, 0.0), max_range);
+}
+
+#pragma clang fp contract(off)
+template <bool RACE, bool BODY, bool WALLS, bool NOISE>
 __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& Q, const BodyParams& H,
-                                         const WallParams& Wl, const int b, const double* __restrict__ x,
+                                         const WallParams& Wl, const NoiseParams& Z, const int b,
+                                         const double* __restrict__ x,
                                          const double* __restrict__ circles, const double* __restrict__ segments,
                                          float* __restrict__ ranges, double* s_dx, double* s_dy,
                                          unsigned long long* s_min, typename SlotOf<BODY>::type* s_slot) {
   static_assert(RACE || !BODY, "bodies are the race-mates'");
   static_assert(BODY || !WALLS, "walls come with the body cast");
+  static_assert(WALLS || !NOISE, "the noise comes with the walls cast");
   using Slot = typename SlotOf<BODY>::type;
   const int tid = threadIdx.x;
   const double ori = x[(size_t)b * 3 + 2];
@@ -211,6 +247,11 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
   if constexpr (WALLS) {
     nc += Wl.S;
     sw = segments + (Wl.wall_rows == 1 ? (size_t)0 : (size_t)b * (size_t)Wl.S * 4);
+  }
+  unsigned long long kt = 0;  // the key of (car, tick): uniform over the workgroup
+  if constexpr (NOISE) {
+    const unsigned long long kc = noise_mix(Z.seed + kNoiseK * (Z.car_base + (unsigned long long)b + 1ull));
+    kt = noise_mix(kc + kNoiseK * ((unsigned long long)Z.tick + 1ull));
   }
   for (int cb = 0; cb < nr; cb += kCastBeamTile) {
     const int nb = min(kCastBeamTile, nr - cb);
@@ -314,20 +355,26 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
       __syncthreads();
     }
     float* out = ranges + (size_t)b * (size_t)nr + cb;
-    for (int i = tid; i < nb; i += kCastThreads) out[i] = (float)__longlong_as_double((long long)s_min[i]);
+    if constexpr (NOISE) {
+      for (int i = tid; i < nb; i += kCastThreads)
+        out[i] = noise_beam((float)__longlong_as_double((long long)s_min[i]), kt, cb + i, Z, P.max_range);
+    } else {
+      for (int i = tid; i < nb; i += kCastThreads) out[i] = (float)__longlong_as_double((long long)s_min[i]);
+    }
     __syncthreads();  // the next tile (or car) resets the minima
   }
 }
 
 // Workgroup w takes cars w, w + nwg, ... below B, or with a list the cars list[w], list[w + nwg], ...
 // below min(*count, B) (plan_listed_kernel's rule: one past the count leaves at that load).
-template <bool RACE, bool BODY = false, bool WALLS = false>
+template <bool RACE, bool BODY = false, bool WALLS = false, bool NOISE = false>
 __device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams& Q, const BodyParams& H, const int B,
                                            const int nwg, const int* __restrict__ list,
                                            const int* __restrict__ count, const double* __restrict__ x,
                                            const double* __restrict__ circles, float* __restrict__ ranges,
                                            const WallParams& Wl = WallParams{},
-                                           const double* __restrict__ segments = nullptr) {
+                                           const double* __restrict__ segments = nullptr,
+                                           const NoiseParams& Z = NoiseParams{}) {
   __shared__ double s_dx[kCastBeamTile];
   __shared__ double s_dy[kCastBeamTile];
   __shared__ unsigned long long s_min[kCastBeamTile];
@@ -336,7 +383,7 @@ __device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams
   for (int k = blockIdx.x; k < n; k += nwg) {
     const int b = list ? list[k] : k;
     if (b >= 0 && b < B)  // uniform over the workgroup
-      cast_one<RACE, BODY, WALLS>(P, Q, H, Wl, b, x, circles, segments, ranges, s_dx, s_dy, s_min, s_slot);
+      cast_one<RACE, BODY, WALLS, NOISE>(P, Q, H, Wl, Z, b, x, circles, segments, ranges, s_dx, s_dy, s_min, s_slot);
   }
 }
 
@@ -376,6 +423,14 @@ __global__ __launch_bounds__(kCastThreads) void cast_scans_walls_kernel(
   cast_scans<true, true, true>(P, Q, H, B, nwg, list, count, x, circles, ranges, Wl, segments);
 }
 
+// The walls cast with rules Z1 and Z2 on every beam it stores (NOISE).
+__global__ __launch_bounds__(kCastThreads) void cast_scans_noisy_kernel(
+    const CastParams P, const RaceParams Q, const BodyParams H, const WallParams Wl, const NoiseParams Z, const int B,
+    const int nwg, const int* __restrict__ list, const int* __restrict__ count, const double* __restrict__ x,
+    const double* __restrict__ circles, const double* __restrict__ segments, float* __restrict__ ranges) {
+  cast_scans<true, true, true, true>(P, Q, H, B, nwg, list, count, x, circles, ranges, Wl, segments, Z);
+}
+
 int cast_scans_grid(WorldFamily family, int B) {
   const int cap = kWorldGrids[family].cast;
   return B < cap ? B : cap;
@@ -386,7 +441,10 @@ hipError_t launch_cast_scans(const World& w, int B, const int* list, const int* 
   if (B <= 0) return hipSuccess;
   const int nwg = cast_scans_grid(w.family, B);
   const dim3 grid(nwg), block(kCastThreads);
-  if (w.family == WORLD_WALLS)
+  if (w.family == WORLD_NOISY)
+    hipLaunchKernelGGL(cast_scans_noisy_kernel, grid, block, 0, s, w.P, w.Q, w.H, w.Wl, w.Z, B, nwg, list, count, x,
+                       w.circles, w.segments, ranges);
+  else if (w.family == WORLD_WALLS)
     hipLaunchKernelGGL(cast_scans_walls_kernel, grid, block, 0, s, w.P, w.Q, w.H, w.Wl, B, nwg, list, count, x,
                        w.circles, w.segments, ranges);
   else if (w.family == WORLD_BODY)

@@ -149,6 +149,10 @@ EXPORTED = (
     "f110qp_gap_refresh_dev",
     "f110qp_rollout_refresh_dev",
     "f110qp_rollout_refresh",
+    "f110qp_default_noise_config",
+    "f110qp_cast_scans_noisy_dev",
+    "f110qp_rollout_noisy_dev",
+    "f110qp_rollout_noisy",
     "f110qp_path_lengths",
     "f110qp_progress_dev",
     "f110qp_standings_dev",
@@ -265,6 +269,16 @@ class RefreshConfig(C.Structure):
     ]
 
 
+class NoiseConfig(C.Structure):
+    _fields_ = [
+        ("seed", C.c_ulonglong),
+        ("car_base", C.c_longlong),
+        ("sigma_abs", C.c_double),
+        ("sigma_rel", C.c_double),
+        ("dropout", C.c_double),
+    ]
+
+
 # f110qp_gap_record (16 bytes) as a numpy record
 GAP_RECORD_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("r_lo", np.float32), ("r_hi", np.float32)])
 
@@ -356,6 +370,11 @@ def load(test: bool = False):
     L.f110qp_gap_refresh_dev.argtypes = [sp, C.c_int] + [fp] * 5
     L.f110qp_rollout_refresh_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, C.c_int] + [fp] * 25
     L.f110qp_rollout_refresh.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, C.c_int] + [fp] * 24
+    nzp = C.POINTER(NoiseConfig)
+    L.f110qp_default_noise_config.argtypes = [nzp]
+    L.f110qp_cast_scans_noisy_dev.argtypes = [sp, wcp, rcp, bcp, wlp, nzp, C.c_int, C.c_int] + [fp] * 7
+    L.f110qp_rollout_noisy_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, nzp, C.c_int] + [fp] * 25
+    L.f110qp_rollout_noisy.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, nzp, C.c_int] + [fp] * 24
     L.f110qp_path_lengths.argtypes = [fp, C.c_int, fp]
     L.f110qp_progress_dev.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_int] + [fp] * 4
     L.f110qp_standings_dev.argtypes = [rcp, C.c_int, C.c_int, fp, C.c_double] + [fp] * 4
@@ -502,6 +521,15 @@ def default_refresh_config(**over) -> RefreshConfig:
     """f110qp_default_refresh_config: every 0 (MPC keeps its first scan, the reference)."""
     c = RefreshConfig()
     load().f110qp_default_refresh_config(C.byref(c))
+    for k, v in over.items():
+        setattr(c, k, v)
+    return c
+
+
+def default_noise_config(**over) -> NoiseConfig:
+    """f110qp_default_noise_config: all zero (no noise); seed, car_base, sigma_abs, sigma_rel, dropout."""
+    c = NoiseConfig()
+    load().f110qp_default_noise_config(C.byref(c))
     for k, v in over.items():
         setattr(c, k, v)
     return c
@@ -986,7 +1014,7 @@ class Solver:
                           iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
                           plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
                           ranges_traj=None, stream=None, _race=None, _contact=None, _body=None, _walls=None,
-                          _refresh=None):
+                          _refresh=None, _noise=None):
         """rollout_replan_dev with every tick's scan cast at that tick's pose (f110qp_rollout_world_dev): wc
         and circles [world_rows,C,3] f64 replace ranges, sc.scan_rows is not read, and the optional
         ranges_traj [T,B,num_ranges] f32 records every car's scan of every tick."""
@@ -1017,6 +1045,8 @@ class Solver:
             name, cfgs, world = "f110qp_rollout_walls_dev", cfgs + [C.byref(walls)], world + [_tp(segments)]
             if _refresh is not None:  # the refresh config behind walls
                 name, cfgs = "f110qp_rollout_refresh_dev", cfgs + [C.byref(_refresh)]
+                if _noise is not None:  # the noise config behind rf
+                    name, cfgs = "f110qp_rollout_noisy_dev", cfgs + [C.byref(_noise)]
         _devs(*self._plan_specs(rp, B, *plan), (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
               *self._traj_specs(T, B, *traj), *self._record_specs(T, B, *rec),
               (ranges_traj, "f32", T * B * int(sc.num_ranges), "ranges_traj", True), *more)
@@ -1106,9 +1136,30 @@ class Solver:
                                _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
                                _walls=(walls, segments), _refresh=rf)
 
+    def rollout_noisy_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
+                          cc: ContactConfig, body: BodyConfig, walls: WallsConfig, rf: RefreshConfig, noise: NoiseConfig,
+                          table, waypoints, x_ref, have_path, circles, segments, x_traj, u_lin_traj, u_applied,
+                          status_traj, clear_traj, crash_tick, nearest_traj=None, iters_traj=None, cost_traj=None,
+                          u_plan=None, x_plan=None, hs_traj=None, kind_traj=None, plan_status_traj=None,
+                          best_traj_traj=None, best_global_traj=None, pose_traj=None, ranges_traj=None, stream=None):
+        """rollout_refresh_dev with seeded range noise and dropout on every scan it casts
+        (f110qp_rollout_noisy_dev): noise follows rf, everything else as there; the all-zero noise config is
+        rollout_refresh_dev."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
+                or not isinstance(walls, WallsConfig) or not isinstance(rf, RefreshConfig) \
+                or not isinstance(noise, NoiseConfig):
+            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig, walls a WallsConfig, "
+                              "rf a RefreshConfig and noise a NoiseConfig")
+        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
+                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
+                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
+                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
+                               _walls=(walls, segments), _refresh=rf, _noise=noise)
+
     def rollout_world(self, x0, u_lin, circles, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
                       wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
-                      scans=False, rc=None, _race=None, _contact=None, _body=None, _segments=None, _refresh=None):
+                      scans=False, rc=None, _race=None, _contact=None, _body=None, _segments=None, _refresh=None,
+                      _noise=None):
         """rollout_replan() in a world of circles (f110qp_rollout_world, synchronous): circles [C,3] (one world
         for all cars) or [B,C,3] float64 replace ranges; wc defaults to f110qp_default_world_config with
         num_circles and world_rows taken from the array. scans=True adds ranges_traj [T,B,num_ranges]."""
@@ -1150,6 +1201,8 @@ class Solver:
             name, cfgs, world = "f110qp_rollout_walls", cfgs + [C.byref(wl)], world + [_p(sg) if sg.size else None]
             if _refresh is not None:  # the refresh config behind walls
                 name, cfgs = "f110qp_rollout_refresh", cfgs + [C.byref(_refresh)]
+                if _noise is not None:  # the noise config behind rf
+                    name, cfgs = "f110qp_rollout_noisy", cfgs + [C.byref(_noise)]
         self._chk(getattr(self.lib, name)(
             self._h, C.byref(self._ticks_config(rc, T)), C.byref(sc), C.byref(rp), C.byref(w),
             *cfgs, B, _p(tab), _p(wp) if wp.shape[0] else None, _p(xr), _p(hv),
@@ -1208,6 +1261,20 @@ class Solver:
         return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
                                   objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
                                   _segments=segments, _refresh=rf)
+
+    def rollout_noisy(self, x0, u_lin, circles, segments, race: RaceConfig, cc: ContactConfig, body: BodyConfig,
+                      rf: RefreshConfig, noise: NoiseConfig, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
+                      wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
+                      scans=False, nearest=True, rc=None):
+        """rollout_refresh() with seeded range noise and dropout on every scan (f110qp_rollout_noisy,
+        synchronous): noise follows rf, everything else as there."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
+                or not isinstance(rf, RefreshConfig) or not isinstance(noise, NoiseConfig):
+            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig, rf a RefreshConfig "
+                              "and noise a NoiseConfig")
+        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
+                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
+                                  _segments=segments, _refresh=rf, _noise=noise)
 
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
@@ -1438,8 +1505,9 @@ def _wall_spec(walls, segments):
     return (segments, "f64", 4 * max(Sn, 0) * max(int(walls.wall_rows), 0), "segments", Sn <= 0)
 
 
-def _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race=_NO, body=_NO, walls=_NO, segments=None):
-    """The body of the four cast_scans*_dev."""
+def _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race=_NO, body=_NO, walls=_NO, segments=None,
+                noise=_NO, tick=0):
+    """The body of the five cast_scans*_dev."""
     import torch
 
     if body is not _NO and not isinstance(body, BodyConfig):
@@ -1453,11 +1521,15 @@ def _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race=_NO, body
           (count, "i32", 1, "count", True))
     if stream is None:
         stream = torch.cuda.current_stream(x.device)
-    family = "_walls" if walls is not _NO else "_body" if body is not _NO else "_race" if race is not _NO else ""
+    if noise is not _NO and not isinstance(noise, NoiseConfig):
+        raise F110QPError("noise must be a NoiseConfig")
+    family = "_noisy" if noise is not _NO else "_walls" if walls is not _NO else "_body" if body is not _NO \
+        else "_race" if race is not _NO else ""
     name = f"f110qp_cast_scans{family}_dev"
-    cfgs = [C.byref(k) for k in (sc, wc, race, body, walls) if k is not _NO]
+    cfgs = [C.byref(k) for k in (sc, wc, race, body, walls, noise) if k is not _NO]
     segs = [_tp(segments)] if walls is not _NO else []
-    _check(getattr(load(), name)(*cfgs, B, _tp(list_), _tp(count), _tp(x), _tp(circles), *segs, _tp(ranges),
+    ticks = [int(tick)] if noise is not _NO else []  # rule Z3's t follows batch
+    _check(getattr(load(), name)(*cfgs, B, *ticks, _tp(list_), _tp(count), _tp(x), _tp(circles), *segs, _tp(ranges),
                                  C.c_void_p(stream.cuda_stream)), name)
 
 
@@ -1524,6 +1596,14 @@ def cast_scans_walls_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body
     """cast_scans_body_dev with straight wall segments in every scan (f110qp_cast_scans_walls_dev): segments
     [wall_rows,S,4] f64 = (ax, ay, bx, by), None for S = 0."""
     _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race, body, walls, segments)
+
+
+def cast_scans_noisy_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig,
+                         noise: NoiseConfig, tick, x, circles, segments, ranges, list_=None, count=None, stream=None):
+    """cast_scans_walls_dev with seeded range noise and dropout on every beam (f110qp_cast_scans_noisy_dev, rules
+    Z1 and Z2 of f110qp.h): noise follows walls, tick (the t of rule Z1's draw) follows it. The oracle is
+    workload.noisy_scan on cast_scans_walls_dev's output."""
+    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race, body, walls, segments, noise, tick)
 
 
 def clearance_walls_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, x, circles, segments,

@@ -644,6 +644,58 @@ def make_wall_world(seed: int = 0, obstacles: int = 40, every: int = 4):
     return np.ascontiguousarray(np.concatenate(segs)), np.ascontiguousarray(w[2 * W:])
 
 
+# ---- a noisy LiDAR (f110qp_cast_scans_noisy_dev, f110qp_rollout_noisy[_dev]; rules Z1 to Z3 of f110qp.h) -------
+
+NOISE_K = np.uint64(0x9E3779B97F4A7C15)
+NOISE_U = float.fromhex("0x1.bb67ae86627e8p-16")  # the double nearest to sqrt(3 / (2^32 - 1))
+
+
+def _noise_mix(z):
+    z = np.asarray(z, np.uint64)
+    with np.errstate(over="ignore"):
+        z = z ^ (z >> np.uint64(30))
+        z = z * np.uint64(0xBF58476D1CE4E5B9)
+        z = z ^ (z >> np.uint64(27))
+        z = z * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return z
+
+
+def scan_noise_draws(seed: int, car: int, tick: int, num_ranges: int):
+    """Rule Z1 for the beams 0 .. num_ranges - 1 of car `car` (car_base + b) at tick `tick`: (h uint64, g int64 in
+    [-131070, 131070], d uint64 below 2^24), all in wrapping unsigned 64-bit arithmetic."""
+    u = lambda v: np.uint64(int(v) & 0xFFFFFFFFFFFFFFFF)  # noqa: E731
+    m = np.uint64(0xFFFF)
+    with np.errstate(over="ignore"):
+        kc = _noise_mix(u(seed) + NOISE_K * u(int(car) + 1))
+        kt = _noise_mix(kc + NOISE_K * u(int(tick) + 1))
+        h = _noise_mix(kt + NOISE_K * np.arange(1, int(num_ranges) + 1, dtype=np.uint64))
+        d = _noise_mix(h + NOISE_K) >> np.uint64(40)
+    g = ((h & m) + ((h >> np.uint64(16)) & m) + ((h >> np.uint64(32)) & m) + (h >> np.uint64(48))).astype(np.int64)
+    return h, g - 131070, d
+
+
+def noisy_scan(ranges, seed: int, car_base: int, tick: int, sigma_abs: float, sigma_rel: float, dropout: float,
+               max_range: float = 10.0) -> np.ndarray:
+    """Rule Z2 on the noise-free scans ranges [B, R] float32 (the walls cast's): car b draws from stream
+    car_base + b. A no-return beam (== (float)max_range) is untouched, a dropped beam becomes one, every other
+    becomes (float)fmin(fmax(q + (sigma * g) * U, 0), max_range) with sigma = sigma_abs + sigma_rel * q."""
+    r = np.ascontiguousarray(ranges, np.float32)
+    if r.ndim != 2:
+        raise ValueError("ranges must be [B, R]")
+    mr = np.float32(max_range)
+    drop24 = int(np.floor(np.float64(dropout) * 16777216.0))
+    out = np.empty_like(r)
+    for b in range(r.shape[0]):
+        _, g, d = scan_noise_draws(seed, int(car_base) + b, tick, r.shape[1])
+        q = r[b].astype(np.float64)
+        sigma = np.float64(sigma_abs) + np.float64(sigma_rel) * q
+        e = (sigma * g.astype(np.float64)) * NOISE_U
+        v = np.fmin(np.fmax(q + e, 0.0), np.float64(max_range)).astype(np.float32)
+        out[b] = np.where(r[b] == mr, r[b], np.where(d < np.uint64(drop24), mr, v))
+    return out
+
+
 # ---- race standings (f110qp_path_lengths, f110qp_progress_dev, f110qp_standings_dev) ------------------------
 
 def path_lengths(wp) -> np.ndarray:

@@ -1294,6 +1294,102 @@ int f110qp_rollout_refresh(f110qp_ctx* ctx, const f110qp_rollout_config* rc, con
                            int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
                            int* nearest_traj, int* crash_tick);
 
+/* ---- a noisy LiDAR: seeded range noise and dropout, for Monte Carlo closed loops --------------------------
+ * Every scan above is the exact geometric range, so two cars with the same start in the same world drive the
+ * same bits. The family below is f110qp_rollout_refresh[_dev] with range noise and dropout on every scan it
+ * casts: one batch gives M independent hypotheses of one situation, and a run repeats exactly. The noise is
+ * built from integers only (a counter-based hash and a sum of four 16-bit fields as the bell curve; no log, cos
+ * or library generator), so any host computes the same bits. A modelling choice of this library, not the
+ * reference's; the all-zero config is the refresh family. Additive: F110QP_API_VERSION stays 6, and no call above
+ * changes its results. The disc-body families get no noise.
+ *
+ * Z1. Draws. All arithmetic is unsigned 64-bit and wraps. K = 0x9E3779B97F4A7C15, and mix(z) is
+ *       z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.
+ *     For car b, tick t and beam i (the beam's index in the whole scan):
+ *       kc = mix(seed + K * (uint64)(car_base + b + 1))
+ *       kt = mix(kc + K * (uint64)(t + 1))
+ *       h  = mix(kt + K * (uint64)(i + 1))
+ *       h2 = mix(h + K)
+ *       g  = (h & 0xffff) + ((h >> 16) & 0xffff) + ((h >> 32) & 0xffff) + (h >> 48) - 131070,
+ *            a signed integer in [-131070, 131070];
+ *       d  = h2 >> 40, 24 bits.
+ *     Known answers for seed 1234, car_base + b = 0, t = 0, beams 0 to 3:
+ *       h = 0x52b6d2127195ace2, 0x47208de8f3630884, 0x4c2edc5013e0a4f2, 0x8f2930e8f7aeddb0
+ *       g = 17217, -12047, -7854, 38257
+ *       d = 5026570, 3948636, 15546533, 623436
+ * Z2. A beam. r is the float32 range f110qp_cast_scans_walls_dev writes for that beam, q = (double)r,
+ *     mr = (float)max_range and drop24 = (unsigned)floor(dropout * 16777216.0) (taken on the host, once per
+ *     call; dropout = 1 drops every beam). In this order:
+ *       1. r == mr (no return): the output is r, untouched;
+ *       2. d < drop24: the output is mr;
+ *       3. otherwise sigma = sigma_abs + sigma_rel * q, e = (sigma * (double)g) * U and the output is
+ *          (float)fmin(fmax(q + e, 0.0), max_range).
+ *     Every product and sum is rounded (no fused multiply-add), as everywhere in this family.
+ *     U = 0x1.bb67ae86627e8p-16, the double nearest to sqrt(3 / (2^32 - 1)): the reciprocal of the standard
+ *     deviation of the sum of four uniform 16-bit fields.
+ *     Consequences. g * U has mean 0 and standard deviation 1 and lies within +-3.4642: the noise is bounded.
+ *     The value of a beam depends only on (r, seed, car_base + b, t, i) and the config: not on the list, the
+ *     grid, the tile, the other cars or the batch size. With sigma_abs = sigma_rel = dropout = 0 the output is
+ *     r exactly. The noise is applied to the float32-rounded range on purpose: the noisy scan is a pure function
+ *     of the noise-free scan.
+ * Z3. Ticks. In a rollout the all-cars cast at row 0 uses t = 0, and tick t's cast (listed or all-cars, refresh
+ *     or not) uses t: tick 0's listed cast at the same pose equals row 0's scan, as in the families above. */
+typedef struct {
+  unsigned long long seed;   /* the run                                                      */
+  long long car_base;        /* >= 0: car b draws from stream car_base + b (what a sharded   */
+                             /* caller sets to the shard's first global car)                 */
+  double sigma_abs;          /* >= 0, metres                                                 */
+  double sigma_rel;          /* >= 0, per metre of range: sigma = sigma_abs + sigma_rel * q  */
+  double dropout;            /* in [0, 1]: share of beams that return nothing                */
+} f110qp_noise_config;
+
+/* Zeroes *noise: no noise. */
+void f110qp_default_noise_config(f110qp_noise_config* noise);
+
+/* f110qp_cast_scans_walls_dev, word for word, with rules Z1 and Z2 on every beam it writes (one launch, the noise
+ * in the kernel's own store loop): noise follows walls, and tick (rule Z3's t) follows batch. F110QP_ERR_INVALID
+ * before any HIP call, on top of that call's rules: a NULL noise, a negative or non-finite sigma_abs or
+ * sigma_rel, dropout outside [0, 1] or NaN, car_base < 0 or car_base + batch above LLONG_MAX, tick < 0. The
+ * all-zero config gives f110qp_cast_scans_walls_dev's bits (through the same kernel as any other config).
+ * Listed cars get the bits of the all-cars cast; unlisted rows are not touched. At most min(batch, 512)
+ * workgroups. */
+int f110qp_cast_scans_noisy_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
+                                const f110qp_race_config* race, const f110qp_body_config* body,
+                                const f110qp_walls_config* walls, const f110qp_noise_config* noise, int batch,
+                                int tick, const int* list, const int* count, const double* x,
+                                const double* circles, const double* segments, float* ranges, void* stream);
+
+/* f110qp_rollout_refresh_dev, word for word, with noise following rf: every cast is f110qp_cast_scans_noisy_dev's
+ * with rule Z3's tick, so the planner, the gap records at row 0 and every refreshed record read noisy scans, and
+ * ranges_traj holds them. The clearances never read the noise. That call's launch count, stream order, parking
+ * and absence of host synchronisation, read-back and allocation inside the loop; every argument is checked before
+ * the first launch (that call's checks, then rf, the noise rules above coming behind the walls'). The all-zero
+ * config gives f110qp_rollout_refresh_dev's bits in every array. */
+int f110qp_rollout_noisy_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                             const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                             const f110qp_race_config* race, const f110qp_contact_config* cc,
+                             const f110qp_body_config* body, const f110qp_walls_config* walls,
+                             const f110qp_refresh_config* rf, const f110qp_noise_config* noise, int batch,
+                             const double* table, const double* waypoints, double* x_ref, int* have_path,
+                             const double* circles, const double* segments, double* x_traj, double* u_lin_traj,
+                             float* u_applied, int* status_traj, int* iters_traj, double* cost_traj, float* u_plan,
+                             float* x_plan, float* hs_traj, int* kind_traj, int* plan_status_traj,
+                             int* best_traj_traj, int* best_global_traj, double* pose_traj, float* ranges_traj,
+                             double* clear_traj, int* nearest_traj, int* crash_tick, void* stream);
+
+/* Same on host pointers (synchronous), staged as f110qp_rollout_refresh: the call adds no array. */
+int f110qp_rollout_noisy(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                         const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                         const f110qp_race_config* race, const f110qp_contact_config* cc,
+                         const f110qp_body_config* body, const f110qp_walls_config* walls,
+                         const f110qp_refresh_config* rf, const f110qp_noise_config* noise, int batch,
+                         const double* table, const double* waypoints, double* x_ref, int* have_path,
+                         const double* circles, const double* segments, double* x_traj, double* u_lin_traj,
+                         float* u_applied, int* status_traj, int* iters_traj, double* cost_traj, float* u_plan,
+                         float* x_plan, float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
+                         int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
+                         int* nearest_traj, int* crash_tick);
+
 /* ---- race standings: progress along the track, laps and positions ---------------------------------------
  * The calls above return poses; the calls below say who is ahead. They run after the fact on x_traj, or on any
  * [rows][B][3] pose array: nothing inside a closed loop reads a standing, so there is no rollout family of
