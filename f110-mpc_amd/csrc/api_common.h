@@ -1,6 +1,6 @@
 // api_common.h — what the C ABI's translation units share: f110qp_api.cpp (the context, the solve
-// entry points), api_rollout.cpp (the closed loops), api_plan.cpp (half-spaces, planning stage) and
-// api_standings.cpp (race standings).
+// entry points), api_rollout.cpp (the closed loops), api_plan.cpp (half-spaces, planning stage),
+// api_standings.cpp (race standings) and api_mc.cpp (Monte Carlo outcomes).
 // Everything here is internal to the library (hidden visibility: no new exported symbol).
 #pragma once
 #include <hip/hip_runtime.h>

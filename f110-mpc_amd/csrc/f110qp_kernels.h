@@ -498,4 +498,22 @@ hipError_t launch_progress(int B, int rows, const double* x, const double* wp, c
 hipError_t launch_standings(int G, int B, int rows, const double* s, double L, double* dist, int* lap, int* rank,
                             hipStream_t stream);
 
+// ---- Monte Carlo outcomes (mc_kernels.hip) ----------------------------------------------------------
+// The quantile fan of v [rows][B] (the model of include/f110qp.h): B = S M G, K = B / M sample sets of M values
+// at stride G; fan [rows][K][Q], count [rows][K] or null. One launch: the wave kernel when M padded to a power
+// of two (mc_fan_padded) is at most 64, the LDS kernel up to F110QP_MC_MAX_HYPOTHESES. mc_fan_grid: the
+// workgroups of that launch for rows x K items, at most 2,048 (wave) or 1,024 (LDS), which stride.
+int mc_fan_padded(int M);
+int mc_fan_grid(int M, long long items);
+hipError_t launch_mc_fan(int M, int G, int Q, const double* prob, int B, int rows, const double* v, double* fan,
+                         int* count, hipStream_t stream);
+// alive [T + 1][K] and crashed [K] or null from crash_tick [B]: one launch, one thread per (row, set).
+hipError_t launch_mc_survival(int M, int G, int B, int T, const int* crash_tick, int* alive, int* crashed,
+                              hipStream_t stream);
+// Every car's record from clear [T + 1][B], status and kind [T][B] (either may be null): one launch, one thread
+// per car. Every output but min_clear may be null.
+hipError_t launch_mc_outcomes(int B, int T, const double* clear, const int* status, const int* kind,
+                              double* min_clear, int* min_row, int* unsolved, int* first_unsolved, int* plan_failed,
+                              hipStream_t stream);
+
 }  // namespace f110qp

@@ -157,7 +157,14 @@ EXPORTED = (
     "f110qp_progress_dev",
     "f110qp_standings_dev",
     "f110qp_race_standings",
+    "f110qp_default_mc_config",
+    "f110qp_mc_fan_dev",
+    "f110qp_mc_survival_dev",
+    "f110qp_mc_outcomes_dev",
+    "f110qp_mc_summary",
 )
+MC_MAX_HYPOTHESES = 4096  # F110QP_MC_MAX_HYPOTHESES
+MC_MAX_PROBS = 8          # F110QP_MC_MAX_PROBS
 CAST_CIRCLE_TILE = 256  # F110QP_CAST_CIRCLE_TILE: circles per LDS tile of the ray-cast kernel
 SCRATCH_NAMES = {0: "none (wave back end)", 1: "LDS fp64", 2: "LDS fp32", 3: "HBM fp64", 4: "HBM fp32"}
 
@@ -279,6 +286,15 @@ class NoiseConfig(C.Structure):
     ]
 
 
+class McConfig(C.Structure):
+    _fields_ = [
+        ("hypotheses", C.c_int),
+        ("group_size", C.c_int),
+        ("num_probs", C.c_int),
+        ("prob", C.c_double * MC_MAX_PROBS),
+    ]
+
+
 # f110qp_gap_record (16 bytes) as a numpy record
 GAP_RECORD_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("r_lo", np.float32), ("r_hi", np.float32)])
 
@@ -379,6 +395,13 @@ def load(test: bool = False):
     L.f110qp_progress_dev.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_int] + [fp] * 4
     L.f110qp_standings_dev.argtypes = [rcp, C.c_int, C.c_int, fp, C.c_double] + [fp] * 4
     L.f110qp_race_standings.argtypes = [rcp, C.c_int, C.c_int, fp, fp, C.c_int] + [fp] * 6
+    mcp = C.POINTER(McConfig)
+    L.f110qp_default_mc_config.argtypes = [mcp]
+    L.f110qp_default_mc_config.restype = None
+    L.f110qp_mc_fan_dev.argtypes = [mcp, C.c_int, C.c_int] + [fp] * 4
+    L.f110qp_mc_survival_dev.argtypes = [mcp, C.c_int, C.c_int] + [fp] * 4
+    L.f110qp_mc_outcomes_dev.argtypes = [C.c_int, C.c_int] + [fp] * 9
+    L.f110qp_mc_summary.argtypes = [mcp, C.c_int, C.c_int] + [fp] * 13
     L.f110qp_select_dev.argtypes = [C.c_int, fp, C.c_int, fp, fp, fp, fp, fp]
     L.f110qp_backend_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
     L.f110qp_lane_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -487,6 +510,25 @@ def default_race_config(**over) -> RaceConfig:
     load().f110qp_default_race_config(C.byref(c))
     for k, v in over.items():
         setattr(c, k, v)
+    return c
+
+
+def default_mc_config(**over) -> McConfig:
+    """f110qp_default_mc_config: hypotheses 1, group_size 1, num_probs 3, prob (0, 0.5, 1). prob=(...) sets the
+    probabilities and, unless num_probs is given too, their number."""
+    c = McConfig()
+    load().f110qp_default_mc_config(C.byref(c))
+    for k, v in over.items():
+        if k == "prob":
+            v = [float(p) for p in v]
+            if len(v) > MC_MAX_PROBS:
+                raise F110QPError(f"at most {MC_MAX_PROBS} probabilities, got {len(v)}")
+            for i in range(MC_MAX_PROBS):
+                c.prob[i] = v[i] if i < len(v) else 0.0
+            if "num_probs" not in over:
+                c.num_probs = len(v)
+        else:
+            setattr(c, k, v)
     return c
 
 
@@ -1691,6 +1733,111 @@ def race_standings(race: RaceConfig, x, waypoints, seg=True, lateral=True, lap=T
     _check(load().f110qp_race_standings(C.byref(race), B, rows, _p(x), _p(wp), wp.shape[0], _p(o["seg"]), _p(o["s"]),
                                         _p(o["lateral"]), _p(o["dist"]), _p(o["lap"]), _p(o["rank"])),
            "f110qp_race_standings")
+    return o
+
+
+def _mc_sets(mc: McConfig, B):
+    """K, the sample sets of a batch of B cars; the layout's rules (the C call checks the rest)."""
+    M, G, Q = int(mc.hypotheses), int(mc.group_size), int(mc.num_probs)
+    if not 1 <= M <= MC_MAX_HYPOTHESES:
+        raise F110QPError(f"hypotheses must be in 1..{MC_MAX_HYPOTHESES}, got {M}")
+    if G < 1 or B % (M * G):
+        raise F110QPError(f"hypotheses x group_size must divide B = {B}, got {M} x {G}")
+    if not 1 <= Q <= MC_MAX_PROBS:
+        raise F110QPError(f"num_probs must be in 1..{MC_MAX_PROBS}, got {Q}")
+    return B // M, Q
+
+
+def mc_fan_dev(mc: McConfig, v, fan, count=None, stream=None):
+    """The quantile fan of every sample set at every row (f110qp_mc_fan_dev): v [rows,B] f64 (or [B]: one row) ->
+    fan [rows,K,Q] f64 and, optionally, count [rows,K] i32, K = B / mc.hypotheses."""
+    import torch
+
+    rows, B = _rows_of(v, None, "v")
+    K, Q = _mc_sets(mc, B)
+    _devs((v, "f64", B * rows, "v"), (fan, "f64", rows * K * Q, "fan"), (count, "i32", rows * K, "count", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(v.device)
+    _check(load().f110qp_mc_fan_dev(C.byref(mc), B, rows, _tp(v), _tp(fan), _tp(count),
+                                    C.c_void_p(stream.cuda_stream)), "f110qp_mc_fan_dev")
+
+
+def mc_survival_dev(mc: McConfig, crash_tick, ticks: int, alive, crashed=None, stream=None):
+    """How many hypotheses of every set are still running at every row (f110qp_mc_survival_dev): crash_tick [B]
+    i32 -> alive [ticks+1,K] i32 and, optionally, crashed [K] i32."""
+    import torch
+
+    if crash_tick is None or len(crash_tick.shape) != 1 or crash_tick.shape[0] < 1:
+        raise F110QPError("crash_tick must be [B]")
+    B, T = int(crash_tick.shape[0]), int(ticks)
+    if T < 1:
+        raise F110QPError(f"ticks must be >= 1, got {T}")
+    K, _ = _mc_sets(mc, B)
+    _devs((crash_tick, "i32", B, "crash_tick"), (alive, "i32", (T + 1) * K, "alive"), (crashed, "i32", K, "crashed", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(crash_tick.device)
+    _check(load().f110qp_mc_survival_dev(C.byref(mc), B, T, _tp(crash_tick), _tp(alive), _tp(crashed),
+                                         C.c_void_p(stream.cuda_stream)), "f110qp_mc_survival_dev")
+
+
+def mc_outcomes_dev(clear_traj, min_clear, status_traj=None, kind_traj=None, min_row=None, unsolved=None,
+                    first_unsolved=None, plan_failed=None, stream=None):
+    """Every car's record (f110qp_mc_outcomes_dev): clear_traj [T+1,B] f64, status_traj and kind_traj [T,B] i32 or
+    None -> min_clear [B] f64 and, optionally, min_row, unsolved, first_unsolved and plan_failed [B] i32."""
+    import torch
+
+    rows, B = _rows_of(clear_traj, None, "clear_traj")
+    if len(clear_traj.shape) != 2 or rows < 2:
+        raise F110QPError(f"clear_traj must be [T + 1, B] with T >= 1, got {tuple(clear_traj.shape)}")
+    T = rows - 1
+    if (unsolved is not None or first_unsolved is not None) and status_traj is None:
+        raise F110QPError("unsolved and first_unsolved need status_traj")
+    if plan_failed is not None and kind_traj is None:
+        raise F110QPError("plan_failed needs kind_traj")
+    _devs((clear_traj, "f64", rows * B, "clear_traj"), (status_traj, "i32", T * B, "status_traj", True),
+          (kind_traj, "i32", T * B, "kind_traj", True), (min_clear, "f64", B, "min_clear"),
+          (min_row, "i32", B, "min_row", True), (unsolved, "i32", B, "unsolved", True),
+          (first_unsolved, "i32", B, "first_unsolved", True), (plan_failed, "i32", B, "plan_failed", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(clear_traj.device)
+    _check(load().f110qp_mc_outcomes_dev(B, T, _tp(clear_traj), _tp(status_traj), _tp(kind_traj), _tp(min_clear),
+                                         _tp(min_row), _tp(unsolved), _tp(first_unsolved), _tp(plan_failed),
+                                         C.c_void_p(stream.cuda_stream)), "f110qp_mc_outcomes_dev")
+
+
+def mc_summary(mc: McConfig, clear_traj, crash_tick, status_traj=None, kind_traj=None, count=True, crashed=True,
+               min_row=True):
+    """The three on host arrays, synchronous (f110qp_mc_summary), the fan taken on clear_traj: clear_traj [T+1,B]
+    f64, crash_tick [B] i32, status_traj and kind_traj [T,B] i32 or None -> a dict of fan [T+1,K,Q], count
+    [T+1,K], alive [T+1,K], crashed [K], min_clear, min_row, unsolved, first_unsolved and plan_failed [B]; an
+    optional output that is switched off, or whose input is None, is None."""
+    clear = _f64(clear_traj, np.shape(clear_traj), "clear_traj")
+    if clear.ndim != 2 or clear.shape[0] < 2 or clear.shape[1] < 1:
+        raise F110QPError(f"clear_traj must be [T + 1, B] with T >= 1, got {clear.shape}")
+    T, B = clear.shape[0] - 1, clear.shape[1]
+    K, Q = _mc_sets(mc, B)
+
+    def ints(a, shape, name):
+        if a is None:
+            return None
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.shape != shape:
+            got = (a.dtype, a.shape) if isinstance(a, np.ndarray) else type(a).__name__
+            raise F110QPError(f"{name} must be an int32 numpy array of shape {shape}, got {got}")
+        return np.ascontiguousarray(a)
+
+    crash = ints(crash_tick, (B,), "crash_tick")
+    if crash is None:
+        raise F110QPError("crash_tick is required")
+    status, kind = ints(status_traj, (T, B), "status_traj"), ints(kind_traj, (T, B), "kind_traj")
+    i32 = lambda shape, on: np.empty(shape, np.int32) if on else None  # noqa: E731
+    o = dict(fan=np.empty((T + 1, K, Q), np.float64), count=i32((T + 1, K), count), alive=i32((T + 1, K), True),
+             crashed=i32((K,), crashed), min_clear=np.empty(B, np.float64), min_row=i32((B,), min_row),
+             unsolved=i32((B,), status is not None), first_unsolved=i32((B,), status is not None),
+             plan_failed=i32((B,), kind is not None))
+    _check(load().f110qp_mc_summary(C.byref(mc), B, T, _p(clear), _p(crash), _p(status), _p(kind), _p(o["fan"]),
+                                    _p(o["count"]), _p(o["alive"]), _p(o["crashed"]), _p(o["min_clear"]),
+                                    _p(o["min_row"]), _p(o["unsolved"]), _p(o["first_unsolved"]), _p(o["plan_failed"])),
+           "f110qp_mc_summary")
     return o
 
 

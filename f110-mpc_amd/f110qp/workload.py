@@ -810,3 +810,94 @@ def make_race_grid(races: int, group_size: int, seed: int = 0, spacing: float = 
     hd = np.arctan2(nxt[:, 1] - wp[k, 1], nxt[:, 0] - wp[k, 0])
     lat = np.tile(np.where(i % 2 == 0, lateral, -lateral), races)
     return np.ascontiguousarray(np.stack([base[:, 0] - np.sin(hd) * lat, base[:, 1] + np.cos(hd) * lat, hd], 1))
+
+
+# ---- Monte Carlo outcomes (f110qp_mc_fan_dev, f110qp_mc_survival_dev, f110qp_mc_outcomes_dev) ---------------
+
+MC_PAD_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
+MC_NAN_BITS = np.uint64(0x7FF8000000000000)
+_MC_SIGN = np.uint64(0x8000000000000000)
+
+
+def mc_keys(v) -> np.ndarray:
+    """Rule M1 and M2 of include/f110qp.h: the uint64 keys of float64 values, ~u when the sign bit is set and
+    u | 1 << 63 otherwise; a NaN (either sign, any payload) gets MC_PAD_KEY, which no number maps to."""
+    u = np.ascontiguousarray(v, np.float64).view(np.uint64)
+    key = np.where(u & _MC_SIGN != 0, ~u, u | _MC_SIGN)
+    return np.where((u & ~_MC_SIGN) > np.uint64(0x7FF0000000000000), MC_PAD_KEY, key)
+
+
+def mc_values(key) -> np.ndarray:
+    """The float64 values of keys: the inverse of mc_keys on numbers."""
+    key = np.asarray(key, np.uint64)
+    return np.where(key & _MC_SIGN != 0, key ^ _MC_SIGN, ~key).view(np.float64)
+
+
+def _mc_layout(B, M, G):
+    M, G = int(M), int(G)
+    if M < 1 or G < 1 or B < 1 or B % (M * G):
+        raise ValueError(f"hypotheses x group_size must divide B = {B}, got {M} x {G}")
+    return B // (M * G), M, G
+
+
+def mc_fan(v, M: int, G: int, prob):
+    """The fan of include/f110qp.h (f110qp_mc_fan_dev) in numpy: v [rows, B] (or [B]) -> (fan [rows, K, Q],
+    count [rows, K] int32). The M members of set k = s G + g are the cars (s M + m) G + g. The uint64 keys are
+    sorted, not the doubles: the NaN keys sort last, count is the number of the others, and quantile q is the key
+    at floor(prob[q] * (count - 1)) turned back into its bits (0x7ff8000000000000 for count 0)."""
+    v = np.asarray(v, np.float64)
+    one = v.ndim == 1
+    v = v[None] if one else v
+    rows, B = v.shape
+    S, M, G = _mc_layout(B, M, G)
+    prob = np.asarray(prob, np.float64).reshape(-1)
+    if prob.size < 1 or not ((prob >= 0) & (prob <= 1)).all():
+        raise ValueError("every prob must be in [0, 1]")
+    key = np.sort(mc_keys(v).reshape(rows, S, M, G).transpose(0, 1, 3, 2).reshape(rows, S * G, M), axis=2)
+    n = (key != MC_PAD_KEY).sum(axis=2).astype(np.int32)
+    pos = np.floor(prob[None, None, :] * (n[:, :, None] - 1).astype(np.float64)).astype(np.int64)
+    got = np.take_along_axis(key, np.maximum(pos, 0), axis=2)
+    bits = np.where(n[:, :, None] > 0, mc_values(got).view(np.uint64), MC_NAN_BITS)
+    fan = np.ascontiguousarray(bits).view(np.float64)
+    return (fan[0], n[0]) if one else (fan, n)
+
+
+def mc_survival(crash_tick, T: int, M: int, G: int):
+    """Rule M4 (f110qp_mc_survival_dev): crash_tick [B] -> (alive [T + 1, K] int32, crashed [K] int32)."""
+    ct = np.asarray(crash_tick, np.int64).reshape(-1)
+    S, M, G = _mc_layout(ct.size, M, G)
+    c = ct.reshape(S, M, G).transpose(0, 2, 1).reshape(S * G, M)
+    r = np.arange(int(T) + 1)[:, None, None]
+    alive = ((c[None] < 0) | (c[None] > r)).sum(axis=2).astype(np.int32)
+    return alive, ((c >= 0) & (c <= int(T))).sum(axis=1).astype(np.int32)
+
+
+def mc_outcomes(clear, status=None, kind=None):
+    """Rule M5 (f110qp_mc_outcomes_dev): clear [T + 1, B], status and kind [T, B] or None -> a dict of min_clear,
+    min_row and, with status, unsolved and first_unsolved, and, with kind, plan_failed (each [B]). MPC ticks are
+    kind 0, PLAN_FAILED ticks kind 3; a usable status is 1 or 2."""
+    clear = np.asarray(clear, np.float64)
+    B = clear.shape[1]
+    c = np.where(np.isnan(clear), np.inf, clear)
+    row = np.argmin(c, axis=0)                                  # the first of equal values: the lowest row
+    best = c[row, np.arange(B)]
+    o = dict(min_clear=best, min_row=np.where(best < np.inf, row, -1).astype(np.int32))
+    if status is not None:
+        status = np.asarray(status)
+        bad = ((status != 1) & (status != 2)) & (True if kind is None else np.asarray(kind) == 0)
+        o["unsolved"] = bad.sum(axis=0).astype(np.int32)
+        o["first_unsolved"] = np.where(bad.any(axis=0), np.argmax(bad, axis=0), -1).astype(np.int32)
+    if kind is not None:
+        o["plan_failed"] = (np.asarray(kind) == 3).sum(axis=0).astype(np.int32)
+    return o
+
+
+def make_mc_batch(x0, M: int, G: int = 1) -> np.ndarray:
+    """Starts [S G, 3] (S situations of G cars) tiled into the Monte Carlo layout [S M G, 3]: car (s M + m) G + g
+    starts where car s G + g of x0 does, for every m."""
+    x0 = np.asarray(x0, np.float64)
+    M, G = int(M), int(G)
+    if x0.ndim != 2 or M < 1 or G < 1 or x0.shape[0] % G:
+        raise ValueError(f"x0 must be [S * G, 3] with G = {G}, got {x0.shape}")
+    S = x0.shape[0] // G
+    return np.ascontiguousarray(np.tile(x0.reshape(S, 1, G, -1), (1, M, 1, 1)).reshape(S * M * G, -1))

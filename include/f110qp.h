@@ -1467,6 +1467,89 @@ int f110qp_race_standings(const f110qp_race_config* race, int batch, int rows, c
                           const double* waypoints, int num_waypoints, int* seg, double* s, double* lateral,
                           double* dist, int* lap, int* rank);
 
+/* ---- Monte Carlo outcomes: per-situation quantile fans, survival, car records ------------------------------
+ * With the noisy family one batch is M reproducible hypotheses of one situation. The calls below say what became
+ * of them, on the device: the order statistics of every situation at every row, how many hypotheses are still
+ * running, and every car's own record. Like the standings they run after the fact, on clear_traj, crash_tick,
+ * status_traj and kind_traj of a rollout, or on any [rows][B] double array (lateral, s and dist of the standings
+ * calls). Every result is a selection or a count: no arithmetic touches a value and there is no tolerance.
+ * Additive: F110QP_API_VERSION stays 6, and no call above changes its results.
+ *
+ * Layout. A batch is S situations x M hypotheses x G cars of one hypothesis (G the race size, 1 without races):
+ * B = S M G and car b = (s M + m) G + g. A sample set is k = s G + g, K = S G = B / M of them; the M members of
+ * set k are the cars (s M + m) G + g for m = 0 .. M-1 with s = k / G and g = k % G: M values at stride G. With the
+ * noisy family every car draws its own stream (car_base + b), so M copies of one start are M hypotheses with
+ * nothing else to set.
+ *
+ * M1. Key. With u the 64 bits of a sample, its key is ~u when the sign bit is set and u | 1 << 63 otherwise,
+ *     compared as unsigned: a total order with -inf < ... < -0 < +0 < ... < +inf.
+ * M2. NaN. A NaN of any payload and either sign is not a sample. n is the number of the set's values at that row
+ *     that are not NaN, and count[r][k] = n.
+ * M3. The fan. fan[r][k][q] is the sample at position (int)floor(prob[q] * (double)(n - 1)) of the ascending
+ *     order of keys, the product being one rounded fp64 product. The output has that sample's own bits, so a -0
+ *     stays -0. For n = 0 the output is the NaN 0x7ff8000000000000. Equal keys are equal bits, so the result does
+ *     not depend on the sort's stability, on the thread mapping or on the batch size.
+ * M4. Survival. alive[r][k], r = 0 .. T, is the number of members with crash_tick < 0 or crash_tick > r: a car
+ *     that crashed at row r is not alive at row r. crashed[k] is the number of members with
+ *     0 <= crash_tick <= T.
+ * M5. Car records. (min_clear, min_row)[b] is the minimum of clear_traj over rows 0 .. T under the clearance
+ *     kernel's replace rule from (+inf, -1): a row replaces the running pair only when its value is smaller, or
+ *     equal with a lower row, so the lowest row wins on equal values, a NaN passes no compare, and a column of
+ *     NaN or of +inf keeps (+inf, -1). A tick is unsolved when kind_traj is NULL or the tick's kind is
+ *     F110QP_TICK_MPC, and its status is neither F110QP_SOLVED nor F110QP_SOLVED_INACCURATE. unsolved[b] counts
+ *     the unsolved ticks, first_unsolved[b] is the first one or -1, plan_failed[b] counts the ticks of kind
+ *     F110QP_TICK_PLAN_FAILED. */
+#define F110QP_MC_MAX_HYPOTHESES 4096
+#define F110QP_MC_MAX_PROBS 8
+typedef struct {
+  int hypotheses;   /* M, 1 .. F110QP_MC_MAX_HYPOTHESES */
+  int group_size;   /* G >= 1 */
+  int num_probs;    /* Q, 1 .. F110QP_MC_MAX_PROBS */
+  double prob[F110QP_MC_MAX_PROBS];  /* each in [0, 1]; any order, repeats allowed */
+} f110qp_mc_config;
+
+/* M 1, G 1, Q 3, prob {0, 0.5, 1} (the rest of prob zero). */
+void f110qp_default_mc_config(f110qp_mc_config* mc);
+
+/* The three device calls take device pointers and are asynchronous on `stream`: one launch each, no allocation,
+ * synchronisation or read-back. F110QP_ERR_INVALID before any HIP call, with a last_error text that names the
+ * field. The config rules, which every call that takes mc applies in full: a NULL mc; hypotheses outside
+ * 1 .. 4096; group_size < 1; batch < 1 or not a multiple of hypotheses x group_size; num_probs outside 1 .. 8; a
+ * prob[q], q < num_probs, that is NaN or outside [0, 1]. The shape rules: rows < 1 or ticks < 1; rows x batch
+ * above 2^30, rows being ticks + 1 where a call takes ticks.
+ *
+ * Rules M1 to M3 on v [rows][B] double -> fan [rows][K][Q] double, count [rows][K] int (may be NULL; fan does not
+ * depend on it). Also invalid: a NULL v or fan. Two kernels by M: sets of at most 64 values (M padded to a power
+ * of two) are sorted by a bitonic network over lane shuffles, 64 / padded M sets per wave; larger ones in LDS by
+ * one 256-thread workgroup per (row, set). Workgroups stride over the (row, set) items, at most 2,048 of them on
+ * the first path and 1,024 on the second (what the device holds at once). For G = 1 a set's loads are
+ * contiguous, for G > 1 they are G doubles apart. */
+int f110qp_mc_fan_dev(const f110qp_mc_config* mc, int batch, int rows, const double* v, double* fan, int* count,
+                      void* stream);
+
+/* Rule M4 on crash_tick [B] int -> alive [ticks + 1][K] int, crashed [K] int (may be NULL). Also invalid: a NULL
+ * crash_tick or alive. */
+int f110qp_mc_survival_dev(const f110qp_mc_config* mc, int batch, int ticks, const int* crash_tick, int* alive,
+                           int* crashed, void* stream);
+
+/* Rule M5 on clear_traj [ticks + 1][B] double, status_traj [ticks][B] int or NULL, kind_traj [ticks][B] int or
+ * NULL -> min_clear [B] double, min_row, unsolved, first_unsolved, plan_failed [B] int (each of the four may be
+ * NULL). No config: a car's record does not depend on the layout. Also invalid: a NULL clear_traj or min_clear;
+ * unsolved or first_unsolved given without status_traj; plan_failed given without kind_traj. */
+int f110qp_mc_outcomes_dev(int batch, int ticks, const double* clear_traj, const int* status_traj,
+                           const int* kind_traj, double* min_clear, int* min_row, int* unsolved,
+                           int* first_unsolved, int* plan_failed, void* stream);
+
+/* The three on host pointers (synchronous), the fan taken on clear_traj (rows = ticks + 1): the four inputs
+ * staged through device buffers that the call owns and frees on every exit path (there is no context), the three
+ * device calls, every output that was given copied back, one synchronisation. status_traj and kind_traj may be
+ * NULL as above; count, crashed, min_row, unsolved, first_unsolved and plan_failed may be NULL. Bit-identical to
+ * the device calls. F110QP_ERR_INVALID as theirs, before any HIP call; also a NULL crash_tick, fan or alive. */
+int f110qp_mc_summary(const f110qp_mc_config* mc, int batch, int ticks, const double* clear_traj,
+                      const int* crash_tick, const int* status_traj, const int* kind_traj, double* fan, int* count,
+                      int* alive, int* crashed, double* min_clear, int* min_row, int* unsolved, int* first_unsolved,
+                      int* plan_failed);
+
 #ifdef __cplusplus
 }
 #endif
