@@ -6,7 +6,8 @@
 // f110qp_cast_scans_body_dev, f110qp_rollout_body[_dev]) and with straight walls (f110qp_cast_scans_walls_dev,
 // f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]) and with a refreshed MPC scan (f110qp_gap_refresh_dev,
 // f110qp_rollout_refresh[_dev]) and with a noisy LiDAR (f110qp_cast_scans_noisy_dev, f110qp_rollout_noisy[_dev]),
-// and the parts of each.
+// and with a raster map (f110qp_cast_scans_grid_dev, f110qp_clearance_grid_dev, f110qp_rollout_grid[_dev]), and the
+// parts of each.
 // Host-side responsibilities only: argument validation, workspaces, H2D/D2H of the host-pointer calls
 // (the staging table of api_stage.h). No C++ exception crosses this boundary.
 #include <cmath>
@@ -161,6 +162,30 @@ static int noise_params(const f110qp_noise_config* noise, int batch, f110qp::Noi
   return F110QP_OK;
 }
 
+// The raster map of f110qp_cast_scans_grid_dev, f110qp_clearance_grid_dev and f110qp_rollout_grid[_dev], checked,
+// into *Gr. obstacles: num_circles + group_size + num_segments, which wall_params has checked to fit an int.
+static int grid_params(const f110qp_grid_config* gc, long long obstacles, const void* grid, f110qp::GridParams* Gr) {
+  if (!gc) return fail(F110QP_ERR_INVALID, "grid config is NULL");
+  if (gc->width < 0 || gc->height < 0) return fail(F110QP_ERR_INVALID, "grid width and height must be >= 0");
+  const long long cells = (long long)gc->width * gc->height;
+  if (cells > 0 && !grid) return fail(F110QP_ERR_INVALID, "width * height > 0 needs the grid");
+  if (!(gc->resolution > 0.0) || !std::isfinite(gc->resolution))
+    return fail(F110QP_ERR_INVALID, "grid resolution must be positive and finite");
+  if (!(gc->reach >= 0.0) || !std::isfinite(gc->reach))
+    return fail(F110QP_ERR_INVALID, "grid reach must be >= 0 and finite");
+  if (!std::isfinite(gc->origin_x) || !std::isfinite(gc->origin_y))
+    return fail(F110QP_ERR_INVALID, "grid origin must be finite");
+  if (obstacles + cells > 0x7fffffffll)
+    return fail(F110QP_ERR_INVALID, "num_circles + group_size + num_segments + width * height does not fit an int");
+  Gr->W = gc->width;
+  Gr->H = gc->height;
+  Gr->ox = gc->origin_x;
+  Gr->oy = gc->origin_y;
+  Gr->res = gc->resolution;
+  Gr->reach = gc->reach;
+  return F110QP_OK;
+}
+
 // The scan geometry of the re-planning kernels' argument records (ReplanStart, ReplanStep).
 template <typename S>
 static void scan_geometry(S* s, const f110qp_scan_config& sc) {
@@ -176,8 +201,9 @@ static void scan_geometry(S* s, const f110qp_scan_config& sc) {
 // nor sc->scan_rows is read), kRace casts see the race-mates, kContact records every row's clearance,
 // kBody is kContact with rectangular bodies in every cast and clearance, kWalls is kBody with straight wall
 // segments next to the circles, kRefresh is kWalls with a refresh period for the scan MPC holds, and kNoisy is
-// kRefresh with rules Z1 to Z3 on every scan it casts.
-enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact, kBody, kWalls, kRefresh, kNoisy };
+// kRefresh with rules Z1 to Z3 on every scan it casts, and kGrid is kNoisy with a raster map under every cast and
+// clearance.
+enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact, kBody, kWalls, kRefresh, kNoisy, kGrid };
 
 // The configs of a rollout call as the caller gave them and, once check_args has passed, the
 // kernels' parameters.
@@ -564,7 +590,8 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
   ContactLoop dcl{};
   if (wl)
     hw = WorldIO{wl->w.circles, (size_t)wl->w.P.world_rows * (size_t)wl->w.P.C * 3 * 8, wl->ranges_traj, wl->w.segments,
-                 wl->w.family >= f110qp::WORLD_WALLS ? (size_t)wl->w.Wl.wall_rows * (size_t)wl->w.Wl.S * 4 * 8 : 0};
+                 wl->w.family >= f110qp::WORLD_WALLS ? (size_t)wl->w.Wl.wall_rows * (size_t)wl->w.Wl.S * 4 * 8 : 0,
+                 wl->w.grid, wl->w.family == f110qp::WORLD_GRID ? (size_t)wl->w.Gr.W * (size_t)wl->w.Gr.H : 0};
   if (cl) dcl = *cl;
   stage::replan_fields(L, io, &d, r, &dr, *cfg.sc, (size_t)cfg.K.T, (size_t)cfg.K.P, (size_t)cfg.rp->num_waypoints,
                        wl ? &hw : nullptr, &dw, cl ? &cl->io : nullptr, &dcl.io);
@@ -575,6 +602,7 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
     dwl.w.circles = dw.circles;
     dwl.ranges_traj = dw.ranges_traj;
     dwl.w.segments = dw.segments;
+    dwl.w.grid = dw.grid;
   }
   if ((rv = replan_ticks(c, cfg, d, dr, s, wl ? &dwl : nullptr, cl ? &dcl : nullptr))) return rv;
   return stage_out(c, L, s);
@@ -602,7 +630,7 @@ static int replan_call(f110qp_ctx* c, LoopCfg cfg, RolloutIO io, const ReplanIO&
 
 // The configs of a world-family call as the caller gave them; a family reads those up to its own (wc: all,
 // race: from kRace and every clearance, cc: from kContact, body: from kBody, walls: from kWalls, rf: from kRefresh,
-// noise: kNoisy and the noisy cast).
+// noise: from kNoisy and the noisy and grid casts, grid: kGrid and the grid cast and clearance).
 struct WorldCfgs {
   const f110qp_world_config* wc;
   const f110qp_race_config* race;
@@ -611,12 +639,15 @@ struct WorldCfgs {
   const f110qp_walls_config* walls;
   const f110qp_refresh_config* rf;
   const f110qp_noise_config* noise;
+  const f110qp_grid_config* grid;
 };
 
 // The world of a cast, a clearance or a world rollout, checked in the one order all of them share, into *w;
 // contact: the call also reads k.cc, whose turn is behind the race's. sc null: no scan geometry (clearances).
+// The clearances (sc null) never read the noise: theirs is not checked.
 static int world_of(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const WorldCfgs& k, bool contact, int batch,
-                    const double* circles, const double* segments, f110qp::World* w) {
+                    const double* circles, const double* segments, f110qp::World* w,
+                    const unsigned char* grid = nullptr) {
   int rv = world_params(sc, k.wc, batch, circles, &w->P);
   if (rv) return rv;
   if (fam >= f110qp::WORLD_RACE && (rv = race_params(k.race, batch, k.wc->num_circles, &w->Q))) return rv;
@@ -626,7 +657,12 @@ static int world_of(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const
   if (walls && (rv = wall_params(k.walls, batch, (long long)k.wc->num_circles + k.race->group_size - 1, segments,
                                  &w->Wl)))
     return rv;
-  if (fam == f110qp::WORLD_NOISY && (rv = noise_params(k.noise, batch, &w->Z))) return rv;
+  if (fam >= f110qp::WORLD_NOISY && sc && (rv = noise_params(k.noise, batch, &w->Z))) return rv;
+  if (fam == f110qp::WORLD_GRID &&
+      (rv = grid_params(k.grid, (long long)k.wc->num_circles + k.race->group_size + k.walls->num_segments, grid,
+                        &w->Gr)))
+    return rv;
+  w->grid = fam == f110qp::WORLD_GRID ? grid : nullptr;
   w->family = fam;
   w->circles = circles;
   w->segments = walls ? segments : nullptr;
@@ -648,17 +684,17 @@ static WorldArrays world_arrays(int batch, const double* table, const double* wp
 }
 
 // f110qp_rollout_world[_dev] (kWorld), _race (kRace), _contact (kContact), _body (kBody), _walls (kWalls),
-// _refresh (kRefresh) and _noisy (kNoisy) on the configs k their family reads.
+// _refresh (kRefresh), _noisy (kNoisy) and _grid (kGrid) on the configs k their family reads.
 static int world_call(f110qp_ctx* c, LoopCfg cfg, const WorldCfgs& k, WorldArrays a, const double* circles,
-                      const double* segments, float* rgt, Where w) {
+                      const double* segments, float* rgt, Where w, const unsigned char* grid = nullptr) {
   static const f110qp::WorldFamily kOf[] = {f110qp::WORLD_CIRCLES, f110qp::WORLD_RACE, f110qp::WORLD_RACE,
                                             f110qp::WORLD_BODY,    f110qp::WORLD_WALLS, f110qp::WORLD_WALLS,
-                                            f110qp::WORLD_NOISY};
+                                            f110qp::WORLD_NOISY,   f110qp::WORLD_GRID};
   WorldLoop wl{};
   int rv = check_args(c, &cfg, &a.io, nullptr, nullptr, &a.r);
   if (rv) return rv;
   const bool contact = cfg.fam >= kContact;
-  if ((rv = world_of(kOf[cfg.fam - kWorld], cfg.sc, k, contact, a.io.B, circles, segments, &wl.w))) return rv;
+  if ((rv = world_of(kOf[cfg.fam - kWorld], cfg.sc, k, contact, a.io.B, circles, segments, &wl.w, grid))) return rv;
   if (cfg.fam >= kRefresh && (rv = refresh_params(k.rf, &wl.every))) return rv;
   if (a.io.B == 0) return F110QP_OK;
   if (contact && (!a.k.clear_traj || !a.k.crash_tick))
@@ -670,18 +706,19 @@ static int world_call(f110qp_ctx* c, LoopCfg cfg, const WorldCfgs& k, WorldArray
   return w.host ? replan_host(c, cfg, a.io, a.r, &wl, clp) : replan_ticks(c, cfg, a.io, a.r, w.stream, &wl, clp);
 }
 
-// f110qp_cast_scans[_race|_body|_walls|_noisy]_dev on the configs k their family reads; tick: rule Z3's t of the
-// noisy cast (0 elsewhere).
+// f110qp_cast_scans[_race|_body|_walls|_noisy|_grid]_dev on the configs k their family reads; tick: rule Z3's t of
+// the noisy and grid casts (0 elsewhere).
 static int cast_call(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const WorldCfgs& k, int batch,
                      const int* list, const int* count, const double* x, const double* circles,
-                     const double* segments, float* ranges, void* stream, int tick = 0) {
-  static const char* const kLaunch[] = {"scan cast launch", "race scan cast launch", "body scan cast launch",
-                                        "walls scan cast launch", "noisy scan cast launch"};
+                     const double* segments, float* ranges, void* stream, int tick = 0,
+                     const unsigned char* grid = nullptr) {
+  static const char* const kLaunch[] = {"scan cast launch",       "race scan cast launch",  "body scan cast launch",
+                                        "walls scan cast launch", "noisy scan cast launch", "grid scan cast launch"};
   int rv = check_scan_config(sc, false, 0);
   if (rv) return rv;
   if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
   f110qp::World w{};
-  if ((rv = world_of(fam, sc, k, false, batch, circles, segments, &w))) return rv;
+  if ((rv = world_of(fam, sc, k, false, batch, circles, segments, &w, grid))) return rv;
   if (tick < 0) return fail(F110QP_ERR_INVALID, "tick < 0");
   w.Z.tick = tick;
   if ((list != nullptr) != (count != nullptr))
@@ -693,14 +730,15 @@ static int cast_call(f110qp::WorldFamily fam, const f110qp_scan_config* sc, cons
   return F110QP_OK;
 }
 
-// f110qp_clearance[_body|_walls]_dev on the configs k their family reads (fam >= WORLD_RACE).
+// f110qp_clearance[_body|_walls|_grid]_dev on the configs k their family reads (fam >= WORLD_RACE).
 static int clearance_call(f110qp::WorldFamily fam, const WorldCfgs& k, int batch, int rows, const double* x,
                           const double* circles, const double* segments, double* clearance, int* nearest,
-                          void* stream) {
-  static const char* const kLaunch[] = {nullptr, "clearance launch", "body clearance launch", "walls clearance launch"};
+                          void* stream, const unsigned char* grid = nullptr) {
+  static const char* const kLaunch[] = {nullptr, "clearance launch", "body clearance launch", "walls clearance launch",
+                                        nullptr, "grid clearance launch"};
   if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
   f110qp::World w{};
-  const int rv = world_of(fam, nullptr, k, false, batch, circles, segments, &w);
+  const int rv = world_of(fam, nullptr, k, false, batch, circles, segments, &w, grid);
   if (rv) return rv;
   if (rows < 1) return fail(F110QP_ERR_INVALID, "rows must be >= 1");
   if (batch == 0) return F110QP_OK;
@@ -1290,6 +1328,66 @@ int f110qp_rollout_noisy(f110qp_ctx* c, const f110qp_rollout_config* rc, const f
                                      bgt, poset, clt, nrt, crash);
   return world_call(c, LoopCfg{kNoisy, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf, noise}, a, circles,
                     segments, rgt, on_host());
+}
+
+// ---- a raster map (f110qp_cast_scans_grid_dev, f110qp_clearance_grid_dev, f110qp_rollout_grid[_dev]) -----------
+
+void f110qp_default_grid_config(f110qp_grid_config* gc) {
+  if (!gc) return;
+  std::memset(gc, 0, sizeof(*gc));
+  gc->resolution = 0.05;  // map_server's usual cell
+  gc->reach = 1.0;
+}
+
+int f110qp_cast_scans_grid_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
+                               const f110qp_race_config* race, const f110qp_body_config* body,
+                               const f110qp_walls_config* walls, const f110qp_noise_config* noise,
+                               const f110qp_grid_config* gc, int batch, int tick, const int* list, const int* count,
+                               const double* x, const double* circles, const double* segments,
+                               const unsigned char* grid, float* ranges, void* stream) {
+  return cast_call(f110qp::WORLD_GRID, sc, WorldCfgs{wc, race, nullptr, body, walls, nullptr, noise, gc}, batch, list,
+                   count, x, circles, segments, ranges, stream, tick, grid);
+}
+
+int f110qp_clearance_grid_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
+                              const f110qp_body_config* body, const f110qp_walls_config* walls,
+                              const f110qp_grid_config* gc, int batch, int rows, const double* x,
+                              const double* circles, const double* segments, const unsigned char* grid,
+                              double* clearance, int* nearest, void* stream) {
+  return clearance_call(f110qp::WORLD_GRID, WorldCfgs{wc, race, nullptr, body, walls, nullptr, nullptr, gc}, batch,
+                        rows, x, circles, segments, clearance, nearest, stream, grid);
+}
+
+int f110qp_rollout_grid_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                            const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                            const f110qp_race_config* race, const f110qp_contact_config* cc,
+                            const f110qp_body_config* body, const f110qp_walls_config* walls,
+                            const f110qp_refresh_config* rf, const f110qp_noise_config* noise,
+                            const f110qp_grid_config* gc, int batch, const double* table, const double* wp, double* xr,
+                            int* have, const double* circles, const double* segments, const unsigned char* grid,
+                            double* xt, double* ult, float* ua, int* stt, int* itt, double* cot, float* up, float* xp,
+                            float* hst, int* kt, int* pst, int* btt, int* bgt, double* poset, float* rgt, double* clt,
+                            int* nrt, int* crash, void* stream) {
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kGrid, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf, noise, gc}, a, circles,
+                    segments, rgt, on_stream(stream), grid);
+}
+
+int f110qp_rollout_grid(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                        const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                        const f110qp_race_config* race, const f110qp_contact_config* cc,
+                        const f110qp_body_config* body, const f110qp_walls_config* walls,
+                        const f110qp_refresh_config* rf, const f110qp_noise_config* noise,
+                        const f110qp_grid_config* gc, int batch, const double* table, const double* wp, double* xr,
+                        int* have, const double* circles, const double* segments, const unsigned char* grid, double* xt,
+                        double* ult, float* ua, int* stt, int* itt, double* cot, float* up, float* xp, float* hst,
+                        int* kt, int* pst, int* btt, int* bgt, double* poset, float* rgt, double* clt, int* nrt,
+                        int* crash) {
+  const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
+                                     bgt, poset, clt, nrt, crash);
+  return world_call(c, LoopCfg{kGrid, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf, noise, gc}, a, circles,
+                    segments, rgt, on_host(), grid);
 }
 
 }  // extern "C"

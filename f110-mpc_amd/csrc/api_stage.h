@@ -70,6 +70,9 @@ struct WorldIO {
   // the walls family's, trailing so that three initialisers still make a WorldIO
   const double* segments;  // [wall_rows][S][4] or null
   size_t segment_bytes;    // 0: no segments
+  // the grid family's, trailing likewise
+  const unsigned char* grid;  // [H][W] or null
+  size_t grid_bytes;          // 0: no map (the field is then not declared)
 };
 
 // What the contact rollout records on top of the race rollout's arrays.
@@ -155,7 +158,7 @@ inline void rollout_fields(Layout& L, const RolloutIO& h, RolloutIO* d, size_t x
 // f110qp_rollout_replan (w null: r.ranges read) and f110qp_rollout_world / _race (w: its circles staged
 // in, its ranges_traj, when given, copied back) and f110qp_rollout_contact (w and k: its three records,
 // every row of them the device's); the walls family's segments (w->segment_bytes > 0) are staged in behind the
-// circles. table_rows = steer_discrete + 1.
+// circles, the grid family's map (w->grid_bytes > 0) behind ranges_traj. table_rows = steer_discrete + 1.
 inline void replan_fields(Layout& L, const RolloutIO& h, RolloutIO* d, const ReplanIO& r, ReplanIO* dr,
                           const f110qp_scan_config& sc, size_t table_rows, size_t xr_points, size_t num_waypoints,
                           const WorldIO* w, WorldIO* dw, const ContactIO* k = nullptr, ContactIO* dk = nullptr) {
@@ -177,6 +180,7 @@ inline void replan_fields(Layout& L, const RolloutIO& h, RolloutIO* d, const Rep
   L.add(w->circles, &dw->circles, w->circle_bytes, true, kIn);
   L.add(w->segments, &dw->segments, w->segment_bytes, true, kIn);
   L.add(w->ranges_traj, &dw->ranges_traj, TB * nr * 4, w->ranges_traj, kOut);
+  if (w->grid_bytes) L.add(w->grid, &dw->grid, w->grid_bytes, true, kIn);  // only the grid family declares it
   if (!k) return;
   *dk = *k;
   L.add(k->clear_traj, &dk->clear_traj, (T + 1) * B * 8, true, kOut);

@@ -40,10 +40,16 @@
 //     k = j - (C + G - 1), index C + G + k in nearest. The thread reads its segment once per pass (32
 //     contiguous bytes) and tests it against every pose of the pass with wall_body (rule W2); like the mate
 //     loop, the pose loop is not unrolled, so there is one wall_body in the code.
+//   WORLD_GRID (f110qp_clearance_grid_dev, f110qp_rollout_grid[_dev]): WORLD_WALLS with the occupied cells of
+//     the raster map (grid_geom.h, rule G2) as a fourth stretch, cell (i, j) at index C + G + S + j W + i in
+//     nearest. It is walked per pose behind the obstacle tiles: the threads stride over the cells of the pose's
+//     window (the body's circumscribed circle plus `reach`, clipped to the map), read each cell's byte and test
+//     an occupied one with grid_cell_body, one copy in the code. The window is uniform over the workgroup.
 #include <hip/hip_runtime.h>
 
 #include "body_geom.h"
 #include "f110qp_kernels.h"
+#include "grid_geom.h"
 #include "wall_geom.h"
 
 namespace f110qp {
@@ -63,12 +69,23 @@ __device__ __forceinline__ void take_min(double& best, int& idx, const double v,
   }
 }
 
+// The first and the second pointer of the kernel's pack (the segments, the map).
+template <typename A, typename... R>
+__device__ __forceinline__ A* pack_first(A* a, R*...) {
+  return a;
+}
+template <typename A, typename G>
+__device__ __forceinline__ G* pack_second(A*, G* g) {
+  return g;
+}
+
 }  // namespace
 
 // The configs a family's instantiation reads, its first kernel argument. Each instantiation keeps the
 // argument list its family's own kernel had, and with it that kernel's instruction stream: an
 // argument that a family does not read still moves the kernarg loads and, through them, the SGPR spills. So
-// the record grows with the family, and the segments pointer is a parameter pack that only WORLD_WALLS fills.
+// the record grows with the family, and the segments pointer (WORLD_WALLS) and the map behind it (WORLD_GRID) are
+// a parameter pack.
 template <WorldFamily FAM>
 struct ClearCfg {
   ClearParams P;
@@ -87,15 +104,26 @@ struct ClearCfg<WORLD_WALLS> {
   BodyParams H;
   WallParams Wl;
 };
+template <>
+struct ClearCfg<WORLD_GRID> {
+  ClearParams P;
+  RaceParams Q;
+  BodyParams H;
+  WallParams Wl;
+  GridParams Gr;
+};
 
 #pragma clang fp contract(off)
-template <WorldFamily FAM, typename... Seg>  // Seg: `const double` for WORLD_WALLS, empty otherwise
+// Seg: `const double` for WORLD_WALLS, `const double, const unsigned char` for WORLD_GRID, empty otherwise
+template <WorldFamily FAM, typename... Seg>
 __global__ __launch_bounds__(kClearThreads) void clearance_kernel(
     const ClearCfg<FAM> W, const int B, const int rows, const int nwg, const double* __restrict__ x,
     const double* __restrict__ circles, Seg* __restrict__... segments, double* __restrict__ clearance,
     int* __restrict__ nearest, const ContactMark M) {
-  static_assert(FAM >= WORLD_RACE && sizeof...(Seg) == (FAM == WORLD_WALLS ? 1 : 0), "segments come with the walls");
-  constexpr bool BODY = FAM >= WORLD_BODY, WALLS = FAM == WORLD_WALLS;
+  static_assert(FAM >= WORLD_RACE && FAM != WORLD_NOISY &&
+                    sizeof...(Seg) == (FAM == WORLD_GRID ? 2 : FAM == WORLD_WALLS ? 1 : 0),
+                "segments come with the walls, the map with the grid");
+  constexpr bool BODY = FAM >= WORLD_BODY, WALLS = FAM >= WORLD_WALLS, GRID = FAM == WORLD_GRID;
   const ClearParams& P = W.P;
   const RaceParams& Q = W.Q;
   __shared__ double s_qx[kClearPoses], s_qy[kClearPoses];
@@ -110,7 +138,7 @@ __global__ __launch_bounds__(kClearThreads) void clearance_kernel(
   for (int b = blockIdx.x; b < B; b += nwg) {
     const double* cw = circles + (P.world_rows == 1 ? (size_t)0 : (size_t)b * (size_t)P.C * 3);
     const double* sw = nullptr;
-    if constexpr (WALLS) sw = (segments, ...) + (W.Wl.wall_rows == 1 ? (size_t)0 : (size_t)b * (size_t)W.Wl.S * 4);
+    if constexpr (WALLS) sw = pack_first(segments...) + (W.Wl.wall_rows == 1 ? (size_t)0 : (size_t)b * (size_t)W.Wl.S * 4);
     const int own = b % Q.G, first = b - own;
     int crash = -1;  // thread 0: the first row at or under the margin
     if (M.crash_tick && !M.init && tid == 0) crash = M.crash_tick[b];
@@ -195,6 +223,27 @@ __global__ __launch_bounds__(kClearThreads) void clearance_kernel(
           }
         }
       }
+      if constexpr (GRID) {  // the occupied cells of every pose's window
+        const unsigned char* gm = pack_second(segments...);
+        if (gm) {
+#pragma unroll 1
+          for (int p = 0; p < np; p++) {
+            int i0, i1, j0, j1;
+            if (!grid_body_window(W.Gr, W.H, s_qx[p], s_qy[p], i0, i1, j0, j1)) continue;  // uniform
+            const int ni = i1 - i0 + 1;
+            const long long cells = (long long)ni * (long long)(j1 - j0 + 1);
+            for (long long k = tid; k < cells; k += kClearThreads) {
+              const int j = j0 + (int)(k / ni), i = i0 + (int)(k % ni);
+              const size_t at = (size_t)j * (size_t)W.Gr.W + (size_t)i;
+              if (!gm[at]) continue;
+              const double v = grid_cell_body(W.Gr, i, j, s_qx[p], s_qy[p], s_c[p], s_s[p], W.H);
+#pragma unroll
+              for (int q = 0; q < kClearPoses; q++)
+                if (q == p) take_min(best[q], idx[q], v, nc + 1 + (int)at);
+            }
+          }
+        }
+      }
       // the wave's (value, index) minimum per pose, then the four waves' through LDS
 #pragma unroll
       for (int p = 0; p < kClearPoses; p++) {
@@ -246,7 +295,11 @@ hipError_t launch_clearance(const World& w, int B, int rows, const double* x, do
   const int nwg = clearance_grid(w.family, B);
   const dim3 grid(nwg), block(kClearThreads);
   const ClearParams P{w.P.C, w.P.world_rows};
-  if (w.family >= WORLD_WALLS)  // WORLD_NOISY: the clearance never reads the noise
+  if (w.family == WORLD_GRID)
+    hipLaunchKernelGGL((clearance_kernel<WORLD_GRID, const double, const unsigned char>), grid, block, 0, s,
+                       ClearCfg<WORLD_GRID>{P, w.Q, w.H, w.Wl, w.Gr}, B, rows, nwg, x, w.circles, w.segments,
+                       w.Gr.W > 0 && w.Gr.H > 0 ? w.grid : nullptr, clearance, nearest, M);
+  else if (w.family >= WORLD_WALLS)  // WORLD_NOISY: the clearance never reads the noise
     hipLaunchKernelGGL((clearance_kernel<WORLD_WALLS, const double>), grid, block, 0, s,
                        ClearCfg<WORLD_WALLS>{P, w.Q, w.H, w.Wl}, B, rows, nwg, x, w.circles, w.segments, clearance,
                        nearest, M);

@@ -424,10 +424,25 @@ struct NoiseParams {
   unsigned drop24;
   int tick;
 };
+// A raster map (grid_geom.h, rules G1 and G2 of include/f110qp.h): one occupancy grid [H][W] of bytes for all
+// cars, nonzero occupied, cell (i, j) the square from (ox + i res, oy + j res); W * H == 0: no map (grid null).
+struct GridParams {
+  int W, H;
+  double ox, oy, res;
+  double reach;  // the clearance alone: how far beyond the body it looks
+};
 // The families, each the one before plus one thing: circles alone (casts only), the race-mates as circles,
 // the cars as rectangles (the slab test in the cast, body_sd / body_pair in the clearance), the segments
-// (rules W1 and W2), the noise on the scans (the clearance never reads it: it is the walls').
-enum WorldFamily { WORLD_CIRCLES = 0, WORLD_RACE = 1, WORLD_BODY = 2, WORLD_WALLS = 3, WORLD_NOISY = 4 };
+// (rules W1 and W2), the noise on the scans (the clearance never reads it: it is the walls'), the raster map
+// (rules G1 and G2) under the noise.
+enum WorldFamily {
+  WORLD_CIRCLES = 0,
+  WORLD_RACE = 1,
+  WORLD_BODY = 2,
+  WORLD_WALLS = 3,
+  WORLD_NOISY = 4,
+  WORLD_GRID = 5
+};
 // One description of the world for both jobs. A family reads the records up to its own.
 struct World {
   WorldFamily family;
@@ -435,9 +450,11 @@ struct World {
   RaceParams Q;
   BodyParams H;
   WallParams Wl;
-  NoiseParams Z;  // the cast of WORLD_NOISY alone
+  NoiseParams Z;  // the casts of WORLD_NOISY and WORLD_GRID alone
   const double* circles;
   const double* segments;
+  GridParams Gr;  // WORLD_GRID alone, as is grid
+  const unsigned char* grid;
 };
 
 // Grid caps: one 256-thread workgroup per car, one wave on each of a CU's four SIMDs, up to what the MI355X's
@@ -450,10 +467,12 @@ struct World {
 //   clearance  race 127 (the fp64 sincos and the eight poses' running minima) -> 4 -> 1,024
 //              body, walls 185 (192) -> 2 -> 512
 //              noisy 191 (192) -> 2 -> 512: the walls' caps, and its clearance is the walls instantiation
+//   grid       cast 216 -> 2 -> 512, with 65,152 B of LDS (the cast's 44,032 B and the 21,120 B square of cell bits):
+//              two workgroups in a CU's 160 KB, the same two; clearance 195 (200) -> 2 -> 512, 640 B
 // Nothing spills a VGPR and no kernel has scratch.
 constexpr struct {
   int cast, clearance;
-} kWorldGrids[5] = {{768, 0}, {768, 1024}, {512, 512}, {512, 512}, {512, 512}};  // by WorldFamily
+} kWorldGrids[6] = {{768, 0}, {768, 1024}, {512, 512}, {512, 512}, {512, 512}, {512, 512}};  // by WorldFamily
 
 // Ray casting, workload._ray_circles on the device: per car the scan of nr beams at pose x [B][3] from the
 // LiDAR lidar_offset ahead, ranges [B][nr] float32. At most cast_scans_grid(family, B) workgroups striding over

@@ -53,10 +53,20 @@
 // dropout draw and a bounded bell curve from four 16-bit fields, integers up to the one fp64 expression of
 // Z2. The car's and the tick's keys are folded once per car (uniform over the workgroup); a beam costs two
 // mixes. No LDS, no launch and no pass over HBM is added. Every noise statement is behind `if constexpr`.
+//
+// A raster map (GRID, cast_scans_grid_kernel): the noisy cast with rule G1 of include/f110qp.h (grid_geom.h)
+// between the last obstacle tile and the store loop of every beam tile. Once per car the workgroup packs the
+// square of cells its beams can reach (max_range to every side of the LiDAR's cell) into LDS, one bit a cell;
+// then thread i walks beams i, i + 256, ... cell by cell, reading bits from LDS, up to the minimum the beam
+// already holds (the parameter only grows along a walk, so a hit behind that minimum cannot count), and folds
+// its hit into the minimum with a plain store: a beam has one walker. A square that does not fit
+// kGridWinWords is not packed and the walk reads the map's bytes from global memory (L2): the same walk, the
+// same bits. No launch is added. Every grid statement is behind `if constexpr`.
 #include <hip/hip_runtime.h>
 
 #include "body_geom.h"
 #include "f110qp_kernels.h"
+#include "grid_geom.h"
 #include "wall_geom.h"
 
 namespace f110qp {
@@ -213,16 +223,20 @@ __device__ __forceinline__ float noise_beam(const float r, const unsigned long l
 }
 
 #pragma clang fp contract(off)
-template <bool RACE, bool BODY, bool WALLS, bool NOISE>
+template <bool RACE, bool BODY, bool WALLS, bool NOISE, bool GRID = false>
 __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& Q, const BodyParams& H,
                                          const WallParams& Wl, const NoiseParams& Z, const int b,
                                          const double* __restrict__ x,
                                          const double* __restrict__ circles, const double* __restrict__ segments,
                                          float* __restrict__ ranges, double* s_dx, double* s_dy,
-                                         unsigned long long* s_min, typename SlotOf<BODY>::type* s_slot) {
+                                         unsigned long long* s_min, typename SlotOf<BODY>::type* s_slot,
+                                         const GridParams& Gp = GridParams{},
+                                         const unsigned char* __restrict__ grid = nullptr,
+                                         unsigned* s_win = nullptr) {
   static_assert(RACE || !BODY, "bodies are the race-mates'");
   static_assert(BODY || !WALLS, "walls come with the body cast");
   static_assert(WALLS || !NOISE, "the noise comes with the walls cast");
+  static_assert(NOISE || !GRID, "the raster map comes with the noisy cast");
   using Slot = typename SlotOf<BODY>::type;
   const int tid = threadIdx.x;
   const double ori = x[(size_t)b * 3 + 2];
@@ -252,6 +266,17 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
   if constexpr (NOISE) {
     const unsigned long long kc = noise_mix(Z.seed + kNoiseK * (Z.car_base + (unsigned long long)b + 1ull));
     kt = noise_mix(kc + kNoiseK * ((unsigned long long)Z.tick + 1ull));
+  }
+  GridStart gs{};  // rule G1's start and the LDS square of this car: uniform over the workgroup
+  GridWindow gw{};
+  if constexpr (GRID) {
+    if (grid) gs = grid_start(Gp, grid, ox, oy);
+    gw.bits = s_win;
+    if (gs.state == 2) {
+      grid_window_shape(Gp, gs, P.max_range, gw);
+      for (int k = tid; k < gw.side * gw.stride; k += kCastThreads) s_win[k] = grid_window_word(Gp, grid, gw, k);
+    }
+    // the barrier behind the first beam tile's directions orders these writes before the walks
   }
   for (int cb = 0; cb < nr; cb += kCastBeamTile) {
     const int nb = min(kCastBeamTile, nr - cb);
@@ -354,6 +379,19 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
       }
       __syncthreads();
     }
+    if constexpr (GRID) {  // rule G1: one walker a beam, behind the last tile's barrier (or the directions')
+      if (gs.state == 1) {
+        for (int i = tid; i < nb; i += kCastThreads) s_min[i] = 0ull;
+      } else if (gs.state == 2) {
+        for (int i = tid; i < nb; i += kCastThreads) {
+          const double cur = __longlong_as_double((long long)s_min[i]);
+          double th;
+          if (grid_walk(Gp, grid, gw, gs, s_dx[i], s_dy[i], cur, th) && th < cur)
+            s_min[i] = (unsigned long long)__double_as_longlong(th);
+        }
+      }
+      // thread i stores the beams it walked: no barrier
+    }
     float* out = ranges + (size_t)b * (size_t)nr + cb;
     if constexpr (NOISE) {
       for (int i = tid; i < nb; i += kCastThreads)
@@ -367,23 +405,35 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
 
 // Workgroup w takes cars w, w + nwg, ... below B, or with a list the cars list[w], list[w + nwg], ...
 // below min(*count, B) (plan_listed_kernel's rule: one past the count leaves at that load).
-template <bool RACE, bool BODY = false, bool WALLS = false, bool NOISE = false>
+template <bool RACE, bool BODY = false, bool WALLS = false, bool NOISE = false, bool GRID = false>
 __device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams& Q, const BodyParams& H, const int B,
                                            const int nwg, const int* __restrict__ list,
                                            const int* __restrict__ count, const double* __restrict__ x,
                                            const double* __restrict__ circles, float* __restrict__ ranges,
                                            const WallParams& Wl = WallParams{},
                                            const double* __restrict__ segments = nullptr,
-                                           const NoiseParams& Z = NoiseParams{}) {
+                                           const NoiseParams& Z = NoiseParams{},
+                                           const GridParams& Gp = GridParams{},
+                                           const unsigned char* __restrict__ grid = nullptr) {
   __shared__ double s_dx[kCastBeamTile];
   __shared__ double s_dy[kCastBeamTile];
   __shared__ unsigned long long s_min[kCastBeamTile];
   __shared__ typename SlotOf<BODY>::type s_slot[kCastCircleTile];
+  unsigned* s_win = nullptr;
+  if constexpr (GRID) {
+    __shared__ unsigned s_bits[kGridWinWords];
+    s_win = s_bits;
+  }
   const int n = list ? min(*count, B) : B;
   for (int k = blockIdx.x; k < n; k += nwg) {
     const int b = list ? list[k] : k;
-    if (b >= 0 && b < B)  // uniform over the workgroup
-      cast_one<RACE, BODY, WALLS, NOISE>(P, Q, H, Wl, Z, b, x, circles, segments, ranges, s_dx, s_dy, s_min, s_slot);
+    if (b >= 0 && b < B) {  // uniform over the workgroup
+      if constexpr (GRID)
+        cast_one<RACE, BODY, WALLS, NOISE, true>(P, Q, H, Wl, Z, b, x, circles, segments, ranges, s_dx, s_dy, s_min,
+                                                 s_slot, Gp, grid, s_win);
+      else
+        cast_one<RACE, BODY, WALLS, NOISE>(P, Q, H, Wl, Z, b, x, circles, segments, ranges, s_dx, s_dy, s_min, s_slot);
+    }
   }
 }
 
@@ -431,6 +481,15 @@ __global__ __launch_bounds__(kCastThreads) void cast_scans_noisy_kernel(
   cast_scans<true, true, true, true>(P, Q, H, B, nwg, list, count, x, circles, ranges, Wl, segments, Z);
 }
 
+// The noisy cast with the raster map of grid_geom.h under every beam (GRID, rule G1).
+__global__ __launch_bounds__(kCastThreads) void cast_scans_grid_kernel(
+    const CastParams P, const RaceParams Q, const BodyParams H, const WallParams Wl, const NoiseParams Z,
+    const GridParams Gp, const int B, const int nwg, const int* __restrict__ list, const int* __restrict__ count,
+    const double* __restrict__ x, const double* __restrict__ circles, const double* __restrict__ segments,
+    const unsigned char* __restrict__ grid, float* __restrict__ ranges) {
+  cast_scans<true, true, true, true, true>(P, Q, H, B, nwg, list, count, x, circles, ranges, Wl, segments, Z, Gp, grid);
+}
+
 int cast_scans_grid(WorldFamily family, int B) {
   const int cap = kWorldGrids[family].cast;
   return B < cap ? B : cap;
@@ -441,7 +500,10 @@ hipError_t launch_cast_scans(const World& w, int B, const int* list, const int* 
   if (B <= 0) return hipSuccess;
   const int nwg = cast_scans_grid(w.family, B);
   const dim3 grid(nwg), block(kCastThreads);
-  if (w.family == WORLD_NOISY)
+  if (w.family == WORLD_GRID)
+    hipLaunchKernelGGL(cast_scans_grid_kernel, grid, block, 0, s, w.P, w.Q, w.H, w.Wl, w.Z, w.Gr, B, nwg, list, count,
+                       x, w.circles, w.segments, w.Gr.W > 0 && w.Gr.H > 0 ? w.grid : nullptr, ranges);
+  else if (w.family == WORLD_NOISY)
     hipLaunchKernelGGL(cast_scans_noisy_kernel, grid, block, 0, s, w.P, w.Q, w.H, w.Wl, w.Z, B, nwg, list, count, x,
                        w.circles, w.segments, ranges);
   else if (w.family == WORLD_WALLS)

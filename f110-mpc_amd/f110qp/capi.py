@@ -153,6 +153,11 @@ EXPORTED = (
     "f110qp_cast_scans_noisy_dev",
     "f110qp_rollout_noisy_dev",
     "f110qp_rollout_noisy",
+    "f110qp_default_grid_config",
+    "f110qp_cast_scans_grid_dev",
+    "f110qp_clearance_grid_dev",
+    "f110qp_rollout_grid_dev",
+    "f110qp_rollout_grid",
     "f110qp_path_lengths",
     "f110qp_progress_dev",
     "f110qp_standings_dev",
@@ -286,6 +291,17 @@ class NoiseConfig(C.Structure):
     ]
 
 
+class GridConfig(C.Structure):
+    _fields_ = [
+        ("width", C.c_int),
+        ("height", C.c_int),
+        ("origin_x", C.c_double),
+        ("origin_y", C.c_double),
+        ("resolution", C.c_double),
+        ("reach", C.c_double),
+    ]
+
+
 class McConfig(C.Structure):
     _fields_ = [
         ("hypotheses", C.c_int),
@@ -391,6 +407,12 @@ def load(test: bool = False):
     L.f110qp_cast_scans_noisy_dev.argtypes = [sp, wcp, rcp, bcp, wlp, nzp, C.c_int, C.c_int] + [fp] * 7
     L.f110qp_rollout_noisy_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, nzp, C.c_int] + [fp] * 25
     L.f110qp_rollout_noisy.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, nzp, C.c_int] + [fp] * 24
+    gcp = C.POINTER(GridConfig)
+    L.f110qp_default_grid_config.argtypes = [gcp]
+    L.f110qp_cast_scans_grid_dev.argtypes = [sp, wcp, rcp, bcp, wlp, nzp, gcp, C.c_int, C.c_int] + [fp] * 8
+    L.f110qp_clearance_grid_dev.argtypes = [wcp, rcp, bcp, wlp, gcp, C.c_int, C.c_int] + [fp] * 7
+    L.f110qp_rollout_grid_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, nzp, gcp, C.c_int] + [fp] * 26
+    L.f110qp_rollout_grid.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, nzp, gcp, C.c_int] + [fp] * 25
     L.f110qp_path_lengths.argtypes = [fp, C.c_int, fp]
     L.f110qp_progress_dev.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_int] + [fp] * 4
     L.f110qp_standings_dev.argtypes = [rcp, C.c_int, C.c_int, fp, C.c_double] + [fp] * 4
@@ -575,6 +597,29 @@ def default_noise_config(**over) -> NoiseConfig:
     for k, v in over.items():
         setattr(c, k, v)
     return c
+
+
+def default_grid_config(**over) -> GridConfig:
+    """f110qp_default_grid_config: zeroes, then resolution 0.05 and reach 1.0; width, height, origin_x, origin_y."""
+    c = GridConfig()
+    load().f110qp_default_grid_config(C.byref(c))
+    for k, v in over.items():
+        setattr(c, k, v)
+    return c
+
+
+def grid_config_of(spec) -> GridConfig:
+    """The GridConfig of anything with a map's fields (workload.GridSpec, as load_map and make_grid_world give)."""
+    return default_grid_config(width=int(spec.width), height=int(spec.height), origin_x=float(spec.origin_x),
+                               origin_y=float(spec.origin_y), resolution=float(spec.resolution),
+                               reach=float(spec.reach))
+
+
+def _grid_spec(gc, grid):
+    if not isinstance(gc, GridConfig):
+        raise F110QPError("grid_cfg must be a GridConfig")
+    n = max(int(gc.width), 0) * max(int(gc.height), 0)
+    return (grid, "u8", n, "grid", n == 0)
 
 
 def _check_race(race, B):
@@ -1056,7 +1101,7 @@ class Solver:
                           iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
                           plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
                           ranges_traj=None, stream=None, _race=None, _contact=None, _body=None, _walls=None,
-                          _refresh=None, _noise=None):
+                          _refresh=None, _noise=None, _grid=None):
         """rollout_replan_dev with every tick's scan cast at that tick's pose (f110qp_rollout_world_dev): wc
         and circles [world_rows,C,3] f64 replace ranges, sc.scan_rows is not read, and the optional
         ranges_traj [T,B,num_ranges] f32 records every car's scan of every tick."""
@@ -1089,6 +1134,9 @@ class Solver:
                 name, cfgs = "f110qp_rollout_refresh_dev", cfgs + [C.byref(_refresh)]
                 if _noise is not None:  # the noise config behind rf
                     name, cfgs = "f110qp_rollout_noisy_dev", cfgs + [C.byref(_noise)]
+                    if _grid is not None:  # (grid_cfg, grid): the config behind noise, the map behind segments
+                        more = more + [_grid_spec(*_grid)]
+                        name, cfgs, world = "f110qp_rollout_grid_dev", cfgs + [C.byref(_grid[0])], world + [_tp(_grid[1])]
         _devs(*self._plan_specs(rp, B, *plan), (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
               *self._traj_specs(T, B, *traj), *self._record_specs(T, B, *rec),
               (ranges_traj, "f32", T * B * int(sc.num_ranges), "ranges_traj", True), *more)
@@ -1198,10 +1246,29 @@ class Solver:
                                _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
                                _walls=(walls, segments), _refresh=rf, _noise=noise)
 
+    def rollout_grid_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
+                         cc: ContactConfig, body: BodyConfig, walls: WallsConfig, rf: RefreshConfig, noise: NoiseConfig,
+                         grid_cfg: GridConfig, table, waypoints, x_ref, have_path, circles, segments, grid, x_traj,
+                         u_lin_traj, u_applied, status_traj, clear_traj, crash_tick, nearest_traj=None, iters_traj=None,
+                         cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None, plan_status_traj=None,
+                         best_traj_traj=None, best_global_traj=None, pose_traj=None, ranges_traj=None, stream=None):
+        """rollout_noisy_dev on a raster map (f110qp_rollout_grid_dev): grid_cfg follows noise, grid [H,W] u8 (None
+        for an empty map) follows segments, everything else as there."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
+                or not isinstance(walls, WallsConfig) or not isinstance(rf, RefreshConfig) \
+                or not isinstance(noise, NoiseConfig) or not isinstance(grid_cfg, GridConfig):
+            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig, walls a WallsConfig, "
+                              "rf a RefreshConfig, noise a NoiseConfig and grid_cfg a GridConfig")
+        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
+                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
+                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
+                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
+                               _walls=(walls, segments), _refresh=rf, _noise=noise, _grid=(grid_cfg, grid))
+
     def rollout_world(self, x0, u_lin, circles, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
                       wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
                       scans=False, rc=None, _race=None, _contact=None, _body=None, _segments=None, _refresh=None,
-                      _noise=None):
+                      _noise=None, _grid=None):
         """rollout_replan() in a world of circles (f110qp_rollout_world, synchronous): circles [C,3] (one world
         for all cars) or [B,C,3] float64 replace ranges; wc defaults to f110qp_default_world_config with
         num_circles and world_rows taken from the array. scans=True adds ranges_traj [T,B,num_ranges]."""
@@ -1245,6 +1312,12 @@ class Solver:
                 name, cfgs = "f110qp_rollout_refresh", cfgs + [C.byref(_refresh)]
                 if _noise is not None:  # the noise config behind rf
                     name, cfgs = "f110qp_rollout_noisy", cfgs + [C.byref(_noise)]
+                    if _grid is not None:  # (grid_cfg, grid [H,W] uint8): the config behind noise, the map behind segments
+                        gc, gm = _grid
+                        gm = np.ascontiguousarray(gm, np.uint8)
+                        if gm.shape != (int(gc.height), int(gc.width)) and gm.size:
+                            raise F110QPError(f"grid must be [height, width] = [{gc.height}, {gc.width}], got {gm.shape}")
+                        name, cfgs, world = "f110qp_rollout_grid", cfgs + [C.byref(gc)], world + [_p(gm) if gm.size else None]
         self._chk(getattr(self.lib, name)(
             self._h, C.byref(self._ticks_config(rc, T)), C.byref(sc), C.byref(rp), C.byref(w),
             *cfgs, B, _p(tab), _p(wp) if wp.shape[0] else None, _p(xr), _p(hv),
@@ -1317,6 +1390,21 @@ class Solver:
         return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
                                   objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
                                   _segments=segments, _refresh=rf, _noise=noise)
+
+    def rollout_grid(self, x0, u_lin, circles, segments, grid, grid_cfg: GridConfig, race: RaceConfig, cc: ContactConfig,
+                     body: BodyConfig, rf: RefreshConfig, noise: NoiseConfig, sc: ScanConfig, rp: ReplanConfig, table,
+                     waypoints, ticks, wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False,
+                     rows=True, scans=False, nearest=True, rc=None):
+        """rollout_noisy() on a raster map (f110qp_rollout_grid, synchronous): grid [H,W] uint8 (nonzero occupied)
+        and grid_cfg follow segments, everything else as there."""
+        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
+                or not isinstance(rf, RefreshConfig) or not isinstance(noise, NoiseConfig) \
+                or not isinstance(grid_cfg, GridConfig):
+            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig, rf a RefreshConfig, "
+                              "noise a NoiseConfig and grid_cfg a GridConfig")
+        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
+                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
+                                  _segments=segments, _refresh=rf, _noise=noise, _grid=(grid_cfg, grid))
 
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
@@ -1548,8 +1636,8 @@ def _wall_spec(walls, segments):
 
 
 def _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race=_NO, body=_NO, walls=_NO, segments=None,
-                noise=_NO, tick=0):
-    """The body of the five cast_scans*_dev."""
+                noise=_NO, tick=0, grid_cfg=_NO, grid=None):
+    """The body of the six cast_scans*_dev."""
     import torch
 
     if body is not _NO and not isinstance(body, BodyConfig):
@@ -1559,24 +1647,26 @@ def _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race=_NO, body
         _check_race(race, B)
     _devs((x, "f64", 3 * B, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
           *([_wall_spec(walls, segments)] if walls is not _NO else []),
+          *([_grid_spec(grid_cfg, grid)] if grid_cfg is not _NO else []),
           (ranges, "f32", B * int(sc.num_ranges), "ranges"), (list_, "i32", B, "list", True),
           (count, "i32", 1, "count", True))
     if stream is None:
         stream = torch.cuda.current_stream(x.device)
     if noise is not _NO and not isinstance(noise, NoiseConfig):
         raise F110QPError("noise must be a NoiseConfig")
-    family = "_noisy" if noise is not _NO else "_walls" if walls is not _NO else "_body" if body is not _NO \
+    family = "_grid" if grid_cfg is not _NO else "_noisy" if noise is not _NO else "_walls" if walls is not _NO else "_body" if body is not _NO \
         else "_race" if race is not _NO else ""
     name = f"f110qp_cast_scans{family}_dev"
-    cfgs = [C.byref(k) for k in (sc, wc, race, body, walls, noise) if k is not _NO]
-    segs = [_tp(segments)] if walls is not _NO else []
+    cfgs = [C.byref(k) for k in (sc, wc, race, body, walls, noise, grid_cfg) if k is not _NO]
+    segs = ([_tp(segments)] if walls is not _NO else []) + ([_tp(grid)] if grid_cfg is not _NO else [])
     ticks = [int(tick)] if noise is not _NO else []  # rule Z3's t follows batch
     _check(getattr(load(), name)(*cfgs, B, *ticks, _tp(list_), _tp(count), _tp(x), _tp(circles), *segs, _tp(ranges),
                                  C.c_void_p(stream.cuda_stream)), name)
 
 
-def _clearance(wc, race, x, circles, clearance, nearest, stream, body=_NO, walls=_NO, segments=None):
-    """The body of the three clearance*_dev."""
+def _clearance(wc, race, x, circles, clearance, nearest, stream, body=_NO, walls=_NO, segments=None, grid_cfg=_NO,
+               grid=None):
+    """The body of the four clearance*_dev."""
     import torch
 
     if body is not _NO and not isinstance(body, BodyConfig):
@@ -1590,12 +1680,14 @@ def _clearance(wc, race, x, circles, clearance, nearest, stream, body=_NO, walls
     _check_race(race, B)
     _devs((x, "f64", 3 * B * rows, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
           *([_wall_spec(walls, segments)] if walls is not _NO else []),
+          *([_grid_spec(grid_cfg, grid)] if grid_cfg is not _NO else []),
           (clearance, "f64", B * rows, "clearance"), (nearest, "i32", B * rows, "nearest", True))
     if stream is None:
         stream = torch.cuda.current_stream(x.device)
-    name = f"f110qp_clearance{'_walls' if walls is not _NO else '_body' if body is not _NO else ''}_dev"
-    cfgs = [C.byref(k) for k in (wc, race, body, walls) if k is not _NO]
-    segs = [_tp(segments)] if walls is not _NO else []
+    family = "_grid" if grid_cfg is not _NO else "_walls" if walls is not _NO else "_body" if body is not _NO else ""
+    name = f"f110qp_clearance{family}_dev"
+    cfgs = [C.byref(k) for k in (wc, race, body, walls, grid_cfg) if k is not _NO]
+    segs = ([_tp(segments)] if walls is not _NO else []) + ([_tp(grid)] if grid_cfg is not _NO else [])
     _check(getattr(load(), name)(*cfgs, B, rows, _tp(x), _tp(circles), *segs, _tp(clearance), _tp(nearest),
                                  C.c_void_p(stream.cuda_stream)), name)
 
@@ -1646,6 +1738,23 @@ def cast_scans_noisy_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body
     Z1 and Z2 of f110qp.h): noise follows walls, tick (the t of rule Z1's draw) follows it. The oracle is
     workload.noisy_scan on cast_scans_walls_dev's output."""
     _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race, body, walls, segments, noise, tick)
+
+
+def cast_scans_grid_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig,
+                        noise: NoiseConfig, grid_cfg: GridConfig, tick, x, circles, segments, grid, ranges, list_=None,
+                        count=None, stream=None):
+    """cast_scans_noisy_dev with a raster map under every beam (f110qp_cast_scans_grid_dev, rule G1 of f110qp.h):
+    grid_cfg follows noise, grid [H,W] u8 (nonzero occupied, None for an empty map) follows segments. The oracle is
+    workload.ray_map folded into the noise-free scan, then workload.noisy_scan."""
+    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race, body, walls, segments, noise, tick, grid_cfg,
+                grid)
+
+
+def clearance_grid_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, grid_cfg: GridConfig, x,
+                       circles, segments, grid, clearance, nearest=None, stream=None):
+    """clearance_walls_dev with the occupied cells of a raster map behind the segments (f110qp_clearance_grid_dev,
+    rule G2): cell (i, j) has index C + G + S + j W + i in nearest. The oracle is workload.clearance_grid."""
+    _clearance(wc, race, x, circles, clearance, nearest, stream, body, walls, segments, grid_cfg, grid)
 
 
 def clearance_walls_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, x, circles, segments,

@@ -901,3 +901,258 @@ def make_mc_batch(x0, M: int, G: int = 1) -> np.ndarray:
         raise ValueError(f"x0 must be [S * G, 3] with G = {G}, got {x0.shape}")
     S = x0.shape[0] // G
     return np.ascontiguousarray(np.tile(x0.reshape(S, 1, G, -1), (1, M, 1, 1)).reshape(S * M * G, -1))
+
+
+# ---- occupancy-grid maps (f110qp_cast_scans_grid_dev, f110qp_clearance_grid_dev, f110qp_rollout_grid[_dev]) -----
+# Rules G1 and G2 of include/f110qp.h in numpy, in csrc/grid_geom.h's expressions and order. A map is (grid, cfg):
+# grid [H, W] uint8, nonzero occupied, row j at y and column i at x; cfg anything with origin_x, origin_y,
+# resolution and reach (a GridSpec here, a capi.GridConfig as well).
+
+class GridSpec:
+    """f110qp_grid_config's fields without the library."""
+
+    def __init__(self, width=0, height=0, origin_x=0.0, origin_y=0.0, resolution=0.05, reach=1.0):
+        self.width, self.height = int(width), int(height)
+        self.origin_x, self.origin_y = float(origin_x), float(origin_y)
+        self.resolution, self.reach = float(resolution), float(reach)
+
+    def __repr__(self):
+        return (f"GridSpec({self.width} x {self.height}, origin ({self.origin_x}, {self.origin_y}), "
+                f"resolution {self.resolution}, reach {self.reach})")
+
+
+def ray_grid(ox, oy, dx, dy, grid, cfg, max_range: float = 10.0):
+    """Rule G1: ranges (float64, the broadcast shape of the arguments) of beams from the origins (ox, oy) along
+    (dx, dy) against the map, max_range where nothing is hit: the walk of the rule, every boundary's parameter
+    computed afresh from the integer boundary, x first on a tie."""
+    g = np.asarray(grid)
+    ox, oy, dx, dy = (np.asarray(v, np.float64) for v in np.broadcast_arrays(ox, oy, dx, dy))
+    shape = dx.shape
+    out = np.full(dx.size, float(max_range))
+    if g.size == 0:
+        return out.reshape(shape)
+    H, W = g.shape
+    ox, oy, dx, dy = (v.ravel() for v in (ox, oy, dx, dy))
+    res, x0, y0 = np.float64(cfg.resolution), np.float64(cfg.origin_x), np.float64(cfg.origin_y)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        px, py = (ox - x0) / res, (oy - y0) / res
+        ok = (px >= 0.0) & (px < W) & (py >= 0.0) & (py < H)
+        a = np.flatnonzero(ok)                                   # the beams still walking
+        ix, iy = np.floor(px[a]).astype(np.int64), np.floor(py[a]).astype(np.int64)
+        inside = g[iy, ix] != 0
+        out[a[inside]] = 0.0
+        a, ix, iy = a[~inside], ix[~inside], iy[~inside]
+        px, py, dx, dy = px[a], py[a], dx[a], dy[a]
+        gx, gy = dx / res, dy / res
+        sx, sy = np.where(dx > 0.0, 1, -1), np.where(dy > 0.0, 1, -1)
+
+        def bound(i, p, d, gd):
+            k = np.where(d > 0.0, i + 1, i).astype(np.float64)
+            return np.where((d > 0.0) | (d < 0.0), (k - p) / gd, np.inf)
+        tx, ty = bound(ix, px, dx, gx), bound(iy, py, dy, gy)
+        for _ in range(W + H + 2):
+            if a.size == 0:
+                break
+            stepx = tx <= ty
+            t = np.where(stepx, tx, ty)
+            ix, iy = ix + np.where(stepx, sx, 0), iy + np.where(stepx, 0, sy)
+            tx, ty = np.where(stepx, bound(ix, px, dx, gx), tx), np.where(stepx, ty, bound(iy, py, dy, gy))
+            go = (t <= max_range) & (ix >= 0) & (ix < W) & (iy >= 0) & (iy < H)
+            hit = go.copy()
+            hit[go] = g[iy[go], ix[go]] != 0
+            out[a[hit]] = t[hit] + 0.0
+            keep = go & ~hit
+            a, ix, iy, px, py, dx, dy, gx, gy, sx, sy, tx, ty = (v[keep] for v in (a, ix, iy, px, py, dx, dy, gx, gy,
+                                                                                   sx, sy, tx, ty))
+    return out.reshape(shape)
+
+
+def ray_map(x, geom, beams, grid, cfg, lidar_offset: float = 0.275, max_range: float = 10.0):
+    """The map's part of f110qp_cast_scans_grid_dev in numpy: ranges [B, beams] float64 of every car's beams at the
+    poses x [B, 3] (geom = (angle_min, angle_increment, ...) as float32). The noise-free scan is np.minimum of this,
+    the circles', the opponents' and the segments' ranges before the cast to float32; rule Z2 runs on that."""
+    x = np.asarray(x, np.float64)
+    with np.errstate(invalid="ignore"):
+        ox, oy = x[:, 0] + lidar_offset * np.cos(x[:, 2]), x[:, 1] + lidar_offset * np.sin(x[:, 2])
+        ang = x[:, 2:3] + (np.float64(geom[0]) + np.float64(geom[1]) * np.arange(beams, dtype=np.float64))[None, :]
+        return ray_grid(ox[:, None], oy[:, None], np.cos(ang), np.sin(ang), grid, cfg, max_range)
+
+
+def cell_body(i, j, cfg, qx, qy, c, s, hl: float = HALF_LENGTH, hw: float = HALF_WIDTH):
+    """Rule G2's value of the cells (i, j) (integer arrays) against the body (qx, qy, c, s), all broadcastable."""
+    res, ox, oy = np.float64(cfg.resolution), np.float64(cfg.origin_x), np.float64(cfg.origin_y)
+    i, j = np.asarray(i), np.asarray(j)
+    x0, x1 = ox + i.astype(np.float64) * res, ox + (i + 1).astype(np.float64) * res
+    y0, y1 = oy + j.astype(np.float64) * res, oy + (j + 1).astype(np.float64) * res
+    v = np.inf
+    for ax, ay, bx, by in ((x0, y0, x1, y0), (x1, y0, x1, y1), (x1, y1, x0, y1), (x0, y1, x0, y0)):
+        v = np.fmin(v, segment_body(ax, ay, bx, by, qx, qy, c, s, hl, hw))
+    centre = (x0 <= qx) & (qx < x1) & (y0 <= qy) & (qy < y1)
+    return np.where(centre, np.fmin(v, 0.0), v)
+
+
+def clearance_grid(x, circles, segments, grid, cfg, group_size: int = 1, center_offset: float = 0.1651,
+                   half_length: float = HALF_LENGTH, half_width: float = HALF_WIDTH):
+    """f110qp_clearance_grid_dev in numpy: clearance_walls() with the occupied cells of the map as a fourth stretch
+    of the obstacle list, cell (i, j) at index C + G + S + j W + i, seen through rule G2's window.
+    -> (clearance [rows, B], nearest [rows, B])."""
+    x = np.asarray(x, np.float64)
+    one = x.ndim == 2
+    x = x[None] if one else x
+    rows, B = x.shape[:2]
+    G, hl, hw = int(group_size), float(half_length), float(half_width)
+    clear, near = clearance_walls(x, circles, segments, G, center_offset, hl, hw)
+    clear, near = np.array(clear), np.array(near)
+    g = np.asarray(grid)
+    if g.size:
+        H, W = g.shape
+        Cn = 0 if circles is None else np.asarray(circles).shape[-2]
+        S = 0 if segments is None else np.asarray(segments).shape[-2]
+        res, ox, oy = np.float64(cfg.resolution), np.float64(cfg.origin_x), np.float64(cfg.origin_y)
+        R = np.sqrt(np.float64(hl) * hl + np.float64(hw) * hw) + np.float64(cfg.reach)
+        for r in range(rows):
+            for b in range(B):
+                with np.errstate(invalid="ignore"):
+                    c, s = np.cos(x[r, b, 2]), np.sin(x[r, b, 2])
+                    qx, qy = x[r, b, 0] + center_offset * c, x[r, b, 1] + center_offset * s
+                if not (np.isfinite(qx) and np.isfinite(qy)):
+                    continue
+                i0, i1 = max(np.floor((qx - R - ox) / res), 0.0), min(np.floor((qx + R - ox) / res), W - 1.0)
+                j0, j1 = max(np.floor((qy - R - oy) / res), 0.0), min(np.floor((qy + R - oy) / res), H - 1.0)
+                if not (i0 <= i1 and j0 <= j1):
+                    continue
+                i0, i1, j0, j1 = int(i0), int(i1), int(j0), int(j1)
+                jj, ii = np.nonzero(g[j0:j1 + 1, i0:i1 + 1])     # row-major: ascending index
+                if ii.size == 0:
+                    continue
+                ii, jj = ii + i0, jj + j0
+                v = cell_body(ii, jj, cfg, qx, qy, c, s, hl, hw)
+                v = np.where(np.isnan(v), np.inf, v)
+                k = int(np.argmin(v))                            # the first of equal values: the lowest index
+                if v[k] < clear[r, b]:                           # equal: the lower index stays
+                    clear[r, b] = v[k]
+                    near[r, b] = Cn + G + S + jj[k] * W + ii[k]
+    return (clear[0], near[0]) if one else (clear, near.astype(np.int32))
+
+
+def rasterize_walls(segments, circles, cfg) -> np.ndarray:
+    """The map [cfg.height, cfg.width] uint8 of segments [S, 4] and circles [C, 3] (either may be None): every cell
+    whose closed square a segment touches or a disc overlaps is occupied, the squares taken 1e-9 cells larger, so
+    the cells of a segment are 4-connected and a closed polyline leaks no beam."""
+    W, H = int(cfg.width), int(cfg.height)
+    res, ox, oy = float(cfg.resolution), float(cfg.origin_x), float(cfg.origin_y)
+    g = np.zeros((H, W), np.uint8)
+    eps = 1e-9
+    for ax, ay, bx, by in (np.zeros((0, 4)) if segments is None else np.asarray(segments, np.float64).reshape(-1, 4)):
+        ax, ay, bx, by = (ax - ox) / res, (ay - oy) / res, (bx - ox) / res, (by - oy) / res  # in cells
+        if not np.isfinite([ax, ay, bx, by]).all():
+            continue
+        i0, i1 = max(int(np.floor(min(ax, bx) - eps)), 0), min(int(np.floor(max(ax, bx) + eps)), W - 1)
+        j0, j1 = max(int(np.floor(min(ay, by) - eps)), 0), min(int(np.floor(max(ay, by) + eps)), H - 1)
+        if i0 > i1 or j0 > j1:
+            continue
+        jj, ii = np.mgrid[j0:j1 + 1, i0:i1 + 1]
+        ex, ey = bx - ax, by - ay
+        lo, hi = np.zeros(ii.shape), np.ones(ii.shape)           # the clip of a + s e, s in [0, 1], to the square
+        for o, e, c0 in ((ax, ex, ii), (ay, ey, jj)):
+            a0, a1 = c0 - eps - o, c0 + 1.0 + eps - o
+            if e == 0.0:
+                miss = (a0 > 0.0) | (a1 < 0.0)
+                lo, hi = np.where(miss, np.inf, lo), np.where(miss, -np.inf, hi)
+            else:
+                lo, hi = np.maximum(lo, np.minimum(a0 / e, a1 / e)), np.minimum(hi, np.maximum(a0 / e, a1 / e))
+        g[j0:j1 + 1, i0:i1 + 1] |= (lo <= hi).astype(np.uint8)
+    for cx, cy, r in (np.zeros((0, 3)) if circles is None else np.asarray(circles, np.float64).reshape(-1, 3)):
+        cx, cy, r = (cx - ox) / res, (cy - oy) / res, abs(r) / res
+        if not np.isfinite([cx, cy, r]).all():
+            continue
+        i0, i1 = max(int(np.floor(cx - r - eps)), 0), min(int(np.floor(cx + r + eps)), W - 1)
+        j0, j1 = max(int(np.floor(cy - r - eps)), 0), min(int(np.floor(cy + r + eps)), H - 1)
+        if i0 > i1 or j0 > j1:
+            continue
+        jj, ii = np.mgrid[j0:j1 + 1, i0:i1 + 1]
+        ddx = np.maximum(np.maximum(ii - cx, cx - (ii + 1.0)), 0.0)
+        ddy = np.maximum(np.maximum(jj - cy, cy - (jj + 1.0)), 0.0)
+        g[j0:j1 + 1, i0:i1 + 1] |= (np.hypot(ddx, ddy) <= r + eps).astype(np.uint8)
+    return g
+
+
+def make_grid_world(seed: int = 0, obstacles: int = 40, resolution: float = 0.05, reach: float = 1.0,
+                    margin: float = 1.0):
+    """make_wall_world(seed, obstacles) rasterised: (grid [H, W] uint8, GridSpec). The map covers the walls and the
+    obstacle circles with `margin` metres to spare; its origin is a whole number of cells from (0, 0)."""
+    sg, ci = make_wall_world(seed, obstacles)
+    pts = np.concatenate([sg[:, :2], sg[:, 2:], ci[:, :2]])
+    lo = np.floor((pts.min(0) - margin) / resolution)
+    hi = np.ceil((pts.max(0) + margin) / resolution)
+    cfg = GridSpec(int(hi[0] - lo[0]), int(hi[1] - lo[1]), lo[0] * resolution, lo[1] * resolution, resolution, reach)
+    return rasterize_walls(sg, ci, cfg), cfg
+
+
+def crop_map(grid, cfg, i0: int, j0: int, width: int, height: int):
+    """The cells [i0, i0 + width) x [j0, j0 + height) of a map as a map of their own (same cell corners up to the
+    rounding of the new origin)."""
+    g = np.ascontiguousarray(np.asarray(grid)[j0:j0 + height, i0:i0 + width])
+    return g, GridSpec(g.shape[1], g.shape[0], cfg.origin_x + i0 * cfg.resolution, cfg.origin_y + j0 * cfg.resolution,
+                       cfg.resolution, cfg.reach)
+
+
+def _pgm_tokens(data: bytes, count: int):
+    """The first `count` whitespace-separated header tokens of a PGM (comments from '#' to the line's end skipped)
+    and the offset of the byte behind the single whitespace that ends the last one."""
+    tok, pos = [], 0
+    while len(tok) < count:
+        while pos < len(data) and (data[pos:pos + 1].isspace() or data[pos:pos + 1] == b"#"):
+            if data[pos:pos + 1] == b"#":
+                while pos < len(data) and data[pos:pos + 1] != b"\n":
+                    pos += 1
+            else:
+                pos += 1
+        start = pos
+        while pos < len(data) and not data[pos:pos + 1].isspace() and data[pos:pos + 1] != b"#":
+            pos += 1
+        if start == pos:
+            raise ValueError("truncated PGM header")
+        tok.append(data[start:pos])
+    return tok, pos + 1
+
+
+def read_pgm(path) -> np.ndarray:
+    """A binary (P5, 8 or 16 bit) or ASCII (P2) PGM as [rows, cols] float64 in [0, 255], top row first."""
+    data = open(path, "rb").read()
+    (magic, w, h, mx), pos = _pgm_tokens(data, 4)
+    w, h, mx = int(w), int(h), int(mx)
+    if magic not in (b"P2", b"P5") or w < 0 or h < 0 or not 0 < mx < 65536:
+        raise ValueError(f"not a PGM this reader knows: {magic!r} {w} x {h} max {mx}")
+    if magic == b"P5":
+        px = np.frombuffer(data, np.uint8 if mx < 256 else np.dtype(">u2"), w * h, pos)
+    else:
+        body = b"\n".join(line.split(b"#")[0] for line in data[pos - 1:].split(b"\n"))
+        px = np.array(body.split()[:w * h], np.int64)
+        if px.size != w * h:
+            raise ValueError("truncated PGM")
+    return px.astype(np.float64).reshape(h, w) * (255.0 / mx)
+
+
+def load_map(pgm_path, yaml_path, reach: float = 1.0):
+    """A map_server map -> (grid [H, W] uint8, GridSpec): the image of pgm_path and the keys `resolution`, `origin`
+    ([x, y, yaw]; the yaw must be 0), `negate` and `occupied_thresh` of yaml_path, read by hand (flat `key: value`
+    lines). map_server's rule: a pixel p in [0, 255] has occupancy (255 - p) / 255, or p / 255 with negate, and is
+    occupied above occupied_thresh (default 0.65); its image has the top row first, the grid row 0 at origin_y."""
+    keys = {}
+    for line in open(yaml_path):
+        line = line.split("#")[0]
+        if ":" in line:
+            k, v = line.split(":", 1)
+            keys[k.strip()] = v.strip()
+    if "resolution" not in keys or "origin" not in keys:
+        raise ValueError("the map's yaml needs resolution and origin")
+    origin = [float(v) for v in keys["origin"].strip("[]").split(",")]
+    if len(origin) < 2 or (len(origin) > 2 and origin[2] != 0.0):
+        raise ValueError(f"origin must be [x, y, 0], got {origin}")
+    negate = int(float(keys.get("negate", "0")))
+    thresh = float(keys.get("occupied_thresh", "0.65"))
+    p = read_pgm(pgm_path)
+    occ = (p if negate else 255.0 - p) / 255.0
+    grid = np.ascontiguousarray((occ > thresh)[::-1].astype(np.uint8))
+    return grid, GridSpec(grid.shape[1], grid.shape[0], origin[0], origin[1], float(keys["resolution"]), reach)

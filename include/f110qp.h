@@ -1390,6 +1390,122 @@ int f110qp_rollout_noisy(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const
                          int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
                          int* nearest_traj, int* crash_tick);
 
+/* ---- occupancy-grid maps: raster walls in the LiDAR, the clearance and the rollout --------------------------
+ * Every world above is hand-built geometry: circles and straight segments. The reference drives in the f1tenth
+ * simulator on a map_server map, a raster image with a resolution and an origin, and a building map has tens of
+ * thousands of boundary edges where the walls cast is linear in the segment count. The family below is
+ * f110qp_rollout_noisy[_dev] with such a map under every cast and every clearance: a beam walks the grid cell by
+ * cell, which costs the beam's length in cells whatever the map holds. Additive: F110QP_API_VERSION stays 6, and
+ * no call above changes its results. The disc-body families get no map.
+ *
+ * grid is [H][W] unsigned char, row j at y, column i at x: cell (i, j) is the square whose lower-left corner is
+ * (origin_x + i resolution, origin_y + j resolution). Nonzero means occupied. There is one map for all cars (no
+ * per-car rows), and outside the map is free space. Arithmetic is this family's: all fp64, every product, sum and
+ * quotient rounded (no fused multiply-add), sincos(double), floor, fmin / fmax.
+ *
+ * G1. A beam against the grid. With the LiDAR origin o and the beam direction d = (cos, sin), both exactly as
+ *     f110qp_cast_scans_dev builds them:
+ *       px = (o.x - origin_x) / resolution,  py likewise;  gx = d.x / resolution,  gy = d.y / resolution;
+ *       ix = (int)floor(px),  iy = (int)floor(py).
+ *     The start cell outside [0, W) x [0, H), or px or py not finite: the grid gives no hit. The start cell
+ *     occupied: th = 0. Otherwise the beam walks. The next boundary in x is kx = ix + 1 when d.x > 0 and kx = ix
+ *     when d.x < 0, its parameter tx = ((double)kx - px) / gx, and tx = +inf when d.x == 0; ty likewise. Both are
+ *     computed afresh from the integer boundary at every step, never accumulated: a cell's entry parameter depends
+ *     on that boundary alone, and it is monotone along the walk. Each step, in this order:
+ *       1. tx <= ty: t = tx and ix moves by the sign of d.x; otherwise t = ty and iy moves by the sign of d.y;
+ *       2. t > max_range, or t is NaN: no hit;
+ *       3. the new cell is outside the map: no hit;
+ *       4. the new cell is occupied: th = t + 0.0 (t, with the -0 that the quotient 0 / g gives for a negative g
+ *          made +0: a LiDAR exactly on a cell boundary that looks down the axis into an occupied neighbour).
+ *     On the tie tx == ty the beam steps in x first: a beam through a lattice corner visits the x-side cell. The
+ *     walk takes at most W + H + 2 steps.
+ *     range = (float)min(circles' th, mates' th, segments' th, grid th, max_range); rule Z2's noise then runs on
+ *     that float as before.
+ *     Consequences. A 4-connected wall cannot leak. Nor can one that is only 8-connected: the walk moves along one
+ *     axis a step, so between two cells that touch at a corner it visits one of the two cells beside that corner,
+ *     and on the exact tie the x-side one. A LiDAR inside an occupied cell reads 0. th is never -0, so rule Z2's
+ *     fmax never meets zeros of two signs. The value of a (beam, map) pair does not depend on the batch, the list,
+ *     the tile, or where the kernel keeps the map.
+ * G2. The rectangle against the grid. The body's frame is that of rules 1 to 3, q its centre. With
+ *     R = sqrt(hl hl + hw hw) + reach, the window is the cells (i, j) with
+ *       floor((q.x - R - origin_x) / resolution) <= i <= floor((q.x + R - origin_x) / resolution)
+ *     and the same in y, clipped to the map. A non-finite pose visits no cell. For each occupied cell of the window
+ *     the corners are x0 = origin_x + (double)i resolution, x1 = origin_x + (double)(i + 1) resolution, y0 and y1
+ *     likewise; v is the minimum (fmin) of rule W2's value over the four edges in the order (x0,y0)-(x1,y0),
+ *     (x1,y0)-(x1,y1), (x1,y1)-(x0,y1), (x0,y1)-(x0,y0); and when x0 <= q.x < x1 && y0 <= q.y < y1 the body's
+ *     centre is in the cell and v = min(v, 0).
+ *     In clearance and nearest the cell has index C + G + S + j W + i, which must fit an int. The update rule, the
+ *     start value (+inf, -1), the NaN rule and the order independence are rule 4's.
+ *     Consequence. The grid's share of the clearance is exact wherever it is <= reach; a larger value, or +inf,
+ *     says only "more than reach". Contact (<= margin, margin far below reach) is therefore exact. */
+typedef struct {
+  int width, height;          /* W, H >= 0 cells; W * H == 0: no map                        */
+  double origin_x, origin_y;  /* world position of the lower-left corner of cell (0, 0)     */
+  double resolution;          /* > 0 and finite, metres per cell                            */
+  double reach;               /* >= 0, metres: how far beyond the body the clearance looks  */
+} f110qp_grid_config;
+
+/* Zeroes *grid_cfg, then resolution 0.05 and reach 1.0. */
+void f110qp_default_grid_config(f110qp_grid_config* grid_cfg);
+
+/* f110qp_cast_scans_noisy_dev, word for word (tick included), with rule G1 under every beam: grid_cfg follows
+ * noise, grid follows segments. No launch is added: the walk runs inside the cast's own launch, between the last
+ * obstacle tile and the store loop that applies rule Z2. The workgroup keeps the cells within max_range of its
+ * LiDAR in LDS, one bit a cell, when that square fits (about 10 m at 0.05 m a cell); otherwise it reads the map
+ * from global memory: the same walk, the same bits. F110QP_ERR_INVALID before any HIP call, on top of that call's
+ * rules: a NULL grid_cfg, a negative width or height, width * height > 0 with grid == NULL, resolution not finite
+ * or <= 0, reach negative or not finite, a non-finite origin, num_circles + group_size + num_segments +
+ * width * height above INT_MAX. width * height == 0 with grid == NULL is valid and gives
+ * f110qp_cast_scans_noisy_dev's bits. At most min(batch, 512) workgroups. */
+int f110qp_cast_scans_grid_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
+                               const f110qp_race_config* race, const f110qp_body_config* body,
+                               const f110qp_walls_config* walls, const f110qp_noise_config* noise,
+                               const f110qp_grid_config* grid_cfg, int batch, int tick, const int* list,
+                               const int* count, const double* x, const double* circles, const double* segments,
+                               const unsigned char* grid, float* ranges, void* stream);
+
+/* f110qp_clearance_walls_dev, word for word, with the occupied cells of the map as a fourth stretch of the obstacle
+ * list (rule G2; one launch, that call's grid-stride launch): grid_cfg follows walls, grid follows segments. Errors
+ * as f110qp_cast_scans_grid_dev's grid rules on top of that call's; an empty map gives f110qp_clearance_walls_dev's
+ * bits. At most min(batch, 512) workgroups. */
+int f110qp_clearance_grid_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
+                              const f110qp_body_config* body, const f110qp_walls_config* walls,
+                              const f110qp_grid_config* grid_cfg, int batch, int rows, const double* x,
+                              const double* circles, const double* segments, const unsigned char* grid,
+                              double* clearance, int* nearest, void* stream);
+
+/* f110qp_rollout_noisy_dev, word for word, with every cast f110qp_cast_scans_grid_dev's and every clearance launch
+ * f110qp_clearance_grid_dev's (grid_cfg follows noise, grid follows segments): that call's launch count, stream
+ * order, parking, refresh and noise ticks, and absence of host synchronisation, read-back and allocation inside
+ * the loop; every argument is checked before the first launch (that call's checks with the grid rules behind the
+ * noise's). An empty map gives f110qp_rollout_noisy_dev's bits in every array. */
+int f110qp_rollout_grid_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                            const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                            const f110qp_race_config* race, const f110qp_contact_config* cc,
+                            const f110qp_body_config* body, const f110qp_walls_config* walls,
+                            const f110qp_refresh_config* rf, const f110qp_noise_config* noise,
+                            const f110qp_grid_config* grid_cfg, int batch, const double* table,
+                            const double* waypoints, double* x_ref, int* have_path, const double* circles,
+                            const double* segments, const unsigned char* grid, double* x_traj, double* u_lin_traj,
+                            float* u_applied, int* status_traj, int* iters_traj, double* cost_traj, float* u_plan,
+                            float* x_plan, float* hs_traj, int* kind_traj, int* plan_status_traj,
+                            int* best_traj_traj, int* best_global_traj, double* pose_traj, float* ranges_traj,
+                            double* clear_traj, int* nearest_traj, int* crash_tick, void* stream);
+
+/* Same on host pointers (synchronous), staged as f110qp_rollout_noisy; the map is staged in once. */
+int f110qp_rollout_grid(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                        const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                        const f110qp_race_config* race, const f110qp_contact_config* cc,
+                        const f110qp_body_config* body, const f110qp_walls_config* walls,
+                        const f110qp_refresh_config* rf, const f110qp_noise_config* noise,
+                        const f110qp_grid_config* grid_cfg, int batch, const double* table, const double* waypoints,
+                        double* x_ref, int* have_path, const double* circles, const double* segments,
+                        const unsigned char* grid, double* x_traj, double* u_lin_traj, float* u_applied,
+                        int* status_traj, int* iters_traj, double* cost_traj, float* u_plan, float* x_plan,
+                        float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
+                        int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
+                        int* nearest_traj, int* crash_tick);
+
 /* ---- race standings: progress along the track, laps and positions ---------------------------------------
  * The calls above return poses; the calls below say who is ahead. They run after the fact on x_traj, or on any
  * [rows][B][3] pose array: nothing inside a closed loop reads a standing, so there is no rollout family of
