@@ -197,13 +197,32 @@ static void scan_geometry(S* s, const f110qp_scan_config& sc) {
 // ---- one rollout call: its configs, its checks, where it runs ----------------------------------------
 
 // The family of a rollout call, in the order each was built on the one before: from kScan a scan
-// config is read, from kReplan the loop re-plans, from kWorld the scans are cast (so neither `ranges`
-// nor sc->scan_rows is read), kRace casts see the race-mates, kContact records every row's clearance,
-// kBody is kContact with rectangular bodies in every cast and clearance, kWalls is kBody with straight wall
-// segments next to the circles, kRefresh is kWalls with a refresh period for the scan MPC holds, and kNoisy is
-// kRefresh with rules Z1 to Z3 on every scan it casts, and kGrid is kNoisy with a raster map under every cast and
-// clearance.
-enum Family { kPlain, kScan, kReplan, kWorld, kRace, kContact, kBody, kWalls, kRefresh, kNoisy, kGrid };
+// config is read, from kReplan the loop re-plans, in kWorld the scans are cast (so neither `ranges`
+// nor sc->scan_rows is read): every world family, told apart by its WorldRow below.
+enum Family { kPlain, kScan, kReplan, kWorld };
+
+// The world families, one row each, in the order each was built on the one before: the world its casts and
+// clearances see, whether its rollout reads cc (every row's clearance is recorded) and rf (the scan MPC holds is
+// refreshed), and what a failed launch of the cast and of the clearance entry point of its name says (null: the
+// family has no such entry point). world: the circles; race: the race-mates in every cast; contact: race with cc;
+// body: rectangular bodies in every cast and clearance; walls: straight segments next to the circles; refresh:
+// walls with rf; noisy: rules Z1 to Z3 on every scan; grid: a raster map under every cast and clearance.
+struct WorldRow {
+  f110qp::WorldFamily world;
+  bool cc, rf;
+  const char* cast_launch;
+  const char* clearance_launch;
+};
+namespace row {
+constexpr WorldRow world{f110qp::WORLD_CIRCLES, false, false, "scan cast launch", nullptr};
+constexpr WorldRow race{f110qp::WORLD_RACE, false, false, "race scan cast launch", "clearance launch"};
+constexpr WorldRow contact{f110qp::WORLD_RACE, true, false, nullptr, nullptr};
+constexpr WorldRow body{f110qp::WORLD_BODY, true, false, "body scan cast launch", "body clearance launch"};
+constexpr WorldRow walls{f110qp::WORLD_WALLS, true, false, "walls scan cast launch", "walls clearance launch"};
+constexpr WorldRow refresh{f110qp::WORLD_WALLS, true, true, nullptr, nullptr};
+constexpr WorldRow noisy{f110qp::WORLD_NOISY, true, true, "noisy scan cast launch", nullptr};
+constexpr WorldRow grid{f110qp::WORLD_GRID, true, true, "grid scan cast launch", "grid clearance launch"};
+}  // namespace row
 
 // The configs of a rollout call as the caller gave them and, once check_args has passed, the
 // kernels' parameters.
@@ -628,18 +647,25 @@ static int replan_call(f110qp_ctx* c, LoopCfg cfg, RolloutIO io, const ReplanIO&
   return w.host ? replan_host(c, cfg, io, r, nullptr) : replan_ticks(c, cfg, io, r, w.stream, nullptr);
 }
 
-// The configs of a world-family call as the caller gave them; a family reads those up to its own (wc: all,
-// race: from kRace and every clearance, cc: from kContact, body: from kBody, walls: from kWalls, rf: from kRefresh,
-// noise: from kNoisy and the noisy and grid casts, grid: kGrid and the grid cast and clearance).
+// The configs of a world-family call as the caller gave them, each set by its name; a call reads those its family
+// takes (wc: all, race: from row::race, cc and rf: the rollouts of the rows that say so, body: from row::body, walls:
+// from row::walls, noise: the casts and rollouts from row::noisy, grid: row::grid) and leaves the others null.
 struct WorldCfgs {
-  const f110qp_world_config* wc;
-  const f110qp_race_config* race;
-  const f110qp_contact_config* cc;
-  const f110qp_body_config* body;
-  const f110qp_walls_config* walls;
-  const f110qp_refresh_config* rf;
-  const f110qp_noise_config* noise;
-  const f110qp_grid_config* grid;
+  const f110qp_world_config* wc = nullptr;
+  const f110qp_race_config* race = nullptr;
+  const f110qp_contact_config* cc = nullptr;
+  const f110qp_body_config* body = nullptr;
+  const f110qp_walls_config* walls = nullptr;
+  const f110qp_refresh_config* rf = nullptr;
+  const f110qp_noise_config* noise = nullptr;
+  const f110qp_grid_config* grid = nullptr;
+  WorldCfgs& Race(const f110qp_race_config* v) { return race = v, *this; }
+  WorldCfgs& Contact(const f110qp_contact_config* v) { return cc = v, *this; }
+  WorldCfgs& Body(const f110qp_body_config* v) { return body = v, *this; }
+  WorldCfgs& Walls(const f110qp_walls_config* v) { return walls = v, *this; }
+  WorldCfgs& Refresh(const f110qp_refresh_config* v) { return rf = v, *this; }
+  WorldCfgs& Noise(const f110qp_noise_config* v) { return noise = v, *this; }
+  WorldCfgs& Grid(const f110qp_grid_config* v) { return grid = v, *this; }
 };
 
 // The world of a cast, a clearance or a world rollout, checked in the one order all of them share, into *w;
@@ -669,7 +695,7 @@ static int world_of(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const
   return F110QP_OK;
 }
 
-// The arrays of a world-family rollout call (a.k: from kContact).
+// The arrays of a world-family rollout call (a.k: the rows with cc).
 struct WorldArrays {
   RolloutIO io;
   ReplanIO r;
@@ -683,19 +709,16 @@ static WorldArrays world_arrays(int batch, const double* table, const double* wp
                      ReplanIO{table, wp, have, nullptr, {hst, kt, pst, btt, bgt, poset}}, ContactIO{clt, nrt, crash}};
 }
 
-// f110qp_rollout_world[_dev] (kWorld), _race (kRace), _contact (kContact), _body (kBody), _walls (kWalls),
-// _refresh (kRefresh), _noisy (kNoisy) and _grid (kGrid) on the configs k their family reads.
-static int world_call(f110qp_ctx* c, LoopCfg cfg, const WorldCfgs& k, WorldArrays a, const double* circles,
-                      const double* segments, float* rgt, Where w, const unsigned char* grid = nullptr) {
-  static const f110qp::WorldFamily kOf[] = {f110qp::WORLD_CIRCLES, f110qp::WORLD_RACE, f110qp::WORLD_RACE,
-                                            f110qp::WORLD_BODY,    f110qp::WORLD_WALLS, f110qp::WORLD_WALLS,
-                                            f110qp::WORLD_NOISY,   f110qp::WORLD_GRID};
+// f110qp_rollout_<family>[_dev] of the eight world families: the family's row f and the configs k it reads.
+static int world_call(f110qp_ctx* c, const WorldRow& f, LoopCfg cfg, const WorldCfgs& k, WorldArrays a,
+                      const double* circles, const double* segments, float* rgt, Where w,
+                      const unsigned char* grid = nullptr) {
   WorldLoop wl{};
   int rv = check_args(c, &cfg, &a.io, nullptr, nullptr, &a.r);
   if (rv) return rv;
-  const bool contact = cfg.fam >= kContact;
-  if ((rv = world_of(kOf[cfg.fam - kWorld], cfg.sc, k, contact, a.io.B, circles, segments, &wl.w, grid))) return rv;
-  if (cfg.fam >= kRefresh && (rv = refresh_params(k.rf, &wl.every))) return rv;
+  const bool contact = f.cc;
+  if ((rv = world_of(f.world, cfg.sc, k, contact, a.io.B, circles, segments, &wl.w, grid))) return rv;
+  if (f.rf && (rv = refresh_params(k.rf, &wl.every))) return rv;
   if (a.io.B == 0) return F110QP_OK;
   if (contact && (!a.k.clear_traj || !a.k.crash_tick))
     return fail(F110QP_ERR_INVALID, "clear_traj/crash_tick must be non-NULL");
@@ -708,17 +731,15 @@ static int world_call(f110qp_ctx* c, LoopCfg cfg, const WorldCfgs& k, WorldArray
 
 // f110qp_cast_scans[_race|_body|_walls|_noisy|_grid]_dev on the configs k their family reads; tick: rule Z3's t of
 // the noisy and grid casts (0 elsewhere).
-static int cast_call(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const WorldCfgs& k, int batch,
+static int cast_call(const WorldRow& f, const f110qp_scan_config* sc, const WorldCfgs& k, int batch,
                      const int* list, const int* count, const double* x, const double* circles,
                      const double* segments, float* ranges, void* stream, int tick = 0,
                      const unsigned char* grid = nullptr) {
-  static const char* const kLaunch[] = {"scan cast launch",       "race scan cast launch",  "body scan cast launch",
-                                        "walls scan cast launch", "noisy scan cast launch", "grid scan cast launch"};
   int rv = check_scan_config(sc, false, 0);
   if (rv) return rv;
   if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
   f110qp::World w{};
-  if ((rv = world_of(fam, sc, k, false, batch, circles, segments, &w, grid))) return rv;
+  if ((rv = world_of(f.world, sc, k, false, batch, circles, segments, &w, grid))) return rv;
   if (tick < 0) return fail(F110QP_ERR_INVALID, "tick < 0");
   w.Z.tick = tick;
   if ((list != nullptr) != (count != nullptr))
@@ -726,19 +747,17 @@ static int cast_call(f110qp::WorldFamily fam, const f110qp_scan_config* sc, cons
   if (batch == 0) return F110QP_OK;
   if (!x || !ranges) return fail(F110QP_ERR_INVALID, "x/ranges must be non-NULL");
   const hipError_t e = f110qp::launch_cast_scans(w, batch, list, count, x, ranges, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, kLaunch[fam]);
+  if (e != hipSuccess) return hip_fail(e, f.cast_launch);
   return F110QP_OK;
 }
 
-// f110qp_clearance[_body|_walls|_grid]_dev on the configs k their family reads (fam >= WORLD_RACE).
-static int clearance_call(f110qp::WorldFamily fam, const WorldCfgs& k, int batch, int rows, const double* x,
+// f110qp_clearance[_body|_walls|_grid]_dev on the configs k their family reads (a row with a clearance).
+static int clearance_call(const WorldRow& f, const WorldCfgs& k, int batch, int rows, const double* x,
                           const double* circles, const double* segments, double* clearance, int* nearest,
                           void* stream, const unsigned char* grid = nullptr) {
-  static const char* const kLaunch[] = {nullptr, "clearance launch", "body clearance launch", "walls clearance launch",
-                                        nullptr, "grid clearance launch"};
   if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
   f110qp::World w{};
-  const int rv = world_of(fam, nullptr, k, false, batch, circles, segments, &w, grid);
+  const int rv = world_of(f.world, nullptr, k, false, batch, circles, segments, &w, grid);
   if (rv) return rv;
   if (rows < 1) return fail(F110QP_ERR_INVALID, "rows must be >= 1");
   if (batch == 0) return F110QP_OK;
@@ -746,7 +765,7 @@ static int clearance_call(f110qp::WorldFamily fam, const WorldCfgs& k, int batch
   if ((long long)rows * batch > (1ll << 30)) return fail(F110QP_ERR_INVALID, "rows x batch too large");
   const hipError_t e = f110qp::launch_clearance(w, batch, rows, x, clearance, nearest,
                                                 f110qp::ContactMark{nullptr, 0, 0, 0.0}, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, kLaunch[fam]);
+  if (e != hipSuccess) return hip_fail(e, f.clearance_launch);
   return F110QP_OK;
 }
 
@@ -1026,7 +1045,7 @@ void f110qp_default_world_config(f110qp_world_config* wc) {
 int f110qp_cast_scans_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc, int batch, const int* list,
                           const int* count, const double* x, const double* circles, float* ranges,
                           void* stream) {
-  return cast_call(f110qp::WORLD_CIRCLES, sc, WorldCfgs{wc}, batch, list, count, x, circles, nullptr, ranges, stream);
+  return cast_call(row::world, sc, WorldCfgs{wc}, batch, list, count, x, circles, nullptr, ranges, stream);
 }
 
 int f110qp_rollout_world_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1037,7 +1056,8 @@ int f110qp_rollout_world_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, con
                              float* rgt, void* stream) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset);
-  return world_call(c, LoopCfg{kWorld, rc, sc, rp}, WorldCfgs{wc}, a, circles, nullptr, rgt, on_stream(stream));
+  const WorldCfgs k = WorldCfgs{wc};
+  return world_call(c, row::world, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, nullptr, rgt, on_stream(stream));
 }
 
 int f110qp_rollout_world(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1048,7 +1068,7 @@ int f110qp_rollout_world(f110qp_ctx* c, const f110qp_rollout_config* rc, const f
                          float* rgt) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset);
-  return world_call(c, LoopCfg{kWorld, rc, sc, rp}, WorldCfgs{wc}, a, circles, nullptr, rgt, on_host());
+  return world_call(c, row::world, LoopCfg{kWorld, rc, sc, rp}, WorldCfgs{wc}, a, circles, nullptr, rgt, on_host());
 }
 
 void f110qp_default_race_config(f110qp_race_config* race) {
@@ -1062,8 +1082,7 @@ void f110qp_default_race_config(f110qp_race_config* race) {
 int f110qp_cast_scans_race_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
                                const f110qp_race_config* race, int batch, const int* list, const int* count,
                                const double* x, const double* circles, float* ranges, void* stream) {
-  return cast_call(f110qp::WORLD_RACE, sc, WorldCfgs{wc, race}, batch, list, count, x, circles, nullptr, ranges,
-                   stream);
+  return cast_call(row::race, sc, WorldCfgs{wc}.Race(race), batch, list, count, x, circles, nullptr, ranges, stream);
 }
 
 int f110qp_rollout_race_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1074,7 +1093,8 @@ int f110qp_rollout_race_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, cons
                             int* btt, int* bgt, double* poset, float* rgt, void* stream) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset);
-  return world_call(c, LoopCfg{kRace, rc, sc, rp}, WorldCfgs{wc, race}, a, circles, nullptr, rgt, on_stream(stream));
+  const WorldCfgs k = WorldCfgs{wc}.Race(race);
+  return world_call(c, row::race, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, nullptr, rgt, on_stream(stream));
 }
 
 int f110qp_rollout_race(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1085,7 +1105,8 @@ int f110qp_rollout_race(f110qp_ctx* c, const f110qp_rollout_config* rc, const f1
                         int* bgt, double* poset, float* rgt) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset);
-  return world_call(c, LoopCfg{kRace, rc, sc, rp}, WorldCfgs{wc, race}, a, circles, nullptr, rgt, on_host());
+  const WorldCfgs k = WorldCfgs{wc}.Race(race);
+  return world_call(c, row::race, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, nullptr, rgt, on_host());
 }
 
 // ---- contact: clearance to walls and race-mates, crashed cars park (f110qp_clearance_dev, ----------------
@@ -1100,8 +1121,8 @@ void f110qp_default_contact_config(f110qp_contact_config* cc) {
 
 int f110qp_clearance_dev(const f110qp_world_config* wc, const f110qp_race_config* race, int batch, int rows,
                          const double* x, const double* circles, double* clearance, int* nearest, void* stream) {
-  return clearance_call(f110qp::WORLD_RACE, WorldCfgs{wc, race}, batch, rows, x, circles, nullptr, clearance, nearest,
-                        stream);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race);
+  return clearance_call(row::race, k, batch, rows, x, circles, nullptr, clearance, nearest, stream);
 }
 
 int f110qp_rollout_contact_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1113,8 +1134,8 @@ int f110qp_rollout_contact_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, c
                                float* rgt, double* clt, int* nrt, int* crash, void* stream) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kContact, rc, sc, rp}, WorldCfgs{wc, race, cc}, a, circles, nullptr, rgt,
-                    on_stream(stream));
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc);
+  return world_call(c, row::contact, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, nullptr, rgt, on_stream(stream));
 }
 
 int f110qp_rollout_contact(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1126,7 +1147,8 @@ int f110qp_rollout_contact(f110qp_ctx* c, const f110qp_rollout_config* rc, const
                            int* nrt, int* crash) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kContact, rc, sc, rp}, WorldCfgs{wc, race, cc}, a, circles, nullptr, rgt, on_host());
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc);
+  return world_call(c, row::contact, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, nullptr, rgt, on_host());
 }
 
 // ---- rectangular car bodies (f110qp_clearance_body_dev, f110qp_cast_scans_body_dev, -----------------------
@@ -1142,16 +1164,16 @@ void f110qp_default_body_config(f110qp_body_config* body) {
 int f110qp_clearance_body_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
                               const f110qp_body_config* body, int batch, int rows, const double* x,
                               const double* circles, double* clearance, int* nearest, void* stream) {
-  return clearance_call(f110qp::WORLD_BODY, WorldCfgs{wc, race, nullptr, body}, batch, rows, x, circles, nullptr,
-                        clearance, nearest, stream);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Body(body);
+  return clearance_call(row::body, k, batch, rows, x, circles, nullptr, clearance, nearest, stream);
 }
 
 int f110qp_cast_scans_body_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc,
                                const f110qp_race_config* race, const f110qp_body_config* body, int batch,
                                const int* list, const int* count, const double* x, const double* circles,
                                float* ranges, void* stream) {
-  return cast_call(f110qp::WORLD_BODY, sc, WorldCfgs{wc, race, nullptr, body}, batch, list, count, x, circles, nullptr,
-                   ranges, stream);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Body(body);
+  return cast_call(row::body, sc, k, batch, list, count, x, circles, nullptr, ranges, stream);
 }
 
 int f110qp_rollout_body_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1164,8 +1186,8 @@ int f110qp_rollout_body_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, cons
                             void* stream) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kBody, rc, sc, rp}, WorldCfgs{wc, race, cc, body}, a, circles, nullptr, rgt,
-                    on_stream(stream));
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body);
+  return world_call(c, row::body, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, nullptr, rgt, on_stream(stream));
 }
 
 int f110qp_rollout_body(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1177,7 +1199,8 @@ int f110qp_rollout_body(f110qp_ctx* c, const f110qp_rollout_config* rc, const f1
                         double* poset, float* rgt, double* clt, int* nrt, int* crash) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kBody, rc, sc, rp}, WorldCfgs{wc, race, cc, body}, a, circles, nullptr, rgt, on_host());
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body);
+  return world_call(c, row::body, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, nullptr, rgt, on_host());
 }
 
 // ---- straight walls (f110qp_cast_scans_walls_dev, f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]) ------
@@ -1193,16 +1216,16 @@ int f110qp_cast_scans_walls_dev(const f110qp_scan_config* sc, const f110qp_world
                                 const f110qp_walls_config* walls, int batch, const int* list, const int* count,
                                 const double* x, const double* circles, const double* segments, float* ranges,
                                 void* stream) {
-  return cast_call(f110qp::WORLD_WALLS, sc, WorldCfgs{wc, race, nullptr, body, walls}, batch, list, count, x, circles,
-                   segments, ranges, stream);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Body(body).Walls(walls);
+  return cast_call(row::walls, sc, k, batch, list, count, x, circles, segments, ranges, stream);
 }
 
 int f110qp_clearance_walls_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
                                const f110qp_body_config* body, const f110qp_walls_config* walls, int batch, int rows,
                                const double* x, const double* circles, const double* segments, double* clearance,
                                int* nearest, void* stream) {
-  return clearance_call(f110qp::WORLD_WALLS, WorldCfgs{wc, race, nullptr, body, walls}, batch, rows, x, circles,
-                        segments, clearance, nearest, stream);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Body(body).Walls(walls);
+  return clearance_call(row::walls, k, batch, rows, x, circles, segments, clearance, nearest, stream);
 }
 
 int f110qp_rollout_walls_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1215,8 +1238,8 @@ int f110qp_rollout_walls_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, con
                              double* poset, float* rgt, double* clt, int* nrt, int* crash, void* stream) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kWalls, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls}, a, circles, segments, rgt,
-                    on_stream(stream));
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls);
+  return world_call(c, row::walls, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_stream(stream));
 }
 
 int f110qp_rollout_walls(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1229,8 +1252,8 @@ int f110qp_rollout_walls(f110qp_ctx* c, const f110qp_rollout_config* rc, const f
                          float* rgt, double* clt, int* nrt, int* crash) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kWalls, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls}, a, circles, segments, rgt,
-                    on_host());
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls);
+  return world_call(c, row::walls, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_host());
 }
 
 // ---- a refreshed MPC scan (f110qp_gap_refresh_dev, f110qp_rollout_refresh[_dev]) -------------------------------
@@ -1265,8 +1288,8 @@ int f110qp_rollout_refresh_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, c
                                double* clt, int* nrt, int* crash, void* stream) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kRefresh, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf}, a, circles, segments,
-                    rgt, on_stream(stream));
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls).Refresh(rf);
+  return world_call(c, row::refresh, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_stream(stream));
 }
 
 int f110qp_rollout_refresh(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1280,8 +1303,8 @@ int f110qp_rollout_refresh(f110qp_ctx* c, const f110qp_rollout_config* rc, const
                            int* crash) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kRefresh, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf}, a, circles, segments,
-                    rgt, on_host());
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls).Refresh(rf);
+  return world_call(c, row::refresh, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_host());
 }
 
 // ---- a noisy LiDAR (f110qp_cast_scans_noisy_dev, f110qp_rollout_noisy[_dev]) ------------------------------------
@@ -1296,8 +1319,8 @@ int f110qp_cast_scans_noisy_dev(const f110qp_scan_config* sc, const f110qp_world
                                 const f110qp_walls_config* walls, const f110qp_noise_config* noise, int batch,
                                 int tick, const int* list, const int* count, const double* x, const double* circles,
                                 const double* segments, float* ranges, void* stream) {
-  return cast_call(f110qp::WORLD_NOISY, sc, WorldCfgs{wc, race, nullptr, body, walls, nullptr, noise}, batch, list,
-                   count, x, circles, segments, ranges, stream, tick);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Body(body).Walls(walls).Noise(noise);
+  return cast_call(row::noisy, sc, k, batch, list, count, x, circles, segments, ranges, stream, tick);
 }
 
 int f110qp_rollout_noisy_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1311,8 +1334,8 @@ int f110qp_rollout_noisy_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, con
                              double* poset, float* rgt, double* clt, int* nrt, int* crash, void* stream) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kNoisy, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf, noise}, a, circles,
-                    segments, rgt, on_stream(stream));
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls).Refresh(rf).Noise(noise);
+  return world_call(c, row::noisy, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_stream(stream));
 }
 
 int f110qp_rollout_noisy(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1326,8 +1349,8 @@ int f110qp_rollout_noisy(f110qp_ctx* c, const f110qp_rollout_config* rc, const f
                          float* rgt, double* clt, int* nrt, int* crash) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kNoisy, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf, noise}, a, circles,
-                    segments, rgt, on_host());
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls).Refresh(rf).Noise(noise);
+  return world_call(c, row::noisy, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_host());
 }
 
 // ---- a raster map (f110qp_cast_scans_grid_dev, f110qp_clearance_grid_dev, f110qp_rollout_grid[_dev]) -----------
@@ -1345,8 +1368,8 @@ int f110qp_cast_scans_grid_dev(const f110qp_scan_config* sc, const f110qp_world_
                                const f110qp_grid_config* gc, int batch, int tick, const int* list, const int* count,
                                const double* x, const double* circles, const double* segments,
                                const unsigned char* grid, float* ranges, void* stream) {
-  return cast_call(f110qp::WORLD_GRID, sc, WorldCfgs{wc, race, nullptr, body, walls, nullptr, noise, gc}, batch, list,
-                   count, x, circles, segments, ranges, stream, tick, grid);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Body(body).Walls(walls).Noise(noise).Grid(gc);
+  return cast_call(row::grid, sc, k, batch, list, count, x, circles, segments, ranges, stream, tick, grid);
 }
 
 int f110qp_clearance_grid_dev(const f110qp_world_config* wc, const f110qp_race_config* race,
@@ -1354,8 +1377,8 @@ int f110qp_clearance_grid_dev(const f110qp_world_config* wc, const f110qp_race_c
                               const f110qp_grid_config* gc, int batch, int rows, const double* x,
                               const double* circles, const double* segments, const unsigned char* grid,
                               double* clearance, int* nearest, void* stream) {
-  return clearance_call(f110qp::WORLD_GRID, WorldCfgs{wc, race, nullptr, body, walls, nullptr, nullptr, gc}, batch,
-                        rows, x, circles, segments, clearance, nearest, stream, grid);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Body(body).Walls(walls).Grid(gc);
+  return clearance_call(row::grid, k, batch, rows, x, circles, segments, clearance, nearest, stream, grid);
 }
 
 int f110qp_rollout_grid_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1370,8 +1393,8 @@ int f110qp_rollout_grid_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, cons
                             int* nrt, int* crash, void* stream) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kGrid, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf, noise, gc}, a, circles,
-                    segments, rgt, on_stream(stream), grid);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls).Refresh(rf).Noise(noise).Grid(gc);
+  return world_call(c, row::grid, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_stream(stream), grid);
 }
 
 int f110qp_rollout_grid(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
@@ -1386,8 +1409,8 @@ int f110qp_rollout_grid(f110qp_ctx* c, const f110qp_rollout_config* rc, const f1
                         int* crash) {
   const WorldArrays a = world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt,
                                      bgt, poset, clt, nrt, crash);
-  return world_call(c, LoopCfg{kGrid, rc, sc, rp}, WorldCfgs{wc, race, cc, body, walls, rf, noise, gc}, a, circles,
-                    segments, rgt, on_host(), grid);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls).Refresh(rf).Noise(noise).Grid(gc);
+  return world_call(c, row::grid, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_host(), grid);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -319,6 +320,87 @@ class F110QPError(RuntimeError):
     pass
 
 
+# ---- the world families: the one table behind their bindings, checks and test helpers -------------------
+# Each family is the one before it plus one config and, some, one world array and output records. A row says what
+# its family adds; a family's entry points take what the rows up to its own add, in the rows' order.
+
+class _Record(NamedTuple):
+    name: str       # of the output record, in the ABI's order ([B], or [ticks + 1, B] with per_row)
+    dtype: str
+    per_row: bool
+    optional: bool  # the _dev calls may pass None; the host calls return it on the flag of its name less "_traj"
+
+
+class _Family(NamedTuple):
+    name: str                      # f110qp_rollout_<name>[_dev]
+    cfg: type                      # the config it adds ...
+    arg: str                       # ... under this public argument name
+    array: str | None = None       # the world array it adds behind the earlier ones (None where its count is 0)
+    records: tuple = ()            # the output records it adds behind ranges_traj
+    cast: str | None = None        # its cast entry point, if it has one
+    clearance: str | None = None   # its clearance entry point, if it has one
+    skips: tuple = ()              # the kinds of entry point ("cast", "clearance") that do not take cfg
+    tick: bool = False             # the casts from here on take `tick` directly behind `batch`
+
+
+WORLD_FAMILIES = (
+    _Family("world", WorldConfig, "wc", array="circles", cast="f110qp_cast_scans_dev"),
+    _Family("race", RaceConfig, "race", cast="f110qp_cast_scans_race_dev", clearance="f110qp_clearance_dev"),
+    _Family("contact", ContactConfig, "cc", skips=("cast", "clearance"),
+            records=(_Record("clear_traj", "f64", True, False), _Record("nearest_traj", "i32", True, True),
+                     _Record("crash_tick", "i32", False, False))),
+    _Family("body", BodyConfig, "body", cast="f110qp_cast_scans_body_dev", clearance="f110qp_clearance_body_dev"),
+    _Family("walls", WallsConfig, "walls", array="segments", cast="f110qp_cast_scans_walls_dev",
+            clearance="f110qp_clearance_walls_dev"),
+    _Family("refresh", RefreshConfig, "rf", skips=("cast", "clearance")),
+    _Family("noisy", NoiseConfig, "noise", cast="f110qp_cast_scans_noisy_dev", skips=("clearance",), tick=True),
+    _Family("grid", GridConfig, "grid_cfg", array="grid", cast="f110qp_cast_scans_grid_dev",
+            clearance="f110qp_clearance_grid_dev"),
+)
+_TRAJ = ("x_traj", "u_lin_traj", "u_applied", "status_traj", "iters_traj", "cost_traj", "u_plan", "x_plan")
+_REC = ("hs_traj", "kind_traj", "plan_status_traj", "best_traj_traj", "best_global_traj", "pose_traj")
+# the ctypes of the parameters that are no array (an array, the context and the stream: c_void_p)
+_CTYPES = {"rc": C.POINTER(RolloutConfig), "sc": C.POINTER(ScanConfig), "rp": C.POINTER(ReplanConfig),
+           "batch": C.c_int, "rows": C.c_int, "tick": C.c_int, **{f.arg: C.POINTER(f.cfg) for f in WORLD_FAMILIES}}
+
+
+def _families(upto: str, kind: str = "rollout"):
+    """The rows up to family `upto` whose config an entry point of `kind` takes."""
+    n = [f.name for f in WORLD_FAMILIES].index(upto) + 1
+    return [f for f in WORLD_FAMILIES[:n] if kind not in f.skips]
+
+
+def _abi(kind: str, upto: str, dev: bool = True):
+    """The parameters of family `upto`'s entry point of `kind` ("rollout", "cast", "clearance") in the ABI's order,
+    under their public names (dev: the call takes a stream)."""
+    fams = _families(upto, kind)
+    cfgs, arrays = [f.arg for f in fams], [f.array for f in fams if f.array]
+    if kind == "cast":
+        return ["sc", *cfgs, "batch", *(["tick"] if any(f.tick for f in fams) else []), "list_", "count", "x", *arrays,
+                "ranges", "stream"]
+    if kind == "clearance":
+        return [*cfgs, "batch", "rows", "x", *arrays, "clearance", "nearest", "stream"]
+    return ["ctx", "rc", "sc", "rp", *cfgs, "batch", "table", "waypoints", "x_ref", "have_path", *arrays, *_TRAJ, *_REC,
+            "ranges_traj", *(r.name for f in fams for r in f.records), *(["stream"] if dev else [])]
+
+
+def _abi_args(names, a):
+    """The device call's values of the parameters `names` out of the arguments a: a config by reference, an int, the
+    context and the stream as they are, a tensor's address."""
+    return [a[n] if n in ("ctx", "stream") else int(a[n]) if _CTYPES.get(n) is C.c_int
+            else C.byref(a[n]) if n in _CTYPES else _tp(a[n]) for n in names]
+
+
+def _check_cfgs(fams, a, whole: bool):
+    """The type check of the configs of the rows `fams` among the arguments a, in front of everything else. whole:
+    the error is the rollout wrappers' sentence over all of them; otherwise it names the first wrong one."""
+    wrong = [f for f in fams if not isinstance(a[f.arg], f.cfg)]
+    if wrong:
+        named = fams if whole else wrong[:1]
+        said = [f"{f.arg} {'a' if i else 'must be a'} {f.cfg.__name__}" for i, f in enumerate(named)]
+        raise F110QPError(", ".join(said[:-1]) + " and " + said[-1] if said[1:] else said[0])
+
+
 _libs = {}
 
 
@@ -370,49 +452,15 @@ def load(test: bool = False):
     L.f110qp_advance_replan_dev.argtypes = [rop, rp, sp, C.c_int, C.c_int] + [fp] * 20
     L.f110qp_rollout_replan_dev.argtypes = [C.c_void_p, rop, sp, rp, C.c_int] + [fp] * 20
     L.f110qp_rollout_replan.argtypes = [C.c_void_p, rop, sp, rp, C.c_int] + [fp] * 19
-    wcp = C.POINTER(WorldConfig)
-    L.f110qp_default_world_config.argtypes = [wcp]
-    L.f110qp_cast_scans_dev.argtypes = [sp, wcp, C.c_int] + [fp] * 6
-    L.f110qp_rollout_world_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, C.c_int] + [fp] * 21
-    L.f110qp_rollout_world.argtypes = [C.c_void_p, rop, sp, rp, wcp, C.c_int] + [fp] * 20
-    rcp = C.POINTER(RaceConfig)
-    L.f110qp_default_race_config.argtypes = [rcp]
-    L.f110qp_cast_scans_race_dev.argtypes = [sp, wcp, rcp, C.c_int] + [fp] * 6
-    L.f110qp_rollout_race_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, C.c_int] + [fp] * 21
-    L.f110qp_rollout_race.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, C.c_int] + [fp] * 20
-    ccp = C.POINTER(ContactConfig)
-    L.f110qp_default_contact_config.argtypes = [ccp]
-    L.f110qp_clearance_dev.argtypes = [wcp, rcp, C.c_int, C.c_int] + [fp] * 5
-    L.f110qp_rollout_contact_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, C.c_int] + [fp] * 24
-    L.f110qp_rollout_contact.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, C.c_int] + [fp] * 23
-    bcp = C.POINTER(BodyConfig)
-    L.f110qp_default_body_config.argtypes = [bcp]
-    L.f110qp_clearance_body_dev.argtypes = [wcp, rcp, bcp, C.c_int, C.c_int] + [fp] * 5
-    L.f110qp_cast_scans_body_dev.argtypes = [sp, wcp, rcp, bcp, C.c_int] + [fp] * 6
-    L.f110qp_rollout_body_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, C.c_int] + [fp] * 24
-    L.f110qp_rollout_body.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, C.c_int] + [fp] * 23
-    wlp = C.POINTER(WallsConfig)
-    L.f110qp_default_walls_config.argtypes = [wlp]
-    L.f110qp_cast_scans_walls_dev.argtypes = [sp, wcp, rcp, bcp, wlp, C.c_int] + [fp] * 7
-    L.f110qp_clearance_walls_dev.argtypes = [wcp, rcp, bcp, wlp, C.c_int, C.c_int] + [fp] * 6
-    L.f110qp_rollout_walls_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, C.c_int] + [fp] * 25
-    L.f110qp_rollout_walls.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, C.c_int] + [fp] * 24
-    rfp = C.POINTER(RefreshConfig)
-    L.f110qp_default_refresh_config.argtypes = [rfp]
     L.f110qp_gap_refresh_dev.argtypes = [sp, C.c_int] + [fp] * 5
-    L.f110qp_rollout_refresh_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, C.c_int] + [fp] * 25
-    L.f110qp_rollout_refresh.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, C.c_int] + [fp] * 24
-    nzp = C.POINTER(NoiseConfig)
-    L.f110qp_default_noise_config.argtypes = [nzp]
-    L.f110qp_cast_scans_noisy_dev.argtypes = [sp, wcp, rcp, bcp, wlp, nzp, C.c_int, C.c_int] + [fp] * 7
-    L.f110qp_rollout_noisy_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, nzp, C.c_int] + [fp] * 25
-    L.f110qp_rollout_noisy.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, nzp, C.c_int] + [fp] * 24
-    gcp = C.POINTER(GridConfig)
-    L.f110qp_default_grid_config.argtypes = [gcp]
-    L.f110qp_cast_scans_grid_dev.argtypes = [sp, wcp, rcp, bcp, wlp, nzp, gcp, C.c_int, C.c_int] + [fp] * 8
-    L.f110qp_clearance_grid_dev.argtypes = [wcp, rcp, bcp, wlp, gcp, C.c_int, C.c_int] + [fp] * 7
-    L.f110qp_rollout_grid_dev.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, nzp, gcp, C.c_int] + [fp] * 26
-    L.f110qp_rollout_grid.argtypes = [C.c_void_p, rop, sp, rp, wcp, rcp, ccp, bcp, wlp, rfp, nzp, gcp, C.c_int] + [fp] * 25
+    # the world families: every argument list from the table (tests/test_capi_families.py holds them to the header)
+    for f in WORLD_FAMILIES:
+        getattr(L, f"f110qp_default_{f.cfg.__name__[:-len('Config')].lower()}_config").argtypes = [C.POINTER(f.cfg)]
+        for symbol, kind, dev in ((f"f110qp_rollout_{f.name}_dev", "rollout", True), (f.cast, "cast", True),
+                                  (f"f110qp_rollout_{f.name}", "rollout", False), (f.clearance, "clearance", True)):
+            if symbol:
+                getattr(L, symbol).argtypes = [_CTYPES.get(n, fp) for n in _abi(kind, f.name, dev)]
+    rcp = C.POINTER(RaceConfig)
     L.f110qp_path_lengths.argtypes = [fp, C.c_int, fp]
     L.f110qp_progress_dev.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_int] + [fp] * 4
     L.f110qp_standings_dev.argtypes = [rcp, C.c_int, C.c_int, fp, C.c_double] + [fp] * 4
@@ -620,6 +668,65 @@ def _grid_spec(gc, grid):
         raise F110QPError("grid_cfg must be a GridConfig")
     n = max(int(gc.width), 0) * max(int(gc.height), 0)
     return (grid, "u8", n, "grid", n == 0)
+
+
+def _wall_spec(walls, segments):
+    if not isinstance(walls, WallsConfig):
+        raise F110QPError("walls must be a WallsConfig")
+    Sn = int(walls.num_segments)
+    return (segments, "f64", 4 * max(Sn, 0) * max(int(walls.wall_rows), 0), "segments", Sn <= 0)
+
+
+def _circle_spec(wc, circles):
+    Cn = int(wc.num_circles)
+    return (circles, "f64", 3 * max(Cn, 0) * max(int(wc.world_rows), 0), "circles", Cn <= 0)
+
+
+def _world_specs(fams, a):
+    """The _devs specs of the world arrays of the rows `fams`, each sized by its row's config."""
+    spec = {"circles": _circle_spec, "segments": _wall_spec, "grid": _grid_spec}
+    return [spec[f.array](a[f.arg], a[f.array]) for f in fams if f.array]
+
+
+def _host_circles(a, B):
+    """(world config, circles) of a host rollout: a copy of wc (default: f110qp_default_world_config) with the
+    counts of the checked array."""
+    circles, wc = a["circles"], a["wc"]
+    if not isinstance(circles, np.ndarray) or circles.dtype != np.float64 or circles.ndim not in (2, 3) \
+            or circles.shape[-1] != 3:
+        raise F110QPError("circles must be a float64 numpy array [C, 3] or [B, C, 3]")
+    ci = np.ascontiguousarray(circles)
+    w = WorldConfig()
+    C.memmove(C.byref(w), C.byref(wc if wc is not None else default_world_config()), C.sizeof(w))
+    w.num_circles = ci.shape[-2]
+    w.world_rows = 1 if ci.ndim == 2 else ci.shape[0]
+    if w.world_rows not in (1, B):
+        raise F110QPError(f"circles must hold one world or B = {B} worlds, got {w.world_rows}")
+    return w, ci
+
+
+def _host_segments(a, B):
+    """(walls config, segments) of a host rollout, the config built from the checked array."""
+    segments = a["segments"]
+    if not isinstance(segments, np.ndarray) or segments.dtype != np.float64 or segments.ndim not in (2, 3) \
+            or segments.shape[-1] != 4:
+        raise F110QPError("segments must be a float64 numpy array [S, 4] or [B, S, 4]")
+    sg = np.ascontiguousarray(segments)
+    wl = default_walls_config(num_segments=sg.shape[-2], wall_rows=1 if sg.ndim == 2 else sg.shape[0])
+    if wl.wall_rows not in (1, B):
+        raise F110QPError(f"segments must hold one set or B = {B} sets, got {wl.wall_rows}")
+    return wl, sg
+
+
+def _host_grid(a, B):
+    """(grid config, map [H,W] uint8) of a host rollout, the caller's config and the checked array."""
+    gc, gm = a["grid_cfg"], np.ascontiguousarray(a["grid"], np.uint8)
+    if gm.shape != (int(gc.height), int(gc.width)) and gm.size:
+        raise F110QPError(f"grid must be [height, width] = [{gc.height}, {gc.width}], got {gm.shape}")
+    return gc, gm
+
+
+_HOST_WORLD = {"circles": _host_circles, "segments": _host_segments, "grid": _host_grid}
 
 
 def _check_race(race, B):
@@ -875,7 +982,10 @@ class Solver:
                                                       _tp(cost), C.c_void_p(stream.cuda_stream)),
                   "f110qp_solve_batch_dev_dbl")
 
-    # ---- the closed-loop families: what their nine bindings share --------------------------------------
+    # ---- the closed-loop families: what their bindings share ------------------------------------------
+    # rollout, rollout_scan and rollout_replan (and their _dev calls) use these pieces by hand. The eight world
+    # families behind them use them through two bodies, _world_dev and _world_host, which read what a family takes
+    # off WORLD_FAMILIES: a new family is a row there and a pair of wrappers that hand their arguments over by name.
 
     @staticmethod
     def _dev_loop(rc, x_ref, x_traj, scan=None):
@@ -1096,54 +1206,68 @@ class Solver:
             _p(wp) if wp.shape[0] else None, _p(xr), _p(hv), _p(rg), *self._out_args(out)), "f110qp_rollout_replan")
         return out
 
+    # ---- the world families: one device body and one host body, both walking WORLD_FAMILIES -----------------------
+
+    def _world_dev(self, family, a):
+        """The body of the eight rollout_<family>_dev; a: the wrapper's arguments by name."""
+        fams = _families(family)
+        _check_cfgs(fams[1:], a, whole=True)
+        T, B = self._dev_loop(a["rc"], a["x_ref"], a["x_traj"])
+        WR = int(a["wc"].world_rows)
+        if WR not in (1, B):
+            raise F110QPError(f"world_rows must be 1 or B = {B}, got {WR}")
+        if fams[1:]:
+            _check_race(a["race"], B)
+        more = []  # behind ranges_traj, row by row: the records a family adds, then its world array
+        for f in fams[1:]:
+            more += [(a[r.name], r.dtype, (T + 1) * B if r.per_row else B, r.name, r.optional) for r in f.records]
+            more += _world_specs([f], a)
+        _devs(*self._plan_specs(a["rp"], B, a["table"], a["waypoints"], a["x_ref"], a["have_path"]),
+              *_world_specs(fams[:1], a), *self._traj_specs(T, B, *(a[n] for n in _TRAJ)),
+              *self._record_specs(T, B, *(a[n] for n in _REC)),
+              (a["ranges_traj"], "f32", T * B * int(a["sc"].num_ranges), "ranges_traj", True), *more)
+        name = f"f110qp_rollout_{family}_dev"
+        call = {**a, "ctx": self._h, "batch": B, "stream": self._stream(a["stream"], a["x_traj"])}
+        self._chk(getattr(self.lib, name)(*_abi_args(_abi("rollout", family), call)), name)
+
+    def _world_host(self, family, a):
+        """The body of the eight rollout_<family>; a: the wrapper's arguments by name. The world config's counts and
+        the walls config come from the arrays' shapes."""
+        fams = _families(family)
+        _check_cfgs([f for f in fams[1:] if f.array != "segments"], a, whole=True)
+        T, B, x0, ul = self._host_start(a["x0"], a["u_lin"], a["ticks"])
+        xr, hv, tab, wp = self._host_plan(a["rp"], B, a["table"], a["waypoints"], a["x_ref"], a["have_path"])
+        cfgs, world = [], []
+        for f in fams:
+            cfg = a.get(f.arg)
+            if f.array:
+                cfg, arr = _HOST_WORLD[f.array](a, B)
+                world.append(_p(arr) if arr.size else None)
+            if f.name == "race":
+                _check_race(cfg, B)
+            cfgs.append(C.byref(cfg))
+        out = self._host_out(T, B, x0, ul, a["objective"], a["plans"], a["rows"],
+                             int(a["sc"].num_ranges) if a["scans"] else 0, (xr, hv))
+        records = [r for f in fams for r in f.records]
+        for r in records:
+            if not r.optional or a[r.name[:-len("_traj")]]:
+                out[r.name] = np.empty((T + 1, B) if r.per_row else B, {"f64": np.float64, "i32": np.int32}[r.dtype])
+        name = f"f110qp_rollout_{family}"
+        self._chk(getattr(self.lib, name)(
+            self._h, C.byref(self._ticks_config(a["rc"], T)), C.byref(a["sc"]), C.byref(a["rp"]), *cfgs, B, _p(tab),
+            _p(wp) if wp.shape[0] else None, _p(xr), _p(hv), *world, *self._out_args(out), _p(out.get("ranges_traj")),
+            *(_p(out.get(r.name)) for r in records)), name)
+        return out
+
     def rollout_world_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, table,
                           waypoints, x_ref, have_path, circles, x_traj, u_lin_traj, u_applied, status_traj,
                           iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None, kind_traj=None,
                           plan_status_traj=None, best_traj_traj=None, best_global_traj=None, pose_traj=None,
-                          ranges_traj=None, stream=None, _race=None, _contact=None, _body=None, _walls=None,
-                          _refresh=None, _noise=None, _grid=None):
+                          ranges_traj=None, stream=None):
         """rollout_replan_dev with every tick's scan cast at that tick's pose (f110qp_rollout_world_dev): wc
         and circles [world_rows,C,3] f64 replace ranges, sc.scan_rows is not read, and the optional
         ranges_traj [T,B,num_ranges] f32 records every car's scan of every tick."""
-        T, B = self._dev_loop(rc, x_ref, x_traj)
-        Cn, WR = int(wc.num_circles), int(wc.world_rows)
-        if WR not in (1, B):
-            raise F110QPError(f"world_rows must be 1 or B = {B}, got {WR}")
-        if _race is not None:
-            _check_race(_race, B)
-        plan = (table, waypoints, x_ref, have_path)
-        traj = (x_traj, u_lin_traj, u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan)
-        rec = (hs_traj, kind_traj, plan_status_traj, best_traj_traj, best_global_traj, pose_traj)
-        name = "f110qp_rollout_world_dev" if _race is None else "f110qp_rollout_race_dev"
-        cfgs, tail, more = ([] if _race is None else [C.byref(_race)]), [], []
-        if _contact is not None:  # (cc, clear_traj, nearest_traj, crash_tick) behind the race rollout's arrays
-            cc, clear_traj, nearest_traj, crash_tick = _contact
-            more = [(clear_traj, "f64", (T + 1) * B, "clear_traj"), (nearest_traj, "i32", (T + 1) * B, "nearest_traj", True),
-                    (crash_tick, "i32", B, "crash_tick")]
-            name, cfgs, tail = "f110qp_rollout_contact_dev", cfgs + [C.byref(cc)], [_tp(clear_traj), _tp(nearest_traj),
-                                                                                   _tp(crash_tick)]
-            if _body is not None:  # the body config behind cc
-                name, cfgs = "f110qp_rollout_body_dev", cfgs + [C.byref(_body)]
-        world = [_tp(circles)]
-        if _walls is not None:  # (walls, segments): the config behind body, the segments behind circles
-            walls, segments = _walls
-            Sn = int(walls.num_segments)
-            more = more + [(segments, "f64", 4 * max(Sn, 0) * max(int(walls.wall_rows), 0), "segments", Sn <= 0)]
-            name, cfgs, world = "f110qp_rollout_walls_dev", cfgs + [C.byref(walls)], world + [_tp(segments)]
-            if _refresh is not None:  # the refresh config behind walls
-                name, cfgs = "f110qp_rollout_refresh_dev", cfgs + [C.byref(_refresh)]
-                if _noise is not None:  # the noise config behind rf
-                    name, cfgs = "f110qp_rollout_noisy_dev", cfgs + [C.byref(_noise)]
-                    if _grid is not None:  # (grid_cfg, grid): the config behind noise, the map behind segments
-                        more = more + [_grid_spec(*_grid)]
-                        name, cfgs, world = "f110qp_rollout_grid_dev", cfgs + [C.byref(_grid[0])], world + [_tp(_grid[1])]
-        _devs(*self._plan_specs(rp, B, *plan), (circles, "f64", 3 * Cn * WR, "circles", Cn <= 0),
-              *self._traj_specs(T, B, *traj), *self._record_specs(T, B, *rec),
-              (ranges_traj, "f32", T * B * int(sc.num_ranges), "ranges_traj", True), *more)
-        self._chk(getattr(self.lib, name)(
-            self._h, C.byref(rc), C.byref(sc), C.byref(rp), C.byref(wc), *cfgs,
-            B, *map(_tp, plan), *world, *map(_tp, traj), *map(_tp, rec), _tp(ranges_traj), *tail,
-            self._stream(stream, x_traj)), name)
+        self._world_dev("world", locals())
 
     def rollout_race_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
                          table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj, u_applied, status_traj,
@@ -1153,12 +1277,7 @@ class Solver:
         """rollout_world_dev with the cars of a race in each other's scans (f110qp_rollout_race_dev): the B cars
         are B / race.group_size races of consecutive cars; every cast reads x_traj row t as the casting poses
         and as the opponents'. circles may be None when wc.num_circles is 0."""
-        if not isinstance(race, RaceConfig):
-            raise F110QPError("race must be a RaceConfig")
-        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
-                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
-                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
-                               _race=race)
+        self._world_dev("race", locals())
 
     def rollout_contact_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig,
                             race: RaceConfig, cc: ContactConfig, table, waypoints, x_ref, have_path, circles, x_traj,
@@ -1168,12 +1287,7 @@ class Solver:
         """rollout_race_dev with every row's clearance recorded and, with cc.stop_on_contact, crashed cars parked
         (f110qp_rollout_contact_dev): clear_traj [T+1,B] f64, crash_tick [B] i32, nearest_traj [T+1,B] i32
         optional; a parked car's kind is TICK_CRASHED."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig):
-            raise F110QPError("race must be a RaceConfig and cc a ContactConfig")
-        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
-                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
-                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
-                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick))
+        self._world_dev("contact", locals())
 
     def rollout_body_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
                          cc: ContactConfig, body: BodyConfig, table, waypoints, x_ref, have_path, circles, x_traj,
@@ -1182,12 +1296,7 @@ class Solver:
                          best_traj_traj=None, best_global_traj=None, pose_traj=None, ranges_traj=None, stream=None):
         """rollout_contact_dev with rectangular car bodies in every cast and every clearance
         (f110qp_rollout_body_dev): body follows cc, everything else as there."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig):
-            raise F110QPError("race must be a RaceConfig, cc a ContactConfig and body a BodyConfig")
-        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
-                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
-                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
-                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body)
+        self._world_dev("body", locals())
 
     def rollout_walls_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
                           cc: ContactConfig, body: BodyConfig, walls: WallsConfig, table, waypoints, x_ref, have_path,
@@ -1198,14 +1307,7 @@ class Solver:
         """rollout_body_dev with straight wall segments next to the circles in every cast and every clearance
         (f110qp_rollout_walls_dev): walls follows body, segments [wall_rows,S,4] f64 (None for S = 0) follows
         circles, everything else as there."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
-                or not isinstance(walls, WallsConfig):
-            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig and walls a WallsConfig")
-        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
-                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
-                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
-                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
-                               _walls=(walls, segments))
+        self._world_dev("walls", locals())
 
     def rollout_refresh_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
                             cc: ContactConfig, body: BodyConfig, walls: WallsConfig, rf: RefreshConfig, table, waypoints,
@@ -1216,15 +1318,7 @@ class Solver:
         """rollout_walls_dev with the scan MPC holds replaced every rf.every ticks by the scan cast at that tick's
         pose (f110qp_rollout_refresh_dev): rf follows walls, everything else as there; rf.every = 0 is
         rollout_walls_dev."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
-                or not isinstance(walls, WallsConfig) or not isinstance(rf, RefreshConfig):
-            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig, walls a WallsConfig "
-                              "and rf a RefreshConfig")
-        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
-                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
-                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
-                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
-                               _walls=(walls, segments), _refresh=rf)
+        self._world_dev("refresh", locals())
 
     def rollout_noisy_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
                           cc: ContactConfig, body: BodyConfig, walls: WallsConfig, rf: RefreshConfig, noise: NoiseConfig,
@@ -1235,16 +1329,7 @@ class Solver:
         """rollout_refresh_dev with seeded range noise and dropout on every scan it casts
         (f110qp_rollout_noisy_dev): noise follows rf, everything else as there; the all-zero noise config is
         rollout_refresh_dev."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
-                or not isinstance(walls, WallsConfig) or not isinstance(rf, RefreshConfig) \
-                or not isinstance(noise, NoiseConfig):
-            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig, walls a WallsConfig, "
-                              "rf a RefreshConfig and noise a NoiseConfig")
-        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
-                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
-                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
-                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
-                               _walls=(walls, segments), _refresh=rf, _noise=noise)
+        self._world_dev("noisy", locals())
 
     def rollout_grid_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
                          cc: ContactConfig, body: BodyConfig, walls: WallsConfig, rf: RefreshConfig, noise: NoiseConfig,
@@ -1254,115 +1339,42 @@ class Solver:
                          best_traj_traj=None, best_global_traj=None, pose_traj=None, ranges_traj=None, stream=None):
         """rollout_noisy_dev on a raster map (f110qp_rollout_grid_dev): grid_cfg follows noise, grid [H,W] u8 (None
         for an empty map) follows segments, everything else as there."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
-                or not isinstance(walls, WallsConfig) or not isinstance(rf, RefreshConfig) \
-                or not isinstance(noise, NoiseConfig) or not isinstance(grid_cfg, GridConfig):
-            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig, walls a WallsConfig, "
-                              "rf a RefreshConfig, noise a NoiseConfig and grid_cfg a GridConfig")
-        self.rollout_world_dev(rc, sc, rp, wc, table, waypoints, x_ref, have_path, circles, x_traj, u_lin_traj,
-                               u_applied, status_traj, iters_traj, cost_traj, u_plan, x_plan, hs_traj, kind_traj,
-                               plan_status_traj, best_traj_traj, best_global_traj, pose_traj, ranges_traj, stream,
-                               _race=race, _contact=(cc, clear_traj, nearest_traj, crash_tick), _body=body,
-                               _walls=(walls, segments), _refresh=rf, _noise=noise, _grid=(grid_cfg, grid))
+        self._world_dev("grid", locals())
 
     def rollout_world(self, x0, u_lin, circles, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
                       wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
-                      scans=False, rc=None, _race=None, _contact=None, _body=None, _segments=None, _refresh=None,
-                      _noise=None, _grid=None):
+                      scans=False, rc=None):
         """rollout_replan() in a world of circles (f110qp_rollout_world, synchronous): circles [C,3] (one world
         for all cars) or [B,C,3] float64 replace ranges; wc defaults to f110qp_default_world_config with
         num_circles and world_rows taken from the array. scans=True adds ranges_traj [T,B,num_ranges]."""
-        T, B, x0, ul = self._host_start(x0, u_lin, ticks)
-        xr, hv, tab, wp = self._host_plan(rp, B, table, waypoints, x_ref, have_path)
-        if not isinstance(circles, np.ndarray) or circles.dtype != np.float64 or circles.ndim not in (2, 3) \
-                or circles.shape[-1] != 3:
-            raise F110QPError("circles must be a float64 numpy array [C, 3] or [B, C, 3]")
-        ci = np.ascontiguousarray(circles)
-        w = WorldConfig()
-        C.memmove(C.byref(w), C.byref(wc if wc is not None else default_world_config()), C.sizeof(w))
-        w.num_circles = ci.shape[-2]
-        w.world_rows = 1 if ci.ndim == 2 else ci.shape[0]
-        if w.world_rows not in (1, B):
-            raise F110QPError(f"circles must hold one world or B = {B} worlds, got {w.world_rows}")
-        if _race is not None:
-            _check_race(_race, B)
-        out = self._host_out(T, B, x0, ul, objective, plans, rows, int(sc.num_ranges) if scans else 0, (xr, hv))
-        name = "f110qp_rollout_world" if _race is None else "f110qp_rollout_race"
-        cfgs, tail = ([] if _race is None else [C.byref(_race)]), []
-        if _contact is not None:  # (cc, nearest): the three records behind the race rollout's arrays
-            out["clear_traj"] = np.empty((T + 1, B), np.float64)
-            if _contact[1]:
-                out["nearest_traj"] = np.empty((T + 1, B), np.int32)
-            out["crash_tick"] = np.empty(B, np.int32)
-            name, cfgs = "f110qp_rollout_contact", cfgs + [C.byref(_contact[0])]
-            tail = [_p(out["clear_traj"]), _p(out.get("nearest_traj")), _p(out["crash_tick"])]
-            if _body is not None:  # the body config behind cc
-                name, cfgs = "f110qp_rollout_body", cfgs + [C.byref(_body)]
-        world = [_p(ci) if ci.size else None]
-        if _segments is not None:  # the walls config behind body, the segments behind circles
-            if not isinstance(_segments, np.ndarray) or _segments.dtype != np.float64 or _segments.ndim not in (2, 3) \
-                    or _segments.shape[-1] != 4:
-                raise F110QPError("segments must be a float64 numpy array [S, 4] or [B, S, 4]")
-            sg = np.ascontiguousarray(_segments)
-            wl = default_walls_config(num_segments=sg.shape[-2], wall_rows=1 if sg.ndim == 2 else sg.shape[0])
-            if wl.wall_rows not in (1, B):
-                raise F110QPError(f"segments must hold one set or B = {B} sets, got {wl.wall_rows}")
-            name, cfgs, world = "f110qp_rollout_walls", cfgs + [C.byref(wl)], world + [_p(sg) if sg.size else None]
-            if _refresh is not None:  # the refresh config behind walls
-                name, cfgs = "f110qp_rollout_refresh", cfgs + [C.byref(_refresh)]
-                if _noise is not None:  # the noise config behind rf
-                    name, cfgs = "f110qp_rollout_noisy", cfgs + [C.byref(_noise)]
-                    if _grid is not None:  # (grid_cfg, grid [H,W] uint8): the config behind noise, the map behind segments
-                        gc, gm = _grid
-                        gm = np.ascontiguousarray(gm, np.uint8)
-                        if gm.shape != (int(gc.height), int(gc.width)) and gm.size:
-                            raise F110QPError(f"grid must be [height, width] = [{gc.height}, {gc.width}], got {gm.shape}")
-                        name, cfgs, world = "f110qp_rollout_grid", cfgs + [C.byref(gc)], world + [_p(gm) if gm.size else None]
-        self._chk(getattr(self.lib, name)(
-            self._h, C.byref(self._ticks_config(rc, T)), C.byref(sc), C.byref(rp), C.byref(w),
-            *cfgs, B, _p(tab), _p(wp) if wp.shape[0] else None, _p(xr), _p(hv),
-            *world, *self._out_args(out), _p(out.get("ranges_traj")), *tail), name)
-        return out
+        return self._world_host("world", locals())
 
     def rollout_race(self, x0, u_lin, circles, race: RaceConfig, sc: ScanConfig, rp: ReplanConfig, table, waypoints,
                      ticks, wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False,
                      rows=True, scans=False, rc=None):
         """rollout_world() with the cars of a race in each other's scans (f110qp_rollout_race, synchronous):
         circles [C,3] or [B,C,3] float64, C = 0 allowed (the world is then the opponents only)."""
-        if not isinstance(race, RaceConfig):
-            raise F110QPError("race must be a RaceConfig")
-        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
-                                  objective, rows, scans, rc, _race=race)
+        return self._world_host("race", locals())
 
     def rollout_contact(self, x0, u_lin, circles, race: RaceConfig, cc: ContactConfig, sc: ScanConfig, rp: ReplanConfig,
                         table, waypoints, ticks, wc: WorldConfig = None, x_ref=None, have_path=None, plans=False,
                         objective=False, rows=True, scans=False, nearest=True, rc=None):
         """rollout_race() with contact (f110qp_rollout_contact, synchronous): adds clear_traj [T+1,B], crash_tick
         [B] and, with nearest=True, nearest_traj [T+1,B]; with cc.stop_on_contact crashed cars park."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig):
-            raise F110QPError("race must be a RaceConfig and cc a ContactConfig")
-        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
-                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest))
+        return self._world_host("contact", locals())
 
     def rollout_body(self, x0, u_lin, circles, race: RaceConfig, cc: ContactConfig, body: BodyConfig, sc: ScanConfig,
                      rp: ReplanConfig, table, waypoints, ticks, wc: WorldConfig = None, x_ref=None, have_path=None,
                      plans=False, objective=False, rows=True, scans=False, nearest=True, rc=None):
         """rollout_contact() with rectangular car bodies (f110qp_rollout_body, synchronous)."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig):
-            raise F110QPError("race must be a RaceConfig, cc a ContactConfig and body a BodyConfig")
-        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
-                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body)
+        return self._world_host("body", locals())
 
     def rollout_walls(self, x0, u_lin, circles, segments, race: RaceConfig, cc: ContactConfig, body: BodyConfig,
                       sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks, wc: WorldConfig = None, x_ref=None,
                       have_path=None, plans=False, objective=False, rows=True, scans=False, nearest=True, rc=None):
         """rollout_body() with straight wall segments [S,4] or [B,S,4] float64 next to the circles
         (f110qp_rollout_walls, synchronous); circles may be an empty [0,3] array."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig):
-            raise F110QPError("race must be a RaceConfig, cc a ContactConfig and body a BodyConfig")
-        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
-                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
-                                  _segments=segments)
+        return self._world_host("walls", locals())
 
     def rollout_refresh(self, x0, u_lin, circles, segments, race: RaceConfig, cc: ContactConfig, body: BodyConfig,
                         rf: RefreshConfig, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
@@ -1370,12 +1382,7 @@ class Solver:
                         scans=False, nearest=True, rc=None):
         """rollout_walls() with the scan MPC holds replaced every rf.every ticks (f110qp_rollout_refresh,
         synchronous): rf follows body, everything else as there."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
-                or not isinstance(rf, RefreshConfig):
-            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig and rf a RefreshConfig")
-        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
-                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
-                                  _segments=segments, _refresh=rf)
+        return self._world_host("refresh", locals())
 
     def rollout_noisy(self, x0, u_lin, circles, segments, race: RaceConfig, cc: ContactConfig, body: BodyConfig,
                       rf: RefreshConfig, noise: NoiseConfig, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
@@ -1383,13 +1390,7 @@ class Solver:
                       scans=False, nearest=True, rc=None):
         """rollout_refresh() with seeded range noise and dropout on every scan (f110qp_rollout_noisy,
         synchronous): noise follows rf, everything else as there."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
-                or not isinstance(rf, RefreshConfig) or not isinstance(noise, NoiseConfig):
-            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig, rf a RefreshConfig "
-                              "and noise a NoiseConfig")
-        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
-                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
-                                  _segments=segments, _refresh=rf, _noise=noise)
+        return self._world_host("noisy", locals())
 
     def rollout_grid(self, x0, u_lin, circles, segments, grid, grid_cfg: GridConfig, race: RaceConfig, cc: ContactConfig,
                      body: BodyConfig, rf: RefreshConfig, noise: NoiseConfig, sc: ScanConfig, rp: ReplanConfig, table,
@@ -1397,14 +1398,7 @@ class Solver:
                      rows=True, scans=False, nearest=True, rc=None):
         """rollout_noisy() on a raster map (f110qp_rollout_grid, synchronous): grid [H,W] uint8 (nonzero occupied)
         and grid_cfg follow segments, everything else as there."""
-        if not isinstance(race, RaceConfig) or not isinstance(cc, ContactConfig) or not isinstance(body, BodyConfig) \
-                or not isinstance(rf, RefreshConfig) or not isinstance(noise, NoiseConfig) \
-                or not isinstance(grid_cfg, GridConfig):
-            raise F110QPError("race must be a RaceConfig, cc a ContactConfig, body a BodyConfig, rf a RefreshConfig, "
-                              "noise a NoiseConfig and grid_cfg a GridConfig")
-        return self.rollout_world(x0, u_lin, circles, sc, rp, table, waypoints, ticks, wc, x_ref, have_path, plans,
-                                  objective, rows, scans, rc, _race=race, _contact=(cc, nearest), _body=body,
-                                  _segments=segments, _refresh=rf, _noise=noise, _grid=(grid_cfg, grid))
+        return self._world_host("grid", locals())
 
     def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
         """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
@@ -1625,111 +1619,83 @@ def plan_listed_dev(rp: ReplanConfig, sc: ScanConfig, list_, count, pose, ranges
                                          _tp(best_global), C.c_void_p(stream.cuda_stream)), "f110qp_plan_listed_dev")
 
 
-_NO = object()  # in place of a config that the family of a cast or a clearance does not take
-
-
-def _wall_spec(walls, segments):
-    if not isinstance(walls, WallsConfig):
-        raise F110QPError("walls must be a WallsConfig")
-    Sn = int(walls.num_segments)
-    return (segments, "f64", 4 * max(Sn, 0) * max(int(walls.wall_rows), 0), "segments", Sn <= 0)
-
-
-def _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race=_NO, body=_NO, walls=_NO, segments=None,
-                noise=_NO, tick=0, grid_cfg=_NO, grid=None):
-    """The body of the six cast_scans*_dev."""
+def _cast_scans(family, a):
+    """The body of the six cast_scans*_dev; a: the wrapper's arguments by name."""
     import torch
 
-    if body is not _NO and not isinstance(body, BodyConfig):
-        raise F110QPError("body must be a BodyConfig")
-    B, Cn, WR = int(x.shape[0]), int(wc.num_circles), int(wc.world_rows)
-    if race is not _NO:
-        _check_race(race, B)
-    _devs((x, "f64", 3 * B, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
-          *([_wall_spec(walls, segments)] if walls is not _NO else []),
-          *([_grid_spec(grid_cfg, grid)] if grid_cfg is not _NO else []),
-          (ranges, "f32", B * int(sc.num_ranges), "ranges"), (list_, "i32", B, "list", True),
-          (count, "i32", 1, "count", True))
-    if stream is None:
-        stream = torch.cuda.current_stream(x.device)
-    if noise is not _NO and not isinstance(noise, NoiseConfig):
-        raise F110QPError("noise must be a NoiseConfig")
-    family = "_grid" if grid_cfg is not _NO else "_noisy" if noise is not _NO else "_walls" if walls is not _NO else "_body" if body is not _NO \
-        else "_race" if race is not _NO else ""
-    name = f"f110qp_cast_scans{family}_dev"
-    cfgs = [C.byref(k) for k in (sc, wc, race, body, walls, noise, grid_cfg) if k is not _NO]
-    segs = ([_tp(segments)] if walls is not _NO else []) + ([_tp(grid)] if grid_cfg is not _NO else [])
-    ticks = [int(tick)] if noise is not _NO else []  # rule Z3's t follows batch
-    _check(getattr(load(), name)(*cfgs, B, *ticks, _tp(list_), _tp(count), _tp(x), _tp(circles), *segs, _tp(ranges),
-                                 C.c_void_p(stream.cuda_stream)), name)
+    fams = _families(family, "cast")
+    _check_cfgs(fams[2:], a, whole=False)  # sc, wc and race are read, not type-checked
+    x = a["x"]
+    B = int(x.shape[0])
+    if fams[1:]:
+        _check_race(a["race"], B)
+    _devs((x, "f64", 3 * B, "x"), *_world_specs(fams, a), (a["ranges"], "f32", B * int(a["sc"].num_ranges), "ranges"),
+          (a["list_"], "i32", B, "list", True), (a["count"], "i32", 1, "count", True))
+    stream = a["stream"] if a["stream"] is not None else torch.cuda.current_stream(x.device)
+    name = fams[-1].cast
+    call = {**a, "batch": B, "stream": C.c_void_p(stream.cuda_stream)}
+    _check(getattr(load(), name)(*_abi_args(_abi("cast", family), call)), name)
 
 
-def _clearance(wc, race, x, circles, clearance, nearest, stream, body=_NO, walls=_NO, segments=None, grid_cfg=_NO,
-               grid=None):
-    """The body of the four clearance*_dev."""
+def _clearance(family, a):
+    """The body of the four clearance*_dev; a: the wrapper's arguments by name."""
     import torch
 
-    if body is not _NO and not isinstance(body, BodyConfig):
-        raise F110QPError("body must be a BodyConfig")
+    fams = _families(family, "clearance")
+    _check_cfgs(fams[2:], a, whole=False)  # wc and race are read, not type-checked
+    x = a["x"]
     if x.dim() not in (2, 3) or x.shape[-1] != 3:
         raise F110QPError(f"x must be [rows, B, 3] or [B, 3], got {tuple(x.shape)}")
     rows, B = (1, int(x.shape[0])) if x.dim() == 2 else (int(x.shape[0]), int(x.shape[1]))
     if rows < 1:
         raise F110QPError("x must hold at least one row")
-    Cn, WR = int(wc.num_circles), int(wc.world_rows)
-    _check_race(race, B)
-    _devs((x, "f64", 3 * B * rows, "x"), (circles, "f64", 3 * max(Cn, 0) * max(WR, 0), "circles", Cn <= 0),
-          *([_wall_spec(walls, segments)] if walls is not _NO else []),
-          *([_grid_spec(grid_cfg, grid)] if grid_cfg is not _NO else []),
-          (clearance, "f64", B * rows, "clearance"), (nearest, "i32", B * rows, "nearest", True))
-    if stream is None:
-        stream = torch.cuda.current_stream(x.device)
-    family = "_grid" if grid_cfg is not _NO else "_walls" if walls is not _NO else "_body" if body is not _NO else ""
-    name = f"f110qp_clearance{family}_dev"
-    cfgs = [C.byref(k) for k in (wc, race, body, walls, grid_cfg) if k is not _NO]
-    segs = ([_tp(segments)] if walls is not _NO else []) + ([_tp(grid)] if grid_cfg is not _NO else [])
-    _check(getattr(load(), name)(*cfgs, B, rows, _tp(x), _tp(circles), *segs, _tp(clearance), _tp(nearest),
-                                 C.c_void_p(stream.cuda_stream)), name)
+    _check_race(a["race"], B)
+    _devs((x, "f64", 3 * B * rows, "x"), *_world_specs(fams, a), (a["clearance"], "f64", B * rows, "clearance"),
+          (a["nearest"], "i32", B * rows, "nearest", True))
+    stream = a["stream"] if a["stream"] is not None else torch.cuda.current_stream(x.device)
+    name = fams[-1].clearance
+    call = {**a, "batch": B, "rows": rows, "stream": C.c_void_p(stream.cuda_stream)}
+    _check(getattr(load(), name)(*_abi_args(_abi("clearance", family), call)), name)
 
 
 def cast_scans_dev(sc: ScanConfig, wc: WorldConfig, x, circles, ranges, list_=None, count=None, stream=None):
     """The simulated LiDAR (f110qp_cast_scans_dev): x [B,3] f64, circles [world_rows,C,3] f64 (None for
     C = 0) -> ranges [B,num_ranges] f32, for all B cars or, with list_ [B] i32 and count [1] i32 on the
     device, for the listed ones."""
-    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream)
+    _cast_scans("world", locals())
 
 
 def cast_scans_race_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, x, circles, ranges, list_=None, count=None,
                         stream=None):
     """cast_scans_dev with the race-mates in every scan (f110qp_cast_scans_race_dev): the B cars are
     B / race.group_size races of consecutive cars, x [B,3] f64 is both the casting poses and the opponents'."""
-    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race)
+    _cast_scans("race", locals())
 
 
 def clearance_dev(wc: WorldConfig, race: RaceConfig, x, circles, clearance, nearest=None, stream=None):
     """Every car's clearance to its world's circles and its race-mates (f110qp_clearance_dev): x [rows,B,3] f64
     (or [B,3]: one row), circles [world_rows,C,3] f64 (None for C = 0) -> clearance [rows,B] f64 and, optionally,
     nearest [rows,B] i32."""
-    _clearance(wc, race, x, circles, clearance, nearest, stream)
+    _clearance("race", locals())
 
 
 def cast_scans_body_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, x, circles, ranges,
                         list_=None, count=None, stream=None):
     """cast_scans_race_dev with every race-mate a rectangle (f110qp_cast_scans_body_dev)."""
-    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race, body)
+    _cast_scans("body", locals())
 
 
 def clearance_body_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, x, circles, clearance, nearest=None,
                        stream=None):
     """clearance_dev with the car and its race-mates rectangles (f110qp_clearance_body_dev)."""
-    _clearance(wc, race, x, circles, clearance, nearest, stream, body)
+    _clearance("body", locals())
 
 
 def cast_scans_walls_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, x,
                          circles, segments, ranges, list_=None, count=None, stream=None):
     """cast_scans_body_dev with straight wall segments in every scan (f110qp_cast_scans_walls_dev): segments
     [wall_rows,S,4] f64 = (ax, ay, bx, by), None for S = 0."""
-    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race, body, walls, segments)
+    _cast_scans("walls", locals())
 
 
 def cast_scans_noisy_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig,
@@ -1737,7 +1703,7 @@ def cast_scans_noisy_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body
     """cast_scans_walls_dev with seeded range noise and dropout on every beam (f110qp_cast_scans_noisy_dev, rules
     Z1 and Z2 of f110qp.h): noise follows walls, tick (the t of rule Z1's draw) follows it. The oracle is
     workload.noisy_scan on cast_scans_walls_dev's output."""
-    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race, body, walls, segments, noise, tick)
+    _cast_scans("noisy", locals())
 
 
 def cast_scans_grid_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig,
@@ -1746,22 +1712,21 @@ def cast_scans_grid_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body:
     """cast_scans_noisy_dev with a raster map under every beam (f110qp_cast_scans_grid_dev, rule G1 of f110qp.h):
     grid_cfg follows noise, grid [H,W] u8 (nonzero occupied, None for an empty map) follows segments. The oracle is
     workload.ray_map folded into the noise-free scan, then workload.noisy_scan."""
-    _cast_scans(sc, wc, x, circles, ranges, list_, count, stream, race, body, walls, segments, noise, tick, grid_cfg,
-                grid)
+    _cast_scans("grid", locals())
 
 
 def clearance_grid_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, grid_cfg: GridConfig, x,
                        circles, segments, grid, clearance, nearest=None, stream=None):
     """clearance_walls_dev with the occupied cells of a raster map behind the segments (f110qp_clearance_grid_dev,
     rule G2): cell (i, j) has index C + G + S + j W + i in nearest. The oracle is workload.clearance_grid."""
-    _clearance(wc, race, x, circles, clearance, nearest, stream, body, walls, segments, grid_cfg, grid)
+    _clearance("grid", locals())
 
 
 def clearance_walls_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, x, circles, segments,
                         clearance, nearest=None, stream=None):
     """clearance_body_dev with straight wall segments behind the circles and the mates
     (f110qp_clearance_walls_dev): segment k has index C + G + k in nearest."""
-    _clearance(wc, race, x, circles, clearance, nearest, stream, body, walls, segments)
+    _clearance("walls", locals())
 
 
 def _rows_of(x, last, name):

@@ -12,11 +12,12 @@ from test_gpu_grid import SEED, grid_cast, grid_clearance
 from test_gpu_rollout import same_bits, solver
 from test_gpu_rollout_contact import check_parked
 from test_gpu_rollout_noisy import rollout_noisy_dev
-from test_gpu_rollout_replan import P, dev, full, replan_buffers
+from test_gpu_rollout_replan import P
 from test_gpu_rollout_scan import scan_config
 from test_gpu_rollout_walls import B, G, N
 from test_gpu_rollout_walls import scene as walls_scene
 from test_gpu_rollout_world import GEOM, R
+from world_loop import rollout_dev
 
 from f110qp import workload
 
@@ -52,31 +53,7 @@ def scene():
 
 def rollout_grid_dev(capi, cuda, s, case, grid, cfg, stop, noise, ticks=T, null=(), every=1):
     """One Solver.rollout_grid_dev call on fresh device arrays -> every array as numpy."""
-    import torch
-
-    x0, ul, circles, sg, wp = case
-    nb = x0.shape[0]
-    d = replan_buffers(cuda, x0, ul, nb, s.horizon, ticks)
-    d["ranges_traj"] = full(cuda, (ticks, nb, R), torch.float32, -7.0)
-    d["clear_traj"] = full(cuda, (ticks + 1, nb), torch.float64, -7.0)
-    d["nearest_traj"] = full(cuda, (ticks + 1, nb), torch.int32, -7)
-    d["crash_tick"] = full(cuda, (nb,), torch.int32, -7)
-    for k in null:
-        del d[k]
-    rp = capi.default_replan_config(num_waypoints=wp.shape[0])
-    s.rollout_grid_dev(capi.default_rollout_config(ticks=ticks), scan_config(capi, R, GEOM), rp,
-                       capi.default_world_config(num_circles=circles.shape[-2]),
-                       capi.default_race_config(group_size=G), capi.default_contact_config(stop_on_contact=stop),
-                       capi.default_body_config(), capi.default_walls_config(num_segments=sg.shape[0]),
-                       capi.default_refresh_config(every=every), noise, capi.grid_config_of(cfg),
-                       dev(cuda, capi.traj_table(rp.plan)), dev(cuda, wp), d["x_ref"], d["have_path"], dev(cuda, circles),
-                       dev(cuda, sg), dev(cuda, grid) if grid.size else None, d["x_traj"], d["u_lin_traj"],
-                       d["u_applied"], d["status"], d["clear_traj"], d["crash_tick"], d.get("nearest_traj"),
-                       d.get("iters"), d.get("cost"), d.get("u_plan"), d.get("x_plan"), d.get("hs_traj"), d.get("kind"),
-                       d.get("plan_status"), d.get("best_traj"), d.get("best_global"), d.get("pose_traj"),
-                       d.get("ranges_traj"))
-    torch.cuda.synchronize(cuda)
-    return {k: v.cpu().numpy() for k, v in d.items()}
+    return rollout_dev(capi, cuda, s, "grid", case, ticks, G, stop, every=every, noise=noise, grid=grid, cfg=cfg, null=null)
 
 
 def noise_of(capi, car_base=0, setting=NOISE):

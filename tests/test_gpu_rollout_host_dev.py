@@ -22,6 +22,7 @@ from test_gpu_rollout_race import race_case
 from test_gpu_rollout_replan import P
 from test_gpu_rollout_scan import scan_config
 from test_gpu_rollout_world import GEOM, ON_MPC, ON_PLAN, R, world_case
+from world_loop import call_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -106,17 +107,14 @@ def _run(capi, cuda, s, family, variant, on):
         else:
             wc = capi.default_world_config(num_circles=circles.shape[-2],
                                            world_rows=1 if circles.ndim == 2 else circles.shape[0])
-            head = (rc, sc, rp, wc)
+            race = capi.default_race_config(group_size=variant)
             if family == "race":
-                race = capi.default_race_config(group_size=variant)
                 host = s.rollout_race(x0, ul, circles, race, sc, rp, table, wp, T, **opt)
-                call, head = s.rollout_race_dev, head + (race,)
             else:
                 host = s.rollout_world(x0, ul, circles, sc, rp, table, wp, T, **opt)
-                call = s.rollout_world_dev
             d = _device_twin(cuda, host, x0, ul)
-            call(*head, dev(table), dev(wp), d["x_ref"], d["have_path"], dev(circles), *common(d), *tail(d),
-                 d.get("ranges_traj"))
+            call_dev(capi, s, family, dict(rc=rc, sc=sc, rp=rp, wc=wc, race=race), {"circles": dev(circles)}, dev(table),
+                     dev(wp), d)
     torch.cuda.synchronize(cuda)
     return host, d
 

@@ -13,11 +13,12 @@ from test_gpu_rollout import same_bits, solver
 from test_gpu_rollout_contact import check_parked
 from test_gpu_rollout_refresh import closing_scene, rollout_refresh_dev, same_run
 from test_gpu_rollout_refresh import run as refresh_run
-from test_gpu_rollout_replan import P, dev, full, replan_buffers
+from test_gpu_rollout_replan import P
 from test_gpu_rollout_scan import scan_config, split_rows
 from test_gpu_rollout_walls import B, G, N, T, scene
 from test_gpu_rollout_world import GEOM, R
 from test_gpu_walls import wall_cast
+from world_loop import rollout_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -27,30 +28,7 @@ NOISE = (0.05, 0.01, 0.02)
 
 def rollout_noisy_dev(capi, cuda, s, case, stop, every, noise, ticks=T, null=(), group=G):
     """One Solver.rollout_noisy_dev call on fresh device arrays -> every array as numpy."""
-    import torch
-
-    x0, ul, circles, sg, wp = case
-    nb = x0.shape[0]
-    d = replan_buffers(cuda, x0, ul, nb, s.horizon, ticks)
-    d["ranges_traj"] = full(cuda, (ticks, nb, R), torch.float32, -7.0)
-    d["clear_traj"] = full(cuda, (ticks + 1, nb), torch.float64, -7.0)
-    d["nearest_traj"] = full(cuda, (ticks + 1, nb), torch.int32, -7)
-    d["crash_tick"] = full(cuda, (nb,), torch.int32, -7)
-    for k in null:
-        del d[k]
-    rp = capi.default_replan_config(num_waypoints=wp.shape[0])
-    s.rollout_noisy_dev(capi.default_rollout_config(ticks=ticks), scan_config(capi, R, GEOM), rp,
-                        capi.default_world_config(num_circles=circles.shape[-2]),
-                        capi.default_race_config(group_size=group), capi.default_contact_config(stop_on_contact=stop),
-                        capi.default_body_config(), capi.default_walls_config(num_segments=sg.shape[0]),
-                        capi.default_refresh_config(every=every), noise, dev(cuda, capi.traj_table(rp.plan)),
-                        dev(cuda, wp), d["x_ref"], d["have_path"], dev(cuda, circles), dev(cuda, sg), d["x_traj"],
-                        d["u_lin_traj"], d["u_applied"], d["status"], d["clear_traj"], d["crash_tick"],
-                        d.get("nearest_traj"), d.get("iters"), d.get("cost"), d.get("u_plan"), d.get("x_plan"),
-                        d.get("hs_traj"), d.get("kind"), d.get("plan_status"), d.get("best_traj"), d.get("best_global"),
-                        d.get("pose_traj"), d.get("ranges_traj"))
-    torch.cuda.synchronize(cuda)
-    return {k: v.cpu().numpy() for k, v in d.items()}
+    return rollout_dev(capi, cuda, s, "noisy", case, ticks, group, stop, every=every, noise=noise, null=null)
 
 
 def noise_of(capi, setting=NOISE, seed=SEED, car_base=0):

@@ -16,6 +16,7 @@ from test_gpu_rollout import same_bits, solver
 from test_gpu_rollout_replan import P, dev, full, replan_buffers
 from test_gpu_rollout_scan import scan_config
 from test_gpu_rollout_world import GEOM, R, compare, rollout_world_dev, world_case
+from world_loop import rollout_dev
 
 from f110qp import workload
 
@@ -36,24 +37,8 @@ def configs(capi, circles, G):
 
 def rollout_race_dev(capi, cuda, s, case, G, T, scans=True, hs=True):
     """One Solver.rollout_race_dev call on fresh device arrays -> every array as numpy."""
-    import torch
-
-    x0, ul, circles, wp = case
-    B, N = x0.shape[0], s.horizon
-    d = replan_buffers(cuda, x0, ul, B, N, T)
-    if not hs:
-        del d["hs_traj"]
-    if scans:
-        d["ranges_traj"] = full(cuda, (T, B, R), torch.float32, -7.0)
-    rp = capi.default_replan_config(num_waypoints=wp.shape[0])
-    wc, race = configs(capi, circles, G)
-    s.rollout_race_dev(capi.default_rollout_config(ticks=T), scan_config(capi, R, GEOM, scan_rows=7), rp, wc, race,
-                       dev(cuda, capi.traj_table(rp.plan)), dev(cuda, wp), d["x_ref"], d["have_path"],
-                       None if circles is None else dev(cuda, circles), d["x_traj"], d["u_lin_traj"], d["u_applied"],
-                       d["status"], d["iters"], d["cost"], d["u_plan"], d["x_plan"], d.get("hs_traj"), d["kind"],
-                       d["plan_status"], d["best_traj"], d["best_global"], d["pose_traj"], d.get("ranges_traj"))
-    torch.cuda.synchronize(cuda)
-    return {k: v.cpu().numpy() for k, v in d.items()}
+    null = (() if hs else ("hs_traj",)) + (() if scans else ("ranges_traj",))
+    return rollout_dev(capi, cuda, s, "race", case, T, group=G, null=null, scan_rows=7)
 
 
 def manual_race_loop(capi, cuda, s, case, G, T, scans, hs):

@@ -10,10 +10,11 @@ import walls_cases as wl_
 from test_gpu_rollout import same_bits, solver
 from test_gpu_rollout_body import rollout_body_dev
 from test_gpu_rollout_contact import check_parked, check_races_before_a_crash, first_row
-from test_gpu_rollout_replan import P, dev, full, replan_buffers
+from test_gpu_rollout_replan import P
 from test_gpu_rollout_scan import scan_config
 from test_gpu_rollout_world import GEOM, R
 from test_gpu_walls import bits, clearance, wall_cast
+from world_loop import rollout_dev
 
 from f110qp import workload
 
@@ -40,30 +41,7 @@ def scene(ahead=AHEAD):
 
 def rollout_walls_dev(capi, cuda, s, case, stop, ticks=T, null=(), segments=True):
     """One Solver.rollout_walls_dev call on fresh device arrays -> every array as numpy."""
-    import torch
-
-    x0, ul, circles, sg, wp = case
-    nb = x0.shape[0]
-    d = replan_buffers(cuda, x0, ul, nb, s.horizon, ticks)
-    d["ranges_traj"] = full(cuda, (ticks, nb, R), torch.float32, -7.0)
-    d["clear_traj"] = full(cuda, (ticks + 1, nb), torch.float64, -7.0)
-    d["nearest_traj"] = full(cuda, (ticks + 1, nb), torch.int32, -7)
-    d["crash_tick"] = full(cuda, (nb,), torch.int32, -7)
-    for k in null:
-        del d[k]
-    rp = capi.default_replan_config(num_waypoints=wp.shape[0])
-    wc = capi.default_world_config(num_circles=circles.shape[-2])
-    wl = capi.default_walls_config(num_segments=sg.shape[0] if segments else 0)
-    s.rollout_walls_dev(capi.default_rollout_config(ticks=ticks), scan_config(capi, R, GEOM), rp, wc,
-                        capi.default_race_config(group_size=G), capi.default_contact_config(stop_on_contact=stop),
-                        capi.default_body_config(), wl, dev(cuda, capi.traj_table(rp.plan)), dev(cuda, wp), d["x_ref"],
-                        d["have_path"], dev(cuda, circles), dev(cuda, sg) if segments else None, d["x_traj"],
-                        d["u_lin_traj"], d["u_applied"], d["status"], d["clear_traj"], d["crash_tick"],
-                        d.get("nearest_traj"), d.get("iters"), d.get("cost"), d.get("u_plan"), d.get("x_plan"),
-                        d.get("hs_traj"), d.get("kind"), d.get("plan_status"), d.get("best_traj"), d.get("best_global"),
-                        d.get("pose_traj"), d.get("ranges_traj"))
-    torch.cuda.synchronize(cuda)
-    return {k: v.cpu().numpy() for k, v in d.items()}
+    return rollout_dev(capi, cuda, s, "walls", case, ticks, G, stop, null=null, segments=segments)
 
 
 _RUNS = {}

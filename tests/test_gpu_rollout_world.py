@@ -13,13 +13,12 @@ import world_cases as wc_
 from test_gpu_rollout import same_bits, solver
 from test_gpu_rollout_replan import P, dev, full, replan_buffers
 from test_gpu_rollout_scan import scan_config
+from world_loop import GEOM, R, rollout_dev
 
 from f110qp import workload
 
 pytestmark = pytest.mark.gpu
 
-R = 1080
-GEOM = wc_.geometry(R)
 OUT = ("x_traj", "u_lin_traj", "u_applied", "status", "kind", "x_ref", "have_path", "pose_traj")
 ON_MPC = ("iters", "cost", "u_plan", "x_plan")
 ON_PLAN = ("plan_status", "best_traj", "best_global")
@@ -41,27 +40,8 @@ def world_config(capi, circles):
 
 def rollout_world_dev(capi, cuda, s, case, T, scans=True, hs=True, start=None):
     """One Solver.rollout_world_dev call on fresh device arrays -> every array as numpy."""
-    import torch
-
-    x0, ul, circles, wp = case
-    B, N = x0.shape[0], s.horizon
-    if start is not None:
-        x0, ul = start["x_traj"][-1], start["u_lin_traj"][-1]
-    d = replan_buffers(cuda, x0, ul, B, N, T)
-    if start is not None:
-        d["x_ref"], d["have_path"] = dev(cuda, start["x_ref"]), dev(cuda, start["have_path"])
-    if not hs:
-        del d["hs_traj"]
-    if scans:
-        d["ranges_traj"] = full(cuda, (T, B, R), torch.float32, -7.0)
-    rp = capi.default_replan_config(num_waypoints=wp.shape[0])
-    s.rollout_world_dev(capi.default_rollout_config(ticks=T), scan_config(capi, R, GEOM, scan_rows=7), rp,
-                        world_config(capi, circles), dev(cuda, capi.traj_table(rp.plan)), dev(cuda, wp), d["x_ref"],
-                        d["have_path"], dev(cuda, circles), d["x_traj"], d["u_lin_traj"], d["u_applied"], d["status"],
-                        d["iters"], d["cost"], d["u_plan"], d["x_plan"], d.get("hs_traj"), d["kind"], d["plan_status"],
-                        d["best_traj"], d["best_global"], d["pose_traj"], d.get("ranges_traj"))
-    torch.cuda.synchronize(cuda)
-    return {k: v.cpu().numpy() for k, v in d.items()}
+    null = (() if hs else ("hs_traj",)) + (() if scans else ("ranges_traj",))
+    return rollout_dev(capi, cuda, s, "world", case, T, null=null, start=start, scan_rows=7)
 
 
 def manual_world_loop(capi, cuda, s, case, T, scans, hs):
