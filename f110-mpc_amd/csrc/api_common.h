@@ -1,10 +1,11 @@
 // api_common.h — what the C ABI's translation units share: f110qp_api.cpp (the context, the solve
 // entry points), api_rollout.cpp (the closed loops), api_plan.cpp (half-spaces, planning stage),
-// api_standings.cpp (race standings) and api_mc.cpp (Monte Carlo outcomes).
+// api_standings.cpp (race standings), api_mc.cpp (Monte Carlo outcomes) and api_field.cpp (the map's distance field).
 // Everything here is internal to the library (hidden visibility: no new exported symbol).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 
@@ -132,6 +133,32 @@ static inline int check_scan_config(const f110qp_scan_config* sc, bool rows, int
   if (!(sc->angle_increment > 0.f)) return fail(F110QP_ERR_INVALID, "angle_increment must be > 0");
   if (rows && sc->scan_rows != 1 && sc->scan_rows != ticks)
     return fail(F110QP_ERR_INVALID, "scan_rows must be 1 or ticks");
+  return F110QP_OK;
+}
+
+// The raster map of f110qp_cast_scans_grid_dev, f110qp_clearance_grid_dev and f110qp_rollout_grid[_dev]
+// (api_rollout.cpp) and of the distance-field calls (api_field.cpp), checked, into *Gr. obstacles:
+// num_circles + group_size + num_segments, which wall_params has checked to fit an int (0 for the field).
+static inline int grid_params(const f110qp_grid_config* gc, long long obstacles, const void* grid,
+                              f110qp::GridParams* Gr) {
+  if (!gc) return fail(F110QP_ERR_INVALID, "grid config is NULL");
+  if (gc->width < 0 || gc->height < 0) return fail(F110QP_ERR_INVALID, "grid width and height must be >= 0");
+  const long long cells = (long long)gc->width * gc->height;
+  if (cells > 0 && !grid) return fail(F110QP_ERR_INVALID, "width * height > 0 needs the grid");
+  if (!(gc->resolution > 0.0) || !std::isfinite(gc->resolution))
+    return fail(F110QP_ERR_INVALID, "grid resolution must be positive and finite");
+  if (!(gc->reach >= 0.0) || !std::isfinite(gc->reach))
+    return fail(F110QP_ERR_INVALID, "grid reach must be >= 0 and finite");
+  if (!std::isfinite(gc->origin_x) || !std::isfinite(gc->origin_y))
+    return fail(F110QP_ERR_INVALID, "grid origin must be finite");
+  if (obstacles + cells > 0x7fffffffll)
+    return fail(F110QP_ERR_INVALID, "num_circles + group_size + num_segments + width * height does not fit an int");
+  Gr->W = gc->width;
+  Gr->H = gc->height;
+  Gr->ox = gc->origin_x;
+  Gr->oy = gc->origin_y;
+  Gr->res = gc->resolution;
+  Gr->reach = gc->reach;
   return F110QP_OK;
 }
 

@@ -162,30 +162,6 @@ static int noise_params(const f110qp_noise_config* noise, int batch, f110qp::Noi
   return F110QP_OK;
 }
 
-// The raster map of f110qp_cast_scans_grid_dev, f110qp_clearance_grid_dev and f110qp_rollout_grid[_dev], checked,
-// into *Gr. obstacles: num_circles + group_size + num_segments, which wall_params has checked to fit an int.
-static int grid_params(const f110qp_grid_config* gc, long long obstacles, const void* grid, f110qp::GridParams* Gr) {
-  if (!gc) return fail(F110QP_ERR_INVALID, "grid config is NULL");
-  if (gc->width < 0 || gc->height < 0) return fail(F110QP_ERR_INVALID, "grid width and height must be >= 0");
-  const long long cells = (long long)gc->width * gc->height;
-  if (cells > 0 && !grid) return fail(F110QP_ERR_INVALID, "width * height > 0 needs the grid");
-  if (!(gc->resolution > 0.0) || !std::isfinite(gc->resolution))
-    return fail(F110QP_ERR_INVALID, "grid resolution must be positive and finite");
-  if (!(gc->reach >= 0.0) || !std::isfinite(gc->reach))
-    return fail(F110QP_ERR_INVALID, "grid reach must be >= 0 and finite");
-  if (!std::isfinite(gc->origin_x) || !std::isfinite(gc->origin_y))
-    return fail(F110QP_ERR_INVALID, "grid origin must be finite");
-  if (obstacles + cells > 0x7fffffffll)
-    return fail(F110QP_ERR_INVALID, "num_circles + group_size + num_segments + width * height does not fit an int");
-  Gr->W = gc->width;
-  Gr->H = gc->height;
-  Gr->ox = gc->origin_x;
-  Gr->oy = gc->origin_y;
-  Gr->res = gc->resolution;
-  Gr->reach = gc->reach;
-  return F110QP_OK;
-}
-
 // The scan geometry of the re-planning kernels' argument records (ReplanStart, ReplanStep).
 template <typename S>
 static void scan_geometry(S* s, const f110qp_scan_config& sc) {

@@ -535,4 +535,20 @@ hipError_t launch_mc_outcomes(int B, int T, const double* clear, const int* stat
                               double* min_clear, int* min_row, int* unsolved, int* first_unsolved, int* plan_failed,
                               hipStream_t stream);
 
+// ---- the raster map's distance field (field_kernels.hip) ---------------------------------------------
+// Rules D1 and D2 of include/f110qp.h for grid [H][W], W and H in 1..32,768: d2 [H][W], nearest [H][W] or null,
+// work [H][W] of scratch. Two launches on the stream (the rows: a wave per row, at most field_rows_grid(H)
+// workgroups striding; the columns: one thread per cell), nothing between them but the stream's order.
+int field_rows_grid(int H);
+hipError_t launch_grid_distance(int W, int H, const unsigned char* grid, int* d2, int* nearest, int* work,
+                                hipStream_t stream);
+// out [H][W] = rule D3's metres of d2 <= radius: one launch, one thread per cell.
+hipError_t launch_grid_inflate(int W, int H, double res, const int* d2, double radius, unsigned char* out,
+                               hipStream_t stream);
+// Rule D4 at rows x B poses x [rows][B][3]: dist [rows][B], cell [rows][B] or null (nearest is read only with
+// it). One launch of at most field_lookup_grid(rows x B) workgroups, which stride. G.reach is not read.
+int field_lookup_grid(long long n);
+hipError_t launch_grid_lookup(const GridParams& G, const int* d2, const int* nearest, int B, int rows,
+                              const double* x, double* dist, int* cell, hipStream_t stream);
+
 }  // namespace f110qp

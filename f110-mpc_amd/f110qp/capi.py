@@ -168,7 +168,13 @@ EXPORTED = (
     "f110qp_mc_survival_dev",
     "f110qp_mc_outcomes_dev",
     "f110qp_mc_summary",
+    "f110qp_grid_distance_dev",
+    "f110qp_grid_inflate_dev",
+    "f110qp_grid_lookup_dev",
+    "f110qp_grid_field",
+    "f110qp_wall_distance",
 )
+FIELD_MAX_SIDE = 32768  # F110QP_FIELD_MAX_SIDE
 MC_MAX_HYPOTHESES = 4096  # F110QP_MC_MAX_HYPOTHESES
 MC_MAX_PROBS = 8          # F110QP_MC_MAX_PROBS
 CAST_CIRCLE_TILE = 256  # F110QP_CAST_CIRCLE_TILE: circles per LDS tile of the ray-cast kernel
@@ -472,6 +478,12 @@ def load(test: bool = False):
     L.f110qp_mc_survival_dev.argtypes = [mcp, C.c_int, C.c_int] + [fp] * 4
     L.f110qp_mc_outcomes_dev.argtypes = [C.c_int, C.c_int] + [fp] * 9
     L.f110qp_mc_summary.argtypes = [mcp, C.c_int, C.c_int] + [fp] * 13
+    gcp = C.POINTER(GridConfig)
+    L.f110qp_grid_distance_dev.argtypes = [gcp] + [fp] * 5
+    L.f110qp_grid_inflate_dev.argtypes = [gcp, fp, C.c_double, fp, fp]
+    L.f110qp_grid_lookup_dev.argtypes = [gcp, fp, fp, C.c_int, C.c_int] + [fp] * 4
+    L.f110qp_grid_field.argtypes = [gcp, fp, C.c_double] + [fp] * 3
+    L.f110qp_wall_distance.argtypes = [gcp, fp, C.c_int, C.c_int] + [fp] * 3
     L.f110qp_select_dev.argtypes = [C.c_int, fp, C.c_int, fp, fp, fp, fp, fp]
     L.f110qp_backend_info.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
     L.f110qp_lane_segments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -1913,6 +1925,95 @@ def mc_summary(mc: McConfig, clear_traj, crash_tick, status_traj=None, kind_traj
                                     _p(o["min_row"]), _p(o["unsolved"]), _p(o["first_unsolved"]), _p(o["plan_failed"])),
            "f110qp_mc_summary")
     return o
+
+
+def _field_cells(grid_cfg):
+    """W, H and W * H of a map for the distance-field calls (the C call checks the rest of the config)."""
+    if not isinstance(grid_cfg, GridConfig):
+        raise F110QPError("grid_cfg must be a GridConfig")
+    W, H = int(grid_cfg.width), int(grid_cfg.height)
+    if not (0 <= W <= FIELD_MAX_SIDE and 0 <= H <= FIELD_MAX_SIDE):
+        raise F110QPError(f"grid width and height must be in 0..{FIELD_MAX_SIDE}, got {W} x {H}")
+    return W, H, W * H
+
+
+def grid_distance_dev(grid_cfg: GridConfig, grid, d2, work, nearest=None, stream=None):
+    """The map's exact distance transform (f110qp_grid_distance_dev): grid [H,W] u8 -> d2 [H,W] i32 (squared cell
+    distance to the nearest occupied cell, INT_MAX on a map without one) and, optionally, nearest [H,W] i32 (that
+    cell's linear index, -1 for none); work [H,W] i32 of scratch."""
+    import torch
+
+    _, _, n = _field_cells(grid_cfg)
+    _devs((grid, "u8", n, "grid", n == 0), (d2, "i32", n, "d2", n == 0), (work, "i32", n, "work", n == 0),
+          (nearest, "i32", n, "nearest", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(d2.device if d2 is not None else None)
+    _check(load().f110qp_grid_distance_dev(C.byref(grid_cfg), _tp(grid), _tp(d2), _tp(nearest), _tp(work),
+                                           C.c_void_p(stream.cuda_stream)), "f110qp_grid_distance_dev")
+
+
+def grid_inflate_dev(grid_cfg: GridConfig, d2, radius: float, out, stream=None):
+    """The map inflated by radius metres (f110qp_grid_inflate_dev): d2 [H,W] i32 -> out [H,W] u8 of 0 / 1, a map
+    for every grid call under the same grid_cfg."""
+    import torch
+
+    _, _, n = _field_cells(grid_cfg)
+    _devs((d2, "i32", n, "d2", n == 0), (out, "u8", n, "out", n == 0))
+    if stream is None:
+        stream = torch.cuda.current_stream(out.device if out is not None else None)
+    _check(load().f110qp_grid_inflate_dev(C.byref(grid_cfg), _tp(d2), float(radius), _tp(out),
+                                          C.c_void_p(stream.cuda_stream)), "f110qp_grid_inflate_dev")
+
+
+def grid_lookup_dev(grid_cfg: GridConfig, d2, x, dist, nearest=None, cell=None, stream=None):
+    """The wall distance at poses (f110qp_grid_lookup_dev): d2 [H,W] i32, x [rows,B,3] f64 (or [B,3]: one row; the
+    heading is not read) -> dist [rows,B] f64 in metres, NaN outside the map, and, with nearest [H,W] i32 given,
+    cell [rows,B] i32 (the nearest occupied cell's linear index, -1 outside the map or on an empty one)."""
+    import torch
+
+    _, _, n = _field_cells(grid_cfg)
+    rows, B = _rows_of(x, 3, "x")
+    if (nearest is None) != (cell is None):
+        raise F110QPError("nearest and cell must be given together")
+    _devs((d2, "i32", n, "d2", n == 0), (nearest, "i32", n, "nearest", True), (x, "f64", 3 * B * rows, "x"),
+          (dist, "f64", B * rows, "dist"), (cell, "i32", B * rows, "cell", True))
+    if stream is None:
+        stream = torch.cuda.current_stream(x.device)
+    _check(load().f110qp_grid_lookup_dev(C.byref(grid_cfg), _tp(d2), _tp(nearest), B, rows, _tp(x), _tp(dist),
+                                         _tp(cell), C.c_void_p(stream.cuda_stream)), "f110qp_grid_lookup_dev")
+
+
+def _host_map(grid_cfg, grid):
+    W, H, _ = _field_cells(grid_cfg)
+    if not isinstance(grid, np.ndarray) or grid.dtype != np.uint8 or grid.shape != (H, W):
+        got = (grid.dtype, grid.shape) if isinstance(grid, np.ndarray) else type(grid).__name__
+        raise F110QPError(f"grid must be a uint8 numpy array [height, width] = [{H}, {W}], got {got}")
+    return np.ascontiguousarray(grid)
+
+
+def grid_field(grid_cfg: GridConfig, grid, nearest=True, radius=None):
+    """The transform and the inflation on host arrays, synchronous (f110qp_grid_field): grid [H,W] u8 -> a dict of
+    d2 [H,W] i32, nearest [H,W] i32 and inflated [H,W] u8 at `radius`; an optional output that is switched off
+    (nearest=False, radius=None) is None."""
+    g = _host_map(grid_cfg, grid)
+    o = dict(d2=np.empty(g.shape, np.int32), nearest=np.empty(g.shape, np.int32) if nearest else None,
+             inflated=np.empty(g.shape, np.uint8) if radius is not None else None)
+    _check(load().f110qp_grid_field(C.byref(grid_cfg), _p(g), float(0.0 if radius is None else radius), _p(o["d2"]),
+                                    _p(o["nearest"]), _p(o["inflated"])), "f110qp_grid_field")
+    return o
+
+
+def wall_distance(grid_cfg: GridConfig, grid, x, cell=True):
+    """The wall distance of poses on host arrays, synchronous (f110qp_wall_distance): grid [H,W] u8, x [rows,B,3]
+    f64 (or [B,3]) -> (dist [rows,B] f64, cell [rows,B] i32 or None)."""
+    g = _host_map(grid_cfg, grid)
+    x = _f64(x, np.shape(x), "x")
+    rows, B = _rows_of(x, 3, "x")
+    dist = np.empty((rows, B), np.float64)
+    c = np.empty((rows, B), np.int32) if cell else None
+    _check(load().f110qp_wall_distance(C.byref(grid_cfg), _p(g), B, rows, _p(x), _p(dist), _p(c)),
+           "f110qp_wall_distance")
+    return dist, c
 
 
 def replan_start_dev(rp: ReplanConfig, sc, x, have_path, x_ref, gap, pose, kind, list_, count, hs=None, stream=None):

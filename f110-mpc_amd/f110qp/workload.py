@@ -1097,6 +1097,71 @@ def crop_map(grid, cfg, i0: int, j0: int, width: int, height: int):
                        cfg.resolution, cfg.reach)
 
 
+# ---- the map's distance field (f110qp_grid_distance_dev, f110qp_grid_inflate_dev, f110qp_grid_lookup_dev) ---------
+# Rules D1 to D4 of include/f110qp.h in numpy, expression for expression, np.float64 where a double is touched.
+
+FIELD_NONE = np.int32(np.iinfo(np.int32).max)  # d2 of a cell on a map without an occupied cell
+FIELD_NAN_BITS = np.uint64(0x7FF8000000000000)
+
+
+def grid_distance(grid, chunk: int = 1 << 22):
+    """Rules D1 and D2 as they are written: every cell against every occupied cell, the candidates in linear-index
+    order so that argmin's first minimum is the least index. grid [H, W] -> (d2 [H, W] int32, nearest [H, W] int32).
+    Cost: cells x occupied cells (in slices of `chunk` pairs): for maps of a few thousand cells."""
+    g = np.asarray(grid)
+    H, W = g.shape
+    d2 = np.full(H * W, FIELD_NONE, np.int32)
+    near = np.full(H * W, -1, np.int32)
+    occ = np.flatnonzero(g.reshape(-1) != 0).astype(np.int64)    # ascending linear index q W + p
+    if occ.size:
+        q, p = occ // W, occ % W
+        step = max(1, chunk // occ.size)
+        for k0 in range(0, H * W, step):
+            k = np.arange(k0, min(k0 + step, H * W), dtype=np.int64)
+            j, i = k // W, k % W
+            v = (i[:, None] - p[None, :]) ** 2 + (j[:, None] - q[None, :]) ** 2
+            a = np.argmin(v, axis=1)
+            d2[k] = v[np.arange(k.size), a]
+            near[k] = occ[a]
+    return d2.reshape(H, W), near.reshape(H, W)
+
+
+def grid_dist_metres(d2, cfg):
+    """Rule D3: resolution * sqrt((double)d2), +inf where d2 is INT_MAX."""
+    d2 = np.asarray(d2, np.int32)
+    with np.errstate(invalid="ignore"):
+        m = np.float64(cfg.resolution) * np.sqrt(d2.astype(np.float64))
+    return np.where(d2 == FIELD_NONE, np.inf, m)
+
+
+def grid_inflate(d2, cfg, radius: float):
+    """The inflation: (dist(d2) <= radius) as uint8."""
+    return (grid_dist_metres(d2, cfg) <= np.float64(radius)).astype(np.uint8)
+
+
+def grid_lookup(x, d2, nearest, cfg):
+    """Rule D4 at the poses x [rows, B, 3] (or [B, 3]; the heading is not read) -> (dist float64, cell int32), NaN
+    (0x7ff8000000000000) and -1 outside the map. nearest None: cell is None."""
+    x = np.asarray(x, np.float64)
+    d2 = np.asarray(d2, np.int32)
+    H, W = d2.shape
+    with np.errstate(invalid="ignore", over="ignore"):
+        px = (x[..., 0] - np.float64(cfg.origin_x)) / np.float64(cfg.resolution)
+        py = (x[..., 1] - np.float64(cfg.origin_y)) / np.float64(cfg.resolution)
+        ok = (px >= 0.0) & (px < W) & (py >= 0.0) & (py < H)
+        ix = np.where(ok, np.floor(px), 0.0).astype(np.int64)
+        iy = np.where(ok, np.floor(py), 0.0).astype(np.int64)
+    if d2.size == 0:
+        ok = np.zeros(px.shape, bool)
+        d2, ix, iy = np.full((1, 1), FIELD_NONE, np.int32), ix * 0, iy * 0
+    dist = np.where(ok, grid_dist_metres(d2, cfg)[iy, ix], FIELD_NAN_BITS.view(np.float64))
+    if nearest is None:
+        return dist, None
+    near = np.asarray(nearest, np.int32)
+    near = near if near.size else np.full((1, 1), -1, np.int32)
+    return dist, np.where(ok, near[iy, ix], -1).astype(np.int32)
+
+
 def _pgm_tokens(data: bytes, count: int):
     """The first `count` whitespace-separated header tokens of a PGM (comments from '#' to the line's end skipped)
     and the offset of the byte behind the single whitespace that ends the last one."""

@@ -1506,6 +1506,87 @@ int f110qp_rollout_grid(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const 
                         int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
                         int* nearest_traj, int* crash_tick);
 
+/* ---- distance field of the raster map: exact transform, inflation, pose lookups -----------------------------
+ * The map of the family above is static: one map serves all cars and all ticks, and rule G2 answers "how far is
+ * the wall" only up to reach. The calls below compute the map's exact Euclidean distance transform once, on the
+ * device, and read two things off it: the map inflated by a radius, and the wall distance at any [rows][B][3]
+ * pose array (x_traj among them). They run after the fact and take no context. Additive: F110QP_API_VERSION
+ * stays 6, and no call above changes its results.
+ *
+ * The map is the grid family's: grid [H][W] unsigned char, nonzero occupied, cell (i, j) at linear index j W + i,
+ * and its f110qp_grid_config as it is. Every call below checks that family's rules on the config first (a NULL
+ * config, a negative width or height, resolution not finite or <= 0, reach negative or not finite, a non-finite
+ * origin), although no call below reads reach in its arithmetic. On top of them width and height are at most
+ * F110QP_FIELD_MAX_SIDE = 32,768: then every squared cell distance is at most 2 x 32,767^2 = 2,147,352,578 <
+ * 2^31 - 1, the sums below fit an int, and INT_MAX is free as a mark.
+ *
+ * D1. Squared distance. d2[j][i] (int) is the minimum over the occupied cells (p, q) of (i - p)^2 + (j - q)^2; it
+ *     is 0 on an occupied cell, and INT_MAX everywhere on a map with no occupied cell. Integer arithmetic alone.
+ * D2. Nearest cell. nearest[j][i] (int) is q W + p of a minimiser of D1, among several the least linear index;
+ *     -1 where d2 is INT_MAX.
+ *     Consequence. The rule is separable. Along a row the nearer of a cell's two occupied row-neighbours wins, and
+ *     the smaller p wins a tie; down a column the least q wins among the rows that reach the minimum, and that
+ *     row's p is its row's. (A minimiser in row q is a nearest occupied cell of row q to column i, and of two
+ *     such cells the one with the smaller p has the smaller index.) So the result depends on nothing but the map:
+ *     not on the order of a search, a tile, or the number of threads.
+ * D3. Metres. dist(d2) = resolution * sqrt((double)d2): fp64, the correctly rounded root, one rounded product, no
+ *     fused multiply-add. dist(INT_MAX) = +inf. It is the distance between the centre of the cell and the centre
+ *     of the nearest occupied cell.
+ *     Consequences. A point in a cell and a point in an occupied cell are each within resolution sqrt(2) / 2 of
+ *     their cell's centre, so for a point q in a free cell the distance from q to the occupied area is at least
+ *     dist - resolution sqrt(2). For the rectangle of rules 1 to 3 centred in that cell, every point of which is
+ *     within sqrt(hl hl + hw hw) of its centre, the grid's share of rule G2's clearance is at least
+ *     dist - resolution sqrt(2) - sqrt(hl hl + hw hw).
+ * D4. Lookup of a point. With px = (x - origin_x) / resolution and py likewise (rule G1's expressions), a point
+ *     is outside the map when it fails 0 <= px < W && 0 <= py < H; a non-finite point fails that test. A point
+ *     outside the map gives dist = NaN (0x7ff8000000000000) and cell = -1: the field says nothing there, and
+ *     f110qp_mc_fan_dev counts a NaN as a missing sample. Otherwise ix = (int)floor(px), iy likewise,
+ *     dist = dist(d2[iy][ix]) and cell = nearest[iy][ix]. The point is the pose's (x, y) as stored: the heading is
+ *     not read, and a caller who wants the body centre passes body centres. That keeps sincos out of the rule, so
+ *     the lookup is exact to the bit.
+ * Inflation. out[j][i] = (dist(d2[j][i]) <= radius) ? 1 : 0, radius >= 0 and finite. Radius 0 gives the map back
+ *     as 0 / 1.
+ *     Consequence, from D3. Take radius >= sqrt(hl hl + hw hw) + resolution sqrt(2). Then a body centred anywhere
+ *     in a cell that the inflated map leaves free has a positive rule-G2 clearance to the original map (as far
+ *     as reach lets rule G2 see: beyond it the rule says "more than reach", which is positive too). */
+#define F110QP_FIELD_MAX_SIDE 32768
+
+/* Rules D1 and D2 on the device, asynchronous on `stream`: grid [H][W] -> d2 [H][W] int and, unless NULL, nearest
+ * [H][W] int. work is [H][W] int of the caller's scratch; its contents after the call are unspecified. Two
+ * launches (the rows, the columns), no allocation, no synchronisation, no read-back. F110QP_ERR_INVALID before
+ * any HIP call: the grid family's rules, a side above F110QP_FIELD_MAX_SIDE, and, with width * height > 0, a NULL
+ * grid, d2 or work. width * height == 0 returns F110QP_OK and launches nothing. */
+int f110qp_grid_distance_dev(const f110qp_grid_config* grid_cfg, const unsigned char* grid, int* d2, int* nearest,
+                             int* work, void* stream);
+
+/* The inflation of d2 [H][W] (f110qp_grid_distance_dev's) at `radius` metres -> out [H][W] unsigned char of 0 / 1,
+ * a map that every call of the grid family accepts under the same grid_cfg. One launch. F110QP_ERR_INVALID before
+ * any HIP call: the rules above, radius negative or not finite, and, with width * height > 0, a NULL d2 or out. */
+int f110qp_grid_inflate_dev(const f110qp_grid_config* grid_cfg, const int* d2, double radius, unsigned char* out,
+                            void* stream);
+
+/* Rule D4 at the poses x [rows][batch][3] double (the heading is not read) -> dist [rows][batch] double and, unless
+ * NULL, cell [rows][batch] int; nearest is NULL exactly when cell is. batch and rows as f110qp_progress_dev
+ * (>= 1, rows x batch <= 2^30). One launch of at most 2,048 workgroups striding over the poses.
+ * F110QP_ERR_INVALID before any HIP call: the rules above, batch or rows < 1 or too large, a NULL x or dist, nearest
+ * given without cell or cell without nearest, and, with width * height > 0, a NULL d2. With width * height == 0
+ * every pose is outside the map. */
+int f110qp_grid_lookup_dev(const f110qp_grid_config* grid_cfg, const int* d2, const int* nearest, int batch, int rows,
+                           const double* x, double* dist, int* cell, void* stream);
+
+/* f110qp_grid_distance_dev and, where `inflated` is not NULL, f110qp_grid_inflate_dev at `radius`, on host pointers
+ * (synchronous): grid [H][W] -> d2 [H][W], nearest [H][W] unless NULL, inflated [H][W] unless NULL (radius is read
+ * only with it). Staged through device buffers that the call owns and frees on every way out, one synchronisation;
+ * the same bits as the device calls. */
+int f110qp_grid_field(const f110qp_grid_config* grid_cfg, const unsigned char* grid, double radius, int* d2,
+                      int* nearest, unsigned char* inflated);
+
+/* f110qp_grid_distance_dev, then f110qp_grid_lookup_dev, on host pointers (synchronous): the map and x
+ * [rows][batch][3] -> dist [rows][batch] and, unless NULL, cell [rows][batch]. Staged as f110qp_grid_field; the same
+ * bits as the device calls. */
+int f110qp_wall_distance(const f110qp_grid_config* grid_cfg, const unsigned char* grid, int batch, int rows,
+                         const double* x, double* dist, int* cell);
+
 /* ---- race standings: progress along the track, laps and positions ---------------------------------------
  * The calls above return poses; the calls below say who is ahead. They run after the fact on x_traj, or on any
  * [rows][B][3] pose array: nothing inside a closed loop reads a standing, so there is no rollout family of
