@@ -65,8 +65,18 @@ __device__ unsigned long long g_sstamps[4096 * kSegStampSlots];
 #endif
 
 // Gain e (K 0 .. 5, k 6 .. 7) of stage t in the fixed-length kernels: its register (gr, the first KQ
-// gains of a stage; constant t and e only) or its scratch row behind the stage's six lam-gain rows;
-// seg_qgain: entry e of the forward sweep's 14 (8 .. 13 the lam-gains) wherever it lives
+// of a stage's 14 values; constant t and e only) or its scratch row behind the stage's six lam-gain
+// rows; seg_qgain: entry e of the forward sweep's 14 (8 .. 13 the lam-gains) wherever it lives.
+// KQ > 8: the lam-gains 8 .. KQ - 1 are registers too and the scratch keeps rows KQ .. 13 only (seg_lrow)
+template <int KQ>
+__device__ __forceinline__ constexpr int seg_lrow(int e) {  // scratch row of lam-gain entry e >= max(8, KQ)
+  return KQ > 8 ? e - KQ : e - 8;
+}
+template <int KQ, int NV, typename G, typename T>
+__device__ __forceinline__ void seg_lput(G& gr, T* sc, int t, int e, double v) {
+  if (e < KQ) gr[t][e] = v;
+  else sc[(t * NV + seg_lrow<KQ>(e)) * 64] = v;
+}
 template <int KQ, int NV, typename G, typename T>
 __device__ __forceinline__ void seg_gput(G& gr, T* sc, int t, int e, double v) {
   if (e < KQ) gr[t][e] = v;
@@ -78,7 +88,8 @@ __device__ __forceinline__ double seg_gget(const G& gr, const T* sc, int t, int 
 }
 template <int KQ, int NV, typename G, typename T>
 __device__ __forceinline__ double seg_qgain(const G& gr, const T* sc, int t, int e) {
-  return e < 8 ? seg_gget<KQ, NV>(gr, sc, t, e) : (double)sc[(t * NV + e - 8) * 64];
+  if (e < 8) return seg_gget<KQ, NV>(gr, sc, t, e);
+  return e < KQ ? gr[t][e] : (double)sc[(t * NV + seg_lrow<KQ>(e)) * 64];
 }
 
 template <int M>
@@ -175,12 +186,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   // front of the staging loads
   // Q > 0: a compile-time segment length, m = mM = q = Q (the launcher's choice). The stage loops unroll
   // fully, the lane's references, PDAS state (one packed word, 4 bits per stage) and the first kQReg
-  // of a stage's gains (K 6, k 2) live in registers from the backward sweep to the output sweep; the
-  // scratch keeps only the lam-gains F (6) and the gains past kQReg. Q == 0: the code below as it was.
+  // of a stage's 14 values (K 6, k 2, the lam-gains F 6) live in registers from the backward sweep to the
+  // output sweep; the scratch keeps only the values past kQReg (at 14 none: the pass loop's LDS traffic
+  // is the two code tables). Q == 0: the code below as it was.
   static_assert(Q == 0 || (EVEN && ROT && FST && !SCR && sizeof(ST) == 8),
                 "fixed segment length: EVEN, heading frame, lam-gains stored, fp64 scratch, no screen");
   constexpr int kQReg = seg_fixedq_reg_gains(Q);
-  constexpr int NV = Q > 0 ? 14 - kQReg : (FST ? 14 : 11);  // scratch doubles per stage: K 6, k 2, then F 6 or S^-1 3
+  // scratch doubles per stage: K 6, k 2, then F 6 or S^-1 3 (Q > 0: the ones that are not registers)
+  constexpr int NV = Q > 0 ? 14 - kQReg : (FST ? 14 : 11);
   extern __shared__ __attribute__((aligned(16))) double seg_smem[];
   const int lane = threadIdx.x;
   const int sl = lane / S;         // QP slot of the wave
@@ -611,7 +624,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         const double L10 = -I01 * W00 - I11 * W01, L11 = -I01 * W10 - I11 * W11;
         const double L12 = -I01 * W20 - I11 * W21;
         if constexpr (Q > 0) {
-          s[0] = L00; s[64] = L01; s[2 * 64] = L02; s[3 * 64] = L10; s[4 * 64] = L11; s[5 * 64] = L12;
+          seg_lput<kQReg, NV>(gr, sc, t, 8, L00); seg_lput<kQReg, NV>(gr, sc, t, 9, L01); seg_lput<kQReg, NV>(gr, sc, t, 10, L02);
+          seg_lput<kQReg, NV>(gr, sc, t, 11, L10); seg_lput<kQReg, NV>(gr, sc, t, 12, L11); seg_lput<kQReg, NV>(gr, sc, t, 13, L12);
         } else if constexpr (FST) {
           s[8 * 64] = L00; s[9 * 64] = L01; s[10 * 64] = L02;
           s[11 * 64] = L10; s[12 * 64] = L11; s[13 * 64] = L12;
