@@ -407,6 +407,43 @@ def _check_cfgs(fams, a, whole: bool):
         raise F110QPError(", ".join(said[:-1]) + " and " + said[-1] if said[1:] else said[0])
 
 
+# ---- the solve entry points: the one table behind their argtypes, the Solver's solve methods and its launchers ------
+# A row per C symbol, saying what tells it from the others. Its parameters are ctx, batch, x0, u_lin, x_ref, halfspace,
+# then group, num_groups if grouped, then u, x, status, iters, then obj, cost if ex, then stream if dev.
+
+class _Solve(NamedTuple):
+    symbol: str
+    grouped: bool = False  # takes group, num_groups
+    fin: str = "f32"       # the element type of x0 / u_lin / x_ref
+    dev: bool = False      # device pointers and a stream (else host arrays, synchronous)
+    ex: bool = False       # takes obj, cost
+    sync: bool = False     # a device call that returns with the results in device memory
+
+
+SOLVE_CALLS = (
+    _Solve("f110qp_solve_batch"),
+    _Solve("f110qp_solve_batch_ex", ex=True),
+    _Solve("f110qp_solve_batch_dev", dev=True),
+    _Solve("f110qp_solve_batch_ex_dev", dev=True, ex=True),
+    _Solve("f110qp_solve_batch_dev_sync", dev=True, sync=True),
+    _Solve("f110qp_solve_grouped", grouped=True),
+    _Solve("f110qp_solve_grouped_ex", grouped=True, ex=True),
+    _Solve("f110qp_solve_grouped_dev", grouped=True, dev=True),
+    _Solve("f110qp_solve_grouped_ex_dev", grouped=True, dev=True, ex=True),
+    _Solve("f110qp_solve_batch_dbl", fin="f64", ex=True),
+    _Solve("f110qp_solve_batch_dev_dbl", fin="f64", dev=True, ex=True),
+    _Solve("f110qp_solve_batch_dev_sync_dbl", fin="f64", dev=True, sync=True),
+    _Solve("f110qp_solve_grouped_dbl", grouped=True, fin="f64", ex=True),
+    _Solve("f110qp_solve_grouped_dev_dbl", grouped=True, fin="f64", dev=True, ex=True),
+)
+_SOLVE_SYMBOL = {row[1:]: row.symbol for row in SOLVE_CALLS}
+
+
+def _solve_argtypes(row: _Solve):
+    fp = C.c_void_p
+    return [fp, C.c_int] + [fp] * 4 + [fp, C.c_int] * row.grouped + [fp] * 4 + [fp, fp] * row.ex + [fp] * row.dev
+
+
 _libs = {}
 
 
@@ -425,20 +462,8 @@ def load(test: bool = False):
     L.f110qp_default_config.argtypes = [C.POINTER(Config), C.c_int]
     L.f110qp_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(Config)]
     L.f110qp_destroy.argtypes = [C.c_void_p]
-    L.f110qp_solve_batch.argtypes = [C.c_void_p, C.c_int] + [fp] * 8
-    L.f110qp_solve_batch_dev.argtypes = [C.c_void_p, C.c_int] + [fp] * 9
-    L.f110qp_solve_batch_dev_sync.argtypes = [C.c_void_p, C.c_int] + [fp] * 9
-    L.f110qp_solve_grouped.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 4
-    L.f110qp_solve_grouped_dev.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 5
-    L.f110qp_solve_batch_ex.argtypes = [C.c_void_p, C.c_int] + [fp] * 10
-    L.f110qp_solve_batch_ex_dev.argtypes = [C.c_void_p, C.c_int] + [fp] * 11
-    L.f110qp_solve_grouped_ex.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 6
-    L.f110qp_solve_grouped_ex_dev.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 7
-    L.f110qp_solve_batch_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 10
-    L.f110qp_solve_batch_dev_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 11
-    L.f110qp_solve_batch_dev_sync_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 9
-    L.f110qp_solve_grouped_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 6
-    L.f110qp_solve_grouped_dev_dbl.argtypes = [C.c_void_p, C.c_int] + [fp] * 5 + [C.c_int] + [fp] * 7
+    for row in SOLVE_CALLS:
+        getattr(L, row.symbol).argtypes = _solve_argtypes(row)
     L.f110qp_default_rollout_config.argtypes = [C.POINTER(RolloutConfig)]
     L.f110qp_advance_dev.argtypes = [C.POINTER(RolloutConfig), C.c_int, C.c_int] + [fp] * 7
     L.f110qp_rollout_dev.argtypes = [C.c_void_p, C.POINTER(RolloutConfig), C.c_int] + [fp] * 11
@@ -767,6 +792,11 @@ def _f64(a, shape, name: str):
     return np.ascontiguousarray(a).reshape(shape)
 
 
+def _f32(a, shape, name: str):
+    """A host input of a float32 call: anything numpy casts to float32."""
+    return np.ascontiguousarray(a, np.float32).reshape(shape)
+
+
 def _tp(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -890,30 +920,7 @@ class Solver:
         self._chk(self.lib.f110qp_gap_screen(self._h, int(batch), C.byref(v)), "f110qp_gap_screen")
         return bool(v.value)
 
-    def solve(self, x0, u_lin, x_ref, halfspace=None, objective=False):
-        """Host arrays in, host arrays out (synchronous). Returns (u[B,N,2], x[B,N+1,3],
-        status[B], iters[B]) and, with objective=True, also (obj[B], cost[B]) float64
-        (f110qp_solve_batch_ex)."""
-        N = self.horizon
-        x0 = np.ascontiguousarray(x0, np.float32).reshape(-1, 3)
-        B = x0.shape[0]
-        ul = np.ascontiguousarray(u_lin, np.float32).reshape(B, 2)
-        S = self.config.x_ref_points or N
-        xr = np.ascontiguousarray(x_ref, np.float32).reshape(B, S, 3)
-        hs = None if halfspace is None else np.ascontiguousarray(halfspace, np.float32).reshape(B, 6)
-        u = np.empty((B, N, 2), np.float32)
-        x = np.empty((B, N + 1, 3), np.float32)
-        st = np.empty(B, np.int32)
-        it = np.empty(B, np.int32)
-        if objective:
-            ob = np.empty(B, np.float64)
-            co = np.empty(B, np.float64)
-            self._chk(self.lib.f110qp_solve_batch_ex(self._h, B, _p(x0), _p(ul), _p(xr), _p(hs), _p(u), _p(x),
-                                                  _p(st), _p(it), _p(ob), _p(co)), "f110qp_solve_batch_ex")
-            return u, x, st, it, ob, co
-        self._chk(self.lib.f110qp_solve_batch(self._h, B, _p(x0), _p(ul), _p(xr), _p(hs), _p(u), _p(x),
-                                           _p(st), _p(it)), "f110qp_solve_batch")
-        return u, x, st, it
+    # ---- the solve family: one host body and one device body, both reading SOLVE_CALLS --------------------------
 
     def _check_dev(self, x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters=None, obj=None, cost=None,
                    group=None, fin="f32"):
@@ -932,67 +939,153 @@ class Solver:
         _devs(*specs)
         return B
 
+    @staticmethod
+    def _stream(stream, t):
+        """The stream argument of a device call: `stream`, or the current stream of tensor t's device."""
+        import torch
+
+        return C.c_void_p((stream if stream is not None else torch.cuda.current_stream(t.device)).cuda_stream)
+
+    def _solve_host(self, fin, x0, u_lin, x_ref, halfspace, objective, grp=None):
+        """The body of the four host solves. fin: "f32" casts x0 / u_lin / x_ref, "f64" takes float64 only and always
+        calls the symbol with obj / cost (null without objective); grp = (group, num_groups): a grouped call."""
+        N = self.horizon
+        arr = _f64 if fin == "f64" else _f32
+        x0 = arr(x0, (-1, 3), "x0")
+        B = x0.shape[0]
+        ul = arr(u_lin, (B, 2), "u_lin")
+        xr = arr(x_ref, (B, self.config.x_ref_points or N, 3), "x_ref")
+        hs = None if halfspace is None else np.ascontiguousarray(halfspace, np.float32).reshape(B, 6)
+        groups = []
+        if grp is not None:
+            g = np.ascontiguousarray(grp[0], np.int32).reshape(B)
+            groups = [_p(g), int(g.max()) + 1 if grp[1] is None else int(grp[1])]
+        out = [np.empty((B, N, 2), np.float32), np.empty((B, N + 1, 3), np.float32), np.empty(B, np.int32),
+               np.empty(B, np.int32)]
+        oc = [np.empty(B, np.float64) if objective else None for _ in range(2)]
+        ex = bool(objective) or fin == "f64"
+        name = _SOLVE_SYMBOL[grp is not None, fin, False, ex, False]
+        self._chk(getattr(self.lib, name)(self._h, B, _p(x0), _p(ul), _p(xr), _p(hs), *groups, *map(_p, out),
+                                          *map(_p, oc if ex else [])), name)
+        return tuple(out + oc) if objective else tuple(out)
+
+    def _solve_dev_call(self, fin, x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, stream, obj=None,
+                        cost=None, grp=None, sync=False):
+        """(C function, its name, its converted arguments) of a device solve, the tensors checked. The symbol takes
+        obj / cost when one is given and, for fin "f64", always; a sync symbol never does."""
+        ex = (fin == "f64" or obj is not None or cost is not None) and not sync
+        name = _SOLVE_SYMBOL[grp is not None, fin, True, ex, sync]
+        if sync and (obj is not None or cost is not None):
+            raise F110QPError(f"{name} has no obj / cost outputs")
+        B = self._check_dev(x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, obj, cost,
+                            group=grp[0] if grp is not None else None, fin=fin)
+        stream = self._stream(stream, x0)
+        args = [self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace)]
+        if grp is not None:
+            args += [_tp(grp[0]), int(grp[1])]
+        args += [_tp(u_out), _tp(x_out), _tp(status), _tp(iters)]
+        if ex:
+            args += [_tp(obj), _tp(cost)]
+        return getattr(self.lib, name), name, (*args, stream)
+
+    def _solve_dev(self, *a, **k):
+        """The body of the four device solves: one checked C call."""
+        fn, name, args = self._solve_dev_call(*a, **k)
+        self._chk(fn(*args), name)
+
+    def _launcher(self, what, *a, **k):
+        """The body of the two prepare_*: everything converted here, the closure one C call."""
+        fn, _, args = self._solve_dev_call("f32", *a, **k)
+
+        def launch():
+            rc = fn(*args)
+            if rc != OK:
+                _check(rc, what, self.lib)
+        return launch
+
+    def solve(self, x0, u_lin, x_ref, halfspace=None, objective=False):
+        """Host arrays in, host arrays out (synchronous). Returns (u[B,N,2], x[B,N+1,3],
+        status[B], iters[B]) and, with objective=True, also (obj[B], cost[B]) float64
+        (f110qp_solve_batch_ex)."""
+        return self._solve_host("f32", x0, u_lin, x_ref, halfspace, objective)
+
+    def solve_dbl(self, x0, u_lin, x_ref, halfspace=None, objective=False):
+        """solve() on float64 x0 / u_lin / x_ref, passed unrounded (f110qp_solve_batch_dbl); any
+        other element type is rejected. Outputs as solve()."""
+        return self._solve_host("f64", x0, u_lin, x_ref, halfspace, objective)
+
+    def solve_grouped(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
+        """Grouped solve on host arrays (f110qp_solve_grouped): group [B] int scenario ids.
+        objective=True also returns (obj[B], cost[B]) (f110qp_solve_grouped_ex)."""
+        return self._solve_host("f32", x0, u_lin, x_ref, halfspace, objective, (group, num_groups))
+
+    def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
+        """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
+        return self._solve_host("f64", x0, u_lin, x_ref, halfspace, objective, (group, num_groups))
+
     def solve_dev(self, x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters=None, stream=None,
                   obj=None, cost=None):
         """Device (torch) tensors in/out, enqueued on `stream` (torch.cuda stream or None =
         current stream). Asynchronous. obj / cost: optional float64 [B] device tensors
         (f110qp_solve_batch_ex_dev)."""
-        import torch
-
-        B = self._check_dev(x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, obj, cost)
-        if stream is None:
-            stream = torch.cuda.current_stream(x0.device)
-        if obj is not None or cost is not None:
-            self._chk(self.lib.f110qp_solve_batch_ex_dev(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace),
-                                                      _tp(u_out), _tp(x_out), _tp(status), _tp(iters), _tp(obj),
-                                                      _tp(cost), C.c_void_p(stream.cuda_stream)),
-                   "f110qp_solve_batch_ex_dev")
-            return
-        self._chk(self.lib.f110qp_solve_batch_dev(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace),
-                                               _tp(u_out), _tp(x_out), _tp(status), _tp(iters),
-                                               C.c_void_p(stream.cuda_stream)), "f110qp_solve_batch_dev")
-
-    def solve_dbl(self, x0, u_lin, x_ref, halfspace=None, objective=False):
-        """solve() on float64 x0 / u_lin / x_ref, passed unrounded (f110qp_solve_batch_dbl); any
-        other element type is rejected. Outputs as solve()."""
-        N = self.horizon
-        x0 = _f64(x0, (-1, 3), "x0")
-        B = x0.shape[0]
-        ul = _f64(u_lin, (B, 2), "u_lin")
-        xr = _f64(x_ref, (B, self.config.x_ref_points or N, 3), "x_ref")
-        hs = None if halfspace is None else np.ascontiguousarray(halfspace, np.float32).reshape(B, 6)
-        u = np.empty((B, N, 2), np.float32)
-        x = np.empty((B, N + 1, 3), np.float32)
-        st = np.empty(B, np.int32)
-        it = np.empty(B, np.int32)
-        ob = np.empty(B, np.float64) if objective else None
-        co = np.empty(B, np.float64) if objective else None
-        self._chk(self.lib.f110qp_solve_batch_dbl(self._h, B, _p(x0), _p(ul), _p(xr), _p(hs), _p(u), _p(x), _p(st),
-                                                  _p(it), _p(ob), _p(co)), "f110qp_solve_batch_dbl")
-        return (u, x, st, it, ob, co) if objective else (u, x, st, it)
+        self._solve_dev("f32", x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, stream, obj, cost)
 
     def solve_dev_dbl(self, x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters=None, stream=None,
                       obj=None, cost=None, sync=False):
         """solve_dev() on float64 device tensors x0 / u_lin / x_ref (f110qp_solve_batch_dev_dbl);
         sync=True: f110qp_solve_batch_dev_sync_dbl (returns with the results in device memory; no
         obj / cost)."""
+        self._solve_dev("f64", x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, stream, obj, cost, sync=sync)
+
+    def solve_grouped_dev(self, x0, u_lin, x_ref, halfspace, group, num_groups, u_out, x_out, status, iters=None,
+                          stream=None, obj=None, cost=None):
+        """Grouped solve on device (torch) tensors; group [B] int32 on the device; obj / cost
+        optional float64 [B] (f110qp_solve_grouped_ex_dev)."""
+        self._solve_dev("f32", x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, stream, obj, cost,
+                        (group, num_groups))
+
+    def solve_grouped_dev_dbl(self, x0, u_lin, x_ref, halfspace, group, num_groups, u_out, x_out, status,
+                              iters=None, stream=None, obj=None, cost=None):
+        """solve_grouped_dev() on float64 device tensors x0 / u_lin / x_ref
+        (f110qp_solve_grouped_dev_dbl)."""
+        self._solve_dev("f64", x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, stream, obj, cost,
+                        (group, num_groups))
+
+    def prepare_dev(self, x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters=None, stream=None,
+                    sync=False):
+        """A launcher for repeated f110qp_solve_batch_dev calls on the same device buffers: the
+        ctypes arguments are converted once, each call is one C call (what a C++ caller of the ABI
+        pays; bench.py's timed steps use it so Python argument marshalling is not the step).
+        sync=True: f110qp_solve_batch_dev_sync (returns with the results in device memory)."""
+        return self._launcher("f110qp_solve_batch_dev", x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters,
+                              stream, sync=sync)
+
+    def prepare_grouped_dev(self, x0, u_lin, x_ref, halfspace, group, num_groups, u_out, x_out, status,
+                            iters=None, stream=None):
+        """prepare_dev for f110qp_solve_grouped_dev."""
+        return self._launcher("f110qp_solve_grouped_dev", x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters,
+                              stream, grp=(group, num_groups))
+
+    def assemble_debug(self, x0, u_lin, x_ref, halfspace=None):
+        """f110qp_assemble_debug_dev for one instance (host arrays in; the device computes; host
+        dict of the CSC arrays out, the oracle.assemble layout)."""
         import torch
 
-        if sync and (obj is not None or cost is not None):
-            raise F110QPError("f110qp_solve_batch_dev_sync_dbl has no obj / cost outputs")
-        B = self._check_dev(x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, obj, cost, fin="f64")
-        if stream is None:
-            stream = torch.cuda.current_stream(x0.device)
-        if sync:
-            self._chk(self.lib.f110qp_solve_batch_dev_sync_dbl(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref),
-                                                               _tp(halfspace), _tp(u_out), _tp(x_out), _tp(status),
-                                                               _tp(iters), C.c_void_p(stream.cuda_stream)),
-                      "f110qp_solve_batch_dev_sync_dbl")
-            return
-        self._chk(self.lib.f110qp_solve_batch_dev_dbl(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace),
-                                                      _tp(u_out), _tp(x_out), _tp(status), _tp(iters), _tp(obj),
-                                                      _tp(cost), C.c_void_p(stream.cuda_stream)),
-                  "f110qp_solve_batch_dev_dbl")
+        N = self.horizon
+        n, m, nzp, nza = qp_dims(N)
+        dev = torch.device("cuda", self.config.device)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32).reshape(-1)).to(dev)  # noqa: E731
+        x0d, uld, xrd = t(x0), t(u_lin), t(x_ref)
+        hsd = None if halfspace is None else t(halfspace)
+        i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)  # noqa: E731
+        f64 = lambda k: torch.empty(k, dtype=torch.float64, device=dev)  # noqa: E731
+        out = {"P_colptr": i32(n + 1), "P_rowind": i32(nzp), "P_val": f64(nzp), "q": f64(n), "A_colptr": i32(n + 1),
+               "A_rowind": i32(nza), "A_val": f64(nza), "l": f64(m), "u": f64(m)}
+        self._chk(self.lib.f110qp_assemble_debug_dev(self._h, _tp(x0d), _tp(uld), _tp(xrd), _tp(hsd),
+                                                     *map(_tp, out.values()), self._stream(None, x0d)),
+                  "f110qp_assemble_debug_dev")
+        torch.cuda.synchronize(dev)
+        return {k: v.cpu().numpy() for k, v in out.items()}
 
     # ---- the closed-loop families: what their bindings share ------------------------------------------
     # rollout, rollout_scan and rollout_replan (and their _dev calls) use these pieces by hand. The eight world
@@ -1042,12 +1135,6 @@ class Solver:
                 (best_traj_traj, "i32", B * T, "best_traj_traj", True),
                 (best_global_traj, "i32", B * T, "best_global_traj", True),
                 (pose_traj, "f64", 4 * B * (T + 1), "pose_traj", True)]
-
-    @staticmethod
-    def _stream(stream, x_traj):
-        import torch
-
-        return C.c_void_p((stream if stream is not None else torch.cuda.current_stream(x_traj.device)).cuda_stream)
 
     @staticmethod
     def _host_start(x0, u_lin, ticks):
@@ -1412,168 +1499,13 @@ class Solver:
         and grid_cfg follow segments, everything else as there."""
         return self._world_host("grid", locals())
 
-    def solve_grouped_dbl(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
-        """solve_grouped() on float64 x0 / u_lin / x_ref (f110qp_solve_grouped_dbl)."""
-        N = self.horizon
-        x0 = _f64(x0, (-1, 3), "x0")
-        B = x0.shape[0]
-        ul = _f64(u_lin, (B, 2), "u_lin")
-        xr = _f64(x_ref, (B, self.config.x_ref_points or N, 3), "x_ref")
-        hs = None if halfspace is None else np.ascontiguousarray(halfspace, np.float32).reshape(B, 6)
-        g = np.ascontiguousarray(group, np.int32).reshape(B)
-        G = int(g.max()) + 1 if num_groups is None else int(num_groups)
-        u = np.empty((B, N, 2), np.float32)
-        x = np.empty((B, N + 1, 3), np.float32)
-        st = np.empty(B, np.int32)
-        it = np.empty(B, np.int32)
-        ob = np.empty(B, np.float64) if objective else None
-        co = np.empty(B, np.float64) if objective else None
-        self._chk(self.lib.f110qp_solve_grouped_dbl(self._h, B, _p(x0), _p(ul), _p(xr), _p(hs), _p(g), G, _p(u),
-                                                    _p(x), _p(st), _p(it), _p(ob), _p(co)), "f110qp_solve_grouped_dbl")
-        return (u, x, st, it, ob, co) if objective else (u, x, st, it)
-
-    def solve_grouped_dev_dbl(self, x0, u_lin, x_ref, halfspace, group, num_groups, u_out, x_out, status,
-                              iters=None, stream=None, obj=None, cost=None):
-        """solve_grouped_dev() on float64 device tensors x0 / u_lin / x_ref
-        (f110qp_solve_grouped_dev_dbl)."""
-        import torch
-
-        B = self._check_dev(x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, obj, cost, group=group,
-                            fin="f64")
-        if stream is None:
-            stream = torch.cuda.current_stream(x0.device)
-        self._chk(self.lib.f110qp_solve_grouped_dev_dbl(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace),
-                                                        _tp(group), int(num_groups), _tp(u_out), _tp(x_out),
-                                                        _tp(status), _tp(iters), _tp(obj), _tp(cost),
-                                                        C.c_void_p(stream.cuda_stream)),
-                  "f110qp_solve_grouped_dev_dbl")
-
-    def prepare_dev(self, x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters=None, stream=None,
-                    sync=False):
-        """A launcher for repeated f110qp_solve_batch_dev calls on the same device buffers: the
-        ctypes arguments are converted once, each call is one C call (what a C++ caller of the ABI
-        pays; bench.py's timed steps use it so Python argument marshalling is not the step).
-        sync=True: f110qp_solve_batch_dev_sync (returns with the results in device memory)."""
-        import torch
-
-        self._check_dev(x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters)
-        if stream is None:
-            stream = torch.cuda.current_stream(x0.device)
-        fn = self.lib.f110qp_solve_batch_dev_sync if sync else self.lib.f110qp_solve_batch_dev
-        args = (self._h, x0.shape[0], _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace), _tp(u_out), _tp(x_out),
-                _tp(status), _tp(iters), C.c_void_p(stream.cuda_stream))
-
-        def launch():
-            rc = fn(*args)
-            if rc != OK:
-                _check(rc, "f110qp_solve_batch_dev", self.lib)
-        return launch
-
-    def prepare_grouped_dev(self, x0, u_lin, x_ref, halfspace, group, num_groups, u_out, x_out, status,
-                            iters=None, stream=None):
-        """prepare_dev for f110qp_solve_grouped_dev."""
-        import torch
-
-        self._check_dev(x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, group=group)
-        if stream is None:
-            stream = torch.cuda.current_stream(x0.device)
-        fn = self.lib.f110qp_solve_grouped_dev
-        args = (self._h, x0.shape[0], _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace), _tp(group), int(num_groups),
-                _tp(u_out), _tp(x_out), _tp(status), _tp(iters), C.c_void_p(stream.cuda_stream))
-
-        def launch():
-            rc = fn(*args)
-            if rc != OK:
-                _check(rc, "f110qp_solve_grouped_dev", self.lib)
-        return launch
-
-    def assemble_debug(self, x0, u_lin, x_ref, halfspace=None):
-        """f110qp_assemble_debug_dev for one instance (host arrays in; the device computes; host
-        dict of the CSC arrays out, the oracle.assemble layout)."""
-        import torch
-
-        N = self.horizon
-        n, m, nzp, nza = qp_dims(N)
-        dev = torch.device("cuda", self.config.device)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32).reshape(-1)).to(dev)  # noqa: E731
-        x0d, uld, xrd = t(x0), t(u_lin), t(x_ref)
-        hsd = None if halfspace is None else t(halfspace)
-        out = {"P_colptr": torch.empty(n + 1, dtype=torch.int32, device=dev),
-               "P_rowind": torch.empty(nzp, dtype=torch.int32, device=dev),
-               "P_val": torch.empty(nzp, dtype=torch.float64, device=dev),
-               "q": torch.empty(n, dtype=torch.float64, device=dev),
-               "A_colptr": torch.empty(n + 1, dtype=torch.int32, device=dev),
-               "A_rowind": torch.empty(nza, dtype=torch.int32, device=dev),
-               "A_val": torch.empty(nza, dtype=torch.float64, device=dev),
-               "l": torch.empty(m, dtype=torch.float64, device=dev),
-               "u": torch.empty(m, dtype=torch.float64, device=dev)}
-        stream = torch.cuda.current_stream(dev)
-        o = out
-        self._chk(self.lib.f110qp_assemble_debug_dev(self._h, _tp(x0d), _tp(uld), _tp(xrd), _tp(hsd), _tp(o["P_colptr"]),
-                                                  _tp(o["P_rowind"]), _tp(o["P_val"]), _tp(o["q"]), _tp(o["A_colptr"]),
-                                                  _tp(o["A_rowind"]), _tp(o["A_val"]), _tp(o["l"]), _tp(o["u"]),
-                                                  C.c_void_p(stream.cuda_stream)), "f110qp_assemble_debug_dev")
-        torch.cuda.synchronize(dev)
-        return {k: v.cpu().numpy() for k, v in out.items()}
-
-    def solve_grouped(self, x0, u_lin, x_ref, group, num_groups=None, halfspace=None, objective=False):
-        """Grouped solve on host arrays (f110qp_solve_grouped): group [B] int scenario ids.
-        objective=True also returns (obj[B], cost[B]) (f110qp_solve_grouped_ex)."""
-        N = self.horizon
-        x0 = np.ascontiguousarray(x0, np.float32).reshape(-1, 3)
-        B = x0.shape[0]
-        ul = np.ascontiguousarray(u_lin, np.float32).reshape(B, 2)
-        S = self.config.x_ref_points or N
-        xr = np.ascontiguousarray(x_ref, np.float32).reshape(B, S, 3)
-        hs = None if halfspace is None else np.ascontiguousarray(halfspace, np.float32).reshape(B, 6)
-        g = np.ascontiguousarray(group, np.int32).reshape(B)
-        G = int(g.max()) + 1 if num_groups is None else int(num_groups)
-        u = np.empty((B, N, 2), np.float32)
-        x = np.empty((B, N + 1, 3), np.float32)
-        st = np.empty(B, np.int32)
-        it = np.empty(B, np.int32)
-        if objective:
-            ob = np.empty(B, np.float64)
-            co = np.empty(B, np.float64)
-            self._chk(self.lib.f110qp_solve_grouped_ex(self._h, B, _p(x0), _p(ul), _p(xr), _p(hs), _p(g), G, _p(u),
-                                                    _p(x), _p(st), _p(it), _p(ob), _p(co)), "f110qp_solve_grouped_ex")
-            return u, x, st, it, ob, co
-        self._chk(self.lib.f110qp_solve_grouped(self._h, B, _p(x0), _p(ul), _p(xr), _p(hs), _p(g), G, _p(u), _p(x),
-                                             _p(st), _p(it)), "f110qp_solve_grouped")
-        return u, x, st, it
-
-    def solve_grouped_dev(self, x0, u_lin, x_ref, halfspace, group, num_groups, u_out, x_out, status, iters=None,
-                          stream=None, obj=None, cost=None):
-        """Grouped solve on device (torch) tensors; group [B] int32 on the device; obj / cost
-        optional float64 [B] (f110qp_solve_grouped_ex_dev)."""
-        import torch
-
-        B = self._check_dev(x0, u_lin, x_ref, halfspace, u_out, x_out, status, iters, obj, cost, group=group)
-        if stream is None:
-            stream = torch.cuda.current_stream(x0.device)
-        if obj is not None or cost is not None:
-            self._chk(self.lib.f110qp_solve_grouped_ex_dev(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace),
-                                                        _tp(group), int(num_groups), _tp(u_out), _tp(x_out),
-                                                        _tp(status), _tp(iters), _tp(obj), _tp(cost),
-                                                        C.c_void_p(stream.cuda_stream)), "f110qp_solve_grouped_ex_dev")
-            return
-        self._chk(self.lib.f110qp_solve_grouped_dev(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(halfspace),
-                                                 _tp(group), int(num_groups), _tp(u_out), _tp(x_out), _tp(status),
-                                                 _tp(iters), C.c_void_p(stream.cuda_stream)),
-               "f110qp_solve_grouped_dev")
-
     def warm_reset(self):
         self._chk(self.lib.f110qp_warm_reset(self._h), "f110qp_warm_reset")
 
     def condense_debug_dev(self, x0, u_lin, x_ref, H_out, g_out, stream=None):
-        import torch
-
-        B = x0.shape[0]
-        if stream is None:
-            stream = torch.cuda.current_stream(x0.device)
-        self._chk(self.lib.f110qp_condense_debug_dev(self._h, B, _tp(x0), _tp(u_lin), _tp(x_ref), _tp(H_out),
-                                                  _tp(g_out), C.c_void_p(stream.cuda_stream)),
-               "f110qp_condense_debug_dev")
+        self._chk(self.lib.f110qp_condense_debug_dev(self._h, x0.shape[0], _tp(x0), _tp(u_lin), _tp(x_ref), _tp(H_out),
+                                                     _tp(g_out), self._stream(stream, x0)),
+                  "f110qp_condense_debug_dev")
 
 
 def advance_dev(rc: RolloutConfig, horizon: int, x, u_plan, status, x_next, u_lin_next, u_applied=None, stream=None):

@@ -1,37 +1,13 @@
 """The world families' bindings against include/f110qp.h (CPU only): the argument lists load() sets are the
 header's, parameter by parameter; the table's configs stand in the header's order; every public rollout wrapper
 refuses a wrong type in each of its config slots, naming the slot, before it reads an array."""
-import ctypes as C
 import inspect
-import os
 import re
 
 import pytest
+from capi_header import CONFIG, ctype_of, declarations
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "f110qp.h")
 FAMILIES = ("world", "race", "contact", "body", "walls", "refresh", "noisy", "grid")
-CONFIG = re.compile(r"const f110qp_(\w+)_config\*")
-
-
-def declarations():
-    """{symbol: [parameter type, ...]} of every function the header declares, comments stripped."""
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    out = {}
-    for name, params in re.findall(r"\b(f110qp_\w+)\(([^()]*)\);", text):
-        out[name] = [re.sub(r"\s*\b\w+(\[\d*\])?$", r"\1", " ".join(p.split())) for p in params.split(",")]
-    return out
-
-
-def ctype_of(capi, decl):
-    if decl in ("f110qp_ctx*", "void*"):
-        return C.c_void_p
-    m = CONFIG.fullmatch(decl)
-    if m:
-        return C.POINTER(getattr(capi, m.group(1).capitalize() + "Config"))
-    if decl == "int":
-        return C.c_int
-    assert decl.endswith("*") or decl.endswith("]"), decl
-    return C.c_void_p
 
 
 def family_symbols(capi):
