@@ -58,20 +58,16 @@
 
 #include <type_traits>
 
+#include "lane_common.h"
 #include "lane_plan.h"
 
 namespace f110qp {
 
 // Diagnostic build only (-DF110QP_STAMPS): per-wave cycles of each sweep type, read back with
-// f110qp_read_lane_stamps(). The shipped library never executes a stamp.
+// f110qp_read_lane_stamps() (the macros: stamps.h).
 #ifdef F110QP_STAMPS
 constexpr int kLaneStampSlots = 8;
 __device__ unsigned long long g_lstamps[4096 * kLaneStampSlots];  // one TU per stamps build
-#define LSTAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define LACC(acc, since) acc += __builtin_amdgcn_s_memtime() - (since)
-#else
-#define LSTAMP(var)
-#define LACC(acc, since)
 #endif
 
 // stages of scratch loaded ahead in the forward and output sweeps: HBM latency is several
@@ -135,7 +131,7 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
   float* const stg = (DREF && !DIN) ? xr_s + 3 * P.N * L : xr_s;
   using StgT = std::conditional_t<DIN && DREF, double, float>;
   StgT* const stgt = reinterpret_cast<StgT*>(stg);
-  LSTAMP(t_start);
+  STAMP(t_start);
 #ifdef F110QP_STAMPS
   unsigned long long acc_bw = 0, acc_fw = 0, acc_out = 0, t_setup = 0, npass = 0;
 #endif
@@ -225,27 +221,9 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
   const double th0 = (double)fTH0;
   const double v = (double)ulg[2 * b + 0], d = (double)ulg[2 * b + 1];
   const double dt = (double)P.dt;
-  const double Lw = (double)0.3302f;
-  double sn, cs, sd, cd;
-  sincos(th0, &sn, &cs);
-  sincos(d, &sd, &cd);
-  const double sec2 = 1.0 / (cd * cd);
-  // ROT (q0 == q1, the shipped params.yaml:1-2): the (x, y) offsets are expressed in the frame
-  // of the heading th0, s = cs dx + sn dy, n = cs dy - sn dx. Q = diag(q0, q0, q2) is invariant
-  // under that rotation and A = I + E, B become A = I + (v dt) e_n e_th', B = [dt 0; 0 0; b20 b21]
-  // (the rotated model.cpp:42-51 with cs^2 + sn^2 = 1): four zero entries that drop ~20 fp64
-  // operations of the backward Riccati stage and ~6 of the forward one.
-  const double a02 = ROT ? 0.0 : -1 * v * sn * dt;                         // :42
-  const double a12 = ROT ? v * dt : v * cs * dt;                           // :43
-  const double b00 = ROT ? dt : cs * dt, b10 = ROT ? 0.0 : sn * dt;        // :48-49
-  const double b20 = (sd / cd) * dt / Lw, b21 = v * sec2 * dt / Lw;        // :50-51
-  const double c0r = v * th0 * sn * dt, c1r = -1 * v * th0 * cs * dt;     // :53-54
-  const double c2 = -1 * d * v * sec2 * dt / Lw;                           // :55
-  // The state is recentred on x0 = (X0, Y0, th0): translation invariance in (x, y) and, for the
-  // heading, x_{i+1} = x_i + a02 th_i + ... + c0 = x_i + a02 (th_i - th0) + ... + (c0 + a02 th0).
-  // c0 + a02 th0 is zero up to rounding (model.cpp:42,53); keeping it as computed stays exact.
-  // (In the rotated frame both are exactly zero in exact arithmetic and dropped.)
-  const double c0 = ROT ? 0.0 : c0r + a02 * th0, c1 = ROT ? 0.0 : c1r + a12 * th0;
+  const LaneModel M = lane_linearize<ROT>(th0, v, d, dt);  // (ROT: the heading frame, linearize.h)
+  const double sn = M.sn, cs = M.cs, a02 = M.a02, a12 = M.a12, b00 = M.b00, b10 = M.b10, b20 = M.b20;
+  const double b21 = M.b21, c0 = M.c0, c1 = M.c1, c2 = M.c2;
   const double q0 = P.q[0], q1 = P.q[1], q2 = P.q[2], r0 = P.r[0], r1 = P.r[1];
   const double ud0 = P.udes[0], ud1 = P.udes[1];
   const double lb0 = (double)P.umin[0], lb1 = (double)P.umin[1];
@@ -315,8 +293,7 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
         lw = lo1;
         hw = hi1;
       }
-      const unsigned l2 = (unsigned)lw & 3u, h2 = (unsigned)hw & 3u & ~l2;
-      ap[i * L] = (int)((l2 & 1u) | ((h2 & 1u) << 1) | ((l2 & 2u) << 1) | ((h2 & 2u) << 2));
+      ap[i * L] = (int)pdas_code((unsigned)lw, (unsigned)hw);
       lw >>= 2;
       hw >>= 2;
     }
@@ -379,7 +356,7 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
 #ifdef F110QP_STAMPS
     npass++;
 #endif
-    LSTAMP(t_bw);
+    STAMP(t_bw);
     {
       // ---- Riccati backward sweep ---------------------------------------------------------
       double rx, ry, rt;
@@ -453,8 +430,8 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
         p1 = hx1 + X01 * k0 + X11 * k1;
         p2 = hx2 + X02 * k0 + X12 * k1;
       }
-      LACC(acc_bw, t_bw);
-      LSTAMP(t_fw);
+      STAMP_ACC(acc_bw, t_bw);
+      STAMP(t_fw);
       // ---- forward sweep: u_i = K_i x_i + k_i, x_{i+1} = A x_i + B u_i + C, costate and the
       // PDAS re-guess. K_i, k_i come through a ring of kRing stages loaded ahead; the ring
       // index is static inside the unrolled group.
@@ -632,7 +609,7 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
           }
         }
       }
-      LACC(acc_fw, t_fw);
+      STAMP_ACC(acc_fw, t_fw);
       if (!changed && !done) {  // KKT point: the gains of this pass (in the scratch) give u*
         done = true;
         iters = pass + 1;  // equality-QP solves incl. the confirming one
@@ -640,7 +617,7 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
     }
   }
   // ---- output sweep, every lane at once: x* by the fp64 rollout of u* ----
-  LSTAMP(t_out);
+  STAMP(t_out);
   {
     const bool solved = done && !bad;
     const float nanv = __int_as_float(0x7fc00000);
@@ -702,7 +679,7 @@ __global__ __launch_bounds__(64) F110QP_LANE_ATTR void lane_kernel(const KParams
       if (iters_out) iters_out[b] = bad ? 0 : (done ? iters : max_pass);
     }
   }
-  LACC(acc_out, t_out);
+  STAMP_ACC(acc_out, t_out);
   if (oo.obj || oo.cost) {
     // objective of the solution (fp64): cost = sum_{i=0..N} 1/2|x_i - r_i|_Q^2 + sum 1/2|u_i - u_des|_R^2
     // (r_N = x_ref[N-1], mpc.cpp:228) by one more rollout from the final gains, and OSQP's

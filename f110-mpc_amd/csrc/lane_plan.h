@@ -32,22 +32,12 @@ constexpr size_t seg_lds_bytes(int N, int S, bool fst = false, bool f32 = false)
 }
 
 // The fixed-length kernels (lane_seg_kernel<..., Q > 0>: EVEN, FST, fp64 scratch, Q stages per segment)
-// keep a lane's references, its PDAS state and the first seg_fixedq_reg_gains of a stage's 14 per-stage
-// values (K 6, then k 2, then the lam-gains F 6) in registers; their LDS holds the values that are not
-// in registers, 14 - seg_fixedq_reg_gains rows of 64 doubles per stage (up to 8: the six F rows, then
-// the gains past the knob; above 8: the F rows past the knob), and behind them the two code tables.
-// At 14, the default, nothing per stage is left in LDS: the request is the tables' 2 kSegTabBytes and
-// the pass loop reads LDS for table entries only (measured against 8: DESIGN.md 2b'). The rules of
-// lane_plan() below still count the run-time-length kernel's LDS. (The references are not staged: every
-// lane loads its own 3 Q scalars from global memory.)
-#ifndef F110QP_SEG_QREG
-#define F110QP_SEG_QREG 14  // (knob: 0 .. 14)
-#endif
-static_assert(F110QP_SEG_QREG >= 0 && F110QP_SEG_QREG <= 14, "register-resident values per stage: 0 .. 14");
-constexpr int seg_fixedq_reg_gains(int Q) { return Q > 0 ? F110QP_SEG_QREG : 0; }
-constexpr size_t seg_fixedq_lds_bytes(int Q) {
-  return (size_t)Q * 64 * 8 * (14 - seg_fixedq_reg_gains(Q)) + 2 * kSegTabBytes;
-}
+// keep a lane's references, its PDAS state and all 14 per-stage values (K 6, k 2, the lam-gains F 6) in
+// registers, so nothing per stage is left in LDS: the request is the two code tables and the pass loop
+// reads LDS for table entries only (measured against 8 of the 14 in registers: DESIGN.md 2b'). The
+// rules of lane_plan() below still count the run-time-length kernel's LDS. (The references are not
+// staged: every lane loads its own 3 Q scalars from global memory.)
+constexpr size_t seg_fixedq_lds_bytes(int /*Q*/) { return 2 * kSegTabBytes; }
 
 // LDS per wave of the sequential kernel (lane_kernel.h) at L QPs per wave: the staged references
 // (12 N L B) + PDAS state (4 N L B), + the Riccati scratch (8 N L sizeof(ST)) when it is in LDS, + the

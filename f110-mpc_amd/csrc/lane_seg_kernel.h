@@ -48,49 +48,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lane_common.h"
 #include "lane_plan.h"
 
 namespace f110qp {
 
 // Diagnostic build only (-DF110QP_STAMPS on lane_seg_inst.hip): per-wave cycles of the setup, each
-// pass phase and the output, read back with f110qp_read_seg_stamps(). Never in the shipped library.
+// pass phase and the output, read back with f110qp_read_seg_stamps() (the macros: stamps.h).
 #ifdef F110QP_STAMPS
 constexpr int kSegStampSlots = 16;
 __device__ unsigned long long g_sstamps[4096 * kSegStampSlots];
-#define SSTAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define SACC(acc, since) acc += __builtin_amdgcn_s_memtime() - (since)
-#else
-#define SSTAMP(var)
-#define SACC(acc, since)
 #endif
-
-// Gain e (K 0 .. 5, k 6 .. 7) of stage t in the fixed-length kernels: its register (gr, the first KQ
-// of a stage's 14 values; constant t and e only) or its scratch row behind the stage's six lam-gain
-// rows; seg_qgain: entry e of the forward sweep's 14 (8 .. 13 the lam-gains) wherever it lives.
-// KQ > 8: the lam-gains 8 .. KQ - 1 are registers too and the scratch keeps rows KQ .. 13 only (seg_lrow)
-template <int KQ>
-__device__ __forceinline__ constexpr int seg_lrow(int e) {  // scratch row of lam-gain entry e >= max(8, KQ)
-  return KQ > 8 ? e - KQ : e - 8;
-}
-template <int KQ, int NV, typename G, typename T>
-__device__ __forceinline__ void seg_lput(G& gr, T* sc, int t, int e, double v) {
-  if (e < KQ) gr[t][e] = v;
-  else sc[(t * NV + seg_lrow<KQ>(e)) * 64] = v;
-}
-template <int KQ, int NV, typename G, typename T>
-__device__ __forceinline__ void seg_gput(G& gr, T* sc, int t, int e, double v) {
-  if (e < KQ) gr[t][e] = v;
-  else sc[(t * NV + 6 + e - KQ) * 64] = v;
-}
-template <int KQ, int NV, typename G, typename T>
-__device__ __forceinline__ double seg_gget(const G& gr, const T* sc, int t, int e) {
-  return e < KQ ? gr[t][e] : (double)sc[(t * NV + 6 + e - KQ) * 64];
-}
-template <int KQ, int NV, typename G, typename T>
-__device__ __forceinline__ double seg_qgain(const G& gr, const T* sc, int t, int e) {
-  if (e < 8) return seg_gget<KQ, NV>(gr, sc, t, e);
-  return e < KQ ? gr[t][e] : (double)sc[(t * NV + seg_lrow<KQ>(e)) * 64];
-}
 
 template <int M>
 struct SegMode {
@@ -185,15 +153,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   // kernel arguments next to their first use, which put two dependent kernarg round trips in
   // front of the staging loads
   // Q > 0: a compile-time segment length, m = mM = q = Q (the launcher's choice). The stage loops unroll
-  // fully, the lane's references, PDAS state (one packed word, 4 bits per stage) and the first kQReg
-  // of a stage's 14 values (K 6, k 2, the lam-gains F 6) live in registers from the backward sweep to the
-  // output sweep; the scratch keeps only the values past kQReg (at 14 none: the pass loop's LDS traffic
-  // is the two code tables). Q == 0: the code below as it was.
+  // fully, the lane's references, PDAS state (one packed word, 4 bits per stage) and a stage's 14
+  // values (gr[t][e]: K 0 .. 5, k 6 .. 7, the lam-gains F 8 .. 13) live in registers from the backward
+  // sweep to the output sweep; LDS holds the two code tables and nothing per stage. Q == 0: the
+  // run-time-length code, references, state and scratch in LDS.
   static_assert(Q == 0 || (EVEN && ROT && FST && !SCR && sizeof(ST) == 8),
                 "fixed segment length: EVEN, heading frame, lam-gains stored, fp64 scratch, no screen");
-  constexpr int kQReg = seg_fixedq_reg_gains(Q);
-  // scratch doubles per stage: K 6, k 2, then F 6 or S^-1 3 (Q > 0: the ones that are not registers)
-  constexpr int NV = Q > 0 ? 14 - kQReg : (FST ? 14 : 11);
+  // Q == 0: scratch doubles per stage: K 6, k 2, then F 6 or S^-1 3
+  constexpr int NV = FST ? 14 : 11;
   extern __shared__ __attribute__((aligned(16))) double seg_smem[];
   const int lane = threadIdx.x;
   const int sl = lane / S;         // QP slot of the wave
@@ -223,7 +190,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   const int mM = EVEN ? q : q + (rem > 0 ? 1 : 0);
   const bool top = seg == S - 1;
 
-  SSTAMP(t_start);
+  STAMP(t_start);
 #ifdef F110QP_STAMPS
   unsigned long long acc_bw = 0, acc_dual = 0, acc_ref = 0, acc_fw = 0, t_setup = 0, npass = 0;
   unsigned long long t_out_loop = 0;  // the output sweep's stage loop
@@ -235,7 +202,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   int* const ap = reinterpret_cast<int*>(lbase + o_ap) + lane;             // [mM][64]
   ST* const sc = reinterpret_cast<ST*>(lbase + o_sc) + lane;               // [mM][NV][64]
   // code tables (wave-uniform base; a lane reads the entry of its own stage's state code)
-  double* const btab = reinterpret_cast<double*>(lbase + o_sc + (size_t)mM * NV * 64 * sizeof(ST));
+  double* const btab = reinterpret_cast<double*>(lbase + o_sc + (Q > 0 ? 0 : (size_t)mM * NV * 64 * sizeof(ST)));
   double* const ftab = btab + 16 * 8;  // (ST = double only)
 
   // per-QP inputs and the warm-start traffic switch (warm_traffic), issued before the staging loads
@@ -306,24 +273,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     key0 = k4.x; key1 = k4.y; key2 = k4.z; key3 = k4.w;
   }
 
-  SSTAMP(t_stg);
-  // ---- per-lane QP data (Model::Linearize, model.cpp:30-59), as lane_kernel.h ----
+  STAMP(t_stg);
+  // ---- per-lane QP data (Model::Linearize, model.cpp:30-59: lane_linearize, linearize.h) ----
   const double X0 = (double)fX0, Y0 = (double)fY0;
   const double th0 = (double)fTH0;
   const double v = (double)fv, d = (double)fd;
   const double dt = (double)P.dt;
-  const double Lw = (double)0.3302f;
-  double sn, cs, sd, cd;
-  sincos(th0, &sn, &cs);
-  sincos(d, &sd, &cd);
-  const double sec2 = 1.0 / (cd * cd);
-  const double a02 = ROT ? 0.0 : -1 * v * sn * dt;                    // model.cpp:42
-  const double a12 = ROT ? v * dt : v * cs * dt;                      // :43
-  const double b00 = ROT ? dt : cs * dt, b10 = ROT ? 0.0 : sn * dt;   // :48-49
-  const double b20 = (sd / cd) * dt / Lw, b21 = v * sec2 * dt / Lw;   // :50-51
-  const double c0r = v * th0 * sn * dt, c1r = -1 * v * th0 * cs * dt;  // :53-54
-  const double c2 = -1 * d * v * sec2 * dt / Lw;                      // :55
-  const double c0 = ROT ? 0.0 : c0r + a02 * th0, c1 = ROT ? 0.0 : c1r + a12 * th0;
+  const LaneModel M = lane_linearize<ROT>(th0, v, d, dt);
+  const double sn = M.sn, cs = M.cs, a02 = M.a02, a12 = M.a12, b00 = M.b00, b10 = M.b10, b20 = M.b20;
+  const double b21 = M.b21, c0 = M.c0, c1 = M.c1, c2 = M.c2;
   const double q0 = P.q[0], q1 = P.q[1], q2 = P.q[2], r0 = P.r[0], r1 = P.r[1];
   const double ud0 = P.udes[0], ud1 = P.udes[1];
   const double lb0 = (double)P.umin[0], lb1 = (double)P.umin[1];
@@ -342,7 +300,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   const double gtoll0 = gtL * (1.0 + r0 * bound_scale(lb0, ub0, ud0));
   const double gtoll1 = gtL * (1.0 + r1 * bound_scale(lb1, ub1, ud1));
 
-  SSTAMP(t_lin);
+  STAMP(t_lin);
   // references of the lane's stages: recentred (ROT: rotated) fp64, lane-major; a non-finite
   // entry flags the QP (one ballot folded over its segment lanes)
   // (the loop runs to the wave-uniform mM: a lane of a shorter segment converts one stage of the
@@ -352,7 +310,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
   // Q > 0: the references, the packed state codes (stage t at bits 4t .. 4t + 3) and the gains kept
   // in registers (constant indices only: every loop over them is fully unrolled)
   double rr[Q > 0 ? 3 * Q : 1];
-  double gr[Q > 0 ? Q : 1][kQReg > 0 ? kQReg : 1];
+  double gr[Q > 0 ? Q : 1][Q > 0 ? 14 : 1];
   unsigned apk = 0u;
   {
     const IN* stg = reinterpret_cast<const IN*>(lbase + o_sc);
@@ -405,7 +363,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     }
     __syncthreads();  // the staging region becomes the Riccati scratch
   }
-  SSTAMP(t_conv);
+  STAMP(t_conv);
   // terminal reference x_ref[N-1] (mpc.cpp:228): the last stage of the top segment
   constexpr int kQL = Q > 0 ? 3 * (Q - 1) : 0;  // (Q > 0: the register copy)
   double rNx, rNy, rNt;
@@ -418,19 +376,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     rNy = __shfl(r64[(3 * (m - 1) + 1) * 64], lane | (S - 1));
     rNt = __shfl(r64[(3 * (m - 1) + 2) * 64], lane | (S - 1));
   }
-  SSTAMP(t_rn);
+  STAMP(t_rn);
 
   // warm start: previous tick's active bounds when the slot's (theta0, v, steer) bits repeat
   const int R = (2 * N + 63) / 64;
   // (IN = double: the *_dbl calls pass no warm state, wt is false; the slot key holds float bits)
   const unsigned kth = __float_as_uint((float)fTH0), kv = __float_as_uint((float)fv), kd = __float_as_uint((float)fd);
   {
-#ifdef F110QP_SEG_SEED_ANY  // measurement knob: seed from the slot's previous set on any key
-                            // (measured C5 31.2 -> 34.9 us: the stale set costs passes)
-    const bool hit = wt && key3 != 0u;
-#else
+    // (seeding from the slot's previous set on any key measured C5 31.2 -> 34.9 us: a stale set costs passes)
     const bool hit = sizeof(IN) == 4 && wt && key3 != 0u && key0 == kth && key1 == kv && key2 == kd;
-#endif
     unsigned long long lw = 0, hw = 0;
     if (wt) {  // (wave-uniform: a call that moves no warm state skips the mask window)
       if (ws.hit_call && __ballot(hit) != 0ull && lane == 0) *ws.hit_call = ws.call;
@@ -465,8 +419,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
       if (wt) {
 #pragma unroll
         for (int t = 0; t < Q; t++) {
-          const unsigned l2 = (unsigned)(lw >> (2 * t)) & 3u, h2 = (unsigned)(hw >> (2 * t)) & 3u & ~l2;
-          const unsigned a = (l2 & 1u) | ((h2 & 1u) << 1) | ((l2 & 2u) << 1) | ((h2 & 2u) << 2);
+          const unsigned a = pdas_code((unsigned)(lw >> (2 * t)), (unsigned)(hw >> (2 * t)));
           apk |= ((tw && 2 * (s0 + t) < N) ? (unsigned)sv : a) << (4 * t);
         }
       } else {
@@ -479,12 +432,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
       }
     } else
     for (int t = 0; t < mM; t++) {
-      const unsigned l2 = (unsigned)(lw >> (2 * t)) & 3u, h2 = (unsigned)(hw >> (2 * t)) & 3u & ~l2;
-      const int a = (int)((l2 & 1u) | ((h2 & 1u) << 1) | ((l2 & 2u) << 1) | ((h2 & 2u) << 2));
+      const int a = (int)pdas_code((unsigned)(lw >> (2 * t)), (unsigned)(hw >> (2 * t)));
       ap[t * 64] = (tw && 2 * (s0 + t) < N) ? sv : a;
     }
   }
-  SSTAMP(t_mask);
+  STAMP(t_mask);
 
   // whether any of the lane's QP's S lanes has its bit set in a ballot
   auto qany = [&](unsigned long long mk) { return ((mk >> (sl * S)) & ((1ull << S) - 1ull)) != 0ull; };
@@ -521,7 +473,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
 #ifdef F110QP_STAMPS
     npass++;
 #endif
-    SSTAMP(t_bw);
+    STAMP(t_bw);
     // ---- 1. backward over the segment: Riccati + the closed-loop map (Phi, psi, Gam) ----
     double P00 = top ? q0 : 0.0, P01 = 0.0, P02 = 0.0, P11 = top ? q1 : 0.0, P12 = 0.0;
     double P22 = top ? q2 : 0.0;
@@ -593,8 +545,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         const double w0 = h0 + H00 * bA0 + H01 * bA1, w1 = h1 + H01 * bA0 + H11 * bA1;
         const double k0 = bA0 - I00 * w0 - I01 * w1, k1 = bA1 - I01 * w0 - I11 * w1;
         if constexpr (Q > 0) {
-          seg_gput<kQReg, NV>(gr, sc, t, 0, K00); seg_gput<kQReg, NV>(gr, sc, t, 1, K01); seg_gput<kQReg, NV>(gr, sc, t, 2, K02); seg_gput<kQReg, NV>(gr, sc, t, 3, K10); seg_gput<kQReg, NV>(gr, sc, t, 4, K11);
-          seg_gput<kQReg, NV>(gr, sc, t, 5, K12); seg_gput<kQReg, NV>(gr, sc, t, 6, k0); seg_gput<kQReg, NV>(gr, sc, t, 7, k1);
+          gr[t][0] = K00; gr[t][1] = K01; gr[t][2] = K02; gr[t][3] = K10; gr[t][4] = K11;
+          gr[t][5] = K12; gr[t][6] = k0; gr[t][7] = k1;
         } else {
           s[0] = K00; s[64] = K01; s[2 * 64] = K02; s[3 * 64] = K10; s[4 * 64] = K11;
           s[5 * 64] = K12; s[6 * 64] = k0; s[7 * 64] = k1;
@@ -624,8 +576,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         const double L10 = -I01 * W00 - I11 * W01, L11 = -I01 * W10 - I11 * W11;
         const double L12 = -I01 * W20 - I11 * W21;
         if constexpr (Q > 0) {
-          seg_lput<kQReg, NV>(gr, sc, t, 8, L00); seg_lput<kQReg, NV>(gr, sc, t, 9, L01); seg_lput<kQReg, NV>(gr, sc, t, 10, L02);
-          seg_lput<kQReg, NV>(gr, sc, t, 11, L10); seg_lput<kQReg, NV>(gr, sc, t, 12, L11); seg_lput<kQReg, NV>(gr, sc, t, 13, L12);
+          gr[t][8] = L00; gr[t][9] = L01; gr[t][10] = L02;
+          gr[t][11] = L10; gr[t][12] = L11; gr[t][13] = L12;
         } else if constexpr (FST) {
           s[8 * 64] = L00; s[9 * 64] = L01; s[10 * 64] = L02;
           s[11 * 64] = L10; s[12 * 64] = L11; s[13 * 64] = L12;
@@ -656,8 +608,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         F02 = n02; F12 = n12; F22 = n22;
       }
     }
-    SACC(acc_bw, t_bw);
-    SSTAMP(t_dual);
+    STAMP_ACC(acc_bw, t_bw);
+    STAMP(t_dual);
     // ---- 2. the segment ends: the boundary problem over the segments, eliminated from both ends ----
     // S <= 4: the lower half of a QP's lanes (x_s^(0) = 0 below) and the upper half (the true terminal
     // cost on top) eliminate towards the middle in lockstep, S / 2 - 1 full steps each, and meet in
@@ -839,8 +791,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         lm2 = top ? 0.0 : T20 * xs0 + T21 * xs1 + T22 * xs2 + t2;
       }
     }
-    SACC(acc_dual, t_dual);
-    SSTAMP(t_ref);
+    STAMP_ACC(acc_dual, t_dual);
+    STAMP(t_ref);
     // ---- 3. refresh: the lam-part of the feed-forward, backward over the segment ----
     // (FST: nothing to refresh; the forward sweep adds F_i lam_j to k_i and the costate at the
     // segment start takes p^lam_s = Phi_s' lam_j. The top lane's lam is 0, so its Phi, zeroed by the
@@ -875,8 +827,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         pl0 = n0; pl1 = n1;
       }
     }
-    SACC(acc_ref, t_ref);
-    SSTAMP(t_fw);
+    STAMP_ACC(acc_ref, t_ref);
+    STAMP(t_fw);
     // ---- 4. forward over the segment: rollout, costate, PDAS re-guess ----
     // Two instantiations as in lane_kernel.h: plain PDAS passes (MODE 0) store the re-guessed
     // state as it is; single-flip passes (MODE 1) take the segment's first change only and
@@ -901,7 +853,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
       constexpr int NG = FST ? 14 : 8;
       double ng[NG];  // stage t + 1's gains, loaded while stage t computes
 #pragma unroll
-      for (int e = 0; e < NG; e++) ng[e] = Q > 0 ? seg_qgain<kQReg, NV>(gr, sc, 0, e) : (double)sc[e * 64];
+      for (int e = 0; e < NG; e++) {
+        if constexpr (Q > 0) ng[e] = gr[0][e];
+        else ng[e] = (double)sc[e * 64];
+      }
       // unrolled by 2: same-box A/B C5 29.6 -> 29.3 us, C2 27.0 -> 26.5, C4 shard neutral
       // (Q > 0: the whole segment; the clamped next-stage indices below become constants and the
       // last stage's prefetch goes away)
@@ -915,11 +870,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         {
           const ST* sn1 = sc + (t + 1 < m ? t + 1 : m - 1) * NV * 64;
 #pragma unroll
-          for (int e = 0; e < NG; e++) ng[e] = Q > 0 ? seg_qgain<kQReg, NV>(gr, sc, t + 1 < m ? t + 1 : m - 1, e) : (double)sn1[e * 64];
+          for (int e = 0; e < NG; e++) {
+            if constexpr (Q > 0) ng[e] = gr[t + 1 < m ? t + 1 : m - 1][e];
+            else ng[e] = (double)sn1[e * 64];
+          }
         }
         // (Q > 0: k + F lam kept in k's place, so that the output sweep reads no lam-gain)
         if constexpr (Q > 0) {
-          seg_gput<kQReg, NV>(gr, sc, t, 6, k0); seg_gput<kQReg, NV>(gr, sc, t, 7, k1);
+          gr[t][6] = k0; gr[t][7] = k1;
         }
         const int old = old_n;
         const double rxi = rx, ryi = ry, rti = rt;
@@ -1005,14 +963,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
       }
     }
     const bool qchanged = qany(__ballot(changed));
-    SACC(acc_fw, t_fw);
+    STAMP_ACC(acc_fw, t_fw);
     if (!qchanged && !done) {
       done = true;
       iters = pass + 1;
     }
   }
 
-  SSTAMP(t_out);
+  STAMP(t_out);
   // the start whose outputs stand: the one that converged first (a converged start keeps its
   // iteration count while its wave sweeps on), the cold one on a tie or when neither converged
   bool owner = owner0, qowner = qowner0;
@@ -1059,7 +1017,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     ga0 = h6[0]; gb0 = h6[1]; gc0 = h6[2]; ga1 = h6[3]; gb1 = h6[4]; gc1 = h6[5];
   }
   int nviol = 0;  // gap rows of this lane's stages the box optimum violates (or within the margin)
-  SSTAMP(t_ol0);
+  STAMP(t_ol0);
   {
     double x0 = xs0, x1 = xs1, x2 = xs2;
     if constexpr (Q > 0) {
@@ -1072,8 +1030,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
         constexpr bool OBJ = decltype(obj_tag)::value != 0;
 #pragma unroll
         for (int t = 0; t < Q; t++) {
-          const double u0 = seg_gget<kQReg, NV>(gr, sc, t, 6) + seg_gget<kQReg, NV>(gr, sc, t, 0) * x0 + seg_gget<kQReg, NV>(gr, sc, t, 1) * x1 + seg_gget<kQReg, NV>(gr, sc, t, 2) * x2;
-          const double u1 = seg_gget<kQReg, NV>(gr, sc, t, 7) + seg_gget<kQReg, NV>(gr, sc, t, 3) * x0 + seg_gget<kQReg, NV>(gr, sc, t, 4) * x1 + seg_gget<kQReg, NV>(gr, sc, t, 5) * x2;
+          const double u0 = gr[t][6] + gr[t][0] * x0 + gr[t][1] * x1 + gr[t][2] * x2;
+          const double u1 = gr[t][7] + gr[t][3] * x0 + gr[t][4] * x1 + gr[t][5] * x2;
           if constexpr (OBJ) {
             qterm(rr[3 * t], rr[3 * t + 1], rr[3 * t + 2], x0, x1, x2);
             J += 0.5 * (r0 * (u0 - ud0) * (u0 - ud0) + r1 * (u1 - ud1) * (u1 - ud1));
@@ -1141,7 +1099,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Q > 0 ? F110
     }
     if (want_obj && top) qterm(rNx, rNy, rNt, x0, x1, x2);  // x_N against x_ref[N-1]
   }
-  SACC(t_out_loop, t_ol0);
+  STAMP_ACC(t_out_loop, t_ol0);
   if (want_obj) {
 #pragma unroll
     for (int k = 1; k < S; k <<= 1) {

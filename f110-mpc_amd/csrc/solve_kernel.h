@@ -36,21 +36,15 @@
 #include "f110qp_kernels.h"
 
 #include "linearize.h"
+#include "stamps.h"
 
 namespace f110qp {
 
 // Diagnostic build only (-DF110QP_STAMPS): per-phase s_memtime deltas of every wave, read back
-// with f110qp_read_stamps(). The shipped library never executes a stamp.
+// with f110qp_read_stamps() (the macros: stamps.h).
 #ifdef F110QP_STAMPS
 constexpr int kStampSlots = 16;
 __device__ unsigned long long g_stamps[65536 * kStampSlots];  // stamps build: one TU (all instantiations)
-#define STAMP(var) unsigned long long var = __builtin_amdgcn_s_memtime()
-#define STAMP_SET(var) var = __builtin_amdgcn_s_memtime()
-#define STAMP_ACC(acc, since) acc += __builtin_amdgcn_s_memtime() - (since)
-#else
-#define STAMP(var)
-#define STAMP_SET(var)
-#define STAMP_ACC(acc, since)
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -566,9 +560,6 @@ __device__ __forceinline__ void chol_delete(Smem<NUM, GAP, RT>& sm, int lane, in
 
 // y = W x with x in sm.vec; W symmetric so the lane reads column v (consecutive addresses
 // across lanes, conflict free). Variables >= NUM get 0.
-#ifndef F110QP_MATVEC_SPLIT
-#define F110QP_MATVEC_SPLIT 1
-#endif
 template <int NUM, bool GAP, int R, typename RT>
 __device__ __forceinline__ void matvec_W(Smem<NUM, GAP, RT>& sm, int lane, float (&y)[R]) {
   int c[R];
@@ -578,7 +569,6 @@ __device__ __forceinline__ void matvec_W(Smem<NUM, GAP, RT>& sm, int lane, float
     c[r] = v < NUM ? v : NUM - 1;
     y[r] = 0.f;
   }
-#if F110QP_MATVEC_SPLIT
   // y_c = sum_j W[c][j] x_j over the lane's own row (W symmetric): four entries of the row and of
   // the broadcast x per 16-B LDS read, four independent accumulator chains (the column form was
   // NUM dependent FMAs and 2 NUM LDS reads per call, one call per GI step)
@@ -605,14 +595,6 @@ __device__ __forceinline__ void matvec_W(Smem<NUM, GAP, RT>& sm, int lane, float
   }
 #pragma unroll
   for (int r = 0; r < R; r++) y[r] = (y[r] + y1[r]) + (y2[r] + y3[r]);
-#else
-#pragma unroll
-  for (int j = 0; j < NUM; j++) {
-    const float xj = sm.vec[j];
-#pragma unroll
-    for (int r = 0; r < R; r++) y[r] = fmaf(sm.W[j][c[r]], xj, y[r]);
-  }
-#endif
 #pragma unroll
   for (int r = 0; r < R; r++) y[r] = (64 * r + lane < NUM) ? y[r] : 0.f;
 }

@@ -1,7 +1,7 @@
 """The fixed-length segment kernels (csrc/lane_seg_kernel.h, Q = 5) with the pass loop's LDS round
-trips taken out: every per-stage value of the forward sweep (K 6, k 2, the lam-gains F 6) may live in
-registers (F110QP_SEG_QREG up to 14, the default), so that the pass loop reads LDS for code-table
-entries only. Whatever the knob is, the fixed-length route must give the run-time-length route's bits
+trips taken out: every per-stage value of the forward sweep (K 6, k 2, the lam-gains F 6) lives in
+registers (all 14; the partial schemes are retired), so that the pass loop reads LDS for code-table
+entries only. The fixed-length route must give the run-time-length route's bits
 (F110QP_SEG_FIXEDQ=0 in the test build: the Q = 0 kernel, whose text did not change) and the oracle's answer at the tolerance of the other seg tests (TOL, and
 test_gpu_dbl's bound on the double inputs). All cases N = 20, S = 4.
 
