@@ -6,8 +6,9 @@
 // f110qp_cast_scans_body_dev, f110qp_rollout_body[_dev]) and with straight walls (f110qp_cast_scans_walls_dev,
 // f110qp_clearance_walls_dev, f110qp_rollout_walls[_dev]) and with a refreshed MPC scan (f110qp_gap_refresh_dev,
 // f110qp_rollout_refresh[_dev]) and with a noisy LiDAR (f110qp_cast_scans_noisy_dev, f110qp_rollout_noisy[_dev]),
-// and with a raster map (f110qp_cast_scans_grid_dev, f110qp_clearance_grid_dev, f110qp_rollout_grid[_dev]), and the
-// parts of each.
+// and with a raster map (f110qp_cast_scans_grid_dev, f110qp_clearance_grid_dev, f110qp_rollout_grid[_dev]) and with
+// that map's casts through its distance field (f110qp_grid_cast_dev, f110qp_rollout_field[_dev]), and the parts of
+// each.
 // Host-side responsibilities only: argument validation, workspaces, H2D/D2H of the host-pointer calls
 // (the staging table of api_stage.h). No C++ exception crosses this boundary.
 #include <cmath>
@@ -182,12 +183,14 @@ enum Family { kPlain, kScan, kReplan, kWorld };
 // refreshed), and what a failed launch of the cast and of the clearance entry point of its name says (null: the
 // family has no such entry point). world: the circles; race: the race-mates in every cast; contact: race with cc;
 // body: rectangular bodies in every cast and clearance; walls: straight segments next to the circles; refresh:
-// walls with rf; noisy: rules Z1 to Z3 on every scan; grid: a raster map under every cast and clearance.
+// walls with rf; noisy: rules Z1 to Z3 on every scan; grid: a raster map under every cast and clearance; field: the
+// grid row with rule F1 on the map's distance field in every cast (its clearance is the grid's).
 struct WorldRow {
   f110qp::WorldFamily world;
   bool cc, rf;
   const char* cast_launch;
   const char* clearance_launch;
+  bool field = false;
 };
 namespace row {
 constexpr WorldRow world{f110qp::WORLD_CIRCLES, false, false, "scan cast launch", nullptr};
@@ -198,6 +201,7 @@ constexpr WorldRow walls{f110qp::WORLD_WALLS, true, false, "walls scan cast laun
 constexpr WorldRow refresh{f110qp::WORLD_WALLS, true, true, nullptr, nullptr};
 constexpr WorldRow noisy{f110qp::WORLD_NOISY, true, true, "noisy scan cast launch", nullptr};
 constexpr WorldRow grid{f110qp::WORLD_GRID, true, true, "grid scan cast launch", "grid clearance launch"};
+constexpr WorldRow field{f110qp::WORLD_GRID, true, true, "field scan cast launch", nullptr, true};
 }  // namespace row
 
 // The configs of a rollout call as the caller gave them and, once check_args has passed, the
@@ -587,6 +591,8 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
     hw = WorldIO{wl->w.circles, (size_t)wl->w.P.world_rows * (size_t)wl->w.P.C * 3 * 8, wl->ranges_traj, wl->w.segments,
                  wl->w.family >= f110qp::WORLD_WALLS ? (size_t)wl->w.Wl.wall_rows * (size_t)wl->w.Wl.S * 4 * 8 : 0,
                  wl->w.grid, wl->w.family == f110qp::WORLD_GRID ? (size_t)wl->w.Gr.W * (size_t)wl->w.Gr.H : 0};
+  // f110qp_rollout_field: d2 and the transform's scratch, [H][W] int each, device only
+  if (wl && wl->w.field) hw.field_bytes = 2 * hw.grid_bytes * sizeof(int);
   if (cl) dcl = *cl;
   stage::replan_fields(L, io, &d, r, &dr, *cfg.sc, (size_t)cfg.K.T, (size_t)cfg.K.P, (size_t)cfg.rp->num_waypoints,
                        wl ? &hw : nullptr, &dw, cl ? &cl->io : nullptr, &dcl.io);
@@ -598,6 +604,12 @@ static int replan_host(f110qp_ctx* c, const LoopCfg& cfg, const RolloutIO& io, c
     dwl.ranges_traj = dw.ranges_traj;
     dwl.w.segments = dw.segments;
     dwl.w.grid = dw.grid;
+    if (dw.field) {  // the map's field, once, in front of the first tick
+      dwl.w.d2 = dw.field;
+      const hipError_t e = f110qp::launch_grid_distance(dwl.w.Gr.W, dwl.w.Gr.H, dw.grid, dw.field, nullptr,
+                                                        dw.field + hw.grid_bytes, s);
+      if (e != hipSuccess) return hip_fail(e, "grid distance launch");
+    }
   }
   if ((rv = replan_ticks(c, cfg, d, dr, s, wl ? &dwl : nullptr, cl ? &dcl : nullptr))) return rv;
   return stage_out(c, L, s);
@@ -646,10 +658,12 @@ struct WorldCfgs {
 
 // The world of a cast, a clearance or a world rollout, checked in the one order all of them share, into *w;
 // contact: the call also reads k.cc, whose turn is behind the race's. sc null: no scan geometry (clearances).
-// The clearances (sc null) never read the noise: theirs is not checked.
+// The clearances (sc null) never read the noise: theirs is not checked. field: the casts read d2 by rule F1, whose
+// two rules come behind the grid's; own_d2: the call computes d2 itself (f110qp_rollout_field) and takes none.
 static int world_of(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const WorldCfgs& k, bool contact, int batch,
                     const double* circles, const double* segments, f110qp::World* w,
-                    const unsigned char* grid = nullptr) {
+                    const unsigned char* grid = nullptr, bool field = false, const int* d2 = nullptr,
+                    bool own_d2 = false) {
   int rv = world_params(sc, k.wc, batch, circles, &w->P);
   if (rv) return rv;
   if (fam >= f110qp::WORLD_RACE && (rv = race_params(k.race, batch, k.wc->num_circles, &w->Q))) return rv;
@@ -664,6 +678,15 @@ static int world_of(f110qp::WorldFamily fam, const f110qp_scan_config* sc, const
       (rv = grid_params(k.grid, (long long)k.wc->num_circles + k.race->group_size + k.walls->num_segments, grid,
                         &w->Gr)))
     return rv;
+  if (field) {
+    if (k.grid->width > F110QP_FIELD_MAX_SIDE || k.grid->height > F110QP_FIELD_MAX_SIDE)
+      return fail(F110QP_ERR_INVALID, "grid width and height must be <= 32768 for the distance field");
+    if (!own_d2 && (long long)k.grid->width * k.grid->height > 0 && !d2)
+      return fail(F110QP_ERR_INVALID, "width * height > 0 needs d2");
+  }
+  w->field = field;
+  w->d2 = field ? d2 : nullptr;
+  w->visits = nullptr;
   w->grid = fam == f110qp::WORLD_GRID ? grid : nullptr;
   w->family = fam;
   w->circles = circles;
@@ -688,12 +711,13 @@ static WorldArrays world_arrays(int batch, const double* table, const double* wp
 // f110qp_rollout_<family>[_dev] of the eight world families: the family's row f and the configs k it reads.
 static int world_call(f110qp_ctx* c, const WorldRow& f, LoopCfg cfg, const WorldCfgs& k, WorldArrays a,
                       const double* circles, const double* segments, float* rgt, Where w,
-                      const unsigned char* grid = nullptr) {
+                      const unsigned char* grid = nullptr, const int* d2 = nullptr) {
   WorldLoop wl{};
   int rv = check_args(c, &cfg, &a.io, nullptr, nullptr, &a.r);
   if (rv) return rv;
   const bool contact = f.cc;
-  if ((rv = world_of(f.world, cfg.sc, k, contact, a.io.B, circles, segments, &wl.w, grid))) return rv;
+  if ((rv = world_of(f.world, cfg.sc, k, contact, a.io.B, circles, segments, &wl.w, grid, f.field, d2, w.host)))
+    return rv;
   if (f.rf && (rv = refresh_params(k.rf, &wl.every))) return rv;
   if (a.io.B == 0) return F110QP_OK;
   if (contact && (!a.k.clear_traj || !a.k.crash_tick))
@@ -705,17 +729,18 @@ static int world_call(f110qp_ctx* c, const WorldRow& f, LoopCfg cfg, const World
   return w.host ? replan_host(c, cfg, a.io, a.r, &wl, clp) : replan_ticks(c, cfg, a.io, a.r, w.stream, &wl, clp);
 }
 
-// f110qp_cast_scans[_race|_body|_walls|_noisy|_grid]_dev on the configs k their family reads; tick: rule Z3's t of
-// the noisy and grid casts (0 elsewhere).
+// f110qp_cast_scans[_race|_body|_walls|_noisy|_grid]_dev and f110qp_grid_cast_dev (row::field: d2 and visits) on the
+// configs k their family reads; tick: rule Z3's t of the noisy and grid casts (0 elsewhere).
 static int cast_call(const WorldRow& f, const f110qp_scan_config* sc, const WorldCfgs& k, int batch,
                      const int* list, const int* count, const double* x, const double* circles,
                      const double* segments, float* ranges, void* stream, int tick = 0,
-                     const unsigned char* grid = nullptr) {
+                     const unsigned char* grid = nullptr, const int* d2 = nullptr, int* visits = nullptr) {
   int rv = check_scan_config(sc, false, 0);
   if (rv) return rv;
   if (batch < 0) return fail(F110QP_ERR_INVALID, "batch < 0");
   f110qp::World w{};
-  if ((rv = world_of(f.world, sc, k, false, batch, circles, segments, &w, grid))) return rv;
+  if ((rv = world_of(f.world, sc, k, false, batch, circles, segments, &w, grid, f.field, d2))) return rv;
+  w.visits = visits;
   if (tick < 0) return fail(F110QP_ERR_INVALID, "tick < 0");
   w.Z.tick = tick;
   if ((list != nullptr) != (count != nullptr))
@@ -1387,6 +1412,51 @@ int f110qp_rollout_grid(f110qp_ctx* c, const f110qp_rollout_config* rc, const f1
                                      bgt, poset, clt, nrt, crash);
   const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls).Refresh(rf).Noise(noise).Grid(gc);
   return world_call(c, row::grid, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_host(), grid);
+}
+
+// ---- the raster map's casts through its distance field (f110qp_grid_cast_dev, f110qp_rollout_field[_dev]) ------
+
+int f110qp_grid_cast_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc, const f110qp_race_config* race,
+                         const f110qp_body_config* body, const f110qp_walls_config* walls,
+                         const f110qp_noise_config* noise, const f110qp_grid_config* gc, int batch, int tick,
+                         const int* list, const int* count, const double* x, const double* circles,
+                         const double* segments, const unsigned char* grid, const int* d2, float* ranges, int* visits,
+                         void* stream) {
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Body(body).Walls(walls).Noise(noise).Grid(gc);
+  return cast_call(row::field, sc, k, batch, list, count, x, circles, segments, ranges, stream, tick, grid, d2, visits);
+}
+
+int f110qp_rollout_field_dev(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                             const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                             const f110qp_race_config* race, const f110qp_contact_config* cc,
+                             const f110qp_body_config* body, const f110qp_walls_config* walls,
+                             const f110qp_refresh_config* rf, const f110qp_noise_config* noise,
+                             const f110qp_grid_config* gc, int batch, const double* table, const double* wp,
+                             double* xr, int* have, const double* circles, const double* segments,
+                             const unsigned char* grid, const int* d2, double* xt, double* ult, float* ua, int* stt,
+                             int* itt, double* cot, float* up, float* xp, float* hst, int* kt, int* pst, int* btt,
+                             int* bgt, double* poset, float* rgt, double* clt, int* nrt, int* crash, void* stream) {
+  const WorldArrays a =
+      world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt, bgt, poset, clt, nrt, crash);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls).Refresh(rf).Noise(noise).Grid(gc);
+  return world_call(c, row::field, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_stream(stream), grid,
+                    d2);
+}
+
+int f110qp_rollout_field(f110qp_ctx* c, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                         const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                         const f110qp_race_config* race, const f110qp_contact_config* cc,
+                         const f110qp_body_config* body, const f110qp_walls_config* walls,
+                         const f110qp_refresh_config* rf, const f110qp_noise_config* noise,
+                         const f110qp_grid_config* gc, int batch, const double* table, const double* wp, double* xr,
+                         int* have, const double* circles, const double* segments, const unsigned char* grid, double* xt,
+                         double* ult, float* ua, int* stt, int* itt, double* cot, float* up, float* xp, float* hst,
+                         int* kt, int* pst, int* btt, int* bgt, double* poset, float* rgt, double* clt, int* nrt,
+                         int* crash) {
+  const WorldArrays a =
+      world_arrays(batch, table, wp, xr, have, xt, ult, ua, stt, itt, cot, up, xp, hst, kt, pst, btt, bgt, poset, clt, nrt, crash);
+  const WorldCfgs k = WorldCfgs{wc}.Race(race).Contact(cc).Body(body).Walls(walls).Refresh(rf).Noise(noise).Grid(gc);
+  return world_call(c, row::field, LoopCfg{kWorld, rc, sc, rp}, k, a, circles, segments, rgt, on_host(), grid);
 }
 
 }  // extern "C"

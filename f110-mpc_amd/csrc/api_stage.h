@@ -73,6 +73,9 @@ struct WorldIO {
   // the grid family's, trailing likewise
   const unsigned char* grid;  // [H][W] or null
   size_t grid_bytes;          // 0: no map (the field is then not declared)
+  // f110qp_rollout_field's, trailing likewise: the map's distance field and its scratch, device only
+  int* field;          // [2][H][W]; the host side is null
+  size_t field_bytes;  // 0: not declared
 };
 
 // What the contact rollout records on top of the race rollout's arrays.
@@ -84,7 +87,7 @@ struct ContactIO {
 
 namespace stage {
 
-enum Dir { kIn = 1, kOut = 2, kInOut = 3 };
+enum Dir { kWork = 0, kIn = 1, kOut = 2, kInOut = 3 };  // kWork: device only, no copy either way
 
 // One array of a host-pointer call. row0 > 0 (the [T+1] trajectories): the leading row0 bytes are the
 // caller's row 0, which is uploaded and not copied back; the rest is copied back and not uploaded.
@@ -181,6 +184,7 @@ inline void replan_fields(Layout& L, const RolloutIO& h, RolloutIO* d, const Rep
   L.add(w->segments, &dw->segments, w->segment_bytes, true, kIn);
   L.add(w->ranges_traj, &dw->ranges_traj, TB * nr * 4, w->ranges_traj, kOut);
   if (w->grid_bytes) L.add(w->grid, &dw->grid, w->grid_bytes, true, kIn);  // only the grid family declares it
+  if (w->field_bytes) L.add(w->field, &dw->field, w->field_bytes, true, kWork);  // only f110qp_rollout_field
   if (!k) return;
   *dk = *k;
   L.add(k->clear_traj, &dk->clear_traj, (T + 1) * B * 8, true, kOut);

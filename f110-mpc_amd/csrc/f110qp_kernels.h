@@ -455,6 +455,11 @@ struct World {
   const double* segments;
   GridParams Gr;  // WORLD_GRID alone, as is grid
   const unsigned char* grid;
+  // the cast alone: rule F1 in place of rule G1 (f110qp_grid_cast_dev). d2 [H][W] is grid's field (null without a
+  // map), visits [B][nr] or null the cells of d2 each beam read
+  bool field;
+  const int* d2;
+  int* visits;
 };
 
 // Grid caps: one 256-thread workgroup per car, one wave on each of a CU's four SIMDs, up to what the MI355X's
@@ -469,6 +474,7 @@ struct World {
 //              noisy 191 (192) -> 2 -> 512: the walls' caps, and its clearance is the walls instantiation
 //   grid       cast 216 -> 2 -> 512, with 65,152 B of LDS (the cast's 44,032 B and the 21,120 B square of cell bits):
 //              two workgroups in a CU's 160 KB, the same two; clearance 195 (200) -> 2 -> 512, 640 B
+//              the field cast (World::field) 213 (216) -> 2 -> 512, 44,032 B: the grid row's cap
 // Nothing spills a VGPR and no kernel has scratch.
 constexpr struct {
   int cast, clearance;

@@ -122,6 +122,116 @@ __device__ __forceinline__ bool grid_walk(const GridParams& G, const unsigned ch
   return false;
 }
 
+// Rule F1's start, uniform over the workgroup: grid_start with the cell's occupancy read from the field, whose
+// value at the start cell goes into D (states 1 and 2).
+#pragma clang fp contract(off)
+__device__ __forceinline__ GridStart grid_field_start(const GridParams& G, const int* __restrict__ d2,
+                                                      const double ox, const double oy, int& D) {
+  GridStart s{};
+  s.px = (ox - G.ox) / G.res;
+  s.py = (oy - G.oy) / G.res;
+  if (!(s.px >= 0.0 && s.px < (double)G.W && s.py >= 0.0 && s.py < (double)G.H)) return s;
+  s.ix = (int)floor(s.px);
+  s.iy = (int)floor(s.py);
+  D = d2[(size_t)s.iy * (size_t)G.W + (size_t)s.ix];
+  s.state = D <= 0 ? 1 : 2;
+  return s;
+}
+
+// Is p / g <= q / h (or, with `strict`, <) for the correctly rounded quotients, p / g and q / h both >= 0 and
+// finite? The products with the reciprocals are within 2^-51 (relative) of the quotients, so a gap of more than
+// 2^-48 between them decides; inside it the quotients themselves are compared.
+#pragma clang fp contract(off)
+__device__ __forceinline__ bool grid_quot_before(const double p, const double g, const double rg, const double q,
+                                                 const double h, const double rh, const bool strict) {
+  const double k = 0x1.0000000000010p+0;  // 1 + 2^-48
+  const double a = p * rg, b = q * rh;
+  if (a * k < b) return true;
+  if (b * k < a) return false;
+  return strict ? p / g < q / h : p / g <= q / h;
+}
+
+// Rule F1 for one beam of a start in state 2 whose cell holds D > 0 in the field: grid_walk's result and bits
+// with the cells between two reads of d2 jumped over. After A x-moves and B y-moves the walk's next boundaries
+// are X(A) = ((double)(kx + sx A) - px) / gx and Y(B) likewise, rule G1's expressions on the integer boundary, both
+// non-decreasing; the walk stands at (A, B) with A + B = n exactly when (A == 0 or X(A - 1) <= Y(B)) and
+// (B == 0 or Y(B - 1) < X(A)), and the parameter of its last move is max(X(A - 1), Y(B - 1)). A jump estimates A
+// from the real-valued crossing counts, moves it by one while a condition fails (kGridJumpFix times at most:
+// the estimate is a move or two off at worst), and past that takes the m moves singly. visits counts the
+// reads of d2, the start cell's among them.
+constexpr int kGridJumpFix = 4;
+#pragma clang fp contract(off)
+__device__ __forceinline__ bool grid_field_walk(const GridParams& G, const int* __restrict__ d2, const GridStart& s,
+                                                int D, const double dx, const double dy, const double limit,
+                                                double& th, int& visits) {
+  const double gx = dx / G.res, gy = dy / G.res;
+  const int sx = dx > 0.0 ? 1 : -1, sy = dy > 0.0 ? 1 : -1;
+  const bool mx = dx > 0.0 || dx < 0.0, my = dy > 0.0 || dy < 0.0;
+  const int kx = dx > 0.0 ? s.ix + 1 : s.ix, ky = dy > 0.0 ? s.iy + 1 : s.iy;
+  // the numerators of X(k) and Y(l): exact differences of an int and px up to one rounding, as the walk's
+  auto nx = [&](const int k) { return (double)(kx + sx * k) - s.px; };
+  auto ny = [&](const int l) { return (double)(ky + sy * l) - s.py; };
+  visits = 1;
+  if (!mx && !my) return false;  // the walk's first step: t = +inf (a direction that is not finite)
+  // the estimate's constants: the crossings by parameter t are about (t - X(0)) |gx| + 1 and (t - Y(0)) |gy| + 1
+  const double ax = fabs(gx), ay = fabs(gy), rgx = 1.0 / gx, rgy = 1.0 / gy;
+  const double x0 = mx ? nx(0) * rgx : 0.0, y0 = my ? ny(0) * rgy : 0.0;
+  const double c0 = x0 * ax + y0 * ay, rs = 1.0 / (ax + ay);
+  int A = 0, B = 0;
+  for (long long left = (long long)G.W + G.H + 2; left > 0;) {
+    int m = (int)__dsqrt_rn((double)(D - 1));  // the largest m with m m < D
+    m = max(m, 1);
+    if ((long long)m > left) m = (int)left;
+    left -= m;
+    const int n = A + B + m;
+    int a;
+    if (!mx) {
+      a = 0;
+    } else if (!my) {
+      a = n;
+    } else {
+      const double te = ((double)(n - 1) + c0) * rs;
+      const double ae = floor((te - x0) * ax) + 1.0;
+      a = (int)fmin(fmax(ae, (double)A), (double)(A + m));
+      int fix = 0;
+      for (; fix < kGridJumpFix; fix++) {
+        const int b = n - a;
+        if (a > 0 && !grid_quot_before(nx(a - 1), gx, rgx, ny(b), gy, rgy, false)) {
+          a--;  // the last x-move comes after the next y-move: one x-move too many
+        } else if (b > 0 && !grid_quot_before(ny(b - 1), gy, rgy, nx(a), gx, rgx, true)) {
+          a++;  // the last y-move does not come before the next x-move: one y-move too many
+        } else {
+          break;
+        }
+      }
+      if (fix == kGridJumpFix) {  // the m moves singly, from (A, B)
+        a = A;
+        int b = B;
+        for (int k = 0; k < m; k++) {
+          if (nx(a) / gx <= ny(b) / gy)
+            a++;
+          else
+            b++;
+        }
+      }
+    }
+    A = a;
+    B = n - a;
+    const double tx = A > 0 ? nx(A - 1) / gx : 0.0, ty = B > 0 ? ny(B - 1) / gy : 0.0;
+    const double t = A > 0 && B > 0 ? fmax(tx, ty) : A > 0 ? tx : ty;
+    if (!(t <= limit)) return false;  // past the range, or NaN
+    const long long ix = (long long)s.ix + (long long)sx * A, iy = (long long)s.iy + (long long)sy * B;
+    if (ix < 0 || ix >= G.W || iy < 0 || iy >= G.H) return false;
+    D = d2[(size_t)iy * (size_t)G.W + (size_t)ix];
+    visits++;
+    if (D <= 0) {
+      th = t + 0.0;  // a -0 (0 / g on a boundary, g < 0) becomes +0
+      return true;
+    }
+  }
+  return false;
+}
+
 // Rule G2 for one occupied cell (i, j) against the body (qx, qy, c, s): the least of rule W2 over the cell's four
 // edges in the rule's order, and 0 at most when the body's centre is in the cell.
 #pragma clang fp contract(off)

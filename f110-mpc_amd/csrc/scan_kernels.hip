@@ -62,6 +62,12 @@
 // its hit into the minimum with a plain store: a beam has one walker. A square that does not fit
 // kGridWinWords is not packed and the walk reads the map's bytes from global memory (L2): the same walk, the
 // same bits. No launch is added. Every grid statement is behind `if constexpr`.
+//
+// The map through its field (FIELD, grid_cast_kernel): the grid cast with rule F1 in place of rule G1. A beam's
+// walker reads d2 where it stands and jumps isqrt(d2 - 1) cells, no cell of which can be occupied, so its cost
+// follows the free space and not the beam's length. The cells are d2's ints from global memory (L2): no square is
+// packed and the 21 KB of LDS come back. Beams of a wave jump different lengths; the loop runs until the last is
+// done. Every field statement is behind `if constexpr`.
 #include <hip/hip_runtime.h>
 
 #include "body_geom.h"
@@ -223,7 +229,7 @@ __device__ __forceinline__ float noise_beam(const float r, const unsigned long l
 }
 
 #pragma clang fp contract(off)
-template <bool RACE, bool BODY, bool WALLS, bool NOISE, bool GRID = false>
+template <bool RACE, bool BODY, bool WALLS, bool NOISE, bool GRID = false, bool FIELD = false>
 __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& Q, const BodyParams& H,
                                          const WallParams& Wl, const NoiseParams& Z, const int b,
                                          const double* __restrict__ x,
@@ -232,11 +238,13 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
                                          unsigned long long* s_min, typename SlotOf<BODY>::type* s_slot,
                                          const GridParams& Gp = GridParams{},
                                          const unsigned char* __restrict__ grid = nullptr,
-                                         unsigned* s_win = nullptr) {
+                                         unsigned* s_win = nullptr, const int* __restrict__ d2 = nullptr,
+                                         int* __restrict__ visits = nullptr) {
   static_assert(RACE || !BODY, "bodies are the race-mates'");
   static_assert(BODY || !WALLS, "walls come with the body cast");
   static_assert(WALLS || !NOISE, "the noise comes with the walls cast");
   static_assert(NOISE || !GRID, "the raster map comes with the noisy cast");
+  static_assert(GRID || !FIELD, "the field is the raster map's");
   using Slot = typename SlotOf<BODY>::type;
   const int tid = threadIdx.x;
   const double ori = x[(size_t)b * 3 + 2];
@@ -269,7 +277,10 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
   }
   GridStart gs{};  // rule G1's start and the LDS square of this car: uniform over the workgroup
   GridWindow gw{};
-  if constexpr (GRID) {
+  int d0 = 0;  // FIELD: d2 at the start cell
+  if constexpr (FIELD) {
+    if (d2) gs = grid_field_start(Gp, d2, ox, oy, d0);
+  } else if constexpr (GRID) {
     if (grid) gs = grid_start(Gp, grid, ox, oy);
     gw.bits = s_win;
     if (gs.state == 2) {
@@ -379,7 +390,24 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
       }
       __syncthreads();
     }
-    if constexpr (GRID) {  // rule G1: one walker a beam, behind the last tile's barrier (or the directions')
+    if constexpr (FIELD) {  // rule F1: one walker a beam, as below; visits is the walker's own store too
+      int* vis = visits ? visits + (size_t)b * (size_t)nr + cb : nullptr;
+      if (gs.state != 2) {
+        for (int i = tid; i < nb; i += kCastThreads) {
+          if (gs.state == 1) s_min[i] = 0ull;
+          if (vis) vis[i] = gs.state;  // 0 reads outside the map, 1 in an occupied cell
+        }
+      } else {
+        for (int i = tid; i < nb; i += kCastThreads) {
+          const double cur = __longlong_as_double((long long)s_min[i]);
+          double th;
+          int v;
+          if (grid_field_walk(Gp, d2, gs, d0, s_dx[i], s_dy[i], cur, th, v) && th < cur)
+            s_min[i] = (unsigned long long)__double_as_longlong(th);
+          if (vis) vis[i] = v;
+        }
+      }
+    } else if constexpr (GRID) {  // rule G1: one walker a beam, behind the last tile's barrier (or the directions')
       if (gs.state == 1) {
         for (int i = tid; i < nb; i += kCastThreads) s_min[i] = 0ull;
       } else if (gs.state == 2) {
@@ -405,7 +433,7 @@ __device__ __forceinline__ void cast_one(const CastParams& P, const RaceParams& 
 
 // Workgroup w takes cars w, w + nwg, ... below B, or with a list the cars list[w], list[w + nwg], ...
 // below min(*count, B) (plan_listed_kernel's rule: one past the count leaves at that load).
-template <bool RACE, bool BODY = false, bool WALLS = false, bool NOISE = false, bool GRID = false>
+template <bool RACE, bool BODY = false, bool WALLS = false, bool NOISE = false, bool GRID = false, bool FIELD = false>
 __device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams& Q, const BodyParams& H, const int B,
                                            const int nwg, const int* __restrict__ list,
                                            const int* __restrict__ count, const double* __restrict__ x,
@@ -414,13 +442,14 @@ __device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams
                                            const double* __restrict__ segments = nullptr,
                                            const NoiseParams& Z = NoiseParams{},
                                            const GridParams& Gp = GridParams{},
-                                           const unsigned char* __restrict__ grid = nullptr) {
+                                           const unsigned char* __restrict__ grid = nullptr,
+                                           const int* __restrict__ d2 = nullptr, int* __restrict__ visits = nullptr) {
   __shared__ double s_dx[kCastBeamTile];
   __shared__ double s_dy[kCastBeamTile];
   __shared__ unsigned long long s_min[kCastBeamTile];
   __shared__ typename SlotOf<BODY>::type s_slot[kCastCircleTile];
   unsigned* s_win = nullptr;
-  if constexpr (GRID) {
+  if constexpr (GRID && !FIELD) {
     __shared__ unsigned s_bits[kGridWinWords];
     s_win = s_bits;
   }
@@ -428,7 +457,10 @@ __device__ __forceinline__ void cast_scans(const CastParams& P, const RaceParams
   for (int k = blockIdx.x; k < n; k += nwg) {
     const int b = list ? list[k] : k;
     if (b >= 0 && b < B) {  // uniform over the workgroup
-      if constexpr (GRID)
+      if constexpr (FIELD)
+        cast_one<RACE, BODY, WALLS, NOISE, true, true>(P, Q, H, Wl, Z, b, x, circles, segments, ranges, s_dx, s_dy,
+                                                       s_min, s_slot, Gp, nullptr, nullptr, d2, visits);
+      else if constexpr (GRID)
         cast_one<RACE, BODY, WALLS, NOISE, true>(P, Q, H, Wl, Z, b, x, circles, segments, ranges, s_dx, s_dy, s_min,
                                                  s_slot, Gp, grid, s_win);
       else
@@ -490,6 +522,16 @@ __global__ __launch_bounds__(kCastThreads) void cast_scans_grid_kernel(
   cast_scans<true, true, true, true, true>(P, Q, H, B, nwg, list, count, x, circles, ranges, Wl, segments, Z, Gp, grid);
 }
 
+// The grid cast with rule F1 on the map's field d2 in place of rule G1 on its bytes (FIELD); visits [B][nr] or null.
+__global__ __launch_bounds__(kCastThreads) void grid_cast_kernel(
+    const CastParams P, const RaceParams Q, const BodyParams H, const WallParams Wl, const NoiseParams Z,
+    const GridParams Gp, const int B, const int nwg, const int* __restrict__ list, const int* __restrict__ count,
+    const double* __restrict__ x, const double* __restrict__ circles, const double* __restrict__ segments,
+    const int* __restrict__ d2, float* __restrict__ ranges, int* __restrict__ visits) {
+  cast_scans<true, true, true, true, true, true>(P, Q, H, B, nwg, list, count, x, circles, ranges, Wl,
+                                                 segments, Z, Gp, nullptr, d2, visits);
+}
+
 int cast_scans_grid(WorldFamily family, int B) {
   const int cap = kWorldGrids[family].cast;
   return B < cap ? B : cap;
@@ -500,7 +542,10 @@ hipError_t launch_cast_scans(const World& w, int B, const int* list, const int* 
   if (B <= 0) return hipSuccess;
   const int nwg = cast_scans_grid(w.family, B);
   const dim3 grid(nwg), block(kCastThreads);
-  if (w.family == WORLD_GRID)
+  if (w.family == WORLD_GRID && w.field)
+    hipLaunchKernelGGL(grid_cast_kernel, grid, block, 0, s, w.P, w.Q, w.H, w.Wl, w.Z, w.Gr, B, nwg, list, count, x,
+                       w.circles, w.segments, w.Gr.W > 0 && w.Gr.H > 0 ? w.d2 : nullptr, ranges, w.visits);
+  else if (w.family == WORLD_GRID)
     hipLaunchKernelGGL(cast_scans_grid_kernel, grid, block, 0, s, w.P, w.Q, w.H, w.Wl, w.Z, w.Gr, B, nwg, list, count,
                        x, w.circles, w.segments, w.Gr.W > 0 && w.Gr.H > 0 ? w.grid : nullptr, ranges);
   else if (w.family == WORLD_NOISY)

@@ -173,6 +173,9 @@ EXPORTED = (
     "f110qp_grid_lookup_dev",
     "f110qp_grid_field",
     "f110qp_wall_distance",
+    "f110qp_grid_cast_dev",
+    "f110qp_rollout_field_dev",
+    "f110qp_rollout_field",
 )
 FIELD_MAX_SIDE = 32768  # F110QP_FIELD_MAX_SIDE
 MC_MAX_HYPOTHESES = 4096  # F110QP_MC_MAX_HYPOTHESES
@@ -376,14 +379,18 @@ def _families(upto: str, kind: str = "rollout"):
     return [f for f in WORLD_FAMILIES[:n] if kind not in f.skips]
 
 
-def _abi(kind: str, upto: str, dev: bool = True):
+def _abi(kind: str, upto: str, dev: bool = True, field: bool = False):
     """The parameters of family `upto`'s entry point of `kind` ("rollout", "cast", "clearance") in the ABI's order,
-    under their public names (dev: the call takes a stream)."""
+    under their public names (dev: the call takes a stream). field: the grid family's calls through the map's
+    distance field (f110qp_grid_cast_dev, f110qp_rollout_field_dev), with d2 behind grid and, the cast, visits behind
+    ranges."""
     fams = _families(upto, kind)
     cfgs, arrays = [f.arg for f in fams], [f.array for f in fams if f.array]
+    if field:
+        arrays.append("d2")
     if kind == "cast":
         return ["sc", *cfgs, "batch", *(["tick"] if any(f.tick for f in fams) else []), "list_", "count", "x", *arrays,
-                "ranges", "stream"]
+                "ranges", *(["visits"] if field else []), "stream"]
     if kind == "clearance":
         return [*cfgs, "batch", "rows", "x", *arrays, "clearance", "nearest", "stream"]
     return ["ctx", "rc", "sc", "rp", *cfgs, "batch", "table", "waypoints", "x_ref", "have_path", *arrays, *_TRAJ, *_REC,
@@ -491,6 +498,10 @@ def load(test: bool = False):
                                   (f"f110qp_rollout_{f.name}", "rollout", False), (f.clearance, "clearance", True)):
             if symbol:
                 getattr(L, symbol).argtypes = [_CTYPES.get(n, fp) for n in _abi(kind, f.name, dev)]
+    # the grid family's calls through the map's field: its lists with the one more array (the host call: its own)
+    L.f110qp_grid_cast_dev.argtypes = [_CTYPES.get(n, fp) for n in _abi("cast", "grid", field=True)]
+    L.f110qp_rollout_field_dev.argtypes = [_CTYPES.get(n, fp) for n in _abi("rollout", "grid", field=True)]
+    L.f110qp_rollout_field.argtypes = [_CTYPES.get(n, fp) for n in _abi("rollout", "grid", dev=False)]
     rcp = C.POINTER(RaceConfig)
     L.f110qp_path_lengths.argtypes = [fp, C.c_int, fp]
     L.f110qp_progress_dev.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_int] + [fp] * 4
@@ -705,6 +716,12 @@ def _grid_spec(gc, grid):
         raise F110QPError("grid_cfg must be a GridConfig")
     n = max(int(gc.width), 0) * max(int(gc.height), 0)
     return (grid, "u8", n, "grid", n == 0)
+
+
+def _field_spec(gc, d2):
+    """The _devs spec of the map's distance field d2 [H,W] i32 (None for an empty map)."""
+    n = max(int(gc.width), 0) * max(int(gc.height), 0)
+    return (d2, "i32", n, "d2", n == 0)
 
 
 def _wall_spec(walls, segments):
@@ -1307,8 +1324,9 @@ class Solver:
 
     # ---- the world families: one device body and one host body, both walking WORLD_FAMILIES -----------------------
 
-    def _world_dev(self, family, a):
-        """The body of the eight rollout_<family>_dev; a: the wrapper's arguments by name."""
+    def _world_dev(self, family, a, field=False):
+        """The body of the eight rollout_<family>_dev; a: the wrapper's arguments by name. field: rollout_field_dev,
+        the grid family's body with d2 behind grid."""
         fams = _families(family)
         _check_cfgs(fams[1:], a, whole=True)
         T, B = self._dev_loop(a["rc"], a["x_ref"], a["x_traj"])
@@ -1321,17 +1339,20 @@ class Solver:
         for f in fams[1:]:
             more += [(a[r.name], r.dtype, (T + 1) * B if r.per_row else B, r.name, r.optional) for r in f.records]
             more += _world_specs([f], a)
+        if field:
+            more.append(_field_spec(a["grid_cfg"], a["d2"]))
         _devs(*self._plan_specs(a["rp"], B, a["table"], a["waypoints"], a["x_ref"], a["have_path"]),
               *_world_specs(fams[:1], a), *self._traj_specs(T, B, *(a[n] for n in _TRAJ)),
               *self._record_specs(T, B, *(a[n] for n in _REC)),
               (a["ranges_traj"], "f32", T * B * int(a["sc"].num_ranges), "ranges_traj", True), *more)
-        name = f"f110qp_rollout_{family}_dev"
+        name = "f110qp_rollout_field_dev" if field else f"f110qp_rollout_{family}_dev"
         call = {**a, "ctx": self._h, "batch": B, "stream": self._stream(a["stream"], a["x_traj"])}
-        self._chk(getattr(self.lib, name)(*_abi_args(_abi("rollout", family), call)), name)
+        self._chk(getattr(self.lib, name)(*_abi_args(_abi("rollout", family, field=field), call)), name)
 
-    def _world_host(self, family, a):
+    def _world_host(self, family, a, name=None):
         """The body of the eight rollout_<family>; a: the wrapper's arguments by name. The world config's counts and
-        the walls config come from the arrays' shapes."""
+        the walls config come from the arrays' shapes. name: another symbol with the family's parameter list
+        (f110qp_rollout_field)."""
         fams = _families(family)
         _check_cfgs([f for f in fams[1:] if f.array != "segments"], a, whole=True)
         T, B, x0, ul = self._host_start(a["x0"], a["u_lin"], a["ticks"])
@@ -1351,7 +1372,7 @@ class Solver:
         for r in records:
             if not r.optional or a[r.name[:-len("_traj")]]:
                 out[r.name] = np.empty((T + 1, B) if r.per_row else B, {"f64": np.float64, "i32": np.int32}[r.dtype])
-        name = f"f110qp_rollout_{family}"
+        name = name or f"f110qp_rollout_{family}"
         self._chk(getattr(self.lib, name)(
             self._h, C.byref(self._ticks_config(a["rc"], T)), C.byref(a["sc"]), C.byref(a["rp"]), *cfgs, B, _p(tab),
             _p(wp) if wp.shape[0] else None, _p(xr), _p(hv), *world, *self._out_args(out), _p(out.get("ranges_traj")),
@@ -1440,6 +1461,18 @@ class Solver:
         for an empty map) follows segments, everything else as there."""
         self._world_dev("grid", locals())
 
+    def rollout_field_dev(self, rc: RolloutConfig, sc: ScanConfig, rp: ReplanConfig, wc: WorldConfig, race: RaceConfig,
+                          cc: ContactConfig, body: BodyConfig, walls: WallsConfig, rf: RefreshConfig,
+                          noise: NoiseConfig, grid_cfg: GridConfig, table, waypoints, x_ref, have_path, circles,
+                          segments, grid, d2, x_traj, u_lin_traj, u_applied, status_traj, clear_traj, crash_tick,
+                          nearest_traj=None, iters_traj=None, cost_traj=None, u_plan=None, x_plan=None, hs_traj=None,
+                          kind_traj=None, plan_status_traj=None, best_traj_traj=None, best_global_traj=None,
+                          pose_traj=None, ranges_traj=None, stream=None):
+        """rollout_grid_dev with every cast grid_cast_dev's (f110qp_rollout_field_dev, rule F1): d2 [H,W] i32, the
+        field grid_distance_dev wrote for grid (None for an empty map), follows grid; the clearances still read
+        grid. The same bits in every array."""
+        self._world_dev("grid", locals(), field=True)
+
     def rollout_world(self, x0, u_lin, circles, sc: ScanConfig, rp: ReplanConfig, table, waypoints, ticks,
                       wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False, rows=True,
                       scans=False, rc=None):
@@ -1498,6 +1531,14 @@ class Solver:
         """rollout_noisy() on a raster map (f110qp_rollout_grid, synchronous): grid [H,W] uint8 (nonzero occupied)
         and grid_cfg follow segments, everything else as there."""
         return self._world_host("grid", locals())
+
+    def rollout_field(self, x0, u_lin, circles, segments, grid, grid_cfg: GridConfig, race: RaceConfig, cc: ContactConfig,
+                      body: BodyConfig, rf: RefreshConfig, noise: NoiseConfig, sc: ScanConfig, rp: ReplanConfig, table,
+                      waypoints, ticks, wc: WorldConfig = None, x_ref=None, have_path=None, plans=False, objective=False,
+                      rows=True, scans=False, nearest=True, rc=None):
+        """rollout_grid() with every cast through the map's distance field (f110qp_rollout_field, synchronous): the
+        same arguments and the same bits; the field is computed on the device once, before the first tick."""
+        return self._world_host("grid", locals(), "f110qp_rollout_field")
 
     def warm_reset(self):
         self._chk(self.lib.f110qp_warm_reset(self._h), "f110qp_warm_reset")
@@ -1563,8 +1604,9 @@ def plan_listed_dev(rp: ReplanConfig, sc: ScanConfig, list_, count, pose, ranges
                                          _tp(best_global), C.c_void_p(stream.cuda_stream)), "f110qp_plan_listed_dev")
 
 
-def _cast_scans(family, a):
-    """The body of the six cast_scans*_dev; a: the wrapper's arguments by name."""
+def _cast_scans(family, a, field=False):
+    """The body of the six cast_scans*_dev; a: the wrapper's arguments by name. field: grid_cast_dev, the grid
+    family's body with d2 behind grid and visits behind ranges."""
     import torch
 
     fams = _families(family, "cast")
@@ -1573,12 +1615,15 @@ def _cast_scans(family, a):
     B = int(x.shape[0])
     if fams[1:]:
         _check_race(a["race"], B)
+    more = []
+    if field:
+        more = [_field_spec(a["grid_cfg"], a["d2"]), (a["visits"], "i32", B * int(a["sc"].num_ranges), "visits", True)]
     _devs((x, "f64", 3 * B, "x"), *_world_specs(fams, a), (a["ranges"], "f32", B * int(a["sc"].num_ranges), "ranges"),
-          (a["list_"], "i32", B, "list", True), (a["count"], "i32", 1, "count", True))
+          (a["list_"], "i32", B, "list", True), (a["count"], "i32", 1, "count", True), *more)
     stream = a["stream"] if a["stream"] is not None else torch.cuda.current_stream(x.device)
-    name = fams[-1].cast
+    name = "f110qp_grid_cast_dev" if field else fams[-1].cast
     call = {**a, "batch": B, "stream": C.c_void_p(stream.cuda_stream)}
-    _check(getattr(load(), name)(*_abi_args(_abi("cast", family), call)), name)
+    _check(getattr(load(), name)(*_abi_args(_abi("cast", family, field=field), call)), name)
 
 
 def _clearance(family, a):
@@ -1657,6 +1702,16 @@ def cast_scans_grid_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body:
     grid_cfg follows noise, grid [H,W] u8 (nonzero occupied, None for an empty map) follows segments. The oracle is
     workload.ray_map folded into the noise-free scan, then workload.noisy_scan."""
     _cast_scans("grid", locals())
+
+
+def grid_cast_dev(sc: ScanConfig, wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig,
+                  noise: NoiseConfig, grid_cfg: GridConfig, tick, x, circles, segments, grid, d2, ranges, visits=None,
+                  list_=None, count=None, stream=None):
+    """cast_scans_grid_dev with every beam jumping the free space its cell's distance says is there
+    (f110qp_grid_cast_dev, rule F1 of f110qp.h): d2 [H,W] i32, the field grid_distance_dev wrote for grid (None for
+    an empty map), follows grid; visits [B,num_ranges] i32 (optional) is the cells of d2 each beam read. The same
+    bits in ranges. The oracle is workload.ray_field."""
+    _cast_scans("grid", locals(), field=True)
 
 
 def clearance_grid_dev(wc: WorldConfig, race: RaceConfig, body: BodyConfig, walls: WallsConfig, grid_cfg: GridConfig, x,

@@ -13,6 +13,8 @@ All arrays are in the include/f110qp.h layouts (float32, row-major).
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 CAR_LENGTH = 0.35  # src/model.cpp:2
@@ -1160,6 +1162,104 @@ def grid_lookup(x, d2, nearest, cfg):
     near = np.asarray(nearest, np.int32)
     near = near if near.size else np.full((1, 1), -1, np.int32)
     return dist, np.where(ok, near[iy, ix], -1).astype(np.int32)
+
+
+# ---- the raster LiDAR through the field (f110qp_grid_cast_dev, f110qp_rollout_field[_dev]) ----------------------
+# Rule F1 of include/f110qp.h in plain Python floats (IEEE doubles, every operation rounded once), one beam at a
+# time, in csrc/grid_geom.h's expressions and order.
+
+FIELD_JUMP_FIX = 4  # kGridJumpFix: corrections of a jump's estimate before the moves are taken singly
+
+
+def _field_beam(px, py, ix, iy, dx, dy, res, d2, W, H, limit):
+    """Rule F1 for one beam from cell (ix, iy) whose field value is > 0: (th or None, visits)."""
+    inf = math.inf
+    gx, gy = dx / res, dy / res
+    sx, sy = (1 if dx > 0.0 else -1), (1 if dy > 0.0 else -1)
+    mx, my = dx > 0.0 or dx < 0.0, dy > 0.0 or dy < 0.0
+    kx, ky = (ix + 1 if dx > 0.0 else ix), (iy + 1 if dy > 0.0 else iy)
+
+    def X(k):  # the k-th boundary parameter ahead in x: rule G1's expression on the integer boundary
+        return (float(kx + sx * k) - px) / gx if mx else inf
+
+    def Y(k):
+        return (float(ky + sy * k) - py) / gy if my else inf
+
+    visits, D, A, B = 1, int(d2[iy, ix]), 0, 0
+    if not mx and not my:
+        return None, visits
+    ax, ay = abs(gx), abs(gy)
+    x0, y0 = (X(0) if mx else 0.0), (Y(0) if my else 0.0)
+    left = W + H + 2
+    while left > 0:
+        m = min(max(1, math.isqrt(D - 1)), left)
+        left -= m
+        n = A + B + m
+        if not mx:
+            a = 0
+        elif not my:
+            a = n
+        else:
+            te = (n - 1 + x0 * ax + y0 * ay) / (ax + ay)
+            a = int(min(max(math.floor((te - x0) * ax) + 1.0, A), A + m))
+            for _ in range(FIELD_JUMP_FIX):
+                b = n - a
+                if a > 0 and not X(a - 1) <= Y(b):
+                    a -= 1
+                elif b > 0 and not Y(b - 1) < X(a):
+                    a += 1
+                else:
+                    break
+            else:  # the m moves singly
+                a, b = A, B
+                for _ in range(m):
+                    if X(a) <= Y(b):
+                        a += 1
+                    else:
+                        b += 1
+        A, B = a, n - a
+        t = max(X(A - 1), Y(B - 1)) if A > 0 and B > 0 else X(A - 1) if A > 0 else Y(B - 1)
+        if not t <= limit:
+            return None, visits
+        cx, cy = ix + sx * A, iy + sy * B
+        if cx < 0 or cx >= W or cy < 0 or cy >= H:
+            return None, visits
+        D = int(d2[cy, cx])
+        visits += 1
+        if D <= 0:
+            return t + 0.0, visits
+    return None, visits
+
+
+def ray_field(ox, oy, dx, dy, d2, cfg, max_range: float = 10.0):
+    """Rule F1: (ranges float64, visits int32), each the broadcast shape of the arguments, of beams from the origins
+    (ox, oy) along (dx, dy) against the map whose distance field is d2 [H, W] int (grid_distance's, or
+    f110qp_grid_distance_dev's): a beam reads d2 where it stands and jumps isqrt(d2 - 1) cells of rule G1's walk
+    at once. ranges equals ray_grid's bit for bit; visits counts the cells of d2 each beam read."""
+    f = np.asarray(d2)
+    ox, oy, dx, dy = (np.asarray(v, np.float64) for v in np.broadcast_arrays(ox, oy, dx, dy))
+    shape = dx.shape
+    out = np.full(dx.size, float(max_range))
+    vis = np.zeros(dx.size, np.int32)
+    if f.size == 0:
+        return out.reshape(shape), vis.reshape(shape)
+    H, W = f.shape
+    res, x0, y0 = float(cfg.resolution), float(cfg.origin_x), float(cfg.origin_y)
+    limit = float(max_range)
+    for k, (bx, by, ddx, ddy) in enumerate(zip(ox.ravel().tolist(), oy.ravel().tolist(), dx.ravel().tolist(),
+                                               dy.ravel().tolist())):
+        px, py = (bx - x0) / res, (by - y0) / res
+        if not (px >= 0.0 and px < W and py >= 0.0 and py < H):
+            continue
+        ix, iy = int(math.floor(px)), int(math.floor(py))
+        vis[k] = 1
+        if f[iy, ix] <= 0:
+            out[k] = 0.0
+            continue
+        th, vis[k] = _field_beam(px, py, ix, iy, ddx, ddy, res, f, W, H, limit)
+        if th is not None:
+            out[k] = th
+    return out.reshape(shape), vis.reshape(shape)
 
 
 def _pgm_tokens(data: bytes, count: int):

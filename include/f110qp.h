@@ -1587,6 +1587,86 @@ int f110qp_grid_field(const f110qp_grid_config* grid_cfg, const unsigned char* g
 int f110qp_wall_distance(const f110qp_grid_config* grid_cfg, const unsigned char* grid, int batch, int rows,
                          const double* x, double* dist, int* cell);
 
+/* ---- raster LiDAR through the distance field: beams skip free space ----------------------------------------
+ * Rule G1 visits every cell of a beam, with one division a visit. d2[j][i] of rule D1 says how far the nearest
+ * occupied cell is, so a beam standing in cell (i, j) can cross that many cells without looking at any of them.
+ * The calls below are the grid family's cast and rollout with rule F1 in place of rule G1: the same arguments with
+ * one more array, the same bits. They are not a family of their own. Additive: F110QP_API_VERSION stays 6, and no
+ * call above changes its results.
+ *
+ * F1. A beam against the grid through its field. d2 is [H][W] int as f110qp_grid_distance_dev writes it for `grid`;
+ *     it is the caller's to keep the two consistent, nothing checks it. A cell is occupied exactly when d2 <= 0.
+ *     The start, px, py, gx, gy, tx, ty, the tie rule and the step budget W + H + 2 are rule G1's, word for word.
+ *     At the start cell: the start cell outside the map, or px or py not finite: the grid gives no hit and
+ *     visits = 0. Otherwise D = d2[iy][ix] and visits = 1; D <= 0: th = 0. Otherwise repeat, while budget is left:
+ *       1. m = max(1, isqrt(D - 1)), capped by the remaining budget (isqrt(D - 1) is the largest m with m m < D;
+ *          INT_MAX gives 46,340). Rule G1's step 1, the move alone, is applied m times without reading the map;
+ *          t is the parameter of the last of them. The budget drops by m;
+ *       2. t > limit, or t is NaN: no hit;
+ *       3. the cell reached is outside the map: no hit;
+ *       4. D = d2 of the cell reached, visits grows by 1; D <= 0: th = t + 0.0.
+ *     limit is what the beam's minimum already holds from circles, mates and segments, at most max_range.
+ *     Consequences. Within m steps the walk stays within m cells of where it stood, which is less than sqrt(D):
+ *     no cell it passes is occupied. The parameter only grows and the map is convex, so a t past the limit or a
+ *     cell outside the map at a skipped step leaves both at the landing too. Rule G1 computes every boundary's
+ *     parameter from the integer boundary, so the walk's state after m steps is a function of the start, the
+ *     direction and m alone, and a jump that lands in that state returns the walk's own bits. Hence th, and with
+ *     it range and rule Z2's output, equal rule G1's bit for bit on every (beam, map) pair with a consistent d2.
+ *     With an inconsistent d2 the result is unspecified; every read is still inside [0, W) x [0, H).
+ *     How the m moves are made is the implementation's choice. With X(k) and Y(l) the k-th and l-th boundary
+ *     parameters ahead in rule G1's expressions (both never decrease), the walk has taken a x-moves and b = m - a
+ *     y-moves exactly when (a == 0 or X(a - 1) <= Y(b)) and (b == 0 or Y(b - 1) < X(a)); then
+ *     t = max(X(a - 1), Y(b - 1)). */
+
+/* f110qp_cast_scans_grid_dev, parameter for parameter, with rule F1 in place of rule G1: d2 follows grid, visits
+ * follows ranges. visits is [batch][num_ranges] int, the cells of d2 each beam read, or NULL; a car that is not
+ * listed keeps its row of visits as it keeps its ranges. grid is not read by this call; it keeps its place so that
+ * one argument list serves both casts. The map's cells are read from global memory (L2): the workgroup keeps no
+ * copy. F110QP_ERR_INVALID before any HIP call: that call's rules, then a side above F110QP_FIELD_MAX_SIDE, then
+ * width * height > 0 with d2 == NULL. width * height == 0 gives f110qp_cast_scans_noisy_dev's bits and visits 0.
+ * One launch, at most min(batch, 512) workgroups. */
+int f110qp_grid_cast_dev(const f110qp_scan_config* sc, const f110qp_world_config* wc, const f110qp_race_config* race,
+                         const f110qp_body_config* body, const f110qp_walls_config* walls,
+                         const f110qp_noise_config* noise, const f110qp_grid_config* grid_cfg, int batch, int tick,
+                         const int* list, const int* count, const double* x, const double* circles,
+                         const double* segments, const unsigned char* grid, const int* d2, float* ranges, int* visits,
+                         void* stream);
+
+/* f110qp_rollout_grid_dev, word for word, with every cast f110qp_grid_cast_dev's (d2 follows grid); every clearance
+ * stays f110qp_clearance_grid_dev's, which reads grid. The same launch count and stream order, no synchronisation
+ * and no allocation inside the loop; that call's checks with f110qp_grid_cast_dev's two behind the grid's. Every
+ * array equals f110qp_rollout_grid_dev's bit for bit when d2 is grid's field. */
+int f110qp_rollout_field_dev(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                             const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                             const f110qp_race_config* race, const f110qp_contact_config* cc,
+                             const f110qp_body_config* body, const f110qp_walls_config* walls,
+                             const f110qp_refresh_config* rf, const f110qp_noise_config* noise,
+                             const f110qp_grid_config* grid_cfg, int batch, const double* table,
+                             const double* waypoints, double* x_ref, int* have_path, const double* circles,
+                             const double* segments, const unsigned char* grid, const int* d2, double* x_traj,
+                             double* u_lin_traj, float* u_applied, int* status_traj, int* iters_traj,
+                             double* cost_traj, float* u_plan, float* x_plan, float* hs_traj, int* kind_traj,
+                             int* plan_status_traj, int* best_traj_traj, int* best_global_traj, double* pose_traj,
+                             float* ranges_traj, double* clear_traj, int* nearest_traj, int* crash_tick,
+                             void* stream);
+
+/* Same on host pointers (synchronous), with f110qp_rollout_grid's parameter list unchanged: the map is staged in
+ * once, f110qp_grid_distance_dev's two launches run on the context's stream into the staging buffer before the
+ * first tick, and the device loop reads that field. On top of f110qp_rollout_grid's rules a side above
+ * F110QP_FIELD_MAX_SIDE is invalid. */
+int f110qp_rollout_field(f110qp_ctx* ctx, const f110qp_rollout_config* rc, const f110qp_scan_config* sc,
+                         const f110qp_replan_config* rp, const f110qp_world_config* wc,
+                         const f110qp_race_config* race, const f110qp_contact_config* cc,
+                         const f110qp_body_config* body, const f110qp_walls_config* walls,
+                         const f110qp_refresh_config* rf, const f110qp_noise_config* noise,
+                         const f110qp_grid_config* grid_cfg, int batch, const double* table, const double* waypoints,
+                         double* x_ref, int* have_path, const double* circles, const double* segments,
+                         const unsigned char* grid, double* x_traj, double* u_lin_traj, float* u_applied,
+                         int* status_traj, int* iters_traj, double* cost_traj, float* u_plan, float* x_plan,
+                         float* hs_traj, int* kind_traj, int* plan_status_traj, int* best_traj_traj,
+                         int* best_global_traj, double* pose_traj, float* ranges_traj, double* clear_traj,
+                         int* nearest_traj, int* crash_tick);
+
 /* ---- race standings: progress along the track, laps and positions ---------------------------------------
  * The calls above return poses; the calls below say who is ahead. They run after the fact on x_traj, or on any
  * [rows][B][3] pose array: nothing inside a closed loop reads a standing, so there is no rollout family of
