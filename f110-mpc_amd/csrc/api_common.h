@@ -92,6 +92,9 @@ struct f110qp_ctx {
   DevBuf gW, gkey, glead;    // grouped mode: W = H^-1, key and leader per group
   DevBuf dgrp;               // host-pointer grouped calls: device copy of the group ids
   DevBuf lscr;               // lane back end: HBM Riccati scratch (when not in LDS)
+  DevBuf segtab;             // fixed-length segment kernels: the constant block of their code tables (lane_plan.h),
+  hipEvent_t segtab_ev = nullptr;       // filled once on the first stream that needs it; the event later
+  bool segtab_done = false;             // calls' streams wait on until it has been seen complete
   DevBuf hand;               // gap rows: counts and lists (f110qp::HandLayout, kHandInts(B) ints)
   DevBuf rplan;              // every rollout: one tick's u_plan | x_plan when the caller keeps neither
   DevBuf rdev;               // every host-pointer rollout: device copies of its arrays (api_stage.h)

@@ -254,6 +254,33 @@ static f110qp::LanePlan info_plan(f110qp_ctx* c, int batch, bool grouped, int* b
   return f110qp::lane_plan(c->kp, batch, lane_knobs(c), c->cfg.gap_mode == F110QP_GAP_ACTIVE);
 }
 
+// The constant block of the fixed-length segment kernels (lane_plan.h), a function of c->kp's bounds,
+// input weights and u_des, which no call changes after f110qp_create: filled on the device by the first
+// call that plans such a kernel, on that call's stream and in front of its launch. Later calls
+// make their stream wait on the fill's event until one of them has seen it complete; after that a call
+// only takes the pointer.
+static int seg_tab(f110qp_ctx* c, hipStream_t s, f110qp::LaneWork* lw) {
+  hipError_t e;
+  if (!c->segtab.p) {
+    if (!c->segtab_ev && (e = hipEventCreateWithFlags(&c->segtab_ev, hipEventDisableTiming)) != hipSuccess)
+      return hip_fail(e, "hipEventCreate segment tables");
+    if ((e = c->segtab.ensure(f110qp::kSegBlockBytes)) != hipSuccess) return hip_fail(e, "hipMalloc segment tables");
+    if ((e = f110qp::launch_seg_tab_fill(c->kp, (double*)c->segtab.p, s)) != hipSuccess ||
+        (e = hipEventRecord(c->segtab_ev, s)) != hipSuccess) {
+      c->segtab.release();  // (the event is kept for the next attempt)
+      return hip_fail(e, "segment table fill");
+    }
+  } else if (!c->segtab_done) {
+    // (every stream waits, the fill's own too: a wait on an event of the same stream is a no-op, and no
+    // stream handle is compared)
+    if (hipEventQuery(c->segtab_ev) == hipSuccess) c->segtab_done = true;
+    else if ((e = hipStreamWaitEvent(s, c->segtab_ev, 0)) != hipSuccess)
+      return hip_fail(e, "hipStreamWaitEvent segment tables");
+  }
+  lw->seg_tab = (const double*)c->segtab.p;
+  return F110QP_OK;
+}
+
 // Back end of a call and, for the lane back end (or the gap screen), its workspace and the plan of its
 // lane launch (resolved here, once per call: launch_solve and arm_signal read it).
 int lane_work(f110qp_ctx* c, int batch, hipStream_t s, int* backend, f110qp::LaneWork* lw, f110qp::LanePlan* plan,
@@ -282,7 +309,7 @@ int lane_work(f110qp_ctx* c, int batch, hipStream_t s, int* backend, f110qp::Lan
   if (e != hipSuccess) return hip_fail(e, "hipMalloc lane workspace");
   lw->scratch = (double*)c->lscr.p;
   *plan = f110qp::lane_plan(c->kp, batch, *lw, lw->screen != 0);
-  return F110QP_OK;
+  return plan->Q > 0 ? seg_tab(c, s, lw) : F110QP_OK;
 }
 
 // Per-group W cache of a grouped call (grows only; every call re-fills the slots it uses).
@@ -514,6 +541,8 @@ void f110qp_destroy(f110qp_ctx* c) {
   c->hin.release(); c->hout.release(); c->din.release(); c->dout.release();
   c->wW.release(); c->wkey.release(); c->wact.release();
   c->lscr.release();
+  c->segtab.release();
+  if (c->segtab_ev) (void)hipEventDestroy(c->segtab_ev);
   c->hand.release();
   c->rplan.release(); c->rdev.release();
   c->gW.release(); c->gkey.release(); c->glead.release(); c->dgrp.release();

@@ -114,6 +114,7 @@ struct LaneWork {
   int seg32 = 0;  // segmented kernel: 1 forces float references and Riccati scratch in LDS
   int twin = 1;   // segmented kernel: two PDAS starts per QP where the grid leaves SIMDs idle
   int fixedq = 1; // segmented kernel: the fixed-length kernels (five-stage segments) where they apply
+  const double* seg_tab = nullptr;  // their code tables: the solver's constant block (lane_plan.h)
   int* hand = nullptr;  // gap rows: counts + per-QP lists (HandLayout, kHandInts(B) ints)
   int screen = 0;       // gap rows: box solve on the lane kernel first, GI only for the QPs whose
                         // box optimum violates a gap row (f110qp_kernels.hip)

@@ -9,6 +9,7 @@
 
 #include "lane_plan.h"
 #endif
+#include "seg_tables.h"
 
 namespace f110qp {
 
@@ -55,5 +56,21 @@ template hipError_t launch_lane<float>(const KParams&, const SolveIO<float>&, co
                                        const LanePlan&, const ObjOut&, hipStream_t);
 template hipError_t launch_lane<double>(const KParams&, const SolveIO<double>&, const WarmState&, const LaneWork&,
                                         const LanePlan&, const ObjOut&, hipStream_t);
+
+
+// The solver's constant block (lane_plan.h): lanes 0 .. 15 write one code's rows of the two tables each,
+// by the expressions of the kernels that build theirs in LDS (fp64 scratch: 1e-10 scaled, both pass kinds).
+__global__ __launch_bounds__(64) void seg_tab_fill_kernel(const KParams P, double* __restrict__ tab) {
+  const int lane = threadIdx.x;
+  const double lb0 = (double)P.umin[0], lb1 = (double)P.umin[1];
+  const double ub0 = (double)P.umax[0], ub1 = (double)P.umax[1];
+  const SegTol t = seg_tolerances(lb0, ub0, lb1, ub1, P.r[0], P.r[1], P.udes[0], P.udes[1], 1e-10, 1e-10);
+  if (lane < 16) seg_code_rows<true>(lane, lb0, ub0, lb1, ub1, t, tab + 8 * lane, tab + 16 * 8 + 8 * lane);
+}
+
+hipError_t launch_seg_tab_fill(const KParams& P, double* tab, hipStream_t s) {
+  hipLaunchKernelGGL(seg_tab_fill_kernel, dim3(1), dim3(64), 0, s, P, tab);
+  return hipGetLastError();
+}
 
 }  // namespace f110qp

@@ -38,6 +38,13 @@ constexpr size_t seg_lds_bytes(int N, int S, bool fst = false, bool f32 = false)
 // rules of lane_plan() below still count the run-time-length kernel's LDS. (The references are not
 // staged: every lane loads its own 3 Q scalars from global memory.)
 constexpr size_t seg_fixedq_lds_bytes(int /*Q*/) { return 2 * kSegTabBytes; }
+// Their tables are a copy of the solver's constant block (LaneWork::seg_tab: btab [16][8] doubles, then
+// ftab [16][8], the layout of the LDS copy), a function of KParams' bounds, input weights and u_des
+// alone. launch_seg_tab_fill (lane_launch.hip) fills kSegBlockBytes of device memory at tab on stream
+// s, one wave, from the functions the run-time-length kernels build their tables with (seg_tables.h);
+// the caller orders it before the solver's first fixed-length launch.
+constexpr size_t kSegBlockBytes = 2 * kSegTabBytes;
+hipError_t launch_seg_tab_fill(const KParams& P, double* tab, hipStream_t s);
 
 // LDS per wave of the sequential kernel (lane_kernel.h) at L QPs per wave: the staged references
 // (12 N L B) + PDAS state (4 N L B), + the Riccati scratch (8 N L sizeof(ST)) when it is in LDS, + the

@@ -3,7 +3,7 @@ Run:  hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude -If110-mpc_amd/csrc -
             -S --cuda-device-only f110-mpc_amd/csrc/lane_seg_inst.hip -o seg.s
       python tools/seg_isa_count.py seg.s [TEMPLATE_ARGS ...]
 TEMPLATE_ARGS: the mangled template arguments that pick the kernels (default: the four Q = 5 ones and
-the Q = 0 S = 4 kernels; `ILi4ELb1ELb1EdLb0ELb1ELb1EfLi5E` is C2's twin kernel). Per kernel: the
+the Q = 0 S = 4 kernels; `lane_seg_kernel_qILi4ELb1EfLi5E` is C2's twin kernel). Per kernel: the
 registers, spills and scratch of its metadata, then every basic block of the pass loop (the kernel's
 depth-1 loop) with more than 40 instructions: its instruction count and the count per class. In the
 Q = 5 kernels the largest block is the backward sweep with the segment ends, the next two are the two
@@ -42,7 +42,7 @@ for l in lines:
             META[m.group(2)] = ent
         else:
             ent[m.group(1)] = int(m.group(2))
-starts = [i for i, l in enumerate(lines) if re.match(r"_ZN6f110qp15lane_seg_kernel\w+:", l)]
+starts = [i for i, l in enumerate(lines) if re.match(r"_ZN6f110qp\d+lane_seg_kernel\w+:", l)]
 for s in starts:
     name = lines[s].split(":")[0]
     if not any(p in name for p in picks):

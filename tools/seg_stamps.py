@@ -35,6 +35,10 @@ for i, n in enumerate(["setup", "backward", "segment ends", "refresh", "forward"
 for i, n in zip(range(8, 16), ["  staging", "  linearize", "  refs to fp64", "  warm + rest", "    rN shfl",
                                 "    mask init", "    rest", "  out loop"]):
     print(f"{n:14s} mean {b[:, i].mean():8.0f}  max {b[:, i].max():8.0f}")
+# what no slot counts: from the setup's last stamp to the first pass's first (the compiler's hoisted loop
+# invariants and AGPR parking land there), the loop control between passes, the stamps' own reads
+rest = tot - b[:, 0:6].sum(axis=1)
+print(f"{'in no slot':14s} mean {rest.mean():8.0f}  max {rest.max():8.0f}  share {rest.mean() / tot.mean() * 100:5.1f}%")
 np_ = np.maximum(b[:, 6], 1)
 print(f"per pass: backward {np.mean(b[:, 1] / np_):.0f}, segment ends {np.mean(b[:, 2] / np_):.0f}, refresh "
       f"{np.mean(b[:, 3] / np_):.0f}, forward {np.mean(b[:, 4] / np_):.0f} cycles; total p50 {np.median(tot):.0f} "
